@@ -6,7 +6,7 @@ out) over the rank's resident batch of synthetic grid points (default 1e8 Float3
 configuration BASELINE.json quotes the metric on).  Inputs are generated on the device before the timed
 region; nothing crosses PCIe inside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dtype f32|f64] [--scaling weak|strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--points P] [--dtype f32|f64] [--scaling weak|strong] [--dump-outputs DIR]
                     [--rotate K] [--workload sb2006|sb2006_chen|sb2006_column|sb2006_aos|sb2006_fields|icenuc|mp0m|mp1m|mp1m_lin|mp1m_column|mp1m_column_lin|
                                              arg2000|arg2000_columns|p3|p3_split|p3_selfcol|mp2m_p3]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -71,6 +71,10 @@ def parse():
                          "reductions, rank-0 JSON — over gloo with a step that does nothing; the line carries \"dry_run\": true and no throughput")
     ap.add_argument("--diagnostics", action="store_true",
                     help="also reduce Σ of the output columns per step (block reduce + RCCL all-reduce of a few doubles)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the floating-point arrays the workload's entry point returned in the last timed step "
+                         "on buffer set 0 (rank 0; inputs seeded, identical from run to run) as DIR/<name>.npy; above DUMP_BUDGET_BYTES in all, "
+                         "a fixed seeded sample of the same positions of every array")
     return ap.parse_args()
 
 
@@ -148,6 +152,71 @@ def pmc_valu(workload: str, dtype: str, n: int):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, so that two builds can be compared output for output
+# ------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 60_000_000      # data of all dumped arrays together (npy headers on top stay far below the 64 MB limit)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def output_arrays(obj, name=""):
+    """(name, tensor) of every floating-point tensor in a workload's result: named tuples and dicts by field, plain tuples by index."""
+    import torch
+    if isinstance(obj, torch.Tensor):
+        if obj.is_floating_point():
+            yield name or "out", obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            yield from output_arrays(v, f"{name}.{k}" if name else str(k))
+    elif isinstance(obj, tuple) and hasattr(obj, "_fields"):
+        for k in obj._fields:
+            yield from output_arrays(getattr(obj, k), f"{name}.{k}" if name else k)
+    elif isinstance(obj, (tuple, list)):
+        for i, v in enumerate(obj):
+            yield from output_arrays(v, f"{name}.{i}" if name else str(i))
+
+
+def snapshot_outputs(result):
+    """Device copies of the result's arrays, flattened; if they exceed DUMP_BUDGET_BYTES together, the same seeded sample of element
+    positions (sorted, per array length) of each.  Called after the timed regions; only gathers on the device."""
+    import torch
+    arrays = list(output_arrays(result))
+    if not arrays:
+        raise RuntimeError("--dump-outputs: the workload returned no floating-point arrays")
+    total = sum(t.numel() * t.element_size() for _, t in arrays)
+    keep = 1.0 if total <= DUMP_BUDGET_BYTES else DUMP_BUDGET_BYTES / total
+    index = {}
+    snap = {}
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        if keep < 1.0:
+            n = flat.numel()
+            if n not in index:
+                g = torch.Generator(device="cpu").manual_seed(DUMP_SAMPLE_SEED)
+                m = max(1, int(n * keep))
+                index[n] = torch.randint(n, (m,), generator=g).sort().values.to(flat.device)
+            flat = flat.index_select(0, index[n])
+        else:
+            flat = flat.clone()
+        snap[name] = flat
+    return snap, {"arrays": len(snap), "total_bytes_full": total, "sampled": keep < 1.0, "sample_seed": DUMP_SAMPLE_SEED if keep < 1.0 else None}
+
+
+def write_outputs(directory, snap):
+    """DIR/<name>.npy, float32 or float64 as computed; returns {name: length}."""
+    import numpy as np
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    lengths = {}
+    for name, t in snap.items():
+        a = t.cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(d / f"{name}.npy", a)
+        lengths[name] = int(a.size)
+    return lengths
+
+
+# ------------------------------------------------------------------------------------------------------------
 # workloads: each returns (state columns, step(), output columns, description dict, cpu_run(cols_np, m, threads))
 # ------------------------------------------------------------------------------------------------------------
 def setup_sb2006(args, dev, dtype, rank):
@@ -179,7 +248,7 @@ def setup_sb2006(args, dev, dtype, rank):
         "workload": "Microphysics2M SB2006 fused warm-rain tendencies (cond/evap, autoconversion, accretion, "
                     "self-collection, breakup, evaporation, number adjustment) + " + ("Chen-2022" if chen else "SB2006") +
                     " rain terminal velocities, limited rain PSD",
-        "columns_in": 7, "columns_out": 6, "diag_cols": list(out[:4]),
+        "columns_in": 7, "columns_out": 6, "diag_cols": list(out[:4]), "outputs": lambda: out,
     }
     return list(state), step, desc, cpu_run
 
@@ -221,7 +290,7 @@ def setup_sb2006_column(args, dev, dtype, rank):
         "kernel": "sb2006_column_kernel",
         "workload": "Microphysics2M SB2006 fused warm-rain tendencies + SB2006 rain fall speeds + first-order upwind sedimentation flux "
                     "divergence of q_rai, n_rai per column of 74 levels (host-model step, SURVEY 8f-4)",
-        "columns_in": 7, "columns_out": 4, "diag_cols": list(out[:4]),
+        "columns_in": 7, "columns_out": 4, "diag_cols": list(out[:4]), "outputs": lambda: out,
     }
     return list(st), step, desc, cpu_run
 
@@ -274,6 +343,7 @@ def setup_sb2006_layout(args, dev, dtype, rank):
                     ("result written as Vector{NamedTuple} (8 fields, 4 zero) through an LDS transpose" if aos else
                      "7 components of a 9-component VIJFH state field → 4 components of a 5-component tendency field"),
         "columns_in": 7, "columns_out": 8 if aos else 4, "diag_cols": [],
+        "outputs": (lambda: {"aos": holder["out"]}) if aos else (lambda: dict(zip(("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt"), outs))),
     }
     return [c.contiguous() for c in state], step, desc, cpu_run
 
@@ -302,7 +372,7 @@ def setup_icenuc(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 20, "f64": 40}[args.dtype],      # 3 in + 2 out
         "kernel": "ice_nucleation_kernel",
         "workload": "IceNucleation ABIFM immersion (kaolinite) + Koop2000 cubic homogeneous rates over (T, a_w, r)",
-        "columns_in": 3, "columns_out": 2, "diag_cols": [holder["out"].rate_het],
+        "columns_in": 3, "columns_out": 2, "diag_cols": [holder["out"].rate_het], "outputs": lambda: holder["out"],
         "cpu_threads": 1,
     }
     return list(state), step, desc, cpu_run
@@ -335,7 +405,7 @@ def setup_cloud_diag(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 36, "f64": 72}[args.dtype],      # 5 in + 4 out
         "kernel": "cloud_diagnostics_kernel",
         "workload": "CloudDiagnostics radar_reflectivity_1M + radar_reflectivity_2M + effective_radius_2M + effective_radius_Liu_Hallet_97 over (rho, q_lcl, q_rai, N_lcl, N_rai), limited rain PSD",
-        "columns_in": 5, "columns_out": 4, "diag_cols": [out.reff_2m],
+        "columns_in": 5, "columns_out": 4, "diag_cols": [out.reff_2m], "outputs": lambda: out,
         "cpu_threads": 1,
     }
     return [rho, q_lcl, q_rai, N_lcl, N_rai], step, desc, cpu_run
@@ -366,7 +436,7 @@ def setup_mp0m(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 12, "f64": 24}[args.dtype],      # 2 in + 1 out
         "kernel": "mp0m_tendencies_kernel",
         "workload": "BulkMicrophysicsTendencies Microphysics0Moment (qc_0 threshold) over (q_lcl, q_icl)",
-        "columns_in": 2, "columns_out": 1, "diag_cols": [out],
+        "columns_in": 2, "columns_out": 1, "diag_cols": [out], "outputs": lambda: {"dq_tot_dt": out},
         "cpu_threads": 1,
     }
     return [q_lcl, q_icl], step, desc, cpu_run
@@ -396,7 +466,7 @@ def setup_mp1m(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 44, "f64": 88}[args.dtype],      # 7 in + 4 out
         "kernel": "mp1m_tendencies_kernel",
         "workload": "Microphysics1M Instantaneous bulk tendencies, default Microphysics1MOptions (13 processes)",
-        "columns_in": 7, "columns_out": 4, "diag_cols": list(out),
+        "columns_in": 7, "columns_out": 4, "diag_cols": list(out), "outputs": lambda: out,
     }
     return list(state), step, desc, cpu_run
 
@@ -428,7 +498,7 @@ def setup_mp1m_lin(args, dev, dtype, rank):
         "kernel": "mp1m_linearized_pair_kernel (Float32: two points per lane in packed arithmetic)" if args.dtype == "f32" else "mp1m_linearized_kernel", "bound": "valu",
         "workload": "Microphysics1M LinearizedAverage bulk tendencies: 2 linearized implicit substeps (13 processes, 4x4 sparse solve, "
                     "T update) per point",
-        "columns_in": 7, "columns_out": 4, "diag_cols": list(out),
+        "columns_in": 7, "columns_out": 4, "diag_cols": list(out), "outputs": lambda: out,
     }
     return list(state), step, desc, cpu_run
 
@@ -476,7 +546,7 @@ def setup_mp1m_column(args, dev, dtype, rank):
         "kernel": "mp1m_column_kernel", "bound": "valu",
         "workload": "Microphysics1M " + ("LinearizedAverage" if lin else "Instantaneous") + " bulk tendencies + Stokes / Chen-2022 fall speeds of cloud liquid, "
                     "cloud ice, rain, snow + first-order upwind sedimentation flux divergence per column of 74 levels (host-model step)",
-        "columns_in": 7, "columns_out": 4, "diag_cols": [],
+        "columns_in": 7, "columns_out": 4, "diag_cols": [], "outputs": lambda: holder["out"],
     }
     return list(st), step, desc, cpu_run
 
@@ -506,7 +576,7 @@ def setup_arg2000(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 36, "f64": 72}[args.dtype],      # 4 in + 5 N_act out
         "kernel": "arg_activation_kernel",
         "workload": "AerosolActivation ARG2000 N_activated_per_mode, 5 shared lognormal kappa-modes x thermodynamic states",
-        "columns_in": 4, "columns_out": 5, "diag_cols": list(out.N_act),
+        "columns_in": 4, "columns_out": 5, "diag_cols": list(out.N_act), "outputs": lambda: out,
     }
     return list(state), step, desc, cpu_run
 
@@ -550,7 +620,7 @@ def setup_arg2000_columns(args, dev, dtype, rank):
         "kernel": "arg_activation_columns_kernel",
         "workload": "AerosolActivation ARG2000 N_activated_per_mode with per-state mode descriptors (r_dry, stdev, N, hygroscopicity per mode and "
                     "state) — the reference's aerosol_activation_kernel!, test/gpu_tests.jl:45-79",
-        "columns_in": 4 + 4 * nm, "columns_out": nm, "diag_cols": list(n_act),
+        "columns_in": 4 + 4 * nm, "columns_out": nm, "diag_cols": list(n_act), "outputs": lambda: out,
     }
     return list(state), step, desc, cpu_run
 
@@ -590,7 +660,7 @@ def setup_p3(args, dev, dtype, rank):
         "kernel": "p3_velocity_kernel<SOLVE> (one launch)" if fused else "p3_shape_kernel + p3_velocity_kernel", "bound": "valu",
         "workload": "P3Scheme state_from_prognostic + get_distribution_logλ (Brent root, incomplete-gamma moments) + D_m + "
                     "number/mass-weighted Chen-2022 fall speeds (ChebyshevGauss(100) x 4 segments, gamma_inc_inv bounds)",
-        "columns_in": 5, "columns_out": 4, "diag_cols": [],
+        "columns_in": 5, "columns_out": 4, "diag_cols": [], "outputs": lambda: holder["out"],
     }
     return list(st) + [rho_a], step, desc, cpu_run
 
@@ -633,7 +703,7 @@ def setup_p3_selfcol(args, dev, dtype, rank):
         "kernel": "p3_shape_kernel + p3_self_collection_kernel", "bound": "valu",
         "workload": "P3State + get_distribution_logλ + ice_self_collection (double quadrature, 8 n² = 12800 integrand evaluations per "
                     "state) — the reference's benchmark_p3_kernel!",
-        "columns_in": 5, "columns_out": 2, "diag_cols": [],
+        "columns_in": 5, "columns_out": 2, "diag_cols": [], "outputs": lambda: {"log_lambda": holder["out"][0], "self_collection": holder["out"][1]},
     }
     return cols + [rho_a], step, desc, cpu_run
 
@@ -677,7 +747,7 @@ def setup_mp2m_p3(args, dev, dtype, rank):
         "bytes_per_point": {"f32": 80, "f64": 160}[args.dtype],      # 12 in + 8 out, each column once (one launch since round 3)
         "kernel": "p3_collision_kernel<FUSED, PointwiseExtra> (one launch: ice processes, 8 lanes per state, + the pointwise part per lane)", "bound": "valu",
         "workload": "bulk_microphysics_tendencies(Microphysics2Moment(), mp{WarmRain, P3IceParams}, …) — BMT:898-1083, quadrature_order 16",
-        "columns_in": 12, "columns_out": 8, "diag_cols": [],
+        "columns_in": 12, "columns_out": 8, "diag_cols": [], "outputs": lambda: holder["out"],
     }
     return cols + [ll], step, desc, cpu_run
 
@@ -866,9 +936,12 @@ def main():
     if world != max(1, args.gpus):
         sys.exit(f"--gpus {args.gpus} does not match WORLD_SIZE={world}")
     dry = args.dry_run_scaffolding
+    if dry and args.dump_outputs:
+        sys.exit("bench.py: --dump-outputs needs a kernel; the dry run of the scaffolding computes nothing")
     if dry:
         args.backend, args.no_cpu_baseline, args.settle = "gloo", True, 0
-    n_dev = torch.cuda.device_count()          # counting devices does not initialise the GPU
+    # counting devices opens the GPU (HIP runtime initialisation): the dry run, which may start many ranks on one node, leaves it closed
+    n_dev = 0 if dry else torch.cuda.device_count()
     if not dry and args.backend == "nccl" and n_dev < int(os.environ.get("LOCAL_WORLD_SIZE", world)):
         # one process per GPU over RCCL: fewer devices than ranks cannot work — say so and leave non-zero before any rank blocks in a collective
         sys.exit(f"bench.py: --gpus {world} with the nccl (RCCL) backend needs {world} visible GPUs, this node has {n_dev}")
@@ -1003,6 +1076,8 @@ def main():
         rot_wall, rot_kern_ms = timed_region(lambda i: steps[i % rotate])
     else:
         rot_wall, rot_kern_ms = same_wall, same_kern_ms
+    # --dump-outputs: buffer set 0's result as the last timed step that computed it left it (taken here, so that it disturbs no timed region)
+    dump = snapshot_outputs(desc["outputs"]()) if args.dump_outputs and rank == 0 else None
 
     # cold probes: what makes the first launches slow — the clock ramp or the address translation of untouched pages?
     probes = None
@@ -1105,6 +1180,9 @@ def main():
             m = min(n, {"sb2006": 20_000_000, "arg2000_columns": 2_000_000, "sb2006_chen": 20_000_000, "sb2006_column": 74 * 270_000, "mp1m_column": 74 * 54_000, "mp1m_column_lin": 74 * 27_000, "sb2006_aos": 20_000_000, "sb2006_fields": 20_000_000, "p3": 100_000, "p3_split": 100_000, "p3_selfcol": 2_000, "mp2m_p3": 20_000}.get(args.workload, 4_000_000))
             cols_np = [np.ascontiguousarray(c[:m].cpu().numpy()) for c in state]
             line["cpu_baseline"] = cpu_baseline(args, cols_np, desc, cpu_run)
+        if dump is not None:
+            snap, info = dump
+            line["dump_outputs"] = dict(info, dir=args.dump_outputs, lengths=write_outputs(args.dump_outputs, snap))
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()

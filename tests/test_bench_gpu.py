@@ -94,3 +94,22 @@ def test_rccl_process_group_path_with_one_rank():
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d["n_gpus"] == 1 and d["config"]["points_total"] == 1000003 and d["value"] > 0
+
+
+def test_dump_outputs_are_the_same_for_any_step_count(tmp_path):
+    """--dump-outputs writes the six result columns of the timed sweep; the inputs are seeded, so another --steps gives the same arrays."""
+    import numpy as np
+    fast = ("--no-cpu-baseline", "--no-cold-probes", "--no-telemetry", "--rotate", "2")
+    d3 = _run("--dump-outputs", str(tmp_path / "a"), *fast)
+    d5 = _run("--dump-outputs", str(tmp_path / "b"), "--steps", "5", *fast)
+    assert d3["steps"] == 3 and d5["steps"] == 5 and d3["ms_per_step"] > 0
+    names = ["dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "vt_rai_n", "vt_rai_m"]
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(f"{n}.npy" for n in names) and d3["dump_outputs"]["arrays"] == 6 and not d3["dump_outputs"]["sampled"]
+    total = 0
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape == (1000003,)
+        assert np.array_equal(a, b, equal_nan=True), f
+        total += a.nbytes
+    assert total <= 64e6

@@ -1,5 +1,5 @@
 """julia/CMXExt.jl — the reference-side binding — checked statically against the reference's struct
-definitions and include/cmx.h by tools/check_julia_shim.py (Julia is not in the image).  The mutation cases prove that the checker
+definitions (the fixture tests/golden/julia_reference.json) and include/cmx.h by tools/check_julia_shim.py (Julia is not in the image).  The mutation cases prove that the checker
 sees the mistakes it is there for, including the one VERDICT r03 found in INTEGRATION.md (`mp.options`, a field that does not exist)."""
 import sys
 from pathlib import Path
@@ -10,7 +10,6 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "tools"))
 import check_julia_shim as cjs  # noqa: E402
 
-needs_reference = pytest.mark.skipif(not cjs.REFERENCE.exists(), reason="/root/reference is not on this machine")
 TEXT = cjs.SHIM.read_text(encoding="utf-8")
 
 
@@ -19,8 +18,7 @@ def test_shim_agrees_with_header_and_reference():
     assert findings == []
     assert summary["mirror_structs"] >= 20 and summary["direct_layout_rows"] >= 35 and summary["ccall_families"] >= 36
     assert summary["c_structs_without_julia_side"] == []
-    if cjs.REFERENCE.exists():
-        assert summary["field_accesses"] >= 150 and summary["qualified_names"] >= 100
+    assert summary["field_accesses"] >= 150 and summary["qualified_names"] >= 100
 
 
 def test_every_entry_family_is_bound():
@@ -81,14 +79,12 @@ def test_checker_catches_header_mismatches(old, new, expect):
     assert any(expect in f for f in findings), findings
 
 
-@needs_reference
 @pytest.mark.parametrize("old,new,expect", MUTATIONS_REFERENCE, ids=[m[2][:40] for m in MUTATIONS_REFERENCE])
 def test_checker_catches_reference_mismatches(old, new, expect):
     findings, _ = cjs.run(verbose=False, shim_text=_mutate(old, new))
     assert any(expect in f for f in findings), findings
 
 
-@needs_reference
 def test_transliteration_matches_every_direct_struct():
     """The header's ASCII spelling of every reference field handed over as it is (νc → nu_c, ρ0 → rho_0, Δa_w_min → delta_a_w_min …)."""
     assert cjs.translit("νc") == "nu_c" and cjs.translit("ρ0") == "rho_0" and cjs.translit("Δa_w_min") == "delta_a_w_min"

@@ -3,8 +3,9 @@
 
 Julia is not in the build image, so the binding cannot be executed here.  This tool reads three texts instead and makes them agree:
 
-  * the reference's own `struct` definitions (/root/reference/src/parameters/*.jl, src/AerosolModel.jl, src/Quadrature.jl) — skipped,
-    with a note, when /root/reference is absent (the GPU box);
+  * the reference's own `struct` definitions (src/parameters/*.jl, src/AerosolModel.jl, src/Quadrature.jl …), as the data fixture
+    tests/golden/julia_reference.json: field names and types per struct, the process-parameter keys and the names each module defines
+    (regenerate it from a reference checkout with `--write-fixture`);
   * include/cmx.h: parameter structs, CMX_ASSERT_PARAM_STRUCT_SIZES, the `#define` flags, every `cmx_*` prototype;
   * julia/CMXExt.jl: `Cmx*` mirror structs (`# == cmx_…`), the DIRECT_LAYOUT table, every field access on a type-annotated argument,
     the flag constants, the version constants, every `ccall(_fn("cmx_…", FT), …)`.
@@ -15,10 +16,12 @@ DIRECT_LAYOUT pair whose transliterated reference field list differs from the C 
 the reference does not define; a `ccall` whose argument-type tuple or argument count differs from the C prototype; a flag constant whose
 value differs from the header; an entry-point family of the header without a binding; unbalanced delimiters or `end`s.
 
-    python tools/check_julia_shim.py            # prints a summary, exit code 1 on any finding
+    python tools/check_julia_shim.py                                  # prints a summary, exit code 1 on any finding
+    python tools/check_julia_shim.py --write-fixture <reference checkout>  # re-extract tests/golden/julia_reference.json
 """
 from __future__ import annotations
 
+import json
 import re
 import sys
 from pathlib import Path
@@ -26,7 +29,7 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 HEADER = REPO / "include" / "cmx.h"
 SHIM = REPO / "julia" / "CMXExt.jl"
-REFERENCE = Path("/root/reference")
+REFERENCE_FIXTURE = REPO / "tests" / "golden" / "julia_reference.json"
 
 IDENT = r"[^\W\d][\w!]*"          # Julia identifier (unicode letters, subscripts are \w)
 
@@ -462,10 +465,17 @@ class Reference:
     TDP_USED_BY_REFERENCE = {"T_freeze", "R_v", "R_d", "cp_d", "cp_l", "cv_l", "LH_v0", "LH_s0", "q_min", "grav", "Rv_over_Rd", "ThermodynamicsParameters"}
     TDP_THERMODYNAMICS_OWN = {"cp_v", "cp_i", "T_0", "T_triple", "press_triple"}
 
-    def __init__(self, root: Path = REFERENCE):
-        self.root = root
+    def __init__(self, root: Path = None):
+        """From the fixture (default), or parsed from the sources of a reference checkout at `root`."""
+        if root is None:
+            d = json.loads(REFERENCE_FIXTURE.read_text(encoding="utf-8"))
+            self.structs = {k: [tuple(f) for f in v] for k, v in d["structs"].items()}
+            self.process_param_keys = set(d["process_param_keys"])
+            self.process_param_inner = set(d["process_param_inner"])
+            self.defined = {k: set(v) for k, v in d["defined"].items()}
+            return
         self.structs = {}
-        self.text = {}
+        self.defined = {}
         for mod, globs in self.MODULE_FILES.items():
             txt = ""
             for g in globs:
@@ -474,7 +484,9 @@ class Reference:
                     txt += "\n" + t
                     for k, v in parse_julia_structs(t).items():
                         self.structs[k] = v
-            self.text[mod] = strip_julia(txt)
+            txt = strip_julia(txt)
+            names = set(re.findall(IDENT, txt)) | set(re.findall(r"[^\W\d]\w*", txt))
+            self.defined[mod] = {nm for nm in names if self._defines_in(txt, nm)}
         opt = strip_julia((root / "src/parameters/Microphysics1MOptions.jl").read_text(encoding="utf-8"))
         i = opt.index("microphysics_1m_process_params(td::CP.ParamDict")
         blk = opt[i:opt.index("\n)\n", i)]
@@ -482,11 +494,19 @@ class Reference:
         self.process_param_inner = set(re.findall(rf"=>\s*:({IDENT})", opt)) | set(re.findall(rf"\(;\s*({IDENT})\s*=", opt)) | \
             set(re.findall(rf",\s*({IDENT})\s*=\s*Frostenberg2023", opt))
 
-    def defines(self, mod: str, name: str) -> bool:
-        t = self.text[mod]
+    @staticmethod
+    def _defines_in(t: str, name: str) -> bool:
         return bool(re.search(rf"\b(struct|abstract type|function)\s+{re.escape(name)}\b", t)
                     or re.search(rf"^\s*(?:@inline\s+)?{re.escape(name)}\(", t, flags=re.M)
                     or re.search(rf"^\s*const\s+{re.escape(name)}\b", t, flags=re.M))
+
+    def defines(self, mod: str, name: str) -> bool:
+        return name in self.defined[mod]
+
+    def to_json(self) -> str:
+        return json.dumps({"structs": {k: [list(f) for f in v] for k, v in sorted(self.structs.items())},
+                           "process_param_keys": sorted(self.process_param_keys), "process_param_inner": sorted(self.process_param_inner),
+                           "defined": {k: sorted(v) for k, v in self.defined.items()}}, ensure_ascii=False, indent=1) + "\n"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -700,12 +720,11 @@ def run(verbose: bool = True, shim_text: str = None):
     n_cc = check_ccalls(shim, hdr, findings)
     n_const = check_consts(shim, hdr, findings)
     summary = {"mirror_structs": len(shim.mirrors), "direct_layout_rows": len(shim.direct), "ccall_families": n_cc, "constants": n_const,
-               "functions": len(shim.functions), "reference": REFERENCE.exists()}
-    if REFERENCE.exists():
-        ref = Reference()
-        check_direct(shim, hdr, ref, findings)
-        summary["field_accesses"] = check_accesses(shim, ref, findings)
-        summary["qualified_names"] = check_names(shim, ref, findings)
+               "functions": len(shim.functions), "reference": str(REFERENCE_FIXTURE.relative_to(REPO))}
+    ref = Reference()
+    check_direct(shim, hdr, ref, findings)
+    summary["field_accesses"] = check_accesses(shim, ref, findings)
+    summary["qualified_names"] = check_names(shim, ref, findings)
     covered = {c for _, (c, _) in shim.mirrors.items()} | {c for _, _, c in shim.direct}
     uncovered = sorted(set(hdr.structs) - covered)
     summary["c_structs_without_julia_side"] = uncovered
@@ -720,4 +739,7 @@ def run(verbose: bool = True, shim_text: str = None):
 
 
 if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "--write-fixture":
+        REFERENCE_FIXTURE.write_text(Reference(Path(sys.argv[2])).to_json(), encoding="utf-8")
+        sys.exit(0)
     sys.exit(1 if run()[0] else 0)
