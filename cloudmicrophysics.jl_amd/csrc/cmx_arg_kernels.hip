@@ -115,14 +115,9 @@ __global__ __launch_bounds__(kArgBS) void arg_activation_kernel(const ArgConsts<
 template <typename FT, int NM, bool SINKS>
 static void launch_arg(const ArgConsts<FT> &c, const ArgIO<FT> &io0, int64_t n, const void *const *ptrs, int nptrs, hipStream_t s) {
     constexpr int VEC = Math<FT>::VEC;
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(io0.T) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (int k = 0; k < nptrs; ++k)
-        if (ptrs[k]) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(ptrs[k]) & 15u) == mis0);
     auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
-    auto launch_range = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, nptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         ArgIO<FT> io = io0;
         io.T += lo; io.p += lo; io.w += lo; io.q_tot += lo;
         io.q_liq = off(io.q_liq, lo); io.q_ice = off(io.q_ice, lo); io.N_liq = off(io.N_liq, lo); io.N_ice = off(io.N_ice, lo);
@@ -132,16 +127,7 @@ static void launch_arg(const ArgConsts<FT> &c, const ArgIO<FT> &io0, int64_t n, 
         const dim3 grid((unsigned)((nv + kArgBS - 1) / kArgBS));
         if (io.want_N && !io.want_M) hipLaunchKernelGGL((arg_activation_kernel<FT, NM, SINKS, V, true>), grid, dim3(kArgBS), 0, s, c, io, nv);
         else hipLaunchKernelGGL((arg_activation_kernel<FT, NM, SINKS, V, false>), grid, dim3(kArgBS), 0, s, c, io, nv);
-    };
-    if (same_mis) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_range(std::integral_constant<int, 1>{}, 0, head);
-        launch_range(std::integral_constant<int, VEC>{}, head, body);
-        launch_range(std::integral_constant<int, 1>{}, head + body, n - head - body);
-    } else {
-        launch_range(std::integral_constant<int, 1>{}, 0, n);
-    }
+    });
 }
 
 template <typename FT, typename AP, typename AD, typename AI, typename TH>
@@ -301,14 +287,9 @@ static void launch_arg_columns(const ArgConsts<FT> &c, const ArgColPar<FT> &par,
                                const void *const *ptrs, int nptrs, hipStream_t s) {
     // Float64 runs one point per lane: the kernel is VALU-bound there and the second point's kept values would cost a wave per SIMD
     constexpr int VEC = sizeof(FT) == 4 ? Math<FT>::VEC : 1;
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(io0.T) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (int k = 0; k < nptrs; ++k)
-        if (ptrs[k]) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(ptrs[k]) & 15u) == mis0);
     auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
-    auto launch_range = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, nptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         ArgIO<FT> io = io0;
         ArgColIO<FT> mc = mc0;
         io.T += lo; io.p += lo; io.w += lo; io.q_tot += lo;
@@ -322,16 +303,7 @@ static void launch_arg_columns(const ArgConsts<FT> &c, const ArgColPar<FT> &par,
         const dim3 grid((unsigned)((nv + kArgColBS<FT> - 1) / kArgColBS<FT>));
         if (!io.want_M) hipLaunchKernelGGL((arg_activation_columns_kernel<FT, NM, SINKS, V, true>), grid, dim3(kArgColBS<FT>), 0, s, c, par, io, mc, nv);
         else hipLaunchKernelGGL((arg_activation_columns_kernel<FT, NM, SINKS, V, false>), grid, dim3(kArgColBS<FT>), 0, s, c, par, io, mc, nv);
-    };
-    if (same_mis && VEC > 1) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_range(std::integral_constant<int, 1>{}, 0, head);
-        launch_range(std::integral_constant<int, VEC>{}, head, body);
-        launch_range(std::integral_constant<int, 1>{}, head + body, n - head - body);
-    } else {
-        launch_range(std::integral_constant<int, 1>{}, 0, n);
-    }
+    });
 }
 
 template <typename FT, typename AP, typename AI, typename TH>

@@ -176,21 +176,15 @@ static int32_t cloud_diagnostics_entry(const RN *rain, const PC *pdf_c, const PR
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;
     const void *ptrs[] = {rho, q_lcl, q_rai, N_lcl, N_rai, Z_1m, Z_2m, reff_2m, reff_lh97};
-    bool vec_ok = true;
-    for (const void *q : ptrs) vec_ok = vec_ok && (!q || aligned16(q));
-    auto launch = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         auto off = [lo](auto *p) { return p ? p + lo : p; };
         const DiagIO<FT> io{rho + lo, off(q_lcl), off(q_rai), off(N_lcl), off(N_rai), off(Z_1m), off(Z_2m), off(reff_2m), off(reff_lh97)};
         const int64_t nvec = count / V;
         const dim3 grid((unsigned)((nvec + kBlock - 1) / kBlock));
         if (limited) hipLaunchKernelGGL((cloud_diagnostics_kernel<FT, V, true>), grid, dim3(kBlock), 0, s, c, io, lh_defaults, nvec);
         else hipLaunchKernelGGL((cloud_diagnostics_kernel<FT, V, false>), grid, dim3(kBlock), 0, s, c, io, lh_defaults, nvec);
-    };
-    const int64_t body = vec_ok ? (n / VEC) * VEC : 0;
-    launch(std::integral_constant<int, VEC>{}, 0, body);
-    launch(std::integral_constant<int, 1>{}, body, n - body);
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

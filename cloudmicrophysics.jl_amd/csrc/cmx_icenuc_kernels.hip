@@ -207,15 +207,10 @@ static int32_t icenuc_entry(const TH *tps, const DU *dust, const KO *koop, const
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = Math<FT>::VEC;
     const void *ptrs[] = {T, a_w, r, delta_a_w, J_het, J_hom, rate_het, rate_hom};
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(T) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (const void *p : ptrs)
-        if (p) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 15u) == mis0);
     const bool linear = flags & CMX_ICENUC_HOM_LINEAR;
     auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
-    auto launch_range = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         IceNucIO<FT> io{T + lo, a_w + lo, off(r, lo), off(delta_a_w, lo), off(J_het, lo), off(J_hom, lo),
                         off(rate_het, lo), off(rate_hom, lo), reinterpret_cast<unsigned long long *>(n_domain_errors)};
         const int64_t nv = count / V;
@@ -229,16 +224,7 @@ static int32_t icenuc_entry(const TH *tps, const DU *dust, const KO *koop, const
             else hipLaunchKernelGGL((ice_nucleation_kernel<FT, false, V, true>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
         } else if (linear) hipLaunchKernelGGL((ice_nucleation_kernel<FT, true, V>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
         else hipLaunchKernelGGL((ice_nucleation_kernel<FT, false, V>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
-    };
-    if (same_mis) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_range(std::integral_constant<int, 1>{}, 0, head);
-        launch_range(std::integral_constant<int, VEC>{}, head, body);
-        launch_range(std::integral_constant<int, 1>{}, head + body, n - head - body);
-    } else {
-        launch_range(std::integral_constant<int, 1>{}, 0, n);
-    }
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "../../include/cmx.h"
+#include "cmx_split.hpp"
 
 namespace cmx {
 
@@ -66,6 +67,22 @@ constexpr int64_t kMaxPoints = 16ll * 0x7fffffffll;
 #endif
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// --- alignment split of the streaming entry points ------------------------------------------------------------------
+// Calls f(std::integral_constant<int, V>{}, lo, count) for each non-empty range of split_aligned (cmx_split.hpp, where the rule is
+// explained): the scalar head (V = 1), the vector body (V = VEC) and the scalar tail (V = 1).  f offsets its IO by lo, picks the
+// instantiation and launches count / V lanes.
+template <typename FT, int VEC, typename F>
+inline void for_each_range(const void *const *cols, int ncols, int64_t n, F &&f) {
+    const Split r = split_aligned(cols, ncols, n, sizeof(FT), VEC);
+    if (r.head > 0) f(std::integral_constant<int, 1>{}, (int64_t)0, r.head);
+    if (r.body > 0) f(std::integral_constant<int, VEC>{}, r.head, r.body);
+    if (r.tail > 0) f(std::integral_constant<int, 1>{}, r.head + r.body, r.tail);
+}
+template <typename FT, int VEC, size_t N, typename F>
+inline void for_each_range(const void *const (&cols)[N], int64_t n, F &&f) {
+    for_each_range<FT, VEC>(cols, (int)N, n, f);
+}
 
 // --- vector column access --------------------------------------------------------------------
 template <typename FT, int VEC> struct VecT;

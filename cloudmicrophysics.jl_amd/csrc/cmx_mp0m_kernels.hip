@@ -47,11 +47,8 @@ static int32_t mp0m_entry(const PR *p, int64_t n, const FT *q_lcl, const FT *q_i
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = Math<FT>::VEC;
     const void *ptrs[] = {q_lcl, q_icl, q_vap_sat, dq_tot_dt, ddq_dq_tot};
-    bool vec_ok = true;
-    for (const void *q : ptrs) vec_ok = vec_ok && (!q || aligned16(q));
-    auto launch = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         const Mp0mIO<FT> io{q_lcl + lo, q_icl + lo, q_vap_sat ? q_vap_sat + lo : nullptr, dq_tot_dt + lo, ddq_dq_tot ? ddq_dq_tot + lo : nullptr};
         const int64_t nvec = count / V;
         const dim3 grid((unsigned)((nvec + kBlock - 1) / kBlock));
@@ -59,10 +56,7 @@ static int32_t mp0m_entry(const PR *p, int64_t n, const FT *q_lcl, const FT *q_i
         if (q_vap_sat) { if (ddq_dq_tot) CMX_LAUNCH(true, true); else CMX_LAUNCH(true, false); }
         else           { if (ddq_dq_tot) CMX_LAUNCH(false, true); else CMX_LAUNCH(false, false); }
 #undef CMX_LAUNCH
-    };
-    const int64_t body = vec_ok ? (n / VEC) * VEC : 0;
-    launch(std::integral_constant<int, VEC>{}, 0, body);
-    launch(std::integral_constant<int, 1>{}, body, n - body);
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

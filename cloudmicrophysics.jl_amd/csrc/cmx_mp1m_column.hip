@@ -238,20 +238,12 @@ static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, co
     const bool def = flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(k.c);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;     // Float64: one point per lane, as in the pointwise kernel
-    // alignment dispatch as in cmx_sb2006_column.hip: scalar head up to the common 16-byte boundary, vector body, scalar tail; the halo
-    // point of each range is read from the full columns, so the three launches compose exactly
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(ptrs[0]) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (const void *p : ptrs) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 15u) == mis0);
-    if (same_mis && VEC > 1) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_column_1m<FT, 1>(def, lin, general, a, io, 0, head, s);
-        launch_column_1m<FT, VEC>(def, lin, general, a, io, head, body / VEC, s);
-        launch_column_1m<FT, 1>(def, lin, general, a, io, head + body, n - head - body, s);
-    } else {
-        launch_column_1m<FT, 1>(def, lin, general, a, io, 0, n, s);
-    }
+    // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches
+    // compose exactly
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+        constexpr int V = decltype(vec_tag)::value;
+        launch_column_1m<FT, V>(def, lin, general, a, io, lo, count / V, s);
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

@@ -200,12 +200,8 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = (sizeof(FT) == 8 && CMX_F64_ONE_POINT_PER_LANE) ? 1 : Math<FT>::VEC;
     const void *ptrs[] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dq_lcl, dq_icl, dq_rai, dq_sno};
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(rho) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (const void *p : ptrs) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 15u) == mis0);
-    auto launch_range = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         Mp1mIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo};
         Mp1mOut<FT> out{dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo};
         const int64_t nv = count / V;
@@ -214,16 +210,7 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
             CMX_LAUNCH_FRONT((mp1m_tendencies_kernel<FT, V, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlock1m<FT>), 0, s, c, in, out, nv);
         else
             CMX_LAUNCH_FRONT((mp1m_tendencies_kernel<FT, V>), grid, dim3(kBlock1m<FT>), 0, s, c, in, out, nv);
-    };
-    if (same_mis) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_range(std::integral_constant<int, 1>{}, 0, head);
-        launch_range(std::integral_constant<int, VEC>{}, head, body);
-        launch_range(std::integral_constant<int, 1>{}, head + body, n - head - body);
-    } else {
-        launch_range(std::integral_constant<int, 1>{}, 0, n);
-    }
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }
@@ -281,35 +268,25 @@ static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
     if (!rho || !T || !q_tot || !q_lcl || !q_icl || !q_rai || !q_sno || !dq_lcl || !dq_icl || !dq_rai || !dq_sno) return CMX_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool def = flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(k.c);
-    auto launch_points = [&](int64_t lo, int64_t count) {       // one point per lane
-        if (count <= 0) return;
+    // Float32: pairs of points in packed arithmetic (8-byte body), the rest one point per lane — the same per-point operations, so the
+    // result does not depend on the alignment split (cmx_split.hpp)
+    constexpr int VEC = (sizeof(FT) == 4 && CMX_1M_LIN_PACKED) ? 2 : 1;
+    const void *ptrs[] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dq_lcl, dq_icl, dq_rai, dq_sno};
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+        constexpr int V = decltype(vec_tag)::value;
         Mp1mLinIO<FT> io{{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo}, {dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo}};
-        const dim3 grid((unsigned)((count + kBlockLin - 1) / kBlockLin));
-        if (def) CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, count);
-        else CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT>), grid, dim3(kBlockLin), 0, s, k, io, count);
-    };
-    if constexpr (sizeof(FT) == 4 && CMX_1M_LIN_PACKED) {
-        // Float32: pairs of points in packed arithmetic wherever all eleven columns share their offset modulo 8 bytes: an odd first point (and an
-        // odd last one) goes through the one-point kernel — the same per-point operations, so the result does not depend on the split
-        const void *ptrs[] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dq_lcl, dq_icl, dq_rai, dq_sno};
-        const uintptr_t mis0 = reinterpret_cast<uintptr_t>(rho) & 7u;
-        bool same_mis = (mis0 % sizeof(FT)) == 0;
-        for (const void *p : ptrs) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 7u) == mis0);
-        if (same_mis && n >= 2) {
-            const int64_t head = mis0 ? 1 : 0, npair = (n - head) / 2;
-            launch_points(0, head);
-            if (npair > 0) {
-                const int64_t lo = head;
-                Mp1mLinIO<float> io{{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo}, {dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo}};
-                const dim3 grid((unsigned)((npair + kBlockLin - 1) / kBlockLin));
-                if (def) CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, npair);
-                else CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<kRuntimeFlags>), grid, dim3(kBlockLin), 0, s, k, io, npair);
+        const int64_t nv = count / V;
+        const dim3 grid((unsigned)((nv + kBlockLin - 1) / kBlockLin));
+        if constexpr (V == 2) {
+            if constexpr (sizeof(FT) == 4) {      // always true here (VEC above); discards the Float32-only kernel from the Float64 entry
+                if (def) CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, nv);
+                else CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<kRuntimeFlags>), grid, dim3(kBlockLin), 0, s, k, io, nv);
             }
-            launch_points(head + 2 * npair, n - head - 2 * npair);
-        } else
-            launch_points(0, n);
-    } else
-        launch_points(0, n);
+        } else {
+            if (def) CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, nv);
+            else CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT>), grid, dim3(kBlockLin), 0, s, k, io, nv);
+        }
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

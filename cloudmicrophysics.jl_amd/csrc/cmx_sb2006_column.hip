@@ -324,22 +324,14 @@ static int32_t column_entry(const WR *wr, const TH *tps, const VL *vel, const ST
     const bool limited = flags & CMX_SB2006_LIMITED;
     const int velk = sbv ? VEL_SB : chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1) or the general instantiation (cmx_math.hpp ChenGamma)
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;     // Float64: one point per lane, as in the pointwise kernel
-    // alignment dispatch as in cmx_sb2006_warm_rain_tendencies_*: a scalar head up to the common 16-byte boundary, the vector body,
-    // a scalar tail; the halo point of each range is read from the full columns, so the three launches compose exactly
+    // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches
+    // compose exactly
     const void *ptrs[] = {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dq_lcl, dn_lcl, dq_rai, dn_rai};
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(rho) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (const void *p : ptrs) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 15u) == mis0);
     const bool cloud = cloud_vel != nullptr;
-    if (same_mis && VEC > 1) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_column<FT, 1>(limited, velk, cloud, intpow, c, cv, io, 0, head, s);
-        launch_column<FT, VEC>(limited, velk, cloud, intpow, c, cv, io, head, body / VEC, s);
-        launch_column<FT, 1>(limited, velk, cloud, intpow, c, cv, io, head + body, n - head - body, s);
-    } else {
-        launch_column<FT, 1>(limited, velk, cloud, intpow, c, cv, io, 0, n, s);
-    }
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+        constexpr int V = decltype(vec_tag)::value;
+        launch_column<FT, V>(limited, velk, cloud, intpow, c, cv, io, lo, count / V, s);
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

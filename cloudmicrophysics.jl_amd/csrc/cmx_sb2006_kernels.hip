@@ -77,33 +77,15 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
     // Float64: one point per lane (8-byte loads).  The kernel is VALU-bound there and the two-points-per-lane variant spends 14 % of
     // its instructions on SGPR spill traffic (60 Float64 constants = 120 SGPRs): 1307 vs 1048 VALU instructions per point.
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;
-    // Alignment dispatch.  The 16-byte body needs every column at the same offset modulo 16 B (true for
-    // any common slice [lo:hi] of aligned columns): `head` points are peeled so the body starts aligned,
-    // the body runs VEC points per lane, the ragged tail one point per lane.  Columns with mixed
-    // misalignment take the one-point-per-lane kernel throughout.  All three compute the identical
-    // instruction sequence per point (-ffp-contract=off), so results do not depend on alignment.
+    // scalar head, vector body, scalar tail: the alignment split of cmx_split.hpp
     const void *ptrs[] = {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dq_lcl, dn_lcl, dq_rai, dn_rai, vt_n, vt_m};
-    const uintptr_t mis0 = reinterpret_cast<uintptr_t>(rho) & 15u;
-    bool same_mis = (mis0 % sizeof(FT)) == 0;
-    for (const void *p : ptrs)
-        if (p) same_mis = same_mis && ((reinterpret_cast<uintptr_t>(p) & 15u) == mis0);
-    auto launch_range = [&](auto vec_tag, int64_t lo, int64_t count) {
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        if (count <= 0) return;
         SbIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, n_lcl + lo, q_rai + lo, n_rai + lo};
         SbOut<FT> out{dq_lcl + lo, dn_lcl + lo, dq_rai + lo, dn_rai + lo, vt_n ? vt_n + lo : nullptr,
                       vt_m ? vt_m + lo : nullptr};
         launch_tendencies<FT, V>(limited, velk, intpow, c, in, out, count / V, s);
-    };
-    if (same_mis) {
-        const int64_t head = std::min<int64_t>(n, mis0 ? (int64_t)((16 - mis0) / sizeof(FT)) : 0);
-        const int64_t body = ((n - head) / VEC) * VEC;
-        launch_range(std::integral_constant<int, 1>{}, 0, head);
-        launch_range(std::integral_constant<int, VEC>{}, head, body);
-        launch_range(std::integral_constant<int, 1>{}, head + body, n - head - body);
-    } else {
-        launch_range(std::integral_constant<int, 1>{}, 0, n);
-    }
+    });
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

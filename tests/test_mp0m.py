@@ -80,7 +80,8 @@ def test_device_is_bit_identical_to_the_oracle(oracle, sfx, n):
         der = cmx.d_remove_precipitation_d_q_tot(mp.precip, d(ql), d(qi), satd)
         assert np.array_equal(out.cpu().numpy(), ref) and np.array_equal(rp.cpu().numpy(), ref)
         assert np.array_equal(der.cpu().numpy(), dref)
-        # misaligned slices take the one-point-per-lane path with the same bits
+        # slices one element in (inputs shifted, output aligned: offsets differ, one scalar range) give the same bits;
+        # common shifts (scalar head + vector body + scalar tail): test_alignment_split_gpu.py
         if n > 8:
             o2 = cmx.remove_precipitation(mp.precip, d(ql)[1:], d(qi)[1:], None if satd is None else satd[1:])
             assert np.array_equal(o2.cpu().numpy(), ref[1:])
