@@ -55,6 +55,12 @@ CMX_1M_DEFAULT_OPTIONS = (CMX_1M_CLOUD_LIQUID_FORMATION | CMX_1M_CLOUD_ICE_FORMA
                           CMX_1M_RAIN_ACNV_KESSLER | CMX_1M_SNOW_ACNV_NO_SUPERSAT | CMX_1M_RAIN_EVAPORATION |
                           CMX_1M_SNOW_DEP_AND_SUBL | CMX_1M_SNOW_MELT | CMX_1M_ACCR_LCL_RAI | CMX_1M_ACCR_LCL_SNO |
                           CMX_1M_ACCR_ICL_RAI | CMX_1M_ACCR_ICL_SNO | CMX_1M_ACCR_RAI_SNO)
+# snow shape of the Chen-2022 snow fall speed: cmx_snow_terminal_velocity_* `snow_shape`; CMX_1M_SED_SNOW_* — column step only
+CMX_SNOW_SHAPE_ASPR = 0
+CMX_SNOW_SHAPE_OBLATE = 1
+CMX_SNOW_SHAPE_PROLATE = 2
+CMX_1M_SED_SNOW_OBLATE = 1 << 17
+CMX_1M_SED_SNOW_PROLATE = 1 << 18
 
 # cmx_mp1m_source_column
 MP1M_SOURCE_COLUMNS = (

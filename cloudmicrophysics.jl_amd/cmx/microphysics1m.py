@@ -7,6 +7,7 @@ Reference broadcasts being replaced:
     BMT.bulk_microphysics_tendencies.(Ref(BMT.Instantaneous()), Ref(BMT.Microphysics1Moment()), Ref(mp), Ref(tps),
                                       ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno)        # BMT:505-514
     @. w = CM1.terminal_velocity(rain, vel, ρ, q)                                      # test/gpu_clima_core_test.jl:39-42
+    @. w = CM1.terminal_velocity(snow, Ch2022.large_ice, ρ, q, CM1.Oblate())          # src/Microphysics1M.jl:299-324
 """
 from __future__ import annotations
 
@@ -18,6 +19,32 @@ import torch
 from . import _abi, _lib
 from .bulk_tendencies import _check_cols, _fam_of, _fields_call, _ptr
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
+
+
+class AbstractSnowShape:
+    """CM1.AbstractSnowShape — snow shape of the Chen-2022 snow fall speed (src/Microphysics1M.jl:66-68)."""
+    _shape = _abi.CMX_SNOW_SHAPE_ASPR
+    _column_bit = 0
+
+
+class Oblate(AbstractSnowShape):
+    """CM1.Oblate — oblate snow: ϕ(r) = 3√π m(r) / (4 ρᵢ a(r)^{3/2}), κ = 1/3 (CM1.aspect_ratio_coeffs, CM1:155-181)."""
+    _shape = _abi.CMX_SNOW_SHAPE_OBLATE
+    _column_bit = _abi.CMX_1M_SED_SNOW_OBLATE
+
+
+class Prolate(AbstractSnowShape):
+    """CM1.Prolate — prolate snow: ϕ(r) = 16 ρᵢ² a(r)³ / (9π m(r)²), κ = −1/6 (CM1:183-195)."""
+    _shape = _abi.CMX_SNOW_SHAPE_PROLATE
+    _column_bit = _abi.CMX_1M_SED_SNOW_PROLATE
+
+
+def _shape_of(snow_shape):
+    if snow_shape is None:
+        return None
+    if not isinstance(snow_shape, (Oblate, Prolate)):
+        raise TypeError(f"snow_shape must be None, Oblate() or Prolate(), got {type(snow_shape).__name__}")
+    return snow_shape
 
 
 class Microphysics1Moment:
@@ -181,19 +208,45 @@ def sedimentation_velocities(mp, stokes, chen_rain, chen_ice, rho, q_lcl=None, q
     return SedimentationVelocities(*outs)
 
 
+def snow_terminal_velocity(mp, chen_ice, rho, q_sno, snow_shape=None, *, stream=None):
+    """The Chen-2022 snow fall speed over columns (`cmx_snow_terminal_velocity_*`): `CM1.terminal_velocity(snow, Ch2022.large_ice, ρ, q,
+    snow_shape)` with `snow_shape = Oblate()` or `Prolate()` (CM1:299-324), or with `snow_shape=None` the fixed aspect ratio of the 4-argument
+    method (CM1:272-297; bit-identical to `sedimentation_velocities(…).w_sno` wherever no input is NaN).  `chen_ice` = the
+    Chen2022VelTypeIce struct of the state's float type.  Returns one new tensor."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    shape = _shape_of(snow_shape)
+    ref = _check_cols([rho, q_sno], ["rho", "q_sno"])
+    fam = _fam_of(ref)
+    if fam is not mp.fam:
+        raise TypeError("parameter float type does not match the state columns")
+    if not isinstance(chen_ice, fam.chen2022_ice_vel):
+        raise TypeError(f"chen_ice: expected the {fam.chen2022_ice_vel.__name__} struct of the state's float type, got {type(chen_ice).__name__}")
+    w = torch.empty_like(ref)
+    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
+    fn = getattr(_lib.lib(), f"cmx_snow_terminal_velocity_{fam.sfx}")
+    with torch.cuda.device(ref.device):
+        st = fn(C.byref(mp.c), C.byref(chen_ice), shape._shape if shape is not None else _abi.CMX_SNOW_SHAPE_ASPR, ref.numel(), _ptr(rho),
+                _ptr(q_sno), _ptr(w), C.c_void_p(s.cuda_stream))
+    _lib.check(fn.__name__, st)
+    return w
+
+
 ColumnStep1M = namedtuple("ColumnStep1M", ["dq_lcl_dt", "dq_icl_dt", "dq_rai_dt", "dq_sno_dt", "precip_rai", "precip_sno"])
 
 
 def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno,
-                                       dt=None, nsub=1, *, q_min=None, precip=True, stream=None) -> ColumnStep1M:
+                                       dt=None, nsub=1, *, q_min=None, precip=True, snow_shape=None, stream=None) -> ColumnStep1M:
     """The operational 1-moment column step in one pass (`cmx_mp1m_column_tendencies_sedimentation_*`): the 1-moment tendencies
     (Instantaneous, or LinearizedAverage with `dt` [, `nsub`]) + the four sedimentation velocities (`sedimentation_velocities`) + the host
     model's first-order upwind flux divergence of q_lcl, q_icl, q_rai, q_sno.  State tensors of shape (n_col, n_lev), level 0 lowest,
-    contiguous; `inv_dz` = n_lev values 1/Δz.  Returns the four total tendencies and (precip=True) the surface rain / snow fluxes."""
+    contiguous; `inv_dz` = n_lev values 1/Δz.  Returns the four total tendencies and (precip=True) the surface rain / snow fluxes.
+    `snow_shape` = Oblate() or Prolate(): the snow fall speed of `snow_terminal_velocity` with that shape (the CMX_1M_SED_SNOW_* bit)."""
     if not isinstance(scheme, Microphysics1Moment) or not isinstance(mode, (Instantaneous, LinearizedAverage)):
         raise TypeError("mode must be Instantaneous() or LinearizedAverage() and scheme Microphysics1Moment()")
     cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
     names = ("rho", "T", "q_tot", "q_lcl", "q_icl", "q_rai", "q_sno")
+    shape = _shape_of(snow_shape)
     if rho.dim() != 2:
         raise ValueError("state tensors must have shape (n_col, n_lev)")
     # validate the 2-D tensors THEMSELVES (ADVICE r03): the kernel reads and writes flat row-major (n_col, n_lev) storage, so a transposed
@@ -227,7 +280,8 @@ def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain,
     s = stream if stream is not None else torch.cuda.current_stream(ref.device)
     fn = getattr(_lib.lib(), f"cmx_mp1m_column_tendencies_sedimentation_{fam.sfx}")
     with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain), C.byref(chen_ice), mp.flags, q_min if lin else 0.0,
+        st = fn(C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain), C.byref(chen_ice), mp.flags | (shape._column_bit if shape else 0),
+                q_min if lin else 0.0,
                 dt if lin else 0.0, int(nsub) if lin else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]),
                 C.c_void_p(s.cuda_stream))
     _lib.check(fn.__name__, st)

@@ -7,6 +7,7 @@
 //         w_icl = CMNonEq.terminal_velocity(cloud_ice, Chen2022VelTypeSmallIce, ρ, q_icl)      :267-281
 //         w_rai = CM1.terminal_velocity(rain, Chen2022VelTypeRain, ρ, q_rai)                   src/Microphysics1M.jl:251-270
 //         w_sno = CM1.terminal_velocity(snow, Chen2022VelTypeLargeIce, ρ, q_sno)               :272-297
+//               … or, with a CMX_1M_SED_SNOW_* bit, (…, q_sno, CM1.Oblate() | CM1.Prolate())   :155-195, 299-324
 //   (3) the host model's first-order upwind ("right-biased") flux divergence of the four falling species — NOT part of the reference
 //       package (ClimaAtmos precipitation advection), the same operator as in cmx_sb2006_column.hip:
 //           F_k = ρ_k χ_k w_k,   ∂χ_k/∂t |sed = (F_{k+1} − F_k)/(ρ_k Δz_k),   F_{n_lev} = 0,   level 0 = lowest level.
@@ -43,151 +44,25 @@ template <typename FT> struct Mp1mColIO {
 // float types read them through the kernel-argument pointer (front_consts<FT, true>): as plain by-value arguments they overflow the
 // SGPR file and were parked in VGPR lanes — 34 v_readlane / v_writelane per Float32 point and 143 VGPRs in the first version.
 template <typename FT> struct Mp1mColKernArgs { Mp1mLinKernArgs<FT> k; Vel1mConsts<FT> vc; };
+// … of the step with a snow shape (CMX_1M_SED_SNOW_*): the fall-speed constants with the shaped snow terms (cmx_mp1m_vel.hpp Vel1mShapeConsts)
+template <typename FT> struct Mp1mColShapeKernArgs { Mp1mLinKernArgs<FT> k; Vel1mShapeConsts<FT> vc; };
 
 #ifndef CMX_1M_COLUMN_PACKED
 #define CMX_1M_COLUMN_PACKED 1      // A/B switch: 0 = one point at a time (rounds 3–4)
 #endif
 template <typename FT, uint32_t FLAGS, bool LIN, bool GENERAL_GAMMA, int VEC, int BS>
 __global__ __launch_bounds__(BS) void mp1m_column_kernel(const Mp1mColKernArgs<FT> a0, const Mp1mColIO<FT> io, const int64_t first, const int64_t nvec) {
-    using M = Math<FT>;
-    const auto &a = front_consts<FT, true>(a0);
-    __shared__ __align__(16) FT halo[BS + 1][4];   // fluxes of every lane's FIRST point, + slot BS for the point that follows the tile
-    // tiles overlap by one lane, as in sb2006_column_kernel (cmx_sb2006_column.hip): lane BS−1 evaluates the next tile's first vector and only
-    // supplies the flux its first point sends down; the flux-only evaluation of that point runs in the last workgroup of a launch only
-    const int64_t tile0 = (int64_t)blockIdx.x * (BS - 1);
-    const int64_t v = tile0 + threadIdx.x;
-    const bool active = v < nvec;
-    const int64_t nvalid = nvec - tile0 < BS ? nvec - tile0 : BS;       // active lanes of this tile (≥ 1)
-    const bool owner = threadIdx.x < BS - 1;
-    const int64_t i0 = first + v * VEC;                                 // flat index of the lane's first point
-
-    FT x[7][VEC];
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) load_col<FT, VEC, true>(io.in[j] + first, v, x[j]);
-    }
-    Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
-    if (nvalid < BS && threadIdx.x == BS - 1) {   // last workgroup of the launch: the point after its last vector, from the raw columns
-        const int64_t e = first + (tile0 + nvalid) * VEC;
-        SedFlux4<FT> f{{FT(0), FT(0), FT(0), FT(0)}};
-        if (e < io.n) f = mp1m_sed_fluxes<FT, GENERAL_GAMMA>(a.vc, io.in[0][e], io.in[3][e], io.in[4][e], io.in[5][e], io.in[6][e]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) halo[BS][s] = f.f[s];
-    }
-    // per point: A = tendency − (own flux)·g (final but for the inflow), g = 1/(ρ Δz)
-    FT A[VEC][4], g[VEC];
-    SedFlux4<FT> F[VEC];
-    int64_t col = 0;
-    int32_t lev = 0;
-    if (active) {
-        if (io.n < ((int64_t)1 << 32)) {                  // i0 = col·n_lev + k; wave-uniform: one v_mul_hi_u32 (cmx_launch.hpp fastdiv)
-            const uint32_t c32 = fastdiv((uint32_t)i0, io.lev_div);
-            col = c32;
-            lev = (int32_t)((uint32_t)i0 - c32 * (uint32_t)io.n_lev);
-        } else {                                          // one double multiply + fix-up per lane; exact below 2^53
-            col = (int64_t)((double)i0 * io.inv_n_lev);
-            int64_t k64 = i0 - col * io.n_lev;
-            if (k64 < 0) { --col; k64 += io.n_lev; }
-            if (k64 >= io.n_lev) { ++col; k64 -= io.n_lev; }
-            lev = (int32_t)k64;
-        }
-        int32_t lv = lev;
-        const auto &k = a.k;
-        // two passes over the lane's points — tendencies, then fluxes — so that only one pass's constants are live at a time
-        FT t[VEC][4];
-        // one value of the value type VT at a time: a point, or — Float32 with four points per lane — a PAIR of points in packed arithmetic (cmx_math.hpp f32x2;
-        // not the run-time-Γ instantiation: an OCML call per lane, nothing to pack)
-        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_1M_COLUMN_PACKED && !GENERAL_GAMMA) ? 2 : 1;
-        using VT = std::conditional_t<L == 2, f32x2, FT>;
-        using MV = Math<VT>;
-        if constexpr (L == 1) {      // (kept verbatim from rounds 3–4: routing the one-point case through the generic form below doubled its registers)
-#pragma unroll
-            for (int p = 0; p < VEC; ++p) {
-                if constexpr (LIN)
-                    mp1m_linearized_point<FT, FLAGS>(k.c, [&](FT dep) -> decltype(auto) { return (consts_after(k, dep).a); }, a0.k.a.nsub, x[0][p], x[1][p], x[2][p],
-                                                     x[3][p], x[4][p], x[5][p], x[6][p], t[p][0], t[p][1], t[p][2], t[p][3]);
-                else
-                    mp1m_tendencies_point<FT, FLAGS>(k.c, x[0][p], x[1][p], x[2][p], x[3][p], x[4][p], x[5][p], x[6][p], t[p][0], t[p][1], t[p][2], t[p][3]);
-            }
-            const auto &vc = consts_after(a, t[VEC - 1][3]).vc;
-#pragma unroll
-            for (int p = 0; p < VEC; ++p) {
-                F[p] = mp1m_sed_fluxes<FT, GENERAL_GAMMA>(vc, x[0][p], x[3][p], x[4][p], x[5][p], x[6][p]);
-                g[p] = io.inv_dz[lv] * M::rcp(max0(x[0][p]));                          // 1/(ρ_k Δz_k)
-                if (++lv == io.n_lev) lv = 0;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) A[p][s] = M::fma(-F[p].f[s], g[p], t[p][s]);
-            }
-        } else {
-            auto val = [&x](int j, int p) -> VT {
-                if constexpr (L == 2) return VT{x[j][p], x[j][p + 1]};
-                else return x[j][p];
-            };
-#pragma unroll
-            for (int p = 0; p < VEC; p += L) {
-                VT tt[4];
-                if constexpr (LIN)
-                    mp1m_linearized_point<VT, FLAGS>(k.c, [&](VT dep) -> decltype(auto) { return (consts_after(k, dep).a); }, a0.k.a.nsub, val(0, p), val(1, p), val(2, p),
-                                                     val(3, p), val(4, p), val(5, p), val(6, p), tt[0], tt[1], tt[2], tt[3]);
-                else
-                    mp1m_tendencies_point<VT, FLAGS>(k.c, val(0, p), val(1, p), val(2, p), val(3, p), val(4, p), val(5, p), val(6, p), tt[0], tt[1], tt[2], tt[3]);
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if constexpr (L == 2) { t[p][s] = tt[s].x; t[p + 1][s] = tt[s].y; }
-                    else t[p][s] = tt[s];
-                }
-            }
-            const auto &vc = consts_after(a, t[VEC - 1][3]).vc;
-#pragma unroll
-            for (int p = 0; p < VEC; p += L) {
-                const SedFlux4<VT> Fp = mp1m_sed_fluxes<VT, GENERAL_GAMMA>(vc, val(0, p), val(3, p), val(4, p), val(5, p), val(6, p));
-                VT gp;                                                                 // 1/(ρ_k Δz_k)
-                if constexpr (L == 2) {
-                    const FT dz0 = io.inv_dz[lv];
-                    if (++lv == io.n_lev) lv = 0;
-                    const FT dz1 = io.inv_dz[lv];
-                    if (++lv == io.n_lev) lv = 0;
-                    gp = VT{dz0, dz1} * MV::rcp(max0(val(0, p)));
-                } else {
-                    gp = io.inv_dz[lv] * MV::rcp(max0(val(0, p)));
-                    if (++lv == io.n_lev) lv = 0;
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    VT tt;
-                    if constexpr (L == 2) tt = VT{t[p][s], t[p + 1][s]};
-                    else tt = t[p][s];
-                    const VT As = MV::fma(-Fp.f[s], gp, tt);
-                    if constexpr (L == 2) { A[p][s] = As.x; A[p + 1][s] = As.y; F[p].f[s] = Fp.f[s].x; F[p + 1].f[s] = Fp.f[s].y; }
-                    else { A[p][s] = As; F[p].f[s] = Fp.f[s]; }
-                }
-                if constexpr (L == 2) { g[p] = gp.x; g[p + 1] = gp.y; }
-                else g[p] = gp;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) halo[threadIdx.x][s] = F[0].f[s];
-    }
-    __syncthreads();
-    if (!active || !owner) return;
-    const int up = (threadIdx.x + 1 < nvalid) ? threadIdx.x + 1 : BS;
-    FT o[4][VEC];
-#pragma unroll
-    for (int p = 0; p < VEC; ++p) {
-        const bool top = lev == io.n_lev - 1;       // nothing enters through the model top
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const FT upf = (p + 1 < VEC) ? F[p + 1 < VEC ? p + 1 : 0].f[s] : halo[up][s];
-            o[s][p] = M::fma(top ? FT(0) : upf, g[p], A[p][s]);      // a select, not a branch per species
-        }
-        if (lev == 0) {                             // surface precipitation fluxes of the column
-            if (io.precip_rai) io.precip_rai[col] = F[p].f[2];
-            if (io.precip_sno) io.precip_sno[col] = F[p].f[3];
-        }
-        if (++lev == io.n_lev) { lev = 0; ++col; }
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) store_col<FT, VEC, true>(io.out[s] + first, v, o[s]);
+    constexpr bool SHAPED = false;
+#include "cmx_mp1m_column_body.inc"
+}
+// with a snow shape (CMX_1M_SED_SNOW_*): the run-time-options instantiation only — the shape would double the kernels of the default-options
+// one, a speed-up of the unshaped step whose integer exponents are not bit-identical to the run-time form
+template <typename FT, bool LIN, bool GENERAL_GAMMA, int VEC, int BS>
+__global__ __launch_bounds__(BS) void mp1m_column_shaped_kernel(const Mp1mColShapeKernArgs<FT> a0, const Mp1mColIO<FT> io, const int64_t first,
+                                                                const int64_t nvec) {
+    constexpr uint32_t FLAGS = kRuntimeFlags;
+    constexpr bool SHAPED = true;
+#include "cmx_mp1m_column_body.inc"
 }
 
 // lanes per workgroup: 256 (same-box A/B, round 4, ms per 1e8 points: Float32 64 lanes 1.156, 128 lanes 1.140, 256 lanes 1.120; Float64 4.74 / 4.63 / 4.55;
@@ -210,12 +85,27 @@ static void launch_column_1m(bool def, bool lin, bool general, const Mp1mColKern
 #undef CMX_G
 #undef CMX_L
 }
+template <typename FT, int VEC>
+static void launch_column_1m_shaped(bool lin, bool general, const Mp1mColShapeKernArgs<FT> &a, const Mp1mColIO<FT> &io, int64_t first, int64_t nvec,
+                                    hipStream_t s) {
+    if (nvec <= 0) return;
+    const dim3 grid((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))), block(kColBS1m);      // tiles overlap by one lane
+#define CMX_L(LN, GG) CMX_LAUNCH_FRONT((mp1m_column_shaped_kernel<FT, LN, GG, VEC, kColBS1m>), grid, block, 0, s, a, io, first, nvec)
+    if (lin) { if (general) CMX_L(true, true); else CMX_L(true, false); }
+    else { if (general) CMX_L(false, true); else CMX_L(false, false); }
+#undef CMX_L
+}
 
 template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
 static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, FT q_min, FT dt,
                                int32_t nsub, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, FT *const *out, FT *precip_rai,
                                FT *precip_sno, void *stream) {
     if (!mp || !tps || !stokes || !chen_rain || !chen_ice || n_col < 0 || n_lev < 1 || nsub < 0) return CMX_ERR_BAD_ARG;
+    // the snow-shape bits belong to this entry alone: stripped before the option checks and the folding
+    const uint32_t shape_bits = flags & (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE);
+    if (shape_bits == (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE)) return CMX_ERR_BAD_ARG;
+    const uint32_t snow_shape = shape_bits == CMX_1M_SED_SNOW_OBLATE ? CMX_SNOW_SHAPE_OBLATE : shape_bits ? CMX_SNOW_SHAPE_PROLATE : CMX_SNOW_SHAPE_ASPR;
+    flags &= ~shape_bits;
     if (const int32_t st = check_flags_1m(flags)) return st;
     const bool lin = nsub > 0;
     if (lin && (!(dt > FT(0)) || !(q_min >= FT(0)))) return CMX_ERR_BAD_ARG;
@@ -240,10 +130,20 @@ static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, co
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;     // Float64: one point per lane, as in the pointwise kernel
     // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches
     // compose exactly
-    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
-        constexpr int V = decltype(vec_tag)::value;
-        launch_column_1m<FT, V>(def, lin, general, a, io, lo, count / V, s);
-    });
+    if (snow_shape != CMX_SNOW_SHAPE_ASPR) {
+        Mp1mColShapeKernArgs<FT> as{};
+        as.k = k;
+        as.vc = make_snow_shape_consts<FT>(*mp, chen_rain, stokes, *chen_ice, snow_shape);
+        for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+            constexpr int V = decltype(vec_tag)::value;
+            launch_column_1m_shaped<FT, V>(lin, general, as, io, lo, count / V, s);
+        });
+    } else {
+        for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+            constexpr int V = decltype(vec_tag)::value;
+            launch_column_1m<FT, V>(def, lin, general, a, io, lo, count / V, s);
+        });
+    }
     CMX_HIP_TRY(hipGetLastError());
     return CMX_OK;
 }

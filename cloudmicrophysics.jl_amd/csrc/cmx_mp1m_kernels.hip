@@ -186,6 +186,23 @@ __global__ __launch_bounds__(kBlock) void mp1m_velocity_kernel(const Vel1mConsts
     if (io.w_icl) io.w_icl[i] = out(vel_icl_chen<FT>(c, rho, rp, io.q_icl[i]));
 }
 
+// ---- the snow fall speed with a snow shape over (ρ, q) columns — CM1:272-324 (cmx_mp1m_vel.hpp vel_snow_shaped) ---------------
+// 2 columns in, 1 out = 12 B/point (f32): VEC points per lane with 16-byte accesses in the body of the alignment split (cmx_split.hpp), one
+// point per lane in its head and tail — the same instructions per point, so the result does not depend on the split
+template <typename FT, int VEC>
+__global__ __launch_bounds__(kBlock) void mp1m_snow_velocity_kernel(const Vel1mShapeConsts<FT> c, const FT *__restrict__ rho, const FT *__restrict__ q,
+                                                                    FT *__restrict__ w, const int64_t nvec) {
+    Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS (no-op for Float32)
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nvec) return;
+    FT r[VEC], x[VEC], y[VEC];
+    load_col<FT, VEC>(rho, i, r);
+    load_col<FT, VEC>(q, i, x);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) y[k] = vel_snow_shaped<FT>(c, r[k], x[k]);
+    store_col<FT, VEC>(w, i, y);
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------
 template <typename FT, typename MP, typename TH>
 static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T,
@@ -364,9 +381,40 @@ static int32_t sedimentation_entry(const MP *mp, const ST *stokes, const CH *che
     return CMX_OK;
 }
 
+// CM1.terminal_velocity(snow, Chen2022VelTypeLargeIce, ρ, q[, Oblate() | Prolate()]) over columns (include/cmx.h cmx_snow_terminal_velocity_*)
+template <typename FT, typename CR, typename MP, typename CI>
+static int32_t snow_velocity_entry(const MP *mp, const CI *chen_ice, uint32_t snow_shape, int64_t n, const FT *rho, const FT *q_sno, FT *w_sno,
+                                   void *stream) {
+    if (!mp || !chen_ice || snow_shape > CMX_SNOW_SHAPE_PROLATE || n < 0) return CMX_ERR_BAD_ARG;
+    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    if (n == 0) return CMX_OK;
+    if (!rho || !q_sno || !w_sno) return CMX_ERR_BAD_ARG;
+    const Vel1mShapeConsts<FT> c = make_snow_shape_consts<FT>(*mp, static_cast<const CR *>(nullptr), static_cast<const cmx_stokes_vel_f64 *>(nullptr), *chen_ice,
+                                                              snow_shape);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const void *ptrs[] = {rho, q_sno, w_sno};
+    for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
+        constexpr int V = decltype(vec_tag)::value;
+        const int64_t nv = count / V;
+        CMX_LAUNCH_FRONT((mp1m_snow_velocity_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, rho + lo, q_sno + lo,
+                         w_sno + lo, nv);
+    });
+    CMX_HIP_TRY(hipGetLastError());
+    return CMX_OK;
+}
+
 }  // namespace cmx
 
 extern "C" {
+
+int32_t cmx_snow_terminal_velocity_f32(const cmx_microphysics_1m_f32 *mp, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t snow_shape, int64_t n,
+                                       const float *rho, const float *q_sno, float *w_sno, void *stream) {
+    return cmx::snow_velocity_entry<float, cmx_chen2022_rain_vel_f32>(mp, chen_ice, snow_shape, n, rho, q_sno, w_sno, stream);
+}
+int32_t cmx_snow_terminal_velocity_f64(const cmx_microphysics_1m_f64 *mp, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t snow_shape, int64_t n,
+                                       const double *rho, const double *q_sno, double *w_sno, void *stream) {
+    return cmx::snow_velocity_entry<double, cmx_chen2022_rain_vel_f64>(mp, chen_ice, snow_shape, n, rho, q_sno, w_sno, stream);
+}
 
 int32_t cmx_sedimentation_velocities_f32(const cmx_microphysics_1m_f32 *mp, const cmx_stokes_vel_f32 *stokes,
                                          const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, int64_t n,

@@ -21,6 +21,12 @@ template <typename FT> struct Vel1mConsts {
     // ϕ^κ Γ(b+4)/3! folded into the amplitudes
     FT sn_A, sn_a1, sn_b1, sn_a2, sn_H, sn_b2, sn_c2;
 };
+// … and the snow fall speed of a given shape (CM1:299-324, vel_snow_chen<FT, true>): one constant more, the power of λ_D⁻¹ in term 2.  It follows
+// every member of Vel1mConsts at the member's own offset; a derived struct instead of a longer Vel1mConsts keeps the kernel-argument
+// segments of the kernels without a shape byte for byte (a longer struct would move the by-value arguments after it).
+template <typename FT> struct Vel1mShapeConsts : Vel1mConsts<FT> {
+    FT sn_e2;   // κα − 4 (−4 for the fixed aspect ratio)
+};
 
 // (VC below: Vel1mConsts<FT>, possibly in the constant address space — kernels whose constants overflow the SGPR file read them through the
 // kernel-argument pointer, cmx_math.hpp front_consts)
@@ -92,24 +98,41 @@ template <typename FT, typename VC> __device__ __forceinline__ FT vel_icl_chen(c
     return vel_icl_chen<FT>(c, rho, rp, q, log2_floored(rp));
 }
 // CM1.terminal_velocity(::Snow, ::Chen2022VelTypeLargeIce, ρ, q): mass-weighted (k = 3), λ_D⁻¹ = 2 λ⁻¹ — CM1:272-297
-template <typename FT, typename VC> __device__ __forceinline__ FT vel_snow_chen(const VC &c, FT rp, FT l2_li, FT q, FT l2_rho) {
+// SHAPED: … with a snow shape (CM1:299-324; VC = Vel1mShapeConsts): ϕ_av^κ = (ϕ₀ Γ)^κ 2^(−κα) (λ_D⁻¹)^(κα) replaces ϕ^κ — the amplitudes and the
+// power of term 1 are folded on the host (add_sedimentation_consts), the power of term 2 is the one extra constant sn_e2 = κα − 4
+template <typename FT, bool SHAPED = false, typename VC> __device__ __forceinline__ FT vel_snow_chen(const VC &c, FT rp, FT l2_li, FT q, FT l2_rho) {
     using M = Math<FT>;
     const FT l2_ld = l2_li + FT(1), lam = M::exp2_fin(-l2_ld);
     const FT l2_ra = c.sn_A * l2_rho;
     // aₖ e^{−4 ln λ_D⁻¹ − (bₖ+4) ln(λ_D + cₖ)}: term 1 has c = 0 → λ_D^{−b₁}·… collapses to one power
     const FT t1 = c.sn_a1 * M::exp2_fin(l2_ra + c.sn_b1 * l2_ld);
-    const FT t2 = c.sn_a2 * M::exp2_fin(l2_ra + c.sn_H * rp * FT(1.4426950408889634) - FT(4) * l2_ld - (c.sn_b2 + FT(4)) * M::log2_pn(lam + c.sn_c2));
+    FT x2 = l2_ra + c.sn_H * rp * FT(1.4426950408889634);
+    if constexpr (SHAPED) x2 = x2 + c.sn_e2 * l2_ld;      // sn_e2 = −4 gives the fixed-aspect-ratio value exactly: x − 4l = x + (−4)l in IEEE arithmetic
+    else x2 = x2 - FT(4) * l2_ld;
+    const FT t2 = c.sn_a2 * M::exp2_fin(x2 - (c.sn_b2 + FT(4)) * M::log2_pn(lam + c.sn_c2));
     return q > c.eps_1m ? FT(M::max(FT(0), t1 + t2)) : FT(0);
 }
-template <typename FT, typename VC> __device__ __forceinline__ FT vel_snow_chen(const VC &c, FT rp, FT l2_li, FT q) {
-    return vel_snow_chen<FT>(c, rp, l2_li, q, log2_floored(rp));
+template <typename FT, bool SHAPED = false, typename VC> __device__ __forceinline__ FT vel_snow_chen(const VC &c, FT rp, FT l2_li, FT q) {
+    return vel_snow_chen<FT, SHAPED>(c, rp, l2_li, q, log2_floored(rp));
+}
+// cmx_snow_terminal_velocity_* per point: the shaped fall speed on the raw (ρ, q) of the point.  ρ⁺ = max(0, ρ) as in the velocity kernel
+// (cmx_mp1m_kernels.hip), so that CMX_SNOW_SHAPE_ASPR is bit-identical to its w_sno wherever no input is NaN; a NaN in ρ or q gives NaN (include/cmx.h
+// "Conventions"), and in Float64 so does ρ ≤ 0 (bad_density), as in every Float64 1-moment entry
+template <typename FT, typename VC> __device__ __forceinline__ FT vel_snow_shaped(const VC &c, FT rho, FT q) {
+    using M = Math<FT>;
+    const FT rp = M::max(FT(0), rho);
+    const FT w = vel_snow_chen<FT, true>(c, rp, vel_l2_li_snow<FT>(c, rp, q), q);
+    typename M::Mask bad = nan_mask(rho, q);
+    if constexpr (M::IS_F64) bad = (bool)((int)bad | (int)bad_density(rho));
+    return bad ? M::nan() : w;
 }
 
 // ---- sedimentation fluxes of the fused column step (cmx_mp1m_column.hip) ------------------------------------------------------------
 template <typename FT> struct SedFlux4 { FT f[4]; };   // lcl, icl, rai, sno
 
 // F = ρ⁺ χ⁺ w(ρ⁺, χ⁺) of the four species of one raw point
-template <typename FT, bool GENERAL_GAMMA, typename VC>
+// SHAPED: the snow flux with the shaped fall speed (VC = Vel1mShapeConsts; cmx_mp1m_column_tendencies_sedimentation_* with a CMX_1M_SED_SNOW_* bit)
+template <typename FT, bool GENERAL_GAMMA, bool SHAPED = false, typename VC>
 __device__ __forceinline__ SedFlux4<FT> mp1m_sed_fluxes(const VC &vc, FT rho, FT q_lcl, FT q_icl, FT q_rai, FT q_sno) {
     using M = Math<FT>;
     const FT r_ = max0(rho), ql = max0(q_lcl), qi = max0(q_icl), qr = max0(q_rai), qs = max0(q_sno);
@@ -124,7 +147,7 @@ __device__ __forceinline__ SedFlux4<FT> mp1m_sed_fluxes(const VC &vc, FT rho, FT
     // with a 100-byte private segment that no instruction touches — tests/test_kernel_resources.py)
     F.f[2] = (r_ * qr) * vel_rain_chen<FT, GENERAL_GAMMA>(v2, r_, vel_l2_li_rain<FT>(v2, r_, qr), qr, GENERAL_GAMMA ? log2_floored(keep(r_)) : l2_rho);
     const VC &v3 = consts_after(v2, F.f[2]);
-    F.f[3] = (r_ * qs) * vel_snow_chen<FT>(v3, r_, vel_l2_li_snow<FT>(v3, r_, qs), qs, l2_rho);
+    F.f[3] = (r_ * qs) * vel_snow_chen<FT, SHAPED>(v3, r_, vel_l2_li_snow<FT>(v3, r_, qs), qs, l2_rho);
     // NaN in → NaN out per species; Float64: ρ ≤ 0 poisons the point, as in the tendencies (cmx_math.hpp bad_density)
     auto poison = [&](FT q_s, FT f) -> FT {
         typename M::Mask bad = nan_mask(rho, q_s);
@@ -158,10 +181,41 @@ static Vel1mConsts<FT> make_vel1m_consts(const MP &mp, const CH *chen, bool *che
     return c;
 }
 
+// The aspect-ratio factor of the Chen-2022 snow fall speed, as amp · (λ_D⁻¹)^ka with λ_D⁻¹ = 2 λ⁻¹ (λ⁻¹: the radius slope parameter, CM1.lambda_inverse):
+//   CMX_SNOW_SHAPE_ASPR     ϕ^κ of the fixed aspect ratio (CM1:287-295): amp = ϕ^κ, ka = 0
+//   CMX_SNOW_SHAPE_OBLATE   ϕ_av^κ, ϕ_av = ϕ₀ (λ⁻¹)^α Γ_aspect (CM1:299-324) with CM1.aspect_ratio_coeffs (CM1:155-195):
+//   CMX_SNOW_SHAPE_PROLATE    amp = (ϕ₀ Γ_aspect)^κ 2^(−κα), ka = κα
+struct SnowAspect { double amp, ka; };
+template <typename MP> static SnowAspect snow_aspect(const MP &mp, uint32_t shape) {
+    const double pi = 3.14159265358979323846;
+    const auto &m = mp.snow.mass;
+    const auto &a = mp.snow.area;
+    const double ri = (double)mp.snow.rho_i, mexp = (double)m.me + (double)m.delta_m, aexp = (double)a.ae + (double)a.delta_a;
+    const double cm = (double)m.chi_m * (double)m.m0, ca = (double)a.chi_a * (double)a.a0, d0 = 2.0 * (double)m.r0;
+    double alpha, phi0, kappa, gam;
+    if (shape == CMX_SNOW_SHAPE_OBLATE) {            // ϕ(r) = 3√π m(r) / (4 ρᵢ a(r)^{3/2})
+        alpha = mexp - 1.5 * aexp;
+        phi0 = 3.0 * std::sqrt(pi) / 4.0 / ri * cm / std::pow(ca, 1.5) / std::pow(d0, alpha);
+        kappa = 1.0 / 3.0;
+        gam = (double)mp.snow.gamma_aspect_oblate;
+    } else if (shape == CMX_SNOW_SHAPE_PROLATE) {    // ϕ(r) = 16 ρᵢ² a(r)³ / (9π m(r)²)
+        alpha = 3.0 * aexp - 2.0 * mexp;
+        phi0 = 16.0 * ri * ri / 9.0 / pi * std::pow(ca, 3.0) / (cm * cm) / std::pow(d0, alpha);
+        kappa = -1.0 / 6.0;
+        gam = (double)mp.snow.gamma_aspect_prolate;
+    } else {
+        return {std::pow((double)mp.snow.phi, (double)mp.snow.kappa), 0.0};
+    }
+    const double ka = kappa * alpha;
+    return {std::pow(phi0 * gam, kappa) * std::exp2(-ka), ka};
+}
+
 // adds the cloud-liquid (Stokes) and Chen-2022 ice constants of the four sedimentation velocities a host model precomputes
-// (ClimaAtmos set_sedimentation_precomputed_quantities; test/gpu_clima_core_test.jl:36-45, KA kernel test/gpu_tests.jl:608-630)
+// (ClimaAtmos set_sedimentation_precomputed_quantities; test/gpu_clima_core_test.jl:36-45, KA kernel test/gpu_tests.jl:608-630);
+// snow_shape (CMX_SNOW_SHAPE_*): the aspect-ratio factor folded into the snow constants (snow_aspect; vel_snow_chen<FT, true> then also
+// needs Vel1mShapeConsts::sn_e2 = ka − 4, see make_snow_shape_consts)
 template <typename FT, typename MP, typename ST, typename CI>
-static void add_sedimentation_consts(Vel1mConsts<FT> &c, const MP &mp, const ST *stokes, const CI *chen_ice) {
+static void add_sedimentation_consts(Vel1mConsts<FT> &c, const MP &mp, const ST *stokes, const CI *chen_ice, uint32_t snow_shape = CMX_SNOW_SHAPE_ASPR) {
     const double pi = 3.14159265358979323846;
     if (stokes) {
         c.st_pref = (FT)((double)stokes->grav / (18.0 * (double)stokes->nu_air));
@@ -190,12 +244,24 @@ static void add_sedimentation_consts(Vel1mConsts<FT> &c, const MP &mp, const ST 
             const double Fl = (double)t.F[0] + (double)t.F[1] * l - std::exp(std::log(-(double)t.F[2]) - ri);
             const double Gl = 1.0 / ((double)t.G[0] + (double)t.G[1] * l * sq + (double)t.G[2] / sq);
             const double Hl = (double)t.H[0] + (double)t.H[1] * ri * ri * sq + std::exp(std::log(-(double)t.H[2]) - ri);
-            const double pk = std::pow((double)mp.snow.phi, (double)mp.snow.kappa);
-            c.sn_A = (FT)Al; c.sn_b1 = (FT)Cl; c.sn_b2 = (FT)Fl; c.sn_H = (FT)Hl; c.sn_c2 = (FT)(1000.0 * Gl);
+            const SnowAspect sa = snow_aspect(mp, snow_shape);
+            const double pk = sa.amp;
+            c.sn_A = (FT)Al; c.sn_b1 = (FT)(Cl + sa.ka); c.sn_b2 = (FT)Fl; c.sn_H = (FT)Hl; c.sn_c2 = (FT)(1000.0 * Gl);
             c.sn_a1 = (FT)(pk * Bl * std::pow(1000.0, Cl) * std::tgamma(Cl + 4.0) / 6.0);
             c.sn_a2 = (FT)(pk * El * std::pow(1000.0, Fl) * std::tgamma(Fl + 4.0) / 6.0);
         }
     }
+}
+
+// the constants of cmx_snow_terminal_velocity_* and of the shaped column step: chen_rain / stokes may be NULL (CR / ST name their types)
+template <typename FT, typename MP, typename CR, typename ST, typename CI>
+static Vel1mShapeConsts<FT> make_snow_shape_consts(const MP &mp, const CR *chen_rain, const ST *stokes, const CI &chen_ice, uint32_t snow_shape,
+                                                   bool *chen_general = nullptr) {
+    Vel1mShapeConsts<FT> c{};
+    static_cast<Vel1mConsts<FT> &>(c) = make_vel1m_consts<FT>(mp, chen_rain, chen_general);
+    add_sedimentation_consts<FT>(c, mp, stokes, &chen_ice, snow_shape);
+    c.sn_e2 = (FT)(snow_aspect(mp, snow_shape).ka - 4.0);
+    return c;
 }
 
 }  // namespace cmx

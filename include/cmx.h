@@ -72,6 +72,8 @@ extern "C" {
  *        for all columns + a one-workgroup-per-column finish, no floating-point atomics).
  *   0.5  round 5: no struct layout changed.  New entry cmx_cloud_diagnostics (CloudDiagnostics over columns); cmx_sb2006_size_distribution refuses the
  *        limited variant of a struct without limiters (CMX_ERR_BAD_ARG instead of silently clamping to 0).
+ *        Later, without a new number (no struct layout changed; entries only added — an older library fails on the symbol lookup):
+ *        cmx_snow_terminal_velocity (the snow fall speed with CM1.Oblate / CM1.Prolate) and the CMX_1M_SED_SNOW_* bits of the column step.
  *        julia/CMXExt.jl (the reference-side binding) checks this number. */
 #define CMX_VERSION_MAJOR 0
 #define CMX_VERSION_MINOR 5
@@ -758,6 +760,14 @@ int32_t cmx_mp1m_linearized_average_fields_f64(const cmx_microphysics_1m_f64 *mp
                                                int32_t nsub, int64_t n_seg, int64_t seg_len, const double *const *in, const int64_t *in_seg_stride,
                                                double *const *out, const int64_t *out_seg_stride, double *out_aos, void *stream);
 
+/* Snow shape of the Chen-2022 snow fall speed: cmx_snow_terminal_velocity_* `snow_shape`, and — as CMX_1M_SED_SNOW_* bits in `flags` — the
+ * w_sno of cmx_mp1m_column_tendencies_sedimentation_* (no other 1-moment entry accepts those bits) */
+#define CMX_SNOW_SHAPE_ASPR       0u          /* CM1.terminal_velocity(snow, Chen2022VelTypeLargeIce, ρ, q): the fixed ϕ^κ           CM1:272-297 */
+#define CMX_SNOW_SHAPE_OBLATE     1u          /* … , ρ, q, CM1.Oblate()                                                          CM1:155-181, 299-324 */
+#define CMX_SNOW_SHAPE_PROLATE    2u          /* … , ρ, q, CM1.Prolate()                                                         CM1:183-195, 299-324 */
+#define CMX_1M_SED_SNOW_OBLATE    (1u << 17)  /* cmx_mp1m_column_tendencies_sedimentation_* only: w_sno with CM1.Oblate()        */
+#define CMX_1M_SED_SNOW_PROLATE   (1u << 18)  /* cmx_mp1m_column_tendencies_sedimentation_* only: w_sno with CM1.Prolate()       */
+
 /* The OPERATIONAL 1-moment column step in one pass (SURVEY §8f-1 + §8f-4): per grid point of n_col columns × n_lev contiguous levels
  * (flat index col·n_lev + k, level 0 = lowest — `parent(field)` of a ClimaCore column field)
  *   tend  = BMT.bulk_microphysics_tendencies(mode, Microphysics1Moment(), mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno[, Δt, nsub])
@@ -771,7 +781,11 @@ int32_t cmx_mp1m_linearized_average_fields_f64(const cmx_microphysics_1m_f64 *mp
  * in = HOST array of the 7 device columns (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), out = HOST array of the 4 device tendency
  * columns; precip_rai / precip_sno (optional, n_col values): the surface fluxes F_0 of rain and snow [kg m⁻² s⁻¹].  44 B/point (f32)
  * instead of the 148 B/point of the three unfused steps.  Results do not depend on tile boundaries or alignment; a NaN in ρ or in a
- * species' q gives a NaN flux of that species (and a NaN tendency of that species in the cell below). */
+ * species' q gives a NaN flux of that species (and a NaN tendency of that species in the cell below).
+ * Snow shape: `flags` may also hold ONE of CMX_1M_SED_SNOW_OBLATE / CMX_1M_SED_SNOW_PROLATE (both: CMX_ERR_BAD_ARG); w_sno is then
+ * cmx_snow_terminal_velocity_* with that shape (CM1:299-324), everything else is unchanged.  Such a call runs the run-time-options kernel
+ * whatever the options: with CMX_1M_DEFAULT_OPTIONS its tendencies may differ from a call without the bit in the last bits (the
+ * default-options kernel takes the powers of λ⁻¹ as integer exponents), not beyond the Float32 / Float64 parity tolerances. */
 int32_t cmx_mp1m_column_tendencies_sedimentation_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
                                                      const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags,
                                                      float q_min, float dt, int32_t nsub, int64_t n_col, int32_t n_lev, const float *inv_dz,
@@ -830,6 +844,17 @@ int32_t cmx_sedimentation_velocities_f64(const cmx_microphysics_1m_f64 *mp, cons
                                          const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, int64_t n,
                                          const double *rho, const double *q_lcl, const double *q_icl, const double *q_rai,
                                          const double *q_sno, double *w_lcl, double *w_icl, double *w_rai, double *w_sno, void *stream);
+
+/* The Chen-2022 snow fall speed with a snow shape — CM1.terminal_velocity(snow, Ch2022.large_ice, ρ, q, shape), src/Microphysics1M.jl:299-324:
+ *   ϕ_av = ϕ₀ λ⁻¹^α Γ_aspect (CM1.aspect_ratio_coeffs, CM1:155-195; Γ_aspect = snow.gamma_aspect_oblate / _prolate)
+ *   w_sno = max(0, ϕ_av^κ Σₖ Chen2022_exponential_pdf(aₖ, bₖ, cₖ, 2 λ⁻¹, 3)) if q > ϵ, else 0      (Common.jl:327-350,414-422)
+ * snow_shape = CMX_SNOW_SHAPE_OBLATE / _PROLATE, or CMX_SNOW_SHAPE_ASPR for the fixed aspect ratio (CM1:272-297): then bit-identical to w_sno of
+ * cmx_sedimentation_velocities_* at every point without a NaN input.  snow_shape > 2: CMX_ERR_BAD_ARG.  A NaN in ρ or q gives NaN; Float64:
+ * ρ ≤ 0 gives NaN; q ≤ ϵ gives exactly 0.  12 B/point (f32); any alignment, results independent of it; launches only, on `stream`. */
+int32_t cmx_snow_terminal_velocity_f32(const cmx_microphysics_1m_f32 *mp, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t snow_shape, int64_t n,
+                                       const float *rho, const float *q_sno, float *w_sno, void *stream);
+int32_t cmx_snow_terminal_velocity_f64(const cmx_microphysics_1m_f64 *mp, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t snow_shape, int64_t n,
+                                       const double *rho, const double *q_sno, double *w_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (6) Abdul-Razzak & Ghan (2000) aerosol activation.

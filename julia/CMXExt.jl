@@ -35,6 +35,7 @@ import CloudMicrophysics.BulkMicrophysicsTendencies as BMT
 import CloudMicrophysics.AerosolModel as AM
 import CloudMicrophysics.AerosolActivation as AA
 import CloudMicrophysics.Quadrature as QUAD
+import CloudMicrophysics.Microphysics1M as CM1
 import Thermodynamics as TD
 const TDP = TD.Parameters
 
@@ -118,6 +119,11 @@ const CMX_1M_ACCR_LCL_SNO = UInt32(1) << 13
 const CMX_1M_ACCR_ICL_RAI = UInt32(1) << 14
 const CMX_1M_ACCR_ICL_SNO = UInt32(1) << 15
 const CMX_1M_ACCR_RAI_SNO = UInt32(1) << 16
+const CMX_SNOW_SHAPE_ASPR = UInt32(0)
+const CMX_SNOW_SHAPE_OBLATE = UInt32(1)
+const CMX_SNOW_SHAPE_PROLATE = UInt32(2)
+const CMX_1M_SED_SNOW_OBLATE = UInt32(1) << 17
+const CMX_1M_SED_SNOW_PROLATE = UInt32(1) << 18
 const CMX_SB2006_NPROC = 19
 const CMX_MP1M_NSRC = 18
 const CMX_ARG_MAX_MODES = 8
@@ -863,21 +869,29 @@ function bulk_microphysics_tendencies_fields!(::BMT.LinearizedAverage, ::BMT.Mic
     return nothing
 end
 
+# snow shape (CM1.Oblate / CM1.Prolate, src/Microphysics1M.jl:66-68) → the `snow_shape` value / the column-step bit; `nothing`: the fixed aspect ratio
+_snow_shape(::Nothing) = CMX_SNOW_SHAPE_ASPR
+_snow_shape(::CM1.Oblate) = CMX_SNOW_SHAPE_OBLATE
+_snow_shape(::CM1.Prolate) = CMX_SNOW_SHAPE_PROLATE
+_sed_snow_bit(::Nothing) = UInt32(0)
+_sed_snow_bit(::CM1.Oblate) = CMX_1M_SED_SNOW_OBLATE
+_sed_snow_bit(::CM1.Prolate) = CMX_1M_SED_SNOW_PROLATE
+
 """
     column_tendencies_sedimentation!(out, mode, BMT.Microphysics1Moment(), mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols, Δt, nsub; …)
 
 The operational 1-moment column step in one pass.  `mode = BMT.Instantaneous()` (then `Δt`, `nsub` are ignored) or `BMT.LinearizedAverage()`;
 `cols` = the 7 state columns (ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno), `out` = the 4 tendency columns; `stokes = CMP.StokesRegimeVelType(FT)`,
-`chen = CMP.Chen2022VelType(FT)`.
+`chen = CMP.Chen2022VelType(FT)`; `snow_shape = CM1.Oblate()` or `CM1.Prolate()`: the snow fall speed of `snow_terminal_velocity!` with that shape.
 """
 function column_tendencies_sedimentation!(out, mode, ::BMT.Microphysics1Moment, mp::CMP.Microphysics1MParams, tps,
     stokes::CMP.StokesRegimeVelType{FT}, chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, Δt = zero(FT), nsub::Integer = 0;
-    precip_rai = nothing, precip_sno = nothing, stream = C_NULL) where {FT}
+    precip_rai = nothing, precip_sno = nothing, snow_shape::Union{Nothing, CM1.AbstractSnowShape} = nothing, stream = C_NULL) where {FT}
     ns = mode isa BMT.LinearizedAverage ? Int32(nsub) : Int32(0)
     st = ccall(_fn("cmx_mp1m_column_tendencies_sedimentation", FT), Int32,
         (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, FT, FT, Int32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT},
             Ptr{FT}, Ptr{Cvoid}),
-        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), FT(TDP.q_min(tps)), FT(Δt), ns,
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp) | _sed_snow_bit(snow_shape), FT(TDP.q_min(tps)), FT(Δt), ns,
         n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols), _ptrs(FT, out), _dp(FT, precip_rai), _dp(FT, precip_sno), stream)
     _check(st, "cmx_mp1m_column_tendencies_sedimentation")
     return out
@@ -914,6 +928,21 @@ function sedimentation_velocities!(w_lcl, w_icl, w_rai, w_sno, mp::CMP.Microphys
         _dp(FT, w_lcl), _dp(FT, w_icl), _dp(FT, w_rai), _dp(FT, w_sno), stream)
     _check(st, "cmx_sedimentation_velocities")
     return nothing
+end
+
+"""
+    snow_terminal_velocity!(w, mp, chen, ρ, q[, snow_shape])
+
+`@. w = CM1.terminal_velocity(mp.precip.snow, chen.large_ice, ρ, q, snow_shape)` with `snow_shape = CM1.Oblate()` or `CM1.Prolate()`
+(src/Microphysics1M.jl:299-324); without it the fixed aspect ratio of the 4-argument method (:272-297).  `chen = CMP.Chen2022VelType(FT)`.
+"""
+function snow_terminal_velocity!(w, mp::CMP.Microphysics1MParams, chen::CMP.Chen2022VelType, ρ::AbstractArray{FT}, q,
+    snow_shape::Union{Nothing, CM1.AbstractSnowShape} = nothing; stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_snow_terminal_velocity", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(pack(chen)), _snow_shape(snow_shape), length(ρ), _dp(FT, ρ), _dp(FT, q), _dp(FT, w), stream)
+    _check(st, "cmx_snow_terminal_velocity")
+    return w
 end
 
 # ----------------------------------------------------------------------------------------------------------------
