@@ -6,6 +6,7 @@ Host-side mirror of the reference's module layout for the hot path:
   cmx.bulk_tendencies   ↔ CloudMicrophysics.BulkMicrophysicsTendencies (BMT) + per-process CM2 rates
   cmx.utilities         ↔ CloudMicrophysics.Utilities (UT): gamma_inc / gamma_inc_inv over columns
   cmx.distribution_tools ↔ CloudMicrophysics.DistributionTools (DT) + the SB2006 PSD accessors of CM2
+  cmx.nucleation        ↔ CloudMicrophysics.Nucleation (aerosol new-particle formation)
   cmx.synthetic         ↔ the state generator of test/gpu_performance.jl:80-136
   cmx.sharding          ↔ (no reference equivalent) one-process-per-GPU sharding + RCCL diagnostic sums
 All compute goes through libcmx.so (include/cmx.h); there is no CPU fallback.
@@ -20,7 +21,11 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
 
 from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_count,  # noqa: F401
                              ice_nucleation_rates, liquid_freezing_rate, h2so4_solution, mohler2006_deposition, MohlerDeposition, deposition_J,
-                             INP_concentration_frequency)
+                             INP_concentration_frequency, P3_deposition_N_i, P3_het_N_i)
+
+from .nucleation import (NucleationRates, PrescribedNucleationRates, apparent_nucleation_rate, h2so4_nucleation_rate,  # noqa: F401
+                         nucleation_rates, nucleation_rates_prescribed, organic_and_h2so4_nucleation_rate,
+                         organic_and_h2so4_nucleation_rate_bioOxOrg_prescribed, organic_nucleation_rate, organic_nucleation_rate_hom_prescribed)
 
 from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Moment, SedimentationVelocities, SourceTerms1M, Tendencies1M,  # noqa: F401
                              TerminalVelocities1M, bulk_microphysics_tendencies_1m, bulk_microphysics_tendencies_1m_fields,

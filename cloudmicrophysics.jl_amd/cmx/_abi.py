@@ -192,6 +192,13 @@ def _family(ft, sfx):
     ns.deposition_dust = _struct(f"cmx_deposition_dust_{sfx}", s("deposition_m", "deposition_c"))
     ns.h2so4_solution_params = _struct(f"cmx_h2so4_solution_params_{sfx}", s("T_max", "T_min", "w_2", "c1", "c2", "c3", "c4", "c5", "c6", "c7"))
     ns.morrison_milbrandt2014 = _struct(f"cmx_morrison_milbrandt2014_{sfx}", s("T_dep_thres", "c1", "c2", "T0", "het_a", "het_B"))
+    # ---- aerosol nucleation (src/parameters/AerosolModalNucleation.jl; the reference spells the first H2S04)
+    ns.h2so4_nucleation = _struct(f"cmx_h2so4_nucleation_{sfx}", s(
+        "p_b_n", "p_b_i", "u_b_n", "u_b_i", "v_b_n", "v_b_i", "w_b_n", "w_b_i", "p_t_n", "p_t_i", "u_t_n", "u_t_i", "v_t_n", "v_t_i",
+        "w_t_n", "w_t_i", "p_A_n", "p_A_i", "a_n", "a_i"))
+    ns.organic_nucleation = _struct(f"cmx_organic_nucleation_{sfx}", s(
+        "a_1", "a_2", "a_3", "a_4", "a_5", "Y_MTO3", "Y_MTOH", "k_MTO3", "k_MTOH", "exp_MTO3", "exp_MTOH"))
+    ns.mixed_nucleation = _struct(f"cmx_mixed_nucleation_{sfx}", s("k_H2SO4org", "k_MTOH", "exp_MTOH"))
     ns.p3_ice_params = _struct(f"cmx_p3_ice_params_{sfx}", [
         ("scheme", ns.p3_params), ("vent", ns.ventilation), ("rho_rim_local", ns.local_rime_density),
         ("vel_rain", ns.chen2022_rain_vel), ("vel_ice", ns.chen2022_ice_vel), ("cloud_pdf", ns.cloud_pdf_sb2006),

@@ -188,6 +188,18 @@ def _declare(lib):
         f = getattr(lib, f"cmx_cloud_diagnostics_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.rain), C.POINTER(fam.cloud_pdf_sb2006), C.POINTER(fam.rain_pdf_sb2006), fam.ft, u32, i64] + [vp] * 9 + [vp]
+        f = getattr(lib, f"cmx_aerosol_nucleation_rates_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.h2so4_nucleation), C.POINTER(fam.organic_nucleation), C.POINTER(fam.mixed_nucleation), i64] + [vp] * 12 + [vp]
+        f = getattr(lib, f"cmx_nucleation_rates_prescribed_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.organic_nucleation), C.POINTER(fam.mixed_nucleation), i64] + [vp] * 6 + [vp]
+        f = getattr(lib, f"cmx_apparent_nucleation_rate_{s}")
+        f.restype = i32
+        f.argtypes = [i64] + [vp] * 7 + [vp]
+        f = getattr(lib, f"cmx_p3_ice_nucleation_counts_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.morrison_milbrandt2014), i64] + [vp] * 6 + [vp]
         f = getattr(lib, f"cmx_column_sums_{s}")
         f.restype = i32
         f.argtypes = [i32, C.POINTER(vp), i64, vp, vp, vp]

@@ -187,3 +187,29 @@ def INP_concentration_frequency(ip, INPC, T, *, stream=None) -> torch.Tensor:
         st = fn(C.byref(ip), ref.numel(), _ptr(INPC), _ptr(T), _ptr(f), C.c_void_p(s.cuda_stream))
     _lib.check(fn.__name__, st)
     return f
+
+
+# ---- the P3 ice-nucleation counts (include/cmx.h §(11)) ------------------------------------------------------------------------------
+def _p3_counts(ip, T, N_l, V_l, dt, want_dep, want_het, stream):
+    ref, fam = _cols1((T, N_l, V_l, dt), ("T", "N_l", "V_l", "dt"))
+    if not isinstance(ip, fam.morrison_milbrandt2014):
+        raise TypeError("ip must be the MorrisonMilbrandt2014 of the columns' float type")
+    N_dep = torch.empty_like(ref) if want_dep else None
+    N_het = torch.empty_like(ref) if want_het else None
+    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
+    fn = getattr(_lib.lib(), f"cmx_p3_ice_nucleation_counts_{fam.sfx}")
+    with torch.cuda.device(ref.device):
+        st = fn(C.byref(ip), ref.numel(), _ptr(T), _ptr(N_l), _ptr(V_l), _ptr(dt), _ptr(N_dep), _ptr(N_het), C.c_void_p(s.cuda_stream))
+    _lib.check(fn.__name__, st)
+    return N_dep, N_het
+
+
+def P3_deposition_N_i(ip, T, *, stream=None) -> torch.Tensor:
+    """CMI_het.P3_deposition_N_i.(Ref(ip), T) [m⁻³] — src/IceNucleation.jl:162-166.  A NaN T gives NaN (the reference's ifelse returns 0)."""
+    return _p3_counts(ip, T, None, None, None, True, False, stream)[0]
+
+
+def P3_het_N_i(ip, T, N_l, V_l, dt, *, stream=None) -> torch.Tensor:
+    """CMI_het.P3_het_N_i.(Ref(ip), T, N_l, V_l, Δt) [m⁻³] — src/IceNucleation.jl:202-205, evaluated as −N_l·expm1(x) in both precisions
+    (the reference's N_l (1 − exp(x)) cancels in Float32).  `dt` is a column, as in the reference's GPU kernel."""
+    return _p3_counts(ip, T, N_l, V_l, dt, False, True, stream)[1]

@@ -232,6 +232,34 @@ DEFAULT_PARAMETERS = {
     "Alpert2022_J_deposition_c_Feldspar": 0.7749623086329027,
     "Alpert2022_J_deposition_m_Ferrihydrite": (4.21854 - 1.2781457) / (0.336486 - 0.0989189),
     "Alpert2022_J_deposition_c_Ferrihydrite": 0.04790839208164743,
+    # ---- aerosol nucleation (src/parameters/AerosolModalNucleation.jl name maps; ClimaParams values are not in the reference tree) -------------
+    # PINNED by test/nucleation_unit_tests.jl:15-97 (Float64, rtol 1e-5), derived in Float64:
+    #   H2SO4 (:15-44, nh3 = negative_ion = 0, T = 208 K, h2so4 = 10^(6:0.5:9) cm⁻³): rate = k_b_n(208)·(h2so4/1e6)^p_b_n, so
+    #     p_b_n = log(r₇/r₁)/log(10³) = 3.95451 (all seven answers to 7e-16) and k_b_n(208 K) = r₁ = 0.004530231195176104.  k_b_n(T) =
+    #     exp(u − exp(v (T/1000 − w))) pins ONE combination of (u, v, w): with u_b_n, v_b_n below, w_b_n = 0.208 − log(u_b_n − log r₁)/v_b_n.
+    #   organic (:46-69, negative_ion = 0, HOM = 10^(6:0.5:8.5) cm⁻³): rate = a_1 x^(a_2 + a_5/x), x = HOM/1e7; x = 1 gives a_1 = 0.0400097, and
+    #     log(rate/a_1)/log x = a_2 + a_5/x at the five other points is linear in 1/x: a_2 = 1.84826, a_5 = 0.186303 (residual 2e-15).
+    #   mixed (:71-97, h2so4 = 2.6e6, bioOxOrg = 10^(5.8:0.25:8.5)): rate = ½ k_H2SO4org h2so4² bioOxOrg·1e-6 → k_H2SO4org = 3.27e-21 at all 11 points.
+    "mam3_nucleation_p_b_n_neutral": 3.95451,
+    "mam3_nucleation_u_b_n_neutral": 9.702, "mam3_nucleation_v_b_n_neutral": 12.614,
+    "mam3_nucleation_w_b_n_neutral": 0.208 - math.log(9.702 - math.log(0.004530231195176104)) / 12.614,
+    "mam3_nucleation_a_1_neutral": 0.0400097, "mam3_nucleation_a_2_neutral": 1.84826, "mam3_nucleation_a_5": 0.186303,
+    "mam3_nucleation_k_H2SO4_mixed_organic_sulfuric_acid_factor": 3.27e-21,
+    # UNPINNED (UNPINNED_DEFAULTS): the remaining Dunne et al. (2016) coefficients as recalled from the paper's supplementary table, the ion-induced
+    # organic pair of Kirkby et al. (2016) as recalled, the HOM yields of Kirkby et al. (2016) in percent (as the ClimaParams names say), and the
+    # monoterpene oxidation rate constants printed in docs/src/AerosolNucleation.md:104-111 (k_MT,O3 = 8.05e-16 exp(444/T), k_MT,OH = 1.2e-11 exp(444/T)).
+    "mam3_nucleation_p_b_i_ion_induced": 3.373738, "mam3_nucleation_u_b_i_ion_induced": -40.70, "mam3_nucleation_v_b_i_ion_induced": 10.0,
+    "mam3_nucleation_w_b_i_ion_induced": 0.0,
+    "mam3_nucleation_p_t_n_neutral": 2.891024, "mam3_nucleation_u_t_n_neutral": 182.2391, "mam3_nucleation_v_t_n_neutral": 1.203451,
+    "mam3_nucleation_w_t_n_neutral": -4.188065,
+    "mam3_nucleation_p_t_i_ion_induced": 3.138719, "mam3_nucleation_u_t_i_ion_induced": 6.13, "mam3_nucleation_v_t_i_ion_induced": 7.1,
+    "mam3_nucleation_w_t_i_ion_induced": -0.06,
+    "mam3_nucleation_p_A_n_neutral": 8.003471, "mam3_nucleation_p_A_i_ion_induced": 3.071246,
+    "mam3_nucleation_a_n_neutral": 1.6e-6, "mam3_nucleation_a_i_ion_induced": 0.00483,
+    "mam3_nucleation_a_3_ion_induced": 0.3435, "mam3_nucleation_a_4_ion_induced": 1.8,
+    "mam3_nucleation_Y_MTO3_percent": 2.9, "mam3_nucleation_Y_MTOH_percent": 1.2,
+    "mam3_nucleation_k_MTO3_organic_factor": 8.05e-16, "mam3_nucleation_k_MTOH_organic_factor": 1.2e-11,
+    "mam3_nucleation_exp_MTO3_organic_factor": 444.0, "mam3_nucleation_exp_MTOH_organic_factor": 444.0,
 }
 
 # the reference's calibrated override file src/parameters/toml/ARG2000.toml (PySDM-based calibration)
@@ -267,6 +295,21 @@ UNPINNED_DEFAULTS = {
     "Alpert2022_J_deposition_c_Feldspar": "back-solved from one KAT with the digitised slope",
     "Alpert2022_J_deposition_m_Ferrihydrite": "slope digitised from a figure script; one KAT pins the intercept given the slope",
     "Alpert2022_J_deposition_c_Ferrihydrite": "back-solved from one KAT with the digitised slope",
+    "mam3_nucleation_u_b_n_neutral": "recalled from Dunne et al. (2016); the KATs pin only k_b_n(208 K), w_b_n is back-solved from it",
+    "mam3_nucleation_v_b_n_neutral": "recalled from Dunne et al. (2016); the KATs pin only k_b_n(208 K), w_b_n is back-solved from it",
+    "mam3_nucleation_w_b_n_neutral": "back-solved from k_b_n(208 K) with the recalled u_b_n, v_b_n",
+    **{f"mam3_nucleation_{k}": "recalled from Dunne et al. (2016): no reference number pins it (the KATs set nh3 = negative_ion = 0)" for k in (
+        "p_b_i_ion_induced", "u_b_i_ion_induced", "v_b_i_ion_induced", "w_b_i_ion_induced", "p_t_n_neutral", "u_t_n_neutral", "v_t_n_neutral",
+        "w_t_n_neutral", "p_t_i_ion_induced", "u_t_i_ion_induced", "v_t_i_ion_induced", "w_t_i_ion_induced", "p_A_n_neutral", "p_A_i_ion_induced",
+        "a_n_neutral", "a_i_ion_induced")},
+    "mam3_nucleation_a_3_ion_induced": "recalled from Kirkby et al. (2016): the KATs set negative_ion = 0",
+    "mam3_nucleation_a_4_ion_induced": "recalled from Kirkby et al. (2016): the KATs set negative_ion = 0",
+    "mam3_nucleation_Y_MTO3_percent": "HOM yield recalled from Kirkby et al. (2016); no reference number pins it",
+    "mam3_nucleation_Y_MTOH_percent": "HOM yield recalled from Kirkby et al. (2016); no reference number pins it",
+    "mam3_nucleation_k_MTO3_organic_factor": "printed in docs/src/AerosolNucleation.md; no known answer pins it",
+    "mam3_nucleation_k_MTOH_organic_factor": "printed in docs/src/AerosolNucleation.md; no known answer pins it",
+    "mam3_nucleation_exp_MTO3_organic_factor": "printed in docs/src/AerosolNucleation.md; no known answer pins it",
+    "mam3_nucleation_exp_MTOH_organic_factor": "printed in docs/src/AerosolNucleation.md; no known answer pins it",
 }
 
 
@@ -825,6 +868,39 @@ def MorrisonMilbrandt2014(FT):
     return td.fam.morrison_milbrandt2014(
         T_dep_thres=td["temperature_homogenous_nucleation"], c1=td["Thompson2004_c1_Cooper"], c2=td["Thompson2004_c2_Cooper"],
         T0=td["temperature_water_freeze"], het_a=td["BarklieGokhale1959_a_parameter"], het_B=td["BarklieGokhale1959_B_parameter"])
+
+
+_H2SO4_NUC_NAMES = (("p_b_n", "p_b_n_neutral"), ("p_b_i", "p_b_i_ion_induced"), ("u_b_n", "u_b_n_neutral"), ("u_b_i", "u_b_i_ion_induced"),
+                    ("v_b_n", "v_b_n_neutral"), ("v_b_i", "v_b_i_ion_induced"), ("w_b_n", "w_b_n_neutral"), ("w_b_i", "w_b_i_ion_induced"),
+                    ("p_t_n", "p_t_n_neutral"), ("p_t_i", "p_t_i_ion_induced"), ("u_t_n", "u_t_n_neutral"), ("u_t_i", "u_t_i_ion_induced"),
+                    ("v_t_n", "v_t_n_neutral"), ("v_t_i", "v_t_i_ion_induced"), ("w_t_n", "w_t_n_neutral"), ("w_t_i", "w_t_i_ion_induced"),
+                    ("p_A_n", "p_A_n_neutral"), ("p_A_i", "p_A_i_ion_induced"), ("a_n", "a_n_neutral"), ("a_i", "a_i_ion_induced"))
+_ORGANIC_NUC_NAMES = (("a_1", "a_1_neutral"), ("a_2", "a_2_neutral"), ("a_3", "a_3_ion_induced"), ("a_4", "a_4_ion_induced"), ("a_5", "a_5"),
+                      ("Y_MTO3", "Y_MTO3_percent"), ("Y_MTOH", "Y_MTOH_percent"), ("k_MTO3", "k_MTO3_organic_factor"),
+                      ("k_MTOH", "k_MTOH_organic_factor"), ("exp_MTO3", "exp_MTO3_organic_factor"), ("exp_MTOH", "exp_MTOH_organic_factor"))
+_MIXED_NUC_NAMES = (("k_H2SO4org", "k_H2SO4_mixed_organic_sulfuric_acid_factor"), ("k_MTOH", "k_MTOH_organic_factor"),
+                    ("exp_MTOH", "exp_MTOH_organic_factor"))
+
+
+def _nucleation_params(FT, ctor, names):
+    td = _td(FT)
+    keys = [f"mam3_nucleation_{k}" for _, k in names]
+    return _tag_unpinned(ctor(**{f: td[k] for (f, _), k in zip(names, keys)}), td, keys)
+
+
+def H2S04NucleationParameters(FT):
+    """CMP.H2S04NucleationParameters (the reference's spelling) — src/parameters/AerosolModalNucleation.jl:4-61 (Dunne et al. 2016)."""
+    return _nucleation_params(FT, _td(FT).fam.h2so4_nucleation, _H2SO4_NUC_NAMES)
+
+
+def OrganicNucleationParameters(FT):
+    """CMP.OrganicNucleationParameters — src/parameters/AerosolModalNucleation.jl:64-103 (Kirkby et al. 2016)."""
+    return _nucleation_params(FT, _td(FT).fam.organic_nucleation, _ORGANIC_NUC_NAMES)
+
+
+def MixedNucleationParameters(FT):
+    """CMP.MixedNucleationParameters — src/parameters/AerosolModalNucleation.jl:105-129 (Riccobono et al. 2014)."""
+    return _nucleation_params(FT, _td(FT).fam.mixed_nucleation, _MIXED_NUC_NAMES)
 
 
 class P3IceParams:

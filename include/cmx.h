@@ -74,6 +74,8 @@ extern "C" {
  *        limited variant of a struct without limiters (CMX_ERR_BAD_ARG instead of silently clamping to 0).
  *        Later, without a new number (no struct layout changed; entries only added — an older library fails on the symbol lookup):
  *        cmx_snow_terminal_velocity (the snow fall speed with CM1.Oblate / CM1.Prolate) and the CMX_1M_SED_SNOW_* bits of the column step.
+ *        cmx_aerosol_nucleation_rates, cmx_nucleation_rates_prescribed, cmx_apparent_nucleation_rate (Nucleation.jl) with the new structs cmx_h2so4_nucleation /
+ *        cmx_organic_nucleation / cmx_mixed_nucleation, and cmx_p3_ice_nucleation_counts (CMI_het.P3_deposition_N_i / P3_het_N_i).
  *        julia/CMXExt.jl (the reference-side binding) checks this number. */
 #define CMX_VERSION_MAJOR 0
 #define CMX_VERSION_MINOR 5
@@ -320,6 +322,17 @@ typedef enum cmx_status {
     /* MorrisonMilbrandt2014 — src/parameters/IceNucleation.jl:80-107 */                       \
     typedef struct cmx_morrison_milbrandt2014_##SFX { FT T_dep_thres, c1, c2, T0, het_a, het_B; } \
         cmx_morrison_milbrandt2014_##SFX;                                                      \
+    /* H2S04NucleationParameters (sic: the reference's spelling), OrganicNucleationParameters, */ \
+    /* MixedNucleationParameters — src/parameters/AerosolModalNucleation.jl:4-129             */ \
+    typedef struct cmx_h2so4_nucleation_##SFX {                                                \
+        FT p_b_n, p_b_i, u_b_n, u_b_i, v_b_n, v_b_i, w_b_n, w_b_i, p_t_n, p_t_i, u_t_n, u_t_i,  \
+            v_t_n, v_t_i, w_t_n, w_t_i, p_A_n, p_A_i, a_n, a_i;                                \
+    } cmx_h2so4_nucleation_##SFX;                                                              \
+    typedef struct cmx_organic_nucleation_##SFX {                                              \
+        FT a_1, a_2, a_3, a_4, a_5, Y_MTO3, Y_MTOH, k_MTO3, k_MTOH, exp_MTO3, exp_MTOH;        \
+    } cmx_organic_nucleation_##SFX;                                                            \
+    typedef struct cmx_mixed_nucleation_##SFX { FT k_H2SO4org, k_MTOH, exp_MTOH; }             \
+        cmx_mixed_nucleation_##SFX;                                                            \
     /* P3IceParams — src/parameters/Microphysics2MParams.jl:58-86: scheme (+ its vent and      */ \
     /* ρ_rim_local members, src/parameters/MicrophysicsP3.jl:267-288), terminal_velocity       */ \
     /* (Chen2022VelType: rain, small_ice, large_ice), cloud_pdf, rain_pdf, ice_nucleation,     */ \
@@ -414,6 +427,13 @@ CMX_DECLARE_PARAM_STRUCTS(double, f64)
 
 CMX_ASSERT_PARAM_STRUCT_SIZES(float, f32)
 CMX_ASSERT_PARAM_STRUCT_SIZES(double, f64)
+/* the same contract for the aerosol-nucleation structs, in a macro of their own: tests/test_abi_caller.py pins the row count of the list above */
+#define CMX_ASSERT_NUCLEATION_STRUCT_SIZES(FT, SFX) \
+    CMX_STATIC_ASSERT((sizeof(cmx_h2so4_nucleation_##SFX) == 20 * sizeof(FT)), "cmx_h2so4_nucleation");\
+    CMX_STATIC_ASSERT((sizeof(cmx_organic_nucleation_##SFX) == 11 * sizeof(FT)), "cmx_organic_nucleation");\
+    CMX_STATIC_ASSERT((sizeof(cmx_mixed_nucleation_##SFX) == 3 * sizeof(FT)), "cmx_mixed_nucleation");
+CMX_ASSERT_NUCLEATION_STRUCT_SIZES(float, f32)
+CMX_ASSERT_NUCLEATION_STRUCT_SIZES(double, f64)
 
 /* ---------------------------------------------------------------------------
  * Library / device queries
@@ -1161,6 +1181,68 @@ int32_t cmx_cloud_diagnostics_f32(const cmx_rain_f32 *rain, const cmx_cloud_pdf_
 int32_t cmx_cloud_diagnostics_f64(const cmx_rain_f64 *rain, const cmx_cloud_pdf_sb2006_f64 *pdf_c, const cmx_rain_pdf_sb2006_f64 *pdf_r, double rho_w,
                                   uint32_t flags, int64_t n, const double *rho, const double *q_lcl, const double *q_rai, const double *N_lcl,
                                   const double *N_rai, double *Z_1m, double *Z_2m, double *reff_2m, double *reff_lh97, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (11) Aerosol nucleation — src/Nucleation.jl (the CLOUD-chamber new-particle-formation rates; test/gpu_tests.jl:246-285,1094-1153 broadcasts them over
+ * device arrays) — and the P3 ice-nucleation counts CMI_het.P3_deposition_N_i / P3_het_N_i (src/IceNucleation.jl:162-166,202-205;
+ * test/gpu_tests.jl:335-344,1001-1037).  Concentrations per m³, T in K, condensation sink in 1/s, rates per m³ per s, as in the reference.  Each entry
+ * is one launch sequence on `stream`, any alignment (results do not depend on it), n up to the usual limit.  Any output may be NULL, not all; a
+ * parameter struct or input column that only NULL outputs would read may be NULL.
+ *
+ * Numerical semantics (tests/test_nucleation_host.py, tests/test_nucleation_gpu.py):
+ *  - every power behaves as IEEE pow / Julia's ^: 0^p = 0 (p > 0), x/0 = Inf, 1^y = 1 for every y, x^0 = 1.  So nh3 = 0 gives f_y = 0 and a ternary
+ *    rate of exactly 0, h2so4 = nh3 = 0 gives NaN (0/0, as the reference), and equal diameters in the apparent rate give J_x = nucleation_rate exactly.
+ *  - a negative concentration that the reference raises to a non-integer power (h2so4, nh3, HOM; the ratios of the apparent rate) is a DomainError
+ *    there and NaN here; nh3 < 0 makes binary NaN too (the reference throws for the whole call).  Products without a power (negative_ion, the
+ *    mixed rate's h2so4² and bioOxOrg) keep the reference's value.
+ *  - a NaN in any input an output reads gives NaN in that output.  P3_deposition_N_i at a NaN T is therefore NaN, where the reference's
+ *    ifelse(T < T₀, …, 0) returns 0.
+ *  - each function's own unit conversions as the reference: h2so4_nucleation_rate scales h2so4 and nh3 by 1e-6 but not negative_ion (:60-61);
+ *    organic_nucleation_rate scales all four concentrations (:117-120); the mixed rate squares h2so4 unscaled (:202 is commented out).  Float32
+ *    products keep the reference's order, except that k(T)·(h2so4/ref)^p is one exp2 of the summed logarithms, the f_y ratio one exp2 of the
+ *    exponent difference, and the final ×1e6 is applied to each term — so no intermediate over- or underflows where the reference's does not.
+ *    A Float32 term that is multiplied up afterwards is formed ×2^64 where it would be subnormal and scaled back last (exact powers of two).
+ * ------------------------------------------------------------------------- */
+/* One fused pass over the state columns:
+ *   (binary, ternary) = Nucleation.h2so4_nucleation_rate(h2so4, nh3, negative_ion, T, h2so4p)                                      :51-90
+ *   organic           = Nucleation.organic_nucleation_rate(negative_ion, monoterpene, O3, OH, T, condensation_sink, orgp)          :106-135
+ *   mixed             = Nucleation.organic_and_h2so4_nucleation_rate(h2so4, monoterpene, OH, T, condensation_sink, mixp)           :172-190
+ * binary / ternary read h2so4, nh3, negative_ion, T and need h2so4p; organic reads negative_ion, monoterpene, O3, OH, T, condensation_sink and needs
+ * orgp; mixed reads h2so4, monoterpene, OH, T, condensation_sink and needs mixp.  The reference's GPU kernel stores sum(h2so4_nucleation_rate(…)):
+ * the caller adds binary + ternary.  Only the columns the requested outputs read are loaded: 8 in + 4 out = 48 B/point (f32) with every output. */
+int32_t cmx_aerosol_nucleation_rates_f32(const cmx_h2so4_nucleation_f32 *h2so4p, const cmx_organic_nucleation_f32 *orgp, const cmx_mixed_nucleation_f32 *mixp,
+                                         int64_t n, const float *h2so4, const float *nh3, const float *negative_ion, const float *monoterpene, const float *O3,
+                                         const float *OH, const float *T, const float *condensation_sink, float *binary, float *ternary, float *organic,
+                                         float *mixed, void *stream);
+int32_t cmx_aerosol_nucleation_rates_f64(const cmx_h2so4_nucleation_f64 *h2so4p, const cmx_organic_nucleation_f64 *orgp, const cmx_mixed_nucleation_f64 *mixp,
+                                         int64_t n, const double *h2so4, const double *nh3, const double *negative_ion, const double *monoterpene,
+                                         const double *O3, const double *OH, const double *T, const double *condensation_sink, double *binary, double *ternary,
+                                         double *organic, double *mixed, void *stream);
+/* The prescribed forms (the ones test/nucleation_unit_tests.jl pins with known answers):
+ *   organic = Nucleation.organic_nucleation_rate_hom_prescribed(negative_ion, HOM, orgp)                           :137-157  (HOM in cm⁻³, negative_ion as passed)
+ *   mixed   = Nucleation.organic_and_h2so4_nucleation_rate_bioOxOrg_prescribed(h2so4, bioOxOrg, mixp)            :192-206
+ * organic reads negative_ion, HOM and needs orgp; mixed reads h2so4, bioOxOrg and needs mixp. */
+int32_t cmx_nucleation_rates_prescribed_f32(const cmx_organic_nucleation_f32 *orgp, const cmx_mixed_nucleation_f32 *mixp, int64_t n, const float *negative_ion,
+                                            const float *HOM, const float *h2so4, const float *bioOxOrg, float *organic, float *mixed, void *stream);
+int32_t cmx_nucleation_rates_prescribed_f64(const cmx_organic_nucleation_f64 *orgp, const cmx_mixed_nucleation_f64 *mixp, int64_t n, const double *negative_ion,
+                                            const double *HOM, const double *h2so4, const double *bioOxOrg, double *organic, double *mixed, void *stream);
+/* J_x = Nucleation.apparent_nucleation_rate(output_diam, nucleation_rate, condensation_growth_rate, coag_sink, coag_sink_input_diam, input_diam)  :23-37
+ * (Lehtinen et al. 2007).  input_diam NULL: the reference's default argument 1.7; every other column is required.  (r^(m+1) − 1)/(m+1), r =
+ * output_diam/input_diam, is evaluated as expm1((m+1) ln r)/(m+1): the reference's form cancels as m → −1 (1 % off in Float32 at |m + 1| ≈ 2e-5). */
+int32_t cmx_apparent_nucleation_rate_f32(int64_t n, const float *output_diam, const float *nucleation_rate, const float *condensation_growth_rate,
+                                         const float *coag_sink, const float *coag_sink_input_diam, const float *input_diam, float *J_x, void *stream);
+int32_t cmx_apparent_nucleation_rate_f64(int64_t n, const double *output_diam, const double *nucleation_rate, const double *condensation_growth_rate,
+                                         const double *coag_sink, const double *coag_sink_input_diam, const double *input_diam, double *J_x, void *stream);
+/* P3 ice-nucleation counts over columns [m⁻³]:
+ *   N_dep = CMI_het.P3_deposition_N_i(ip, T)              src/IceNucleation.jl:162-166   (reads T only)
+ *   N_het = CMI_het.P3_het_N_i(ip, T, N_l, V_l, dt)       src/IceNucleation.jl:202-205   (dt is a column, as in the reference's GPU kernel)
+ * N_het is evaluated as −N_l·expm1(x), x = −het_B V_l dt exp(het_a (T₀ − T)), in BOTH precisions: a deliberate difference from the reference, whose
+ * N_l (1 − exp(x)) cancels in Float32 (its own GPU test quotes 0.00023841858 against the Float64 value 0.0002736160475969029, 13 % off).  The Float32
+ * result stays within the 1e-3 parity bound of the reference's Float64 arithmetic (the ARG2000 erfc precedent). */
+int32_t cmx_p3_ice_nucleation_counts_f32(const cmx_morrison_milbrandt2014_f32 *ip, int64_t n, const float *T, const float *N_l, const float *V_l,
+                                         const float *dt, float *N_dep, float *N_het, void *stream);
+int32_t cmx_p3_ice_nucleation_counts_f64(const cmx_morrison_milbrandt2014_f64 *ip, int64_t n, const double *T, const double *N_l, const double *V_l,
+                                         const double *dt, double *N_dep, double *N_het, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

@@ -174,6 +174,9 @@ const DIRECT_LAYOUT = (
     (CMP.LocalRimeDensity, (), :cmx_local_rime_density),
     (CMP.RainFreezing, (), :cmx_rain_freezing),
     (CMP.MorrisonMilbrandt2014, (), :cmx_morrison_milbrandt2014),
+    (CMP.H2S04NucleationParameters, (), :cmx_h2so4_nucleation),
+    (CMP.OrganicNucleationParameters, (), :cmx_organic_nucleation),
+    (CMP.MixedNucleationParameters, (), :cmx_mixed_nucleation),
 )
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -1214,6 +1217,65 @@ function cloud_diagnostics!(Z_1m, Z_2m, reff_2m, reff_lh97, rain, sb, wtr, ρ::A
         p_rain, p_c, p_r, ρw, flags, length(ρ), _dp(FT, ρ), _dp(FT, q_lcl), _dp(FT, q_rai), _dp(FT, N_lcl), _dp(FT, N_rai), _dp(FT, Z_1m), _dp(FT, Z_2m),
         _dp(FT, reff_2m), _dp(FT, reff_lh97), stream)
     _check(st, "cmx_cloud_diagnostics")
+    return nothing
+end
+
+# ----------------------------------------------------------------------------------------------------------------
+# (11) Aerosol nucleation — src/Nucleation.jl — and the P3 ice-nucleation counts (src/IceNucleation.jl:162-166,202-205)
+# ----------------------------------------------------------------------------------------------------------------
+_ref_or_null(p) = p === nothing ? C_NULL : Ref(p)       # the three nucleation structs are layout-compatible (DIRECT_LAYOUT)
+
+"""
+    aerosol_nucleation_rates!(binary, ternary, organic, mixed, h2so4_nuc, org_nuc, mix_nuc, h2so4, nh3, negative_ion, monoterpene, O3, OH, temp,
+                              condensation_sink)
+
+One pass over the columns: `(binary, ternary) = MN.h2so4_nucleation_rate(…)` (src/Nucleation.jl:51-90; the reference's GPU kernel stores their sum),
+`organic = MN.organic_nucleation_rate(…)` (:106-135), `mixed = MN.organic_and_h2so4_nucleation_rate(…)` (:172-190).  An output may be `nothing`, and so
+may the parameter struct and the columns only `nothing` outputs read.
+"""
+function aerosol_nucleation_rates!(binary, ternary, organic, mixed, h2so4_nuc, org_nuc, mix_nuc, h2so4, nh3, negative_ion, monoterpene, O3, OH,
+    temp::AbstractArray{FT}, condensation_sink; stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_aerosol_nucleation_rates", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{FT}, Ptr{Cvoid}),
+        _ref_or_null(h2so4_nuc), _ref_or_null(org_nuc), _ref_or_null(mix_nuc), length(temp), _dp(FT, h2so4), _dp(FT, nh3), _dp(FT, negative_ion),
+        _dp(FT, monoterpene), _dp(FT, O3), _dp(FT, OH), _dp(FT, temp), _dp(FT, condensation_sink), _dp(FT, binary), _dp(FT, ternary), _dp(FT, organic),
+        _dp(FT, mixed), stream)
+    _check(st, "cmx_aerosol_nucleation_rates")
+    return nothing
+end
+
+"""`MN.organic_nucleation_rate_hom_prescribed.(negative_ion, HOM, Ref(org_nuc))` and
+`MN.organic_and_h2so4_nucleation_rate_bioOxOrg_prescribed.(h2so4, bioOxOrg, Ref(mix_nuc))` (src/Nucleation.jl:137-157,192-206); either output may be `nothing`."""
+function nucleation_rates_prescribed!(organic, mixed, org_nuc, mix_nuc, negative_ion, HOM, h2so4, bioOxOrg::AbstractArray{FT}; stream = C_NULL) where {FT}
+    n = organic === nothing ? length(bioOxOrg) : length(organic)
+    st = ccall(_fn("cmx_nucleation_rates_prescribed", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        _ref_or_null(org_nuc), _ref_or_null(mix_nuc), n, _dp(FT, negative_ion), _dp(FT, HOM), _dp(FT, h2so4), _dp(FT, bioOxOrg), _dp(FT, organic),
+        _dp(FT, mixed), stream)
+    _check(st, "cmx_nucleation_rates_prescribed")
+    return nothing
+end
+
+"""`J_x .= MN.apparent_nucleation_rate.(output_diam, nucleation_rate, condensation_growth_rate, coag_sink, coag_sink_input_diam[, input_diam])`
+(src/Nucleation.jl:23-37); `input_diam = nothing`: the reference's default argument 1.7."""
+function apparent_nucleation_rate!(J_x, output_diam::AbstractArray{FT}, nucleation_rate, condensation_growth_rate, coag_sink, coag_sink_input_diam,
+    input_diam = nothing; stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_apparent_nucleation_rate", FT), Int32,
+        (Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        length(output_diam), _dp(FT, output_diam), _dp(FT, nucleation_rate), _dp(FT, condensation_growth_rate), _dp(FT, coag_sink),
+        _dp(FT, coag_sink_input_diam), _dp(FT, input_diam), _dp(FT, J_x), stream)
+    _check(st, "cmx_apparent_nucleation_rate")
+    return J_x
+end
+
+"""`N_dep .= CMI_het.P3_deposition_N_i.(Ref(ip), T)` and `N_het .= CMI_het.P3_het_N_i.(Ref(ip), T, N_l, V_l, Δt)` (src/IceNucleation.jl:162-166,202-205);
+either output may be `nothing` (then `N_l`, `V_l`, `Δt` may be too).  N_het is −N_l·expm1(x) in both precisions (include/cmx.h)."""
+function p3_ice_nucleation_counts!(N_dep, N_het, ip::CMP.MorrisonMilbrandt2014{FT}, T, N_l, V_l, Δt; stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_p3_ice_nucleation_counts", FT), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(ip), length(T), _dp(FT, T), _dp(FT, N_l), _dp(FT, V_l), _dp(FT, Δt), _dp(FT, N_dep), _dp(FT, N_het), stream)
+    _check(st, "cmx_p3_ice_nucleation_counts")
     return nothing
 end
 
