@@ -1,4 +1,4 @@
-"""Loader for libcmx.so (the C-ABI shared library, include/cmx.h).
+"""Loader for libcmx.so (the C-ABI shared library, include/cmx.h) and the one way the wrappers call it.
 
 There is no fallback: if the HIP extension is missing or fails to load, every
 product entry point raises `CmxLibraryError`.  Build it with
@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
+
+import torch
 
 from . import _abi
 
@@ -227,3 +229,14 @@ def check(fn_name, status):
         detail = lib().cmx_last_hip_error().decode() if status == _abi.CMX_ERR_HIP else ""
         raise CmxStatusError(fn_name, status, detail)
     return status
+
+
+def call(stem, fam, device, *args, stream=None):
+    """Calls `{stem}_{fam.sfx}`(*args, stream) on `device` (stream: the device's current stream by default) and raises
+    CmxStatusError if it fails.  Nothing else: the wrappers are captured into graphs (tests/test_graphs_gpu.py)."""
+    fn = getattr(lib(), f"{stem}_{fam.sfx}")
+    s = stream if stream is not None else torch.cuda.current_stream(device)
+    with torch.cuda.device(device):
+        st = fn(*args, C.c_void_p(s.cuda_stream))
+    return check(fn.__name__, st)
+

@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 
 def _tup(x):
@@ -105,13 +105,8 @@ def aerosol_activation(ap, ad: AerosolDistribution, aip, tps, T, p, w, q_tot, q_
         m_act = tuple(torch.empty_like(ref) for _ in range(nm)) if "M_act" in want else None
         s_max = torch.empty_like(ref) if "S_max" in want else None
     arr = lambda cols_: (C.c_void_p * nm)(*[c.data_ptr() for c in cols_]) if cols_ is not None else None  # noqa: E731
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_arg2000_activation_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ap), C.byref(adc), C.byref(aip), C.byref(tps), ref.numel(), _ptr(T), _ptr(p), _ptr(w), _ptr(q_tot),
-                _ptr(q_liq), _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), arr(n_act), arr(m_act), _ptr(s_max),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_arg2000_activation", fam, ref.device, C.byref(ap), C.byref(adc), C.byref(aip), C.byref(tps), ref.numel(), _ptr(T), _ptr(p),
+              _ptr(w), _ptr(q_tot), _ptr(q_liq), _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), arr(n_act), arr(m_act), _ptr(s_max), stream=stream)
     return ActivationResult(n_act, m_act, s_max)
 
 
@@ -127,12 +122,8 @@ def total_activated(ap, ad: AerosolDistribution, aip, tps, T, p, w, q_tot, q_liq
     adc = ad.c_struct(ap, fam)
     n_tot = torch.empty_like(ref) if "N" in want else None
     m_tot = torch.empty_like(ref) if "M" in want else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_arg2000_total_activated_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ap), C.byref(adc), C.byref(aip), C.byref(tps), ref.numel(), _ptr(T), _ptr(p), _ptr(w), _ptr(q_tot),
-                _ptr(q_liq), _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), _ptr(n_tot), _ptr(m_tot), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_arg2000_total_activated", fam, ref.device, C.byref(ap), C.byref(adc), C.byref(aip), C.byref(tps), ref.numel(), _ptr(T), _ptr(p),
+              _ptr(w), _ptr(q_tot), _ptr(q_liq), _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), _ptr(n_tot), _ptr(m_tot), stream=stream)
     return n_tot, m_tot
 
 
@@ -181,13 +172,8 @@ def aerosol_activation_columns(ap, modes: Sequence[ModeColumns], aip, tps, T, p,
         m_act = tuple(torch.empty_like(ref) for _ in range(nm)) if "M_act" in want else None
         s_max = torch.empty_like(ref) if "S_max" in want else None
     arr = lambda cols_: (C.c_void_p * nm)(*[c.data_ptr() for c in cols_]) if cols_ is not None else None  # noqa: E731
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_arg2000_activation_columns_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ap), C.byref(aip), C.byref(tps), nm, ref.numel(), _ptr(T), _ptr(p), _ptr(w), _ptr(q_tot), _ptr(q_liq),
-                _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), arr([m.r_dry for m in modes]), arr([m.stdev for m in modes]),
-                arr([m.N for m in modes]), arr([m.hygroscopicity for m in modes]),
-                arr([m.molar_mass_mix for m in modes]) if have_mm else None, arr(n_act), arr(m_act), _ptr(s_max),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_arg2000_activation_columns", fam, ref.device, C.byref(ap), C.byref(aip), C.byref(tps), nm, ref.numel(), _ptr(T), _ptr(p), _ptr(w),
+              _ptr(q_tot), _ptr(q_liq), _ptr(q_ice), _ptr(N_liq), _ptr(N_ice), arr([m.r_dry for m in modes]), arr([m.stdev for m in modes]),
+              arr([m.N for m in modes]), arr([m.hygroscopicity for m in modes]), arr([m.molar_mass_mix for m in modes]) if have_mm else None,
+              arr(n_act), arr(m_act), _ptr(s_max), stream=stream)
     return ActivationResult(n_act, m_act, s_max)

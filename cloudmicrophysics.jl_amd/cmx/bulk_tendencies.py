@@ -23,6 +23,7 @@ from typing import Optional
 import torch
 
 from . import _abi, _lib
+from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -50,30 +51,6 @@ SB2006ProcessRates = namedtuple("SB2006ProcessRates", _abi.SB2006_PROCESS_COLUMN
 Tendencies2MP3 = namedtuple(
     "Tendencies2MP3",
     ["dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dn_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt"])
-
-
-def _fam_of(t: torch.Tensor):
-    if t.dtype == torch.float32:
-        return _abi.F32
-    if t.dtype == torch.float64:
-        return _abi.F64
-    raise TypeError(f"state columns must be float32 or float64, got {t.dtype}")
-
-
-def _check_cols(cols, names):
-    ref = cols[0]
-    if not ref.is_cuda:
-        raise ValueError("state columns must be resident on the GPU (torch device 'cuda'); cmx has no CPU path")
-    for t, nm in zip(cols, names):
-        if t.dtype != ref.dtype or t.device != ref.device or t.shape != ref.shape:
-            raise ValueError(f"column {nm}: dtype/device/shape differ from {names[0]}")
-        if not t.is_contiguous():
-            raise ValueError(f"column {nm} must be contiguous (structure-of-arrays)")
-    return ref
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
 def _warm_rain(mp):
@@ -109,12 +86,8 @@ def _bulk_tendencies_2m_p3(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q
     outs = [torch.empty_like(ref) for _ in range(8)]
     out_p = (C.c_void_p * 8)(*[t.data_ptr() for t in outs])
     flags = mp.ice.flags | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_microphysics_2m_p3_tendencies_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], _ptr(inpc_log_shift),
-                out_p, C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_microphysics_2m_p3_tendencies", fam, ref.device, C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), flags, ref.numel(),
+              *[_ptr(t) for t in cols], _ptr(inpc_log_shift), out_p, stream=stream)
     return Tendencies2MP3(*outs, torch.zeros((), dtype=ref.dtype, device=ref.device).expand_as(ref))
 
 
@@ -160,67 +133,12 @@ def bulk_microphysics_tendencies(scheme, mp, tps, rho, T, q_tot, q_lcl, n_lcl, q
     velp = (vel_params if vel_params is not None else rain_vel_params(fam.sfx)) if vflag else None
     if velp is not None and not isinstance(velp, fam.rain_vel):
         raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_sb2006_warm_rain_tendencies_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(wr.c), C.byref(tps), C.byref(velp) if velp is not None else None, flags, ref.numel(),
-                *[_ptr(t) for t in cols], *[_ptr(o) for o in out], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sb2006_warm_rain_tendencies", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp) if velp is not None else None, flags,
+              ref.numel(), *[_ptr(t) for t in cols], *[_ptr(o) for o in out], stream=stream)
     return out
 
 
 AOS_FIELDS = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt")
-
-
-def _segments(t: torch.Tensor, name: str):
-    """(n_seg, seg_len, stride) of a column given as a 1-D contiguous tensor or a 2-D (n_seg, seg_len) view whose rows are
-    contiguous — e.g. `parent(field)[h, f, :]` of a ClimaCore VIJFH array seen from C order as (Nh, Nf, Nv·Ni·Nj)."""
-    if t.dim() == 1 and t.stride(0) == 1:
-        return 1, t.numel(), 0
-    if t.dim() == 2 and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1]:
-        return t.shape[0], t.shape[1], t.stride(0)
-    raise TypeError(f"{name}: expected a contiguous 1-D column or a (n_seg, seg_len) view with contiguous rows")
-
-
-def _fields_call(fn_name, params_c, tps, flags, cols, names, n_out, n_aos, out, aos, stream, extra=()):
-    """Shared driver of the `_fields` entry points (segmented columns in; segmented columns or an (n, n_aos) array of rows out)."""
-    ref = cols[0]
-    fam = _fam_of(ref)
-    n_seg, seg_len, _ = _segments(ref, names[0])
-    strides = []
-    for c, nm in zip(cols, names):
-        if not c.is_cuda or c.device != ref.device or c.dtype != ref.dtype:
-            raise TypeError(f"{nm}: all columns must live on the same GPU with the same dtype")
-        ns, sl, st = _segments(c, nm)
-        if (ns, sl) != (n_seg, seg_len):
-            raise ValueError(f"{nm}: shape differs from {names[0]}")
-        strides.append(st)
-    n = n_seg * seg_len
-    in_p = (C.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
-    in_s = (C.c_int64 * len(cols))(*strides)
-    out_p = out_s = aos_t = None
-    if aos:
-        if out is not None:
-            raise TypeError("out is the SoA form; aos=True allocates the array-of-rows result")
-        aos_t = torch.empty((n, n_aos), dtype=ref.dtype, device=ref.device)
-    else:
-        if out is None:
-            out = [torch.empty(ref.shape, dtype=ref.dtype, device=ref.device) for _ in range(n_out)]
-        ostr = []
-        for o in out:
-            ns, sl, st = _segments(o, "out")
-            if (ns, sl) != (n_seg, seg_len) or o.dtype != ref.dtype or o.device != ref.device:
-                raise ValueError("out: shape / dtype / device differs from the inputs")
-            ostr.append(st)
-        out_p = (C.c_void_p * n_out)(*[o.data_ptr() for o in out])
-        out_s = (C.c_int64 * n_out)(*ostr)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"{fn_name}_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params_c), C.byref(tps), flags, *extra, n_seg, seg_len, in_p, in_s, out_p, out_s, C.c_void_p(aos_t.data_ptr()) if aos else None,
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
-    return aos_t if aos else out
 
 
 def bulk_microphysics_tendencies_2m_p3_fields(scheme, mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, log_lambda,
@@ -269,11 +187,8 @@ def bulk_microphysics_tendencies_2m_p3_fields(scheme, mp, tps, rho, T, q_tot, q_
     in_p, in_s = (C.c_void_p * 13)(*ptrs), (C.c_int64 * 13)(*strides)
     out_p, out_s = (C.c_void_p * 8)(*[o.data_ptr() for o in out]), (C.c_int64 * 8)(*ostr)
     flags = mp.ice.flags | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_microphysics_2m_p3_tendencies_fields_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), flags, n_seg, seg_len, in_p, in_s, out_p, out_s, C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_microphysics_2m_p3_tendencies_fields", fam, ref.device, C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), flags, n_seg,
+              seg_len, in_p, in_s, out_p, out_s, stream=stream)
     return Tendencies2MP3(*out, torch.zeros((), dtype=ref.dtype, device=ref.device).expand(ref.shape))
 
 
@@ -319,12 +234,8 @@ def sb2006_process_rates(mp, tps, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, *, 
     arr = (C.c_void_p * _abi.CMX_SB2006_NPROC)(*[o.data_ptr() if o is not None else None for o in outs])
     flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | vflag
     velp = rain_vel_params(fam.sfx) if vflag else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_sb2006_process_rates_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(wr.c), C.byref(tps), C.byref(velp) if velp is not None else None, flags, ref.numel(),
-                *[_ptr(t) for t in cols], arr, C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sb2006_process_rates", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp) if velp is not None else None, flags,
+              ref.numel(), *[_ptr(t) for t in cols], arr, stream=stream)
     return SB2006ProcessRates(*outs)
 
 
@@ -345,11 +256,7 @@ def column_sums(cols, stream=None, workspace: Optional[torch.Tensor] = None) -> 
     elif workspace.dtype != torch.float64 or workspace.device != ref.device or workspace.numel() < need or not workspace.is_contiguous():
         raise ValueError(f"workspace: a contiguous float64 device tensor of at least {need} elements")
     arr = (C.c_void_p * len(cols))(*[t.data_ptr() for t in cols])
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_column_sums_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(len(cols), arr, ref.numel(), _ptr(sums), _ptr(workspace), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_column_sums", fam, ref.device, len(cols), arr, ref.numel(), _ptr(sums), _ptr(workspace), stream=stream)
     return sums
 
 
@@ -366,12 +273,8 @@ def cloud_terminal_velocity(pdf_c, vel, q_liq, rho, N_liq, *, stream=None) -> Cl
     if not isinstance(pdf_c, fam.cloud_pdf_sb2006) or not isinstance(vel, fam.stokes_vel):
         raise TypeError("parameter float type does not match the state columns")
     out = CloudTerminalVelocity(torch.empty_like(ref), torch.empty_like(ref))
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_sb2006_cloud_terminal_velocity_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(pdf_c), C.byref(vel), ref.numel(), *[_ptr(t) for t in cols], _ptr(out.vt_n), _ptr(out.vt_m),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sb2006_cloud_terminal_velocity", fam, ref.device, C.byref(pdf_c), C.byref(vel), ref.numel(), *[_ptr(t) for t in cols],
+              _ptr(out.vt_n), _ptr(out.vt_m), stream=stream)
     return out
 
 
@@ -410,13 +313,10 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
     else:
         _check_cols([ref, *out[:4]], ["rho", *ColumnTendencies2M._fields[:4]])
     flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | flag
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_sb2006_column_tendencies_sedimentation_{fam.sfx}")
     velp = rain_vel_params(fam.sfx)
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(wr.c), C.byref(tps), C.byref(velp), C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev,
-                _ptr(inv_dz), *[_ptr(t) for t in cols], *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sb2006_column_tendencies_sedimentation", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
+              C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev, _ptr(inv_dz), *[_ptr(t) for t in cols],
+              *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)
     return out
 
 
@@ -442,11 +342,7 @@ def bulk_2m_cloud_to_rain(schemes, scheme: str, q_lcl, rho, N_d=None, q_rai=None
         raise ValueError("pass N_d (autoconversion) and / or q_rai (accretion)")
     acnv = torch.empty_like(ref) if N_d is not None else None
     accr = torch.empty_like(ref) if q_rai is not None else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_bulk_2m_cloud_to_rain_{fam.sfx}")
     flags = _SCHEMES_2M[scheme] | (_abi.CMX_2M_SMOOTH_TRANSITION if smooth_transition else 0)
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(schemes), flags, ref.numel(), _ptr(q_lcl), _ptr(q_rai), _ptr(rho), _ptr(N_d), _ptr(acnv), _ptr(accr),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_bulk_2m_cloud_to_rain", fam, ref.device, C.byref(schemes), flags, ref.numel(), _ptr(q_lcl), _ptr(q_rai), _ptr(rho), _ptr(N_d),
+              _ptr(acnv), _ptr(accr), stream=stream)
     return CloudToRain2M(acnv, accr)

@@ -17,7 +17,7 @@ from collections import namedtuple
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 
 def _call(ref, *, rain=None, sb=None, rho_w=0.0, rho, q_lcl=None, q_rai=None, N_lcl=None, N_rai=None, want, stream=None, out=None):
@@ -43,13 +43,9 @@ def _call(ref, *, rain=None, sb=None, rho_w=0.0, rho, q_lcl=None, q_rai=None, N_
         flags = _abi.CMX_SB2006_LIMITED if limited else 0
     if rain is not None and not isinstance(rain, fam.rain):
         raise TypeError("rain parameter float type does not match the state columns")
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_cloud_diagnostics_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(rain) if rain is not None else None, C.byref(pdf_c) if pdf_c is not None else None, C.byref(pdf_r) if pdf_r is not None else None,
-                rho_w, flags, ref.numel(), _ptr(rho), _ptr(q_lcl), _ptr(q_rai), _ptr(N_lcl), _ptr(N_rai), _ptr(outs["Z_1m"]), _ptr(outs["Z_2m"]),
-                _ptr(outs["reff_2m"]), _ptr(outs["reff_lh97"]), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_cloud_diagnostics", fam, ref.device, C.byref(rain) if rain is not None else None, C.byref(pdf_c) if pdf_c is not None else None,
+              C.byref(pdf_r) if pdf_r is not None else None, rho_w, flags, ref.numel(), _ptr(rho), _ptr(q_lcl), _ptr(q_rai), _ptr(N_lcl), _ptr(N_rai),
+              _ptr(outs["Z_1m"]), _ptr(outs["Z_2m"]), _ptr(outs["reff_2m"]), _ptr(outs["reff_lh97"]), stream=stream)
     return outs
 
 

@@ -14,7 +14,7 @@ from collections import namedtuple
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 Distribution = namedtuple("Distribution", ["quantile", "cdf"])
 SizeDistribution = namedtuple("SizeDistribution", ["n_D", "D_min", "D_max"])
@@ -28,11 +28,8 @@ def generalized_gamma(nu: float, mu: float, B: torch.Tensor, Y=None, x=None, *, 
         raise ValueError("pass Y (quantile) and / or x (cdf)")
     fam = _fam_of(ref)
     out = Distribution(torch.empty_like(ref) if Y is not None else None, torch.empty_like(ref) if x is not None else None)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_generalized_gamma_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(nu, mu, ref.numel(), _ptr(B), _ptr(Y), _ptr(x), _ptr(out.quantile), _ptr(out.cdf), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_generalized_gamma", fam, ref.device, nu, mu, ref.numel(), _ptr(B), _ptr(Y), _ptr(x), _ptr(out.quantile), _ptr(out.cdf),
+              stream=stream)
     return out
 
 
@@ -44,11 +41,8 @@ def exponential_distribution(D_mean: torch.Tensor, Y=None, D=None, *, stream=Non
         raise ValueError("pass Y (quantile) and / or D (cdf)")
     fam = _fam_of(ref)
     out = Distribution(torch.empty_like(ref) if Y is not None else None, torch.empty_like(ref) if D is not None else None)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_exponential_distribution_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(ref.numel(), _ptr(D_mean), _ptr(Y), _ptr(D), _ptr(out.quantile), _ptr(out.cdf), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_exponential_distribution", fam, ref.device, ref.numel(), _ptr(D_mean), _ptr(Y), _ptr(D), _ptr(out.quantile), _ptr(out.cdf),
+              stream=stream)
     return out
 
 
@@ -79,10 +73,6 @@ def size_distribution(pdf, q, rho, N, D=None, *, p=None, bounds=True, is_limited
                              "(RainParticlePDF_SB2006(FT, is_limited=True)); this one is the not-limited variant")
     out = SizeDistribution(torch.empty_like(ref) if D is not None else None, torch.empty_like(ref) if bounds else None, torch.empty_like(ref) if bounds else None)
     flags = (_abi.CMX_PSD_CLOUD if cloud else 0) | (_abi.CMX_SB2006_LIMITED if (is_limited and not cloud) else 0)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_sb2006_size_distribution_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(pdf) if cloud else None, None if cloud else C.byref(pdf), flags, p, ref.numel(), _ptr(q), _ptr(rho), _ptr(N), _ptr(D), _ptr(out.n_D),
-                _ptr(out.D_min), _ptr(out.D_max), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sb2006_size_distribution", fam, ref.device, C.byref(pdf) if cloud else None, None if cloud else C.byref(pdf), flags, p,
+              ref.numel(), _ptr(q), _ptr(rho), _ptr(N), _ptr(D), _ptr(out.n_D), _ptr(out.D_min), _ptr(out.D_max), stream=stream)
     return out

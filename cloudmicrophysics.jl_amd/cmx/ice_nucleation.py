@@ -17,7 +17,7 @@ from collections import namedtuple
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 IceNucleationRates = namedtuple("IceNucleationRates",
                                 ["delta_a_w", "J_het", "J_hom", "rate_het", "rate_hom", "n_domain_errors"])
@@ -54,15 +54,11 @@ def ice_nucleation_rates(tps, dust, koop, T, a_w, r=None, *, linear=False, want=
         outs = {k: (torch.empty_like(ref) if k in want else None) for k in names}
         nerr = (torch.zeros(_abi.CMX_ICENUC_ERR_WORDS, dtype=torch.int64, device=ref.device)
                 if (count_domain_errors and not linear) else None)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
     if h2so4 is not None and not isinstance(h2so4, fam.h2so4_solution_params):
         raise TypeError("h2so4 must be the H2SO4SolutionParameters of the columns' float type")
-    fn = getattr(_lib.lib(), f"cmx_ice_nucleation_rates_{'xT_' if h2so4 is not None else ''}{fam.sfx}")
     head = (C.byref(tps), C.byref(dust), C.byref(koop)) + ((C.byref(h2so4),) if h2so4 is not None else ())
-    with torch.cuda.device(ref.device):
-        st = fn(*head, _abi.CMX_ICENUC_HOM_LINEAR if linear else 0, ref.numel(),
-                _ptr(T), _ptr(a_w), _ptr(r), *[_ptr(outs[k]) for k in names], _ptr(nerr), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call(f"cmx_ice_nucleation_rates{'_xT' if h2so4 is not None else ''}", fam, ref.device, *head, _abi.CMX_ICENUC_HOM_LINEAR if linear else 0,
+              ref.numel(), _ptr(T), _ptr(a_w), _ptr(r), *[_ptr(outs[k]) for k in names], _ptr(nerr), stream=stream)
     return IceNucleationRates(*[outs[k] for k in names], nerr)
 
 
@@ -89,11 +85,7 @@ def _water_activity(tps, T, e, stream):
         raise TypeError("parameter float type does not match the state columns")
     ice = torch.empty_like(ref) if e is None else None
     eT = torch.empty_like(ref) if e is not None else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_water_activity_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(tps), ref.numel(), _ptr(T), _ptr(e), _ptr(ice), _ptr(eT), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_water_activity", fam, ref.device, C.byref(tps), ref.numel(), _ptr(T), _ptr(e), _ptr(ice), _ptr(eT), stream=stream)
     return ice, eT
 
 
@@ -116,12 +108,8 @@ def liquid_freezing_rate(ice_params, tps, q, rho, N, T, *, cloud: bool = False, 
         raise TypeError("parameter float type does not match the state columns")
     out = LiquidFreezingRate(torch.empty_like(q), torch.empty_like(q))
     flags = (_abi.CMX_FREEZE_CLOUD_PSD if cloud else 0) | (_abi.CMX_P3_RAIN_PDF_LIMITED if ice_params.is_limited else 0)
-    s = stream if stream is not None else torch.cuda.current_stream(q.device)
-    fn = getattr(_lib.lib(), f"cmx_liquid_freezing_rate_{fam.sfx}")
-    with torch.cuda.device(q.device):
-        st = fn(C.byref(ice_params.c), C.byref(tps), flags, q.numel(), *[C.c_void_p(t.data_ptr()) for t in cols],
-                C.c_void_p(out.dn_frz.data_ptr()), C.c_void_p(out.dq_frz.data_ptr()), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_liquid_freezing_rate", fam, q.device, C.byref(ice_params.c), C.byref(tps), flags, q.numel(),
+              *[C.c_void_p(t.data_ptr()) for t in cols], C.c_void_p(out.dn_frz.data_ptr()), C.c_void_p(out.dq_frz.data_ptr()), stream=stream)
     return out
 
 
@@ -135,11 +123,8 @@ def h2so4_solution(prs, tps, x_sulph, T, *, stream=None):
     """(CO.H2SO4_soln_saturation_vapor_pressure.(Ref(prs), x, T) [Pa], CO.a_w_xT.(Ref(prs), Ref(tps), x, T)) — src/Common.jl:188-246."""
     ref, fam = _cols1((x_sulph, T), ("x_sulph", "T"))
     p_sol, a_w = torch.empty_like(ref), torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_h2so4_solution_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(prs), C.byref(tps), ref.numel(), _ptr(x_sulph), _ptr(T), _ptr(p_sol), _ptr(a_w), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_h2so4_solution", fam, ref.device, C.byref(prs), C.byref(tps), ref.numel(), _ptr(x_sulph), _ptr(T), _ptr(p_sol), _ptr(a_w),
+              stream=stream)
     return p_sol, a_w
 
 
@@ -156,12 +141,8 @@ def mohler2006_deposition(dust, ip, S_i, T, dSi_dt=None, N_aer=None, *, stream=N
     frac = torch.empty_like(ref)
     rate = torch.empty_like(ref) if dSi_dt is not None else None
     nerr = torch.zeros(1, dtype=torch.int64, device=ref.device)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_mohler2006_deposition_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(dust), C.byref(ip), ref.numel(), _ptr(S_i), _ptr(T), _ptr(dSi_dt), _ptr(N_aer), _ptr(frac), _ptr(rate), _ptr(nerr),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_mohler2006_deposition", fam, ref.device, C.byref(dust), C.byref(ip), ref.numel(), _ptr(S_i), _ptr(T), _ptr(dSi_dt), _ptr(N_aer),
+              _ptr(frac), _ptr(rate), _ptr(nerr), stream=stream)
     return MohlerDeposition(frac, rate, nerr)
 
 
@@ -169,11 +150,7 @@ def deposition_J(dust, delta_a_w, *, stream=None) -> torch.Tensor:
     """CMI_het.deposition_J.(Ref(dust), Δa_w) [m⁻² s⁻¹] — src/IceNucleation.jl:81-102."""
     ref, fam = _cols1((delta_a_w,), ("delta_a_w",))
     J = torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_deposition_J_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(dust), ref.numel(), _ptr(delta_a_w), _ptr(J), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_deposition_J", fam, ref.device, C.byref(dust), ref.numel(), _ptr(delta_a_w), _ptr(J), stream=stream)
     return J
 
 
@@ -181,11 +158,7 @@ def INP_concentration_frequency(ip, INPC, T, *, stream=None) -> torch.Tensor:
     """CMI_het.INP_concentration_frequency.(Ref(ip), INPC, T) — src/IceNucleation.jl:219-226 (Frostenberg et al. 2023)."""
     ref, fam = _cols1((INPC, T), ("INPC", "T"))
     f = torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_inp_concentration_frequency_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ip), ref.numel(), _ptr(INPC), _ptr(T), _ptr(f), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_inp_concentration_frequency", fam, ref.device, C.byref(ip), ref.numel(), _ptr(INPC), _ptr(T), _ptr(f), stream=stream)
     return f
 
 
@@ -196,11 +169,8 @@ def _p3_counts(ip, T, N_l, V_l, dt, want_dep, want_het, stream):
         raise TypeError("ip must be the MorrisonMilbrandt2014 of the columns' float type")
     N_dep = torch.empty_like(ref) if want_dep else None
     N_het = torch.empty_like(ref) if want_het else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_ice_nucleation_counts_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ip), ref.numel(), _ptr(T), _ptr(N_l), _ptr(V_l), _ptr(dt), _ptr(N_dep), _ptr(N_het), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_ice_nucleation_counts", fam, ref.device, C.byref(ip), ref.numel(), _ptr(T), _ptr(N_l), _ptr(V_l), _ptr(dt), _ptr(N_dep),
+              _ptr(N_het), stream=stream)
     return N_dep, N_het
 
 

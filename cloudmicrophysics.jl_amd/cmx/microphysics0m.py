@@ -14,7 +14,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 from .parameters import Microphysics0MParams
 
 
@@ -33,11 +33,8 @@ def _call(p0m, q_lcl, q_icl, q_vap_sat, want, want_derivative, out, stream):
     else:
         _check_cols([ref, out], ["q_lcl", "out"])
     der = torch.empty_like(ref) if want_derivative else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_mp0m_tendencies_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(p0m), ref.numel(), _ptr(q_lcl), _ptr(q_icl), _ptr(q_vap_sat), _ptr(out), _ptr(der), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_mp0m_tendencies", fam, ref.device, C.byref(p0m), ref.numel(), _ptr(q_lcl), _ptr(q_icl), _ptr(q_vap_sat), _ptr(out), _ptr(der),
+              stream=stream)
     return out, der
 
 

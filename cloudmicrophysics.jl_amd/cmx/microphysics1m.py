@@ -17,7 +17,7 @@ from collections import namedtuple
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _fields_call, _ptr
+from ._cols import _check_cols, _fam_of, _fields_call, _ptr
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -91,25 +91,19 @@ def bulk_microphysics_tendencies_1m(mode, scheme, mp, tps, rho, T, q_tot, q_lcl,
         out = Tendencies1M(*[torch.empty_like(ref) for _ in range(4)])
     else:
         _check_cols([ref] + list(out), ["rho"] + ["out"] * 4)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
     if isinstance(mode, LinearizedAverage):
         if dt is None or not dt > 0 or int(nsub) < 1:
             raise ValueError("LinearizedAverage needs dt > 0 and nsub >= 1")
         if q_min is None:
             from .parameters import DEFAULT_PARAMETERS
             q_min = DEFAULT_PARAMETERS["specific_humidity_minimum"]
-        fn = getattr(_lib.lib(), f"cmx_mp1m_linearized_average_{fam.sfx}")
-        with torch.cuda.device(ref.device):
-            st = fn(C.byref(mp.c), C.byref(tps), mp.flags, q_min, dt, int(nsub), ref.numel(), *[_ptr(t) for t in cols],
-                    *[_ptr(o) for o in out], C.c_void_p(s.cuda_stream))
+        _lib.call("cmx_mp1m_linearized_average", fam, ref.device, C.byref(mp.c), C.byref(tps), mp.flags, q_min, dt, int(nsub), ref.numel(),
+                  *[_ptr(t) for t in cols], *[_ptr(o) for o in out], stream=stream)
     else:
         if dt is not None:
             raise TypeError("Instantaneous() takes no dt")
-        fn = getattr(_lib.lib(), f"cmx_mp1m_tendencies_{fam.sfx}")
-        with torch.cuda.device(ref.device):
-            st = fn(C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols], *[_ptr(o) for o in out],
-                    C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+        _lib.call("cmx_mp1m_tendencies", fam, ref.device, C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols],
+                  *[_ptr(o) for o in out], stream=stream)
     return out
 
 
@@ -148,11 +142,8 @@ def microphysics_source_terms_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_
     ref, fam = _prep(mp, tps, cols)
     outs = [torch.empty_like(ref) for _ in range(_abi.CMX_MP1M_NSRC)]
     arr = (C.c_void_p * _abi.CMX_MP1M_NSRC)(*[o.data_ptr() for o in outs])
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_mp1m_source_terms_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols], arr, C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_mp1m_source_terms", fam, ref.device, C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols], arr,
+              stream=stream)
     return SourceTerms1M(*outs)
 
 
@@ -171,12 +162,8 @@ def terminal_velocity_1m(mp, rho, q_rai=None, q_sno=None, *, chen=False, stream=
     mk = lambda on: torch.empty_like(ref) if on else None  # noqa: E731
     out = TerminalVelocities1M(mk(q_rai is not None), mk(q_sno is not None), mk(chen))
     ch = Chen2022VelTypeRain(fam.sfx) if chen else None
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_mp1m_terminal_velocity_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), C.byref(ch) if ch is not None else None, ref.numel(), _ptr(rho), _ptr(q_rai), _ptr(q_sno),
-                *[_ptr(o) for o in out], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_mp1m_terminal_velocity", fam, ref.device, C.byref(mp.c), C.byref(ch) if ch is not None else None, ref.numel(), _ptr(rho),
+              _ptr(q_rai), _ptr(q_sno), *[_ptr(o) for o in out], stream=stream)
     return out
 
 
@@ -198,13 +185,9 @@ def sedimentation_velocities(mp, stokes, chen_rain, chen_ice, rho, q_lcl=None, q
     if fam is not mp.fam:
         raise TypeError("parameter float type does not match the state columns")
     outs = [torch.empty_like(ref) if q is not None else None for q in qs]
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
     ref_or_null = lambda x: C.byref(x) if x is not None else None  # noqa: E731
-    fn = getattr(_lib.lib(), f"cmx_sedimentation_velocities_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), ref_or_null(stokes), ref_or_null(chen_rain), ref_or_null(chen_ice), ref.numel(), _ptr(rho),
-                *[_ptr(q) for q in qs], *[_ptr(o) for o in outs], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_sedimentation_velocities", fam, ref.device, C.byref(mp.c), ref_or_null(stokes), ref_or_null(chen_rain), ref_or_null(chen_ice),
+              ref.numel(), _ptr(rho), *[_ptr(q) for q in qs], *[_ptr(o) for o in outs], stream=stream)
     return SedimentationVelocities(*outs)
 
 
@@ -223,12 +206,8 @@ def snow_terminal_velocity(mp, chen_ice, rho, q_sno, snow_shape=None, *, stream=
     if not isinstance(chen_ice, fam.chen2022_ice_vel):
         raise TypeError(f"chen_ice: expected the {fam.chen2022_ice_vel.__name__} struct of the state's float type, got {type(chen_ice).__name__}")
     w = torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_snow_terminal_velocity_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), C.byref(chen_ice), shape._shape if shape is not None else _abi.CMX_SNOW_SHAPE_ASPR, ref.numel(), _ptr(rho),
-                _ptr(q_sno), _ptr(w), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_snow_terminal_velocity", fam, ref.device, C.byref(mp.c), C.byref(chen_ice),
+              shape._shape if shape is not None else _abi.CMX_SNOW_SHAPE_ASPR, ref.numel(), _ptr(rho), _ptr(q_sno), _ptr(w), stream=stream)
     return w
 
 
@@ -277,12 +256,7 @@ def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain,
     pr = [torch.empty(n_col, dtype=ref.dtype, device=ref.device) if precip else None for _ in range(2)]
     in_p = (C.c_void_p * 7)(*[c.data_ptr() for c in flat])
     out_p = (C.c_void_p * 4)(*[o.data_ptr() for o in out])
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_mp1m_column_tendencies_sedimentation_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain), C.byref(chen_ice), mp.flags | (shape._column_bit if shape else 0),
-                q_min if lin else 0.0,
-                dt if lin else 0.0, int(nsub) if lin else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_mp1m_column_tendencies_sedimentation", fam, ref.device, C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain),
+              C.byref(chen_ice), mp.flags | (shape._column_bit if shape else 0), q_min if lin else 0.0, dt if lin else 0.0, int(nsub) if lin else 0,
+              n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]), stream=stream)
     return ColumnStep1M(*out, *pr)

@@ -19,7 +19,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 NucleationRates = namedtuple("NucleationRates", ["binary", "ternary", "organic", "mixed"])
 PrescribedNucleationRates = namedtuple("PrescribedNucleationRates", ["organic", "mixed"])
@@ -63,12 +63,8 @@ def nucleation_rates(h2so4_params=None, organic_params=None, mixed_params=None, 
     op = _need(organic_params, fam.organic_nucleation, "organic_params") if "organic" in want else None
     mp = _need(mixed_params, fam.mixed_nucleation, "mixed_params") if "mixed" in want else None
     outs = {k: (torch.empty_like(ref) if k in want else None) for k in NucleationRates._fields}
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_aerosol_nucleation_rates_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(hp, op, mp, ref.numel(), *[_ptr(c if n in need else None) for n, c in zip(names, cols)],
-                *[_ptr(outs[k]) for k in NucleationRates._fields], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_aerosol_nucleation_rates", fam, ref.device, hp, op, mp, ref.numel(),
+              *[_ptr(c if n in need else None) for n, c in zip(names, cols)], *[_ptr(outs[k]) for k in NucleationRates._fields], stream=stream)
     return NucleationRates(*[outs[k] for k in NucleationRates._fields])
 
 
@@ -108,12 +104,8 @@ def nucleation_rates_prescribed(organic_params=None, mixed_params=None, *, negat
     op = _need(organic_params, fam.organic_nucleation, "organic_params") if "organic" in want else None
     mp = _need(mixed_params, fam.mixed_nucleation, "mixed_params") if "mixed" in want else None
     outs = {k: (torch.empty_like(ref) if k in want else None) for k in PrescribedNucleationRates._fields}
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_nucleation_rates_prescribed_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(op, mp, ref.numel(), *[_ptr(c if n in need else None) for n, c in zip(names, cols)], _ptr(outs["organic"]), _ptr(outs["mixed"]),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_nucleation_rates_prescribed", fam, ref.device, op, mp, ref.numel(), *[_ptr(c if n in need else None) for n, c in zip(names, cols)],
+              _ptr(outs["organic"]), _ptr(outs["mixed"]), stream=stream)
     return PrescribedNucleationRates(outs["organic"], outs["mixed"])
 
 
@@ -135,9 +127,5 @@ def apparent_nucleation_rate(output_diam, nucleation_rate, condensation_growth_r
         raise ValueError("every column but input_diam is required")
     ref, fam = _cols(cols, names)
     J = torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_apparent_nucleation_rate_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(ref.numel(), *[_ptr(c) for c in cols], _ptr(J), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_apparent_nucleation_rate", fam, ref.device, ref.numel(), *[_ptr(c) for c in cols], _ptr(J), stream=stream)
     return J

@@ -14,7 +14,7 @@ from collections import namedtuple
 import torch
 
 from . import _abi, _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 from .parameters import ParametersP3
 
 P3Shape = namedtuple("P3Shape", ["F_rim", "rho_rim", "log_lambda", "D_m", "log_N0"])
@@ -46,13 +46,8 @@ def p3_shape(params: ParametersP3, rho_q_ice, rho_n_ice, x3, x4, *, from_state=F
         raise ValueError(f"unknown output(s) {sorted(unknown)}")
     outs = {k: (torch.empty_like(ref) if k in want else None) for k in P3Shape._fields}
     flags = params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_shape_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params.c), flags, int(brent_iters), ref.numel(), *[_ptr(t) for t in cols[:4]],
-                _ptr(log_lambda_guess) if log_lambda_guess is not None else None,
-                *[_ptr(outs[k]) for k in P3Shape._fields], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_shape", fam, ref.device, C.byref(params.c), flags, int(brent_iters), ref.numel(), *[_ptr(t) for t in cols[:4]],
+              _ptr(log_lambda_guess) if log_lambda_guess is not None else None, *[_ptr(outs[k]) for k in P3Shape._fields], stream=stream)
     return P3Shape(*[outs[k] for k in P3Shape._fields])
 
 
@@ -84,12 +79,8 @@ def p3_terminal_velocities(params: ParametersP3, velocity_params, rho_air, rho_q
         raise ValueError(f"unknown output(s) {sorted(unknown)}")
     outs = {k: (torch.empty_like(ref) if k in want else None) for k in P3Velocities._fields}
     flags = params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0) | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_terminal_velocities_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags, p, ref.numel(), *[_ptr(t) for t in cols],
-                _ptr(outs["v_n"]), _ptr(outs["v_m"]), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_terminal_velocities", fam, ref.device, C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags, p, ref.numel(),
+              *[_ptr(t) for t in cols], _ptr(outs["v_n"]), _ptr(outs["v_m"]), stream=stream)
     return P3Velocities(outs["v_n"], outs["v_m"])
 
 
@@ -118,12 +109,8 @@ def p3_shape_and_terminal_velocities(params: ParametersP3, velocity_params, rho_
         raise TypeError("quadrature float type does not match the state columns")
     out = P3ShapeVelocities(*[torch.empty_like(ref) for _ in range(4)])
     flags = params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0) | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_shape_terminal_velocities_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags, int(brent_iters), p, ref.numel(), *[_ptr(t) for t in cols],
-                _ptr(guess), *[_ptr(t) for t in out], C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_shape_terminal_velocities", fam, ref.device, C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags,
+              int(brent_iters), p, ref.numel(), *[_ptr(t) for t in cols], _ptr(guess), *[_ptr(t) for t in out], stream=stream)
     return out
 
 
@@ -149,12 +136,8 @@ def p3_ice_melt(params: ParametersP3, velocity_params, aps, tps, vent, T, rho_ai
         raise TypeError("quadrature float type does not match the state columns")
     out = P3Melt(torch.empty_like(ref), torch.empty_like(ref))
     flags = params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0) | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_ice_melt_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params.c), C.byref(velocity_params), C.byref(aps), C.byref(tps), C.byref(vent), C.byref(quad), flags, p,
-                ref.numel(), *[_ptr(t) for t in cols], _ptr(out.dNdt), _ptr(out.dLdt), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_ice_melt", fam, ref.device, C.byref(params.c), C.byref(velocity_params), C.byref(aps), C.byref(tps), C.byref(vent),
+              C.byref(quad), flags, p, ref.numel(), *[_ptr(t) for t in cols], _ptr(out.dNdt), _ptr(out.dLdt), stream=stream)
     return out
 
 
@@ -177,12 +160,8 @@ def p3_ice_self_collection(params: ParametersP3, velocity_params, rho_air, rho_q
         raise TypeError("quadrature float type does not match the state columns")
     out = torch.empty_like(ref)
     flags = params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0) | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_ice_self_collection_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags, ref.numel(), *[_ptr(t) for t in cols], _ptr(out),
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_ice_self_collection", fam, ref.device, C.byref(params.c), C.byref(velocity_params), C.byref(quad), flags, ref.numel(),
+              *[_ptr(t) for t in cols], _ptr(out), stream=stream)
     return out
 
 
@@ -212,12 +191,8 @@ def p3_liquid_ice_collisions(ice_params, aps, tps, rho_air, T, rho_q_ice, rho_n_
     src_p = (C.c_void_p * 7)(*[t.data_ptr() for t in src.values()])
     rates_p = (C.c_void_p * 10)(*[t.data_ptr() for t in rates.values()]) if want_rates else None
     flags = ice_params.flags | (_abi.CMX_P3_INPUT_IS_STATE if from_state else 0) | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_liquid_ice_collisions_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(ice_params.c), C.byref(aps), C.byref(tps), C.byref(quad), flags, ref.numel(), *[_ptr(t) for t in cols], src_p, rates_p,
-                C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_liquid_ice_collisions", fam, ref.device, C.byref(ice_params.c), C.byref(aps), C.byref(tps), C.byref(quad), flags, ref.numel(),
+              *[_ptr(t) for t in cols], src_p, rates_p, stream=stream)
     return (src, rates) if want_rates else src
 
 
@@ -233,9 +208,6 @@ def p3_het_ice_nucleation(aerosol, tps, q_lcl, N_lcl, RH, T, rho_air, *, stream=
     if not isinstance(aerosol, fam.abifm_dust) or not isinstance(tps, fam.thermo):
         raise TypeError("parameter float type does not match the state columns")
     out = P3HetNucleation(torch.empty_like(ref), torch.empty_like(ref))
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_p3_het_ice_nucleation_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(C.byref(aerosol), C.byref(tps), ref.numel(), *[_ptr(t) for t in cols], _ptr(out.dNdt), _ptr(out.dLdt), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_p3_het_ice_nucleation", fam, ref.device, C.byref(aerosol), C.byref(tps), ref.numel(), *[_ptr(t) for t in cols], _ptr(out.dNdt),
+              _ptr(out.dLdt), stream=stream)
     return out

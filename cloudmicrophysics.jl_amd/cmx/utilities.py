@@ -7,13 +7,12 @@
 The kernels behind them call the same device routines as the P3 shape solver, the quantile bounds and the collision integrals."""
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import torch
 
 from . import _lib
-from .bulk_tendencies import _check_cols, _fam_of, _ptr
+from ._cols import _check_cols, _fam_of, _ptr
 
 GammaInc = namedtuple("GammaInc", ["P", "Q"])
 
@@ -23,11 +22,7 @@ def gamma_inc(a: torch.Tensor, x: torch.Tensor, *, stream=None) -> GammaInc:
     ref = _check_cols([a, x], ["a", "x"])
     fam = _fam_of(ref)
     out = GammaInc(torch.empty_like(ref), torch.empty_like(ref))
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_gamma_inc_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(ref.numel(), _ptr(a), _ptr(x), _ptr(out.P), _ptr(out.Q), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_gamma_inc", fam, ref.device, ref.numel(), _ptr(a), _ptr(x), _ptr(out.P), _ptr(out.Q), stream=stream)
     return out
 
 
@@ -36,9 +31,5 @@ def gamma_inc_inv(a: torch.Tensor, p: torch.Tensor, q: torch.Tensor, *, stream=N
     ref = _check_cols([a, p, q], ["a", "p", "q"])
     fam = _fam_of(ref)
     out = torch.empty_like(ref)
-    s = stream if stream is not None else torch.cuda.current_stream(ref.device)
-    fn = getattr(_lib.lib(), f"cmx_gamma_inc_inv_{fam.sfx}")
-    with torch.cuda.device(ref.device):
-        st = fn(ref.numel(), _ptr(a), _ptr(p), _ptr(q), _ptr(out), C.c_void_p(s.cuda_stream))
-    _lib.check(fn.__name__, st)
+    _lib.call("cmx_gamma_inc_inv", fam, ref.device, ref.numel(), _ptr(a), _ptr(p), _ptr(q), _ptr(out), stream=stream)
     return out

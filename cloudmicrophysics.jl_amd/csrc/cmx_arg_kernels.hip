@@ -115,18 +115,16 @@ __global__ __launch_bounds__(kArgBS) void arg_activation_kernel(const ArgConsts<
 template <typename FT, int NM, bool SINKS>
 static void launch_arg(const ArgConsts<FT> &c, const ArgIO<FT> &io0, int64_t n, const void *const *ptrs, int nptrs, hipStream_t s) {
     constexpr int VEC = Math<FT>::VEC;
-    auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
     for_each_range<FT, VEC>(ptrs, nptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
         ArgIO<FT> io = io0;
         io.T += lo; io.p += lo; io.w += lo; io.q_tot += lo;
-        io.q_liq = off(io.q_liq, lo); io.q_ice = off(io.q_ice, lo); io.N_liq = off(io.N_liq, lo); io.N_ice = off(io.N_ice, lo);
-        io.S_max = off(io.S_max, lo); io.N_tot = off(io.N_tot, lo); io.M_tot = off(io.M_tot, lo);
-        for (int j = 0; j < CMX_ARG_MAX_MODES; ++j) { io.N_act[j] = off(io.N_act[j], lo); io.M_act[j] = off(io.M_act[j], lo); }
+        io.q_liq = shift(io.q_liq, lo); io.q_ice = shift(io.q_ice, lo); io.N_liq = shift(io.N_liq, lo); io.N_ice = shift(io.N_ice, lo);
+        io.S_max = shift(io.S_max, lo); io.N_tot = shift(io.N_tot, lo); io.M_tot = shift(io.M_tot, lo);
+        for (int j = 0; j < CMX_ARG_MAX_MODES; ++j) { io.N_act[j] = shift(io.N_act[j], lo); io.M_act[j] = shift(io.M_act[j], lo); }
         const int64_t nv = count / V;
-        const dim3 grid((unsigned)((nv + kArgBS - 1) / kArgBS));
-        if (io.want_N && !io.want_M) hipLaunchKernelGGL((arg_activation_kernel<FT, NM, SINKS, V, true>), grid, dim3(kArgBS), 0, s, c, io, nv);
-        else hipLaunchKernelGGL((arg_activation_kernel<FT, NM, SINKS, V, false>), grid, dim3(kArgBS), 0, s, c, io, nv);
+        if (io.want_N && !io.want_M) launch<kArgBS>(arg_activation_kernel<FT, NM, SINKS, V, true>, nv, s, c, io, nv);
+        else launch<kArgBS>(arg_activation_kernel<FT, NM, SINKS, V, false>, nv, s, c, io, nv);
     });
 }
 
@@ -134,9 +132,8 @@ template <typename FT, typename AP, typename AD, typename AI, typename TH>
 static int32_t arg_entry(const AP *ap, const AD *ad, const AI *aip, const TH *tps, int64_t n, const FT *T, const FT *p,
                          const FT *w, const FT *q_tot, const FT *q_liq, const FT *q_ice, const FT *N_liq, const FT *N_ice,
                          FT *const *N_act, FT *const *M_act, FT *S_max, void *stream, FT *N_tot = nullptr, FT *M_tot = nullptr) {
-    if (!ap || !ad || !aip || !tps || n < 0 || ad->n_modes < 1 || ad->n_modes > CMX_ARG_MAX_MODES) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!ap || !ad || !aip || !tps || ad->n_modes < 1 || ad->n_modes > CMX_ARG_MAX_MODES) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!T || !p || !w || !q_tot) return CMX_ERR_BAD_ARG;
     const ArgConsts<FT> c = make_arg_consts<FT>(*ap, *ad, *aip, *tps);
     ArgIO<FT> io{};
@@ -164,8 +161,7 @@ static int32_t arg_entry(const AP *ap, const AD *ad, const AI *aip, const TH *tp
         default: return CMX_ERR_BAD_ARG;
     }
 #undef CMX_ARG_CASE
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // ---- aerosol that varies in space: mode descriptors are columns (test/gpu_tests.jl:45-79) --------------------------------
@@ -287,22 +283,20 @@ static void launch_arg_columns(const ArgConsts<FT> &c, const ArgColPar<FT> &par,
                                const void *const *ptrs, int nptrs, hipStream_t s) {
     // Float64 runs one point per lane: the kernel is VALU-bound there and the second point's kept values would cost a wave per SIMD
     constexpr int VEC = sizeof(FT) == 4 ? Math<FT>::VEC : 1;
-    auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
     for_each_range<FT, VEC>(ptrs, nptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
         ArgIO<FT> io = io0;
         ArgColIO<FT> mc = mc0;
         io.T += lo; io.p += lo; io.w += lo; io.q_tot += lo;
-        io.q_liq = off(io.q_liq, lo); io.q_ice = off(io.q_ice, lo); io.N_liq = off(io.N_liq, lo); io.N_ice = off(io.N_ice, lo);
-        io.S_max = off(io.S_max, lo);
+        io.q_liq = shift(io.q_liq, lo); io.q_ice = shift(io.q_ice, lo); io.N_liq = shift(io.N_liq, lo); io.N_ice = shift(io.N_ice, lo);
+        io.S_max = shift(io.S_max, lo);
         for (int j = 0; j < NM; ++j) {
-            io.N_act[j] = off(io.N_act[j], lo); io.M_act[j] = off(io.M_act[j], lo);
-            mc.r_dry[j] += lo; mc.stdev[j] += lo; mc.N[j] += lo; mc.hyg[j] += lo; mc.mmix[j] = off(mc.mmix[j], lo);
+            io.N_act[j] = shift(io.N_act[j], lo); io.M_act[j] = shift(io.M_act[j], lo);
+            mc.r_dry[j] += lo; mc.stdev[j] += lo; mc.N[j] += lo; mc.hyg[j] += lo; mc.mmix[j] = shift(mc.mmix[j], lo);
         }
         const int64_t nv = count / V;
-        const dim3 grid((unsigned)((nv + kArgColBS<FT> - 1) / kArgColBS<FT>));
-        if (!io.want_M) hipLaunchKernelGGL((arg_activation_columns_kernel<FT, NM, SINKS, V, true>), grid, dim3(kArgColBS<FT>), 0, s, c, par, io, mc, nv);
-        else hipLaunchKernelGGL((arg_activation_columns_kernel<FT, NM, SINKS, V, false>), grid, dim3(kArgColBS<FT>), 0, s, c, par, io, mc, nv);
+        if (!io.want_M) launch<kArgColBS<FT>>(arg_activation_columns_kernel<FT, NM, SINKS, V, true>, nv, s, c, par, io, mc, nv);
+        else launch<kArgColBS<FT>>(arg_activation_columns_kernel<FT, NM, SINKS, V, false>, nv, s, c, par, io, mc, nv);
     });
 }
 
@@ -311,9 +305,8 @@ static int32_t arg_columns_entry(const AP *ap, const AI *aip, const TH *tps, int
                                  const FT *w, const FT *q_tot, const FT *q_liq, const FT *q_ice, const FT *N_liq, const FT *N_ice,
                                  const FT *const *r_dry, const FT *const *stdev, const FT *const *N_mode, const FT *const *hyg,
                                  const FT *const *mmix, FT *const *N_act, FT *const *M_act, FT *S_max, void *stream) {
-    if (!ap || !aip || !tps || n < 0 || n_modes < 1 || n_modes > CMX_ARG_MAX_MODES) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!ap || !aip || !tps || n_modes < 1 || n_modes > CMX_ARG_MAX_MODES) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!T || !p || !w || !q_tot || !r_dry || !stdev || !N_mode || !hyg) return CMX_ERR_BAD_ARG;
     if (M_act && !mmix) return CMX_ERR_BAD_ARG;
     // thermodynamic / parameter constants from the shared builder with an empty distribution
@@ -348,8 +341,7 @@ static int32_t arg_columns_entry(const AP *ap, const AI *aip, const TH *tps, int
         default: return CMX_ERR_BAD_ARG;
     }
 #undef CMX_ARGC_CASE
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

@@ -108,10 +108,9 @@ static int32_t column_sums(int32_t ncols, const FT *const *cols, int64_t n, doub
     if (!workspace) return CMX_ERR_BAD_ARG;
     int64_t chunk = (n + CMX_COLUMN_SUMS_PARTIALS - 1) / CMX_COLUMN_SUMS_PARTIALS;
     chunk = (chunk + 1023) / 1024 * 1024;
-    hipLaunchKernelGGL((column_partials_kernel<FT>), dim3(CMX_COLUMN_SUMS_PARTIALS, (unsigned)ncols), dim3(kBlock), 0, s, a, n, chunk, workspace);
-    hipLaunchKernelGGL(column_finish_kernel, dim3((unsigned)ncols), dim3(kBlock), 0, s, workspace, sums);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch_grid(column_partials_kernel<FT>, dim3(CMX_COLUMN_SUMS_PARTIALS, (unsigned)ncols), dim3(kBlock), 0, s, a, n, chunk, workspace);
+    launch_grid(column_finish_kernel, dim3((unsigned)ncols), dim3(kBlock), 0, s, static_cast<const double *>(workspace), sums);
+    return launched();
 }
 
 }  // namespace cmx

@@ -122,8 +122,8 @@ __global__ __launch_bounds__(kBlock) void cloud_diagnostics_kernel(const DiagCon
 template <typename FT, typename RN, typename PC, typename PR>
 static int32_t cloud_diagnostics_entry(const RN *rain, const PC *pdf_c, const PR *pdf_r, FT rho_w, uint32_t flags, int64_t n, const FT *rho, const FT *q_lcl,
                                        const FT *q_rai, const FT *N_lcl, const FT *N_rai, FT *Z_1m, FT *Z_2m, FT *reff_2m, FT *reff_lh97, void *stream) {
-    if (n < 0 || (flags & ~(uint32_t)CMX_SB2006_LIMITED)) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
+    if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (!Z_1m && !Z_2m && !reff_2m && !reff_lh97) return CMX_ERR_BAD_ARG;
     if ((Z_1m && !rain) || ((Z_2m || reff_2m) && (!pdf_c || !pdf_r)) || (reff_lh97 && !(rho_w > FT(0)))) return CMX_ERR_BAD_ARG;
     const bool limited = flags & CMX_SB2006_LIMITED;
@@ -178,15 +178,13 @@ static int32_t cloud_diagnostics_entry(const RN *rain, const PC *pdf_c, const PR
     const void *ptrs[] = {rho, q_lcl, q_rai, N_lcl, N_rai, Z_1m, Z_2m, reff_2m, reff_lh97};
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        auto off = [lo](auto *p) { return p ? p + lo : p; };
-        const DiagIO<FT> io{rho + lo, off(q_lcl), off(q_rai), off(N_lcl), off(N_rai), off(Z_1m), off(Z_2m), off(reff_2m), off(reff_lh97)};
+        const DiagIO<FT> io{rho + lo, shift(q_lcl, lo), shift(q_rai, lo), shift(N_lcl, lo), shift(N_rai, lo), shift(Z_1m, lo), shift(Z_2m, lo),
+                            shift(reff_2m, lo), shift(reff_lh97, lo)};
         const int64_t nvec = count / V;
-        const dim3 grid((unsigned)((nvec + kBlock - 1) / kBlock));
-        if (limited) hipLaunchKernelGGL((cloud_diagnostics_kernel<FT, V, true>), grid, dim3(kBlock), 0, s, c, io, lh_defaults, nvec);
-        else hipLaunchKernelGGL((cloud_diagnostics_kernel<FT, V, false>), grid, dim3(kBlock), 0, s, c, io, lh_defaults, nvec);
+        if (limited) launch<kBlock>(cloud_diagnostics_kernel<FT, V, true>, nvec, s, c, io, lh_defaults, nvec);
+        else launch<kBlock>(cloud_diagnostics_kernel<FT, V, false>, nvec, s, c, io, lh_defaults, nvec);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

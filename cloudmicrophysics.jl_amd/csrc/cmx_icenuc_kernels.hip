@@ -198,9 +198,8 @@ template <typename FT, typename TH, typename DU, typename KO, typename HS>
 static int32_t icenuc_entry(const TH *tps, const DU *dust, const KO *koop, const HS *h2so4, bool from_x, uint32_t flags, int64_t n, const FT *T,
                             const FT *a_w, const FT *r, FT *delta_a_w, FT *J_het, FT *J_hom, FT *rate_het, FT *rate_hom,
                             int64_t *n_domain_errors, void *stream) {
-    if (!tps || !dust || !koop || n < 0 || (flags & ~CMX_ICENUC_HOM_LINEAR) || (from_x && !h2so4)) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!tps || !dust || !koop || (flags & ~CMX_ICENUC_HOM_LINEAR) || (from_x && !h2so4)) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!T || !a_w || ((rate_het || rate_hom) && !r)) return CMX_ERR_BAD_ARG;
     IceNucConsts<FT> c = make_icenuc_consts<FT>(*tps, dust, koop);
     if (from_x) add_h2so4_consts<FT>(c, *h2so4);
@@ -208,41 +207,35 @@ static int32_t icenuc_entry(const TH *tps, const DU *dust, const KO *koop, const
     constexpr int VEC = Math<FT>::VEC;
     const void *ptrs[] = {T, a_w, r, delta_a_w, J_het, J_hom, rate_het, rate_hom};
     const bool linear = flags & CMX_ICENUC_HOM_LINEAR;
-    auto off = [](auto *p, int64_t lo) { return p ? p + lo : p; };
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        IceNucIO<FT> io{T + lo, a_w + lo, off(r, lo), off(delta_a_w, lo), off(J_het, lo), off(J_hom, lo),
-                        off(rate_het, lo), off(rate_hom, lo), reinterpret_cast<unsigned long long *>(n_domain_errors)};
+        IceNucIO<FT> io{T + lo, a_w + lo, shift(r, lo), shift(delta_a_w, lo), shift(J_het, lo), shift(J_hom, lo),
+                        shift(rate_het, lo), shift(rate_hom, lo), reinterpret_cast<unsigned long long *>(n_domain_errors)};
         const int64_t nv = count / V;
-        const unsigned grid = (unsigned)((nv + kBlock - 1) / kBlock);
         const bool rates_only = !delta_a_w && !J_het && !J_hom && rate_het && rate_hom;
         if (from_x) {   // the solution-droplet input mode: one instantiation per homogeneous-rate form
-            if (linear) hipLaunchKernelGGL((ice_nucleation_kernel<FT, true, V, false, true>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
-            else hipLaunchKernelGGL((ice_nucleation_kernel<FT, false, V, false, true>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
+            if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V, false, true>, nv, s, c, io, nv);
+            else launch<kBlock>(ice_nucleation_kernel<FT, false, V, false, true>, nv, s, c, io, nv);
         } else if (rates_only) {
-            if (linear) hipLaunchKernelGGL((ice_nucleation_kernel<FT, true, V, true>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
-            else hipLaunchKernelGGL((ice_nucleation_kernel<FT, false, V, true>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
-        } else if (linear) hipLaunchKernelGGL((ice_nucleation_kernel<FT, true, V>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
-        else hipLaunchKernelGGL((ice_nucleation_kernel<FT, false, V>), dim3(grid), dim3(kBlock), 0, s, c, io, nv);
+            if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V, true>, nv, s, c, io, nv);
+            else launch<kBlock>(ice_nucleation_kernel<FT, false, V, true>, nv, s, c, io, nv);
+        } else if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V>, nv, s, c, io, nv);
+        else launch<kBlock>(ice_nucleation_kernel<FT, false, V>, nv, s, c, io, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 template <typename FT, typename TH>
 static int32_t water_activity_entry(const TH *tps, int64_t n, const FT *T, const FT *e, FT *a_w_ice, FT *a_w_eT,
                                     void *stream) {
-    if (!tps || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!tps) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!T || (a_w_eT && !e)) return CMX_ERR_BAD_ARG;
     const IceNucConsts<FT> c =
         make_icenuc_consts<FT>(*tps, (const cmx_abifm_dust_f64 *)nullptr, (const cmx_koop2000_f64 *)nullptr);
     WaterActIO<FT> io{T, e, a_w_ice, a_w_eT};
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL((water_activity_kernel<FT>), dim3(grid), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), c, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(water_activity_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
+    return launched();
 }
 
 // P3.het_ice_nucleation(aerosol, tps, q_lcl, N_lcl, RH, T, ρₐ) — src/P3_processes.jl:20-46: ABIFM immersion freezing on an assumed
@@ -266,16 +259,13 @@ __global__ __launch_bounds__(kBlock) void p3_het_nucleation_kernel(const IceNucC
 template <typename FT, typename TH, typename DU>
 static int32_t p3_het_nucleation_entry(const DU *dust, const TH *tps, int64_t n, const FT *q_lcl, const FT *N_lcl, const FT *RH, const FT *T,
                                        const FT *rho, FT *dNdt, FT *dLdt, void *stream) {
-    if (!dust || !tps || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!dust || !tps) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q_lcl || !N_lcl || !RH || !T || !rho || (!dNdt && !dLdt)) return CMX_ERR_BAD_ARG;
     using KO = std::conditional_t<std::is_same_v<FT, float>, cmx_koop2000_f32, cmx_koop2000_f64>;
     const IceNucConsts<FT> c = make_icenuc_consts<FT>(*tps, dust, (const KO *)nullptr);
-    hipLaunchKernelGGL((p3_het_nucleation_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), c, q_lcl, N_lcl, RH, T, rho, dNdt, dLdt, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(p3_het_nucleation_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, q_lcl, N_lcl, RH, T, rho, dNdt, dLdt, n);
+    return launched();
 }
 
 // ---- round 3: the remaining public functions of the subsystems this library replaces (VERDICT r02 row g) ------------------------------
@@ -352,56 +342,46 @@ __global__ __launch_bounds__(kBlock) void inp_frequency_kernel(const InpFreqCons
 
 template <typename FT, typename HS, typename TH>
 static int32_t h2so4_entry(const HS *prs, const TH *tps, int64_t n, const FT *x, const FT *T, FT *p_sol, FT *a_w, void *stream) {
-    if (!prs || n < 0 || (a_w && !tps) || (!p_sol && !a_w)) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if (!prs || (a_w && !tps) || (!p_sol && !a_w)) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!x || !T) return CMX_ERR_BAD_ARG;
     IceNucConsts<FT> c{};
     if (tps) c = make_icenuc_consts<FT>(*tps, (const cmx_abifm_dust_f64 *)nullptr, (const cmx_koop2000_f64 *)nullptr);
     add_h2so4_consts<FT>(c, *prs);
-    hipLaunchKernelGGL((h2so4_solution_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), c,
-                       x, T, p_sol, a_w, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(h2so4_solution_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, x, T, p_sol, a_w, n);
+    return launched();
 }
 template <typename FT, typename DU, typename IP>
 static int32_t mohler_entry(const DU *dust, const IP *ip, int64_t n, const FT *S_i, const FT *T, const FT *dSi_dt, const FT *N_aer, FT *act_frac,
                             FT *dep_rate, int64_t *n_err, void *stream) {
-    if (!dust || !ip || n < 0 || (!act_frac && !dep_rate)) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if (!dust || !ip || (!act_frac && !dep_rate)) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!S_i || !T || (dep_rate && (!dSi_dt || !N_aer))) return CMX_ERR_BAD_ARG;
     const double l2e = 1.4426950408889634074;
     const MohlerConsts<FT> c{(FT)ip->S_i_max, (FT)ip->T_thr, (FT)dust->S0_warm, (FT)dust->S0_cold, (FT)((double)dust->a_warm * l2e),
                              (FT)((double)dust->a_cold * l2e), (FT)dust->a_warm, (FT)dust->a_cold};
-    hipLaunchKernelGGL((mohler_deposition_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
-                       c, S_i, T, dSi_dt, N_aer, act_frac, dep_rate, reinterpret_cast<unsigned long long *>(n_err), n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(mohler_deposition_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream),
+                   c, S_i, T, dSi_dt, N_aer, act_frac, dep_rate, reinterpret_cast<unsigned long long *>(n_err), n);
+    return launched();
 }
 template <typename FT, typename DU> static int32_t deposition_J_entry(const DU *dust, int64_t n, const FT *d, FT *J, void *stream) {
-    if (!dust || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if (!dust) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!d || !J) return CMX_ERR_BAD_ARG;
     const double l2_10 = 3.3219280948873623479;
-    hipLaunchKernelGGL((deposition_J_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream),
-                       (FT)((double)dust->deposition_m * l2_10), (FT)(((double)dust->deposition_c + 4.0) * l2_10), d, J, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(deposition_J_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream),
+                   (FT)((double)dust->deposition_m * l2_10), (FT)(((double)dust->deposition_c + 4.0) * l2_10), d, J, n);
+    return launched();
 }
 template <typename FT, typename IP> static int32_t inp_frequency_entry(const IP *ip, int64_t n, const FT *INPC, const FT *T, FT *freq, void *stream) {
-    if (!ip || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if (!ip) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!INPC || !T || !freq) return CMX_ERR_BAD_ARG;
     const double l2e = 1.4426950408889634074, pi = 3.14159265358979323846, two_s2 = 2.0 * (double)ip->sigma * (double)ip->sigma;
     const InpFreqConsts<FT> c{(FT)ip->T_freeze, (FT)((double)ip->b / 10.0), (FT)ip->log_a, (FT)0.69314718055994530942, (FT)(l2e / two_s2),
                               (FT)(1.0 / std::sqrt(pi * two_s2))};
-    hipLaunchKernelGGL((inp_frequency_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), c,
-                       INPC, T, freq, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(inp_frequency_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, INPC, T, freq, n);
+    return launched();
 }
 
 }  // namespace cmx

@@ -24,13 +24,22 @@ void set_hip_error(hipError_t e, const char *where);   // cmx_common.hip
         }                                                 \
     } while (0)
 
+// The epilogue of every entry that launched: `return launched();` reports a failed launch as CMX_ERR_HIP (where-text for cmx_last_hip_error()).
+inline int32_t launched() {
+    CMX_HIP_TRY(hipGetLastError());
+    return CMX_OK;
+}
+
 // --- geometry ------------------------------------------------------------------------------
 // MI355X: 256 CUs in 8 XCDs.  The streaming kernels are NON-persistent: one short-lived workgroup per tile
 // (256 lanes; 128 for the SB2006 sweep), one lane owns 16 bytes of every column, so the grid is ≫ 256 workgroups and
 // workgroup b lands on XCD b % 8 — consecutive workgroups stream consecutive tiles and each XCD L2 sees a disjoint,
 // dense address set.  (A grid-stride loop over CUs × k resident workgroups was measured slower with 13 concurrent
-// streams, DESIGN.md §4: every wave of the chip sits in the same load → compute → store phase.)  `grid_for` (capped,
-// grid-stride) is kept for the reduction kernel only; `tile_grid` sizes and range-checks the one-workgroup-per-tile grids.
+// streams, DESIGN.md §4: every wave of the chip sits in the same load → compute → store phase.)
+// Who sizes which grid: launch() below sizes the one-lane-per-item grids of the point kernels and the layout adapters with
+// tile_grid; `grid_for` (capped, grid-stride) sizes sb2006_process_kernel only.  A geometry of their own have the column-sum
+// reduction (fixed 2-D grid, cmx_common.hip), the column kernels (tiles that overlap by one lane, cmx_*_column.hip) and the P3
+// collision kernels (collision_geometry with dynamic LDS, cmx_p3_collisions.hip).
 constexpr int kBlock = 256;
 
 struct DeviceInfo { int cus; int blocks_per_cu; };
@@ -44,18 +53,45 @@ inline int grid_for(int64_t work_items, int items_per_block = kBlock) {
     return (int)(g < 1 ? 1 : g);
 }
 
-// Number of workgroups for `work_items` items at `items_per_block` each, or -1 if that exceeds what one launch can
-// express (HIP: 2^31 − 1 workgroups in x).  Callers return CMX_ERR_UNSUPPORTED instead of silently truncating the grid.
-inline int64_t tile_grid(int64_t work_items, int64_t items_per_block) {
-    const int64_t g = (work_items + items_per_block - 1) / items_per_block;
-    return g > (int64_t)0x7fffffff ? -1 : (g < 1 ? 1 : g);
-}
-
 // Upper bound on the points / states of ONE call, checked by every entry point (CMX_ERR_UNSUPPORTED above it): the streaming kernels give a
 // workgroup at least 16 points, so n ≤ 16·(2^31 − 1) ≈ 3.4e10 keeps their grids inside HIP's 2^31 − 1 workgroups; at ≥ 12 B per point that is
 // beyond the 288 GB of HBM anyway.  The P3 collision kernels have SMALLER tiles (Float32: 64-lane workgroups = 8 states at 8 lanes per state, 4 at
 // 16) and check their own rounded-up tile count (collision_geometry, cmx_p3_collisions.hip): CMX_ERR_UNSUPPORTED above 8·(2^31 − 8) resp. 4·(…) states.
 constexpr int64_t kMaxPoints = 16ll * 0x7fffffffll;
+
+// The point-count rule of the entry points: n < 0 → CMX_ERR_BAD_ARG, n > kMaxPoints → CMX_ERR_UNSUPPORTED (one launch cannot express the
+// grid), n == 0 → CMX_OK.  An entry that validates more arguments before it returns for n == 0 uses CMX_TRY_COUNT_LIMIT and tests n == 0 itself.
+inline int32_t count_limit_status(int64_t n) { return n < 0 ? CMX_ERR_BAD_ARG : n > kMaxPoints ? CMX_ERR_UNSUPPORTED : CMX_OK; }
+#define CMX_TRY_COUNT_LIMIT(n)                                                    \
+    do {                                                                          \
+        if (const int32_t st_ = ::cmx::count_limit_status(n)) return st_;         \
+    } while (0)
+#define CMX_TRY_COUNT(n)                                                          \
+    do {                                                                          \
+        CMX_TRY_COUNT_LIMIT(n);                                                   \
+        if ((n) == 0) return CMX_OK;                                              \
+    } while (0)
+
+// Workgroups for `lanes` lanes at `bs` each.  launch() passes at most kMaxPoints lanes (the count rule) at bs ≥ 16, which stays within HIP's
+// 2^31 − 1 workgroups in x.
+inline int64_t tile_grid(int64_t lanes, int64_t bs) { return (lanes + bs - 1) / bs; }
+
+// Every launch goes through these two.  The arguments must have exactly the kernel's parameter types (after decay): no conversion happens
+// at the launch, and a kernel whose Float64 instantiation reads its constants through front_consts() (cmx_math.hpp) from the start of the
+// kernel-argument segment cannot be called with the constants struct anywhere but first.
+// launch_grid: a geometry of the caller's own (kernel<<<grid, block, lds, stream>>>(args...)).
+template <typename... P, typename... A>
+inline void launch_grid(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A &...args) {
+    static_assert(sizeof...(P) == sizeof...(A) && (std::is_same_v<std::remove_cv_t<P>, std::decay_t<A>> && ...),
+                  "launch arguments must have the kernel's parameter types");
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
+// launch<BS>: one lane per item, kernel<<<tile_grid(lanes, BS), BS, 0, stream>>>(args...).
+template <int BS, typename... P, typename... A>
+inline void launch(void (*kernel)(P...), int64_t lanes, hipStream_t stream, const A &...args) {
+    static_assert(BS >= 16, "kMaxPoints assumes at least 16 lanes per workgroup");
+    launch_grid(kernel, dim3((unsigned)tile_grid(lanes, BS)), dim3(BS), 0, stream, args...);
+}
 
 // The two heaviest Float64 kernels (SB2006, 1-moment) run one point per lane (8-byte loads) instead of two (16-byte): they are
 // VALU-bound, not HBM-bound, and the two-points-per-lane variants spend VALU instructions on SGPR-spill traffic for the 2-SGPR
@@ -83,6 +119,9 @@ template <typename FT, int VEC, size_t N, typename F>
 inline void for_each_range(const void *const (&cols)[N], int64_t n, F &&f) {
     for_each_range<FT, VEC>(cols, (int)N, n, f);
 }
+
+// An optional (NULL-able) column offset by lo points: the column of range [lo, lo + count) of for_each_range.
+template <typename T> inline T *shift(T *p, int64_t lo) { return p ? p + lo : p; }
 
 // --- vector column access --------------------------------------------------------------------
 template <typename FT, int VEC> struct VecT;
@@ -166,19 +205,6 @@ __host__ __device__ __forceinline__ uint32_t fastdiv(uint32_t n, const FastDivU3
 #endif
     return (t + ((n - t) >> f.sh1)) >> f.sh2;
 }
-
-// Launch of a kernel whose Float64 instantiation reads its constants through front_consts() (cmx_math.hpp), i.e. straight from the start of the
-// kernel-argument segment: the constants struct MUST be the first kernel parameter.  The macro checks that at compile time — the first
-// parameter type of the kernel is the type of the first argument passed — so reordering or prepending a parameter no longer compiles
-// (nothing enforced the assumption).  K is the parenthesised kernel name, as for hipLaunchKernelGGL.
-template <typename K> struct first_kernel_param;
-template <typename A0, typename... A> struct first_kernel_param<void (*)(A0, A...)> { using type = std::remove_cv_t<A0>; };
-#define CMX_LAUNCH_FRONT(K, grid, block, lds, stream, c, ...)                                                                                     \
-    do {                                                                                                                                         \
-        static_assert(std::is_same_v<typename ::cmx::first_kernel_param<decltype(&K)>::type, std::remove_cv_t<std::remove_reference_t<decltype(c)>>>, \
-                      "front_consts() reads the constants struct as the FIRST kernel argument");                                                 \
-        hipLaunchKernelGGL(K, grid, block, lds, stream, c, __VA_ARGS__);                                                                         \
-    } while (0)
 
 // Byte offset of the LAST parameter of a kernel inside its kernel-argument segment, derived from the kernel's own signature (the
 // one-launch 2M + P3 kernel found its EXTRA argument with offsetof() on a hand-copied mirror struct that nothing tied to the parameter list).

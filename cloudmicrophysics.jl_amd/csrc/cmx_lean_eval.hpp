@@ -45,14 +45,11 @@ __global__ __launch_bounds__(kBlock) void lean_eval_kernel(const int which, cons
 }
 
 template <int TAG> static int32_t lean_eval_entry(int32_t which, int64_t n, const double *x, double *y, void *stream) {
-    if (which < 0 || which > 19 || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if (which < 0 || which > 19) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!x || !y) return CMX_ERR_BAD_ARG;
-    hipLaunchKernelGGL((lean_eval_kernel<TAG>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), which, n,
-                       x, y);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(lean_eval_kernel<TAG>, n, reinterpret_cast<hipStream_t>(stream), which, n, x, y);
+    return launched();
 }
 
 }  // namespace cmx

@@ -40,25 +40,22 @@ __global__ __launch_bounds__(kBlock) void mp0m_tendencies_kernel(const FT tau_pr
 template <typename FT, typename PR>
 static int32_t mp0m_entry(const PR *p, int64_t n, const FT *q_lcl, const FT *q_icl, const FT *q_vap_sat, FT *dq_tot_dt, FT *ddq_dq_tot,
                           void *stream) {
-    if (!p || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!p) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q_lcl || !q_icl || !dq_tot_dt) return CMX_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = Math<FT>::VEC;
     const void *ptrs[] = {q_lcl, q_icl, q_vap_sat, dq_tot_dt, ddq_dq_tot};
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        const Mp0mIO<FT> io{q_lcl + lo, q_icl + lo, q_vap_sat ? q_vap_sat + lo : nullptr, dq_tot_dt + lo, ddq_dq_tot ? ddq_dq_tot + lo : nullptr};
+        const Mp0mIO<FT> io{q_lcl + lo, q_icl + lo, shift(q_vap_sat, lo), dq_tot_dt + lo, shift(ddq_dq_tot, lo)};
         const int64_t nvec = count / V;
-        const dim3 grid((unsigned)((nvec + kBlock - 1) / kBlock));
-#define CMX_LAUNCH(S, D) hipLaunchKernelGGL((mp0m_tendencies_kernel<FT, V, S, D>), grid, dim3(kBlock), 0, s, p->tau_precip, p->qc_0, p->S_0, io, nvec)
+#define CMX_LAUNCH(S, D) launch<kBlock>(mp0m_tendencies_kernel<FT, V, S, D>, nvec, s, p->tau_precip, p->qc_0, p->S_0, io, nvec)
         if (q_vap_sat) { if (ddq_dq_tot) CMX_LAUNCH(true, true); else CMX_LAUNCH(true, false); }
         else           { if (ddq_dq_tot) CMX_LAUNCH(false, true); else CMX_LAUNCH(false, false); }
 #undef CMX_LAUNCH
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

@@ -78,7 +78,7 @@ static void launch_column_1m(bool def, bool lin, bool general, const Mp1mColKern
     if (nvec <= 0) return;
     const dim3 grid((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))), block(kColBS1m);      // tiles overlap by one lane
     constexpr uint32_t DEF = CMX_1M_DEFAULT_OPTIONS | kDefExpBit;
-#define CMX_L(FL, LN, GG) CMX_LAUNCH_FRONT((mp1m_column_kernel<FT, FL, LN, GG, VEC, kColBS1m>), grid, block, 0, s, a, io, first, nvec)
+#define CMX_L(FL, LN, GG) launch_grid(mp1m_column_kernel<FT, FL, LN, GG, VEC, kColBS1m>, grid, block, 0, s, a, io, first, nvec)
 #define CMX_G(FL, LN) do { if (general) CMX_L(FL, LN, true); else CMX_L(FL, LN, false); } while (0)
     if (def) { if (lin) CMX_G(DEF, true); else CMX_G(DEF, false); }
     else { if (lin) CMX_G(kRuntimeFlags, true); else CMX_G(kRuntimeFlags, false); }
@@ -90,7 +90,7 @@ static void launch_column_1m_shaped(bool lin, bool general, const Mp1mColShapeKe
                                     hipStream_t s) {
     if (nvec <= 0) return;
     const dim3 grid((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))), block(kColBS1m);      // tiles overlap by one lane
-#define CMX_L(LN, GG) CMX_LAUNCH_FRONT((mp1m_column_shaped_kernel<FT, LN, GG, VEC, kColBS1m>), grid, block, 0, s, a, io, first, nvec)
+#define CMX_L(LN, GG) launch_grid(mp1m_column_shaped_kernel<FT, LN, GG, VEC, kColBS1m>, grid, block, 0, s, a, io, first, nvec)
     if (lin) { if (general) CMX_L(true, true); else CMX_L(true, false); }
     else { if (general) CMX_L(false, true); else CMX_L(false, false); }
 #undef CMX_L
@@ -144,8 +144,7 @@ static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, co
             launch_column_1m<FT, V>(def, lin, general, a, io, lo, count / V, s);
         });
     }
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

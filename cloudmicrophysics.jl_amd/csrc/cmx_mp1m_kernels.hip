@@ -208,8 +208,8 @@ template <typename FT, typename MP, typename TH>
 static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T,
                                    const FT *q_tot, const FT *q_lcl, const FT *q_icl, const FT *q_rai, const FT *q_sno,
                                    FT *dq_lcl, FT *dq_icl, FT *dq_rai, FT *dq_sno, void *stream) {
-    if (!mp || !tps || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    if (!mp || !tps) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (const int32_t st = check_flags_1m(flags)) return st;
     if (n == 0) return CMX_OK;
     if (!rho || !T || !q_tot || !q_lcl || !q_icl || !q_rai || !q_sno || !dq_lcl || !dq_icl || !dq_rai || !dq_sno) return CMX_ERR_BAD_ARG;
@@ -222,14 +222,12 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
         Mp1mIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo};
         Mp1mOut<FT> out{dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo};
         const int64_t nv = count / V;
-        const dim3 grid((unsigned)((nv + kBlock1m<FT> - 1) / kBlock1m<FT>));
         if (flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(c))
-            CMX_LAUNCH_FRONT((mp1m_tendencies_kernel<FT, V, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlock1m<FT>), 0, s, c, in, out, nv);
+            launch<kBlock1m<FT>>(mp1m_tendencies_kernel<FT, V, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, c, in, out, nv);
         else
-            CMX_LAUNCH_FRONT((mp1m_tendencies_kernel<FT, V>), grid, dim3(kBlock1m<FT>), 0, s, c, in, out, nv);
+            launch<kBlock1m<FT>>(mp1m_tendencies_kernel<FT, V>, nv, s, c, in, out, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // host-model layouts: the Instantaneous tendencies as a policy of the generic adapter kernel (cmx_layout.hpp)
@@ -277,8 +275,7 @@ template <typename FT, typename MP, typename TH>
 static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, FT q_min, FT dt, int32_t nsub, int64_t n, const FT *rho,
                                    const FT *T, const FT *q_tot, const FT *q_lcl, const FT *q_icl, const FT *q_rai, const FT *q_sno,
                                    FT *dq_lcl, FT *dq_icl, FT *dq_rai, FT *dq_sno, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     Mp1mLinKernArgs<FT> k{};
     if (const int32_t st = make_lin_kernargs<FT>(mp, tps, flags, q_min, dt, nsub, k)) return st;
     if (n == 0) return CMX_OK;
@@ -293,19 +290,17 @@ static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
         constexpr int V = decltype(vec_tag)::value;
         Mp1mLinIO<FT> io{{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo}, {dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo}};
         const int64_t nv = count / V;
-        const dim3 grid((unsigned)((nv + kBlockLin - 1) / kBlockLin));
         if constexpr (V == 2) {
             if constexpr (sizeof(FT) == 4) {      // always true here (VEC above); discards the Float32-only kernel from the Float64 entry
-                if (def) CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, nv);
-                else CMX_LAUNCH_FRONT((mp1m_linearized_pair_kernel<kRuntimeFlags>), grid, dim3(kBlockLin), 0, s, k, io, nv);
+                if (def) launch<kBlockLin>(mp1m_linearized_pair_kernel<CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, k, io, nv);
+                else launch<kBlockLin>(mp1m_linearized_pair_kernel<kRuntimeFlags>, nv, s, k, io, nv);
             }
         } else {
-            if (def) CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>), grid, dim3(kBlockLin), 0, s, k, io, nv);
-            else CMX_LAUNCH_FRONT((mp1m_linearized_kernel<FT>), grid, dim3(kBlockLin), 0, s, k, io, nv);
+            if (def) launch<kBlockLin>(mp1m_linearized_kernel<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, k, io, nv);
+            else launch<kBlockLin>(mp1m_linearized_kernel<FT>, nv, s, k, io, nv);
         }
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 template <typename FT, typename MP, typename TH>
@@ -323,8 +318,8 @@ template <typename FT, typename MP, typename TH>
 static int32_t sources_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T,
                                 const FT *q_tot, const FT *q_lcl, const FT *q_icl, const FT *q_rai, const FT *q_sno,
                                 FT *const out[CMX_MP1M_NSRC], void *stream) {
-    if (!mp || !tps || !out || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    if (!mp || !tps || !out) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (const int32_t st = check_flags_1m(flags)) return st;
     if (n == 0) return CMX_OK;
     if (!rho || !T || !q_tot || !q_lcl || !q_icl || !q_rai || !q_sno) return CMX_ERR_BAD_ARG;
@@ -332,32 +327,27 @@ static int32_t sources_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int
     Mp1mIn<FT> in{rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno};
     Mp1mSrcOut<FT> o;
     for (int k = 0; k < CMX_MP1M_NSRC; ++k) o.col[k] = out[k];
-    CMX_LAUNCH_FRONT((mp1m_sources_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), c, in, o, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(mp1m_sources_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, in, o, n);
+    return launched();
 }
 
 // the Chen-2022 rain table selects the instantiation: polynomial Γ on its window (fast) or run-time Γ for any exponent (general)
 template <typename FT> static void launch_velocity(bool general_gamma, const Vel1mConsts<FT> &c, const Vel1mIO<FT> &io, int64_t n, void *stream) {
-    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
-    if (general_gamma) hipLaunchKernelGGL((mp1m_velocity_kernel<FT, true>), grid, dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), c, io, n);
-    else hipLaunchKernelGGL((mp1m_velocity_kernel<FT, false>), grid, dim3(kBlock), 0, reinterpret_cast<hipStream_t>(stream), c, io, n);
+    if (general_gamma) launch<kBlock>(mp1m_velocity_kernel<FT, true>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
+    else launch<kBlock>(mp1m_velocity_kernel<FT, false>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
 }
 
 template <typename FT, typename MP, typename CH>
 static int32_t velocity_1m_entry(const MP *mp, const CH *chen, int64_t n, const FT *rho, const FT *q_rai, const FT *q_sno,
                                  FT *vt_rai, FT *vt_sno, FT *vt_chen, void *stream) {
-    if (!mp || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!mp) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!rho || ((vt_rai || vt_chen) && !q_rai) || (vt_sno && !q_sno) || (vt_chen && !chen)) return CMX_ERR_BAD_ARG;
     bool general = false;
     const Vel1mConsts<FT> c = make_vel1m_consts<FT>(*mp, chen, &general);
     Vel1mIO<FT> io{rho, q_rai, q_sno, vt_rai, vt_sno, vt_chen, nullptr, nullptr, nullptr, nullptr, nullptr};
     launch_velocity<FT>(general, c, io, n, stream);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // The four bulk sedimentation velocities a host model precomputes (ClimaAtmos set_sedimentation_precomputed_quantities;
@@ -366,9 +356,8 @@ template <typename FT, typename MP, typename ST, typename CH, typename CI>
 static int32_t sedimentation_entry(const MP *mp, const ST *stokes, const CH *chen_rain, const CI *chen_ice, int64_t n, const FT *rho,
                                    const FT *q_lcl, const FT *q_icl, const FT *q_rai, const FT *q_sno, FT *w_lcl, FT *w_icl, FT *w_rai,
                                    FT *w_sno, void *stream) {
-    if (!mp || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!mp) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!rho || (w_lcl && (!q_lcl || !stokes)) || (w_icl && (!q_icl || !chen_ice)) || (w_rai && (!q_rai || !chen_rain)) ||
         (w_sno && (!q_sno || !chen_ice)))
         return CMX_ERR_BAD_ARG;
@@ -377,17 +366,15 @@ static int32_t sedimentation_entry(const MP *mp, const ST *stokes, const CH *che
     add_sedimentation_consts<FT>(c, *mp, stokes, chen_ice);
     Vel1mIO<FT> io{rho, q_rai, q_sno, nullptr, nullptr, w_rai, q_lcl, q_icl, w_lcl, w_icl, w_sno};
     launch_velocity<FT>(general, c, io, n, stream);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // CM1.terminal_velocity(snow, Chen2022VelTypeLargeIce, ρ, q[, Oblate() | Prolate()]) over columns (include/cmx.h cmx_snow_terminal_velocity_*)
 template <typename FT, typename CR, typename MP, typename CI>
 static int32_t snow_velocity_entry(const MP *mp, const CI *chen_ice, uint32_t snow_shape, int64_t n, const FT *rho, const FT *q_sno, FT *w_sno,
                                    void *stream) {
-    if (!mp || !chen_ice || snow_shape > CMX_SNOW_SHAPE_PROLATE || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!mp || !chen_ice || snow_shape > CMX_SNOW_SHAPE_PROLATE) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!rho || !q_sno || !w_sno) return CMX_ERR_BAD_ARG;
     const Vel1mShapeConsts<FT> c = make_snow_shape_consts<FT>(*mp, static_cast<const CR *>(nullptr), static_cast<const cmx_stokes_vel_f64 *>(nullptr), *chen_ice,
                                                               snow_shape);
@@ -396,11 +383,9 @@ static int32_t snow_velocity_entry(const MP *mp, const CI *chen_ice, uint32_t sn
     for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
         const int64_t nv = count / V;
-        CMX_LAUNCH_FRONT((mp1m_snow_velocity_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, rho + lo, q_sno + lo,
-                         w_sno + lo, nv);
+        launch<kBlock>(mp1m_snow_velocity_kernel<FT, V>, nv, s, c, rho + lo, q_sno + lo, w_sno + lo, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

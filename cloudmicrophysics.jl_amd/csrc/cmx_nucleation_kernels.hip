@@ -137,14 +137,10 @@ __global__ __launch_bounds__(kBlock) void p3_ice_nucleation_counts_kernel(const 
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-template <typename FT> static inline const FT *off(const FT *p, int64_t lo) { return p ? p + lo : p; }
-template <typename FT> static inline FT *off(FT *p, int64_t lo) { return p ? p + lo : p; }
-
 template <typename FT, typename HP, typename OP, typename MP>
 static int32_t aerosol_nucleation_entry(const HP *hp, const OP *op, const MP *mp, int64_t n, const FT *h2so4, const FT *nh3, const FT *ion, const FT *mt,
                                         const FT *o3, const FT *oh, const FT *T, const FT *cs, FT *binary, FT *ternary, FT *organic, FT *mixed, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
+    CMX_TRY_COUNT_LIMIT(n);
     const bool wh = binary || ternary;
     if (!wh && !organic && !mixed) return CMX_ERR_BAD_ARG;
     if ((wh && !hp) || (organic && !op) || (mixed && !mp)) return CMX_ERR_BAD_ARG;
@@ -162,20 +158,18 @@ static int32_t aerosol_nucleation_entry(const HP *hp, const OP *op, const MP *mp
     const void *ptrs[] = {h_, a_, ion_, mt_, o3_, oh_, T, cs_, binary, ternary, organic, mixed};
     for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
-        const NucIO<FT> io{off(h_, lo), off(a_, lo), off(ion_, lo), off(mt_, lo), off(o3_, lo), off(oh_, lo), T + lo, off(cs_, lo),
-                           off(binary, lo), off(ternary, lo), off(organic, lo), off(mixed, lo)};
+        const NucIO<FT> io{shift(h_, lo), shift(a_, lo), shift(ion_, lo), shift(mt_, lo), shift(o3_, lo), shift(oh_, lo), T + lo, shift(cs_, lo),
+                           shift(binary, lo), shift(ternary, lo), shift(organic, lo), shift(mixed, lo)};
         const int64_t nv = count / V;
-        CMX_LAUNCH_FRONT((aerosol_nucleation_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, io, nv);
+        launch<kBlock>(aerosol_nucleation_kernel<FT, V>, nv, s, c, io, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 template <typename FT, typename OP, typename MP>
 static int32_t nucleation_prescribed_entry(const OP *op, const MP *mp, int64_t n, const FT *ion, const FT *hom, const FT *h2so4, const FT *bio, FT *organic,
                                            FT *mixed, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
+    CMX_TRY_COUNT_LIMIT(n);
     if (!organic && !mixed) return CMX_ERR_BAD_ARG;
     if ((organic && !op) || (mixed && !mp)) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
@@ -186,18 +180,16 @@ static int32_t nucleation_prescribed_entry(const OP *op, const MP *mp, int64_t n
     const void *ptrs[] = {ion_, hom_, h_, bio_, organic, mixed};
     for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        const NucPrescribedIO<FT> io{off(ion_, lo), off(hom_, lo), off(h_, lo), off(bio_, lo), off(organic, lo), off(mixed, lo)};
+        const NucPrescribedIO<FT> io{shift(ion_, lo), shift(hom_, lo), shift(h_, lo), shift(bio_, lo), shift(organic, lo), shift(mixed, lo)};
         const int64_t nv = count / V;
-        CMX_LAUNCH_FRONT((nucleation_prescribed_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, io, nv);
+        launch<kBlock>(nucleation_prescribed_kernel<FT, V>, nv, s, c, io, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 template <typename FT>
 static int32_t apparent_nucleation_entry(int64_t n, const FT *od, const FT *nr, const FT *gr, const FT *cs, const FT *csi, const FT *id, FT *J, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
+    CMX_TRY_COUNT_LIMIT(n);
     if (!J) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!od || !nr || !gr || !cs || !csi) return CMX_ERR_BAD_ARG;
@@ -205,19 +197,18 @@ static int32_t apparent_nucleation_entry(int64_t n, const FT *od, const FT *nr, 
     const void *ptrs[] = {od, nr, gr, cs, csi, id, J};
     for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        const ApparentIO<FT> io{od + lo, nr + lo, gr + lo, cs + lo, csi + lo, off(id, lo), J + lo};
+        const ApparentIO<FT> io{od + lo, nr + lo, gr + lo, cs + lo, csi + lo, shift(id, lo), J + lo};
         const int64_t nv = count / V;
-        hipLaunchKernelGGL((apparent_nucleation_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, io, FT(1.7), nv);
+        launch<kBlock>(apparent_nucleation_kernel<FT, V>, nv, s, io, FT(1.7), nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 template <typename FT, typename IP>
 static int32_t p3_ice_nucleation_counts_entry(const IP *ip, int64_t n, const FT *T, const FT *Nl, const FT *Vl, const FT *dt, FT *N_dep, FT *N_het,
                                               void *stream) {
-    if (!ip || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
+    if (!ip) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (!N_dep && !N_het) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!T || (N_het && (!Nl || !Vl || !dt))) return CMX_ERR_BAD_ARG;
@@ -227,12 +218,11 @@ static int32_t p3_ice_nucleation_counts_entry(const IP *ip, int64_t n, const FT 
     const void *ptrs[] = {T, Nl_, Vl_, dt_, N_dep, N_het};
     for_each_range<FT, Math<FT>::VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        const P3NucIO<FT> io{T + lo, off(Nl_, lo), off(Vl_, lo), off(dt_, lo), off(N_dep, lo), off(N_het, lo)};
+        const P3NucIO<FT> io{T + lo, shift(Nl_, lo), shift(Vl_, lo), shift(dt_, lo), shift(N_dep, lo), shift(N_het, lo)};
         const int64_t nv = count / V;
-        hipLaunchKernelGGL((p3_ice_nucleation_counts_kernel<FT, V>), dim3((unsigned)((nv + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c, io, nv);
+        launch<kBlock>(p3_ice_nucleation_counts_kernel<FT, V>, nv, s, c, io, nv);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

@@ -975,9 +975,8 @@ static int32_t launch_collision_kernel(const P3Consts<FT> &c, const P3VelConsts<
     if (!collision_geometry<FT>(group, quad.n, n, grid, block, lds)) return CMX_ERR_UNSUPPORTED;
     auto go = [&](auto kern) -> int32_t {
         if (lds > 48 * 1024) CMX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, grid, block, lds, st, c, v, k, quad, io, n, ex);
-        CMX_HIP_TRY(hipGetLastError());
-        return CMX_OK;
+        launch_grid(kern, grid, block, lds, st, c, v, k, quad, io, n, ex);
+        return launched();
     };
     if (group == 8)
         return aspect ? go(&p3_collision_kernel<FT, QUAD, true, FUSED, 8, EXTRA>) : go(&p3_collision_kernel<FT, QUAD, false, FUSED, 8, EXTRA>);
@@ -991,10 +990,10 @@ template <typename FT, typename IP, typename AP, typename TH, typename QUAD>
 static int32_t p3_collision_entry(const IP *ip, const AP *aps, const TH *tps, const QUAD *quad, uint32_t flags, int64_t n, const FT *rho_q,
                                   const FT *rho_n, const FT *x3, const FT *x4, const FT *L_c, const FT *N_c, const FT *L_r, const FT *N_r,
                                   const FT *rho_a, const FT *T, const FT *loglam, FT *const *sources, FT *const *rates, void *stream) {
-    if (!ip || !aps || !tps || !quad || n < 0 ||
+    if (!ip || !aps || !tps || !quad ||
         (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED)))
         return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     if (quad->n < 1 || quad->n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho_q || !rho_n || !x3 || !x4 || !L_c || !N_c || !L_r || !N_r || !rho_a || !T || !loglam || (!sources && !rates)) return CMX_ERR_BAD_ARG;
@@ -1031,28 +1030,25 @@ __global__ __launch_bounds__(kBlock) void liquid_freezing_kernel(const Pointwise
 template <typename FT, typename IP, typename TH>
 static int32_t liquid_freezing_entry(const IP *ip, const TH *tps, uint32_t flags, int64_t n, const FT *q, const FT *rho, const FT *N, const FT *T,
                                      FT *dn, FT *dq, void *stream) {
-    if (!ip || !tps || n < 0 || (flags & ~(uint32_t)(CMX_FREEZE_CLOUD_PSD | CMX_P3_RAIN_PDF_LIMITED))) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!ip || !tps || (flags & ~(uint32_t)(CMX_FREEZE_CLOUD_PSD | CMX_P3_RAIN_PDF_LIMITED))) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q || !rho || !N || !T || (!dn && !dq)) return CMX_ERR_BAD_ARG;
     using WR = std::conditional_t<std::is_same_v<FT, float>, cmx_warm_rain_2m_f32, cmx_warm_rain_2m_f64>;
     WR wr{};
     const PointwiseConsts<FT> k = make_pointwise_consts<FT>(wr, *ip, *tps);
-    const dim3 grid((unsigned)((n + kBlock - 1) / kBlock)), block(kBlock);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_FREEZE_CLOUD_PSD) hipLaunchKernelGGL((liquid_freezing_kernel<FT, true, true>), grid, block, 0, st, k, q, rho, N, T, dn, dq, n);
-    else if (flags & CMX_P3_RAIN_PDF_LIMITED) hipLaunchKernelGGL((liquid_freezing_kernel<FT, false, true>), grid, block, 0, st, k, q, rho, N, T, dn, dq, n);
-    else hipLaunchKernelGGL((liquid_freezing_kernel<FT, false, false>), grid, block, 0, st, k, q, rho, N, T, dn, dq, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    if (flags & CMX_FREEZE_CLOUD_PSD) launch<kBlock>(liquid_freezing_kernel<FT, true, true>, n, st, k, q, rho, N, T, dn, dq, n);
+    else if (flags & CMX_P3_RAIN_PDF_LIMITED) launch<kBlock>(liquid_freezing_kernel<FT, false, true>, n, st, k, q, rho, N, T, dn, dq, n);
+    else launch<kBlock>(liquid_freezing_kernel<FT, false, false>, n, st, k, q, rho, N, T, dn, dq, n);
+    return launched();
 }
 
 template <typename FT, typename WR, typename IP, typename TH>
 static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T, const FT *q_tot,
                              const FT *q_lcl, const FT *n_lcl, const FT *q_rai, const FT *n_rai, const FT *q_ice, const FT *n_ice, const FT *q_rim,
                              const FT *b_rim, const FT *loglam, const FT *shift, FT *const *out, void *stream, const SegLayout *lay = nullptr) {
-    if (!wr || !ip || !tps || n < 0 || (flags & ~(CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED))) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    if (!wr || !ip || !tps || (flags & ~(CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED))) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (ip->quad.n < 1 || ip->quad.n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho || !T || !q_tot || !q_lcl || !n_lcl || !q_rai || !n_rai || !q_ice || !n_ice || !q_rim || !b_rim || !loglam || !out) return CMX_ERR_BAD_ARG;
@@ -1097,15 +1093,14 @@ static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t
     FusedIO<FT> fio{rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, shift, {}};
     for (int q = 0; q < 8; ++q) fio.out[q] = out[q];
     if (lay) fio.lay = *lay;
-    const dim3 block(kBlock), grid1((unsigned)((n + kBlock - 1) / kBlock));
     if (intpow) {
-        if (limited) hipLaunchKernelGGL((mp2m_p3_pointwise_kernel<FT, true, true>), grid1, block, 0, st, sc, c, pk, fio, n);
-        else hipLaunchKernelGGL((mp2m_p3_pointwise_kernel<FT, false, true>), grid1, block, 0, st, sc, c, pk, fio, n);
+        if (limited) launch<kBlock>(mp2m_p3_pointwise_kernel<FT, true, true>, n, st, sc, c, pk, fio, n);
+        else launch<kBlock>(mp2m_p3_pointwise_kernel<FT, false, true>, n, st, sc, c, pk, fio, n);
     } else {
-        if (limited) hipLaunchKernelGGL((mp2m_p3_pointwise_kernel<FT, true>), grid1, block, 0, st, sc, c, pk, fio, n);
-        else hipLaunchKernelGGL((mp2m_p3_pointwise_kernel<FT, false>), grid1, block, 0, st, sc, c, pk, fio, n);
+        if (limited) launch<kBlock>(mp2m_p3_pointwise_kernel<FT, true>, n, st, sc, c, pk, fio, n);
+        else launch<kBlock>(mp2m_p3_pointwise_kernel<FT, false>, n, st, sc, c, pk, fio, n);
     }
-    CMX_HIP_TRY(hipGetLastError());
+    if (const int32_t e = launched()) return e;      // the pointwise launch, before the collision kernel's
     return launch_collision_kernel<FT, QUAD, true>(c, v, k, ip->quad, io, n, !(flags & CMX_P3_NO_ASPECT_RATIO), st);
 }
 

@@ -121,17 +121,14 @@ __global__ __launch_bounds__(kP3BS) void p3_shape_kernel(const P3Consts<FT> c, c
 template <typename FT, typename PR>
 static int32_t p3_entry(const PR *params, uint32_t flags, int32_t brent_iters, int64_t n, const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4,
                         const FT *guess, FT *F_rim, FT *rho_rim, FT *loglam, FT *D_m, FT *logN0, void *stream) {
-    if (!params || n < 0 || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO))) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!params || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO))) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!rho_q || !rho_n || !x3 || !x4) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
     c.brent_iters = brent_iters > 0 ? brent_iters : PM<FT>::kBrent;
     P3IO<FT> io{rho_q, rho_n, x3, x4, guess, F_rim, rho_rim, loglam, D_m, logN0};
-    hipLaunchKernelGGL((p3_shape_kernel<FT>), dim3((unsigned)((n + kP3BS - 1) / kP3BS)), dim3(kP3BS), 0,
-                       reinterpret_cast<hipStream_t>(stream), c, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kP3BS>(p3_shape_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
+    return launched();
 }
 
 
@@ -272,9 +269,9 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_velocity_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, FT p, int64_t n, const FT *rho_q,
                                  const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *loglam, FT *v_n, FT *v_m,
                                  void *stream) {
-    if (!params || !vel || !quad || n < 0 || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
+    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
         return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !loglam) return CMX_ERR_BAD_ARG;
@@ -282,14 +279,12 @@ static int32_t p3_velocity_entry(const PR *params, const VR *vel, const QUAD *qu
     c.brent_iters = 0;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, (double)p);
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, v_n, v_m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    const dim3 grid((unsigned)((n + kP3BS - 1) / kP3BS)), block(kP3BS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (flags & CMX_P3_NO_ASPECT_RATIO)
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, false>), grid, block, 0, st, c, v, *quad, io, n);
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false>, n, st, c, v, *quad, io, n);
     else
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, true>), grid, block, 0, st, c, v, *quad, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true>, n, st, c, v, *quad, io, n);
+    return launched();
 }
 
 // cmx_p3_shape_terminal_velocities_*: shape solve + D_m + number- / mass-weighted fall speeds in ONE launch (BASELINE config 5)
@@ -297,9 +292,9 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_shape_velocity_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, int32_t brent_iters, FT p, int64_t n,
                                        const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *guess,
                                        FT *loglam, FT *D_m, FT *v_n, FT *v_m, void *stream) {
-    if (!params || !vel || !quad || n < 0 || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
+    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
         return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a) return CMX_ERR_BAD_ARG;
@@ -307,24 +302,22 @@ static int32_t p3_shape_velocity_entry(const PR *params, const VR *vel, const QU
     c.brent_iters = brent_iters > 0 ? brent_iters : PM<FT>::kBrent;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, (double)p);
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, nullptr, v_n, v_m, nullptr, nullptr, nullptr, guess, loglam, D_m};
-    const dim3 grid((unsigned)((n + kP3BS - 1) / kP3BS)), block(kP3BS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (flags & CMX_P3_NO_ASPECT_RATIO)
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, false, false, true>), grid, block, 0, st, c, v, *quad, io, n);
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false, false, true>, n, st, c, v, *quad, io, n);
     else
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, true, false, true>), grid, block, 0, st, c, v, *quad, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true, false, true>, n, st, c, v, *quad, io, n);
+    return launched();
 }
 
 template <typename FT, typename PR, typename VR, typename AP, typename TH, typename VT, typename QUAD>
 static int32_t p3_melt_entry(const PR *params, const VR *vel, const AP *aps, const TH *tps, const VT *vent, const QUAD *quad, uint32_t flags,
                              FT p, int64_t n, const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *T,
                              const FT *loglam, FT *dNdt, FT *dLdt, void *stream) {
-    if (!params || !vel || !aps || !tps || !vent || !quad || n < 0 ||
+    if (!params || !vel || !aps || !tps || !vent || !quad ||
         (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
         return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !T || !loglam) return CMX_ERR_BAD_ARG;
@@ -337,14 +330,12 @@ static int32_t p3_melt_entry(const PR *params, const VR *vel, const AP *aps, con
     v.LH_f0 = (FT)((double)tps->LH_s0 - (double)tps->LH_v0); v.dcp_f = (FT)((double)tps->cp_l - (double)tps->cp_i);
     v.T_0 = (FT)tps->T_0; v.T_freeze = (FT)params->T_freeze;
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, nullptr, nullptr, T, dNdt, dLdt, nullptr, nullptr, nullptr};
-    const dim3 grid((unsigned)((n + kP3BS - 1) / kP3BS)), block(kP3BS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (flags & CMX_P3_NO_ASPECT_RATIO)
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, false, true>), grid, block, 0, st, c, v, *quad, io, n);
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false, true>, n, st, c, v, *quad, io, n);
     else
-        hipLaunchKernelGGL((p3_velocity_kernel<FT, QUAD, true, true>), grid, block, 0, st, c, v, *quad, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true, true>, n, st, c, v, *quad, io, n);
+    return launched();
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -447,9 +438,9 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_self_collection_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, int64_t n, const FT *rho_q,
                                         const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *loglam, FT *dNdt,
                                         void *stream) {
-    if (!params || !vel || !quad || n < 0 || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
+    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
         return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    CMX_TRY_COUNT_LIMIT(n);
     if (quad->n < 1 || quad->n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !loglam || !dNdt) return CMX_ERR_BAD_ARG;
@@ -457,14 +448,12 @@ static int32_t p3_self_collection_entry(const PR *params, const VR *vel, const Q
     c.brent_iters = 0;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, 1e-6);
     P3SelfIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, dNdt};
-    const dim3 grid((unsigned)((n + kP3BS - 1) / kP3BS)), block(kP3BS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (flags & CMX_P3_NO_ASPECT_RATIO)
-        hipLaunchKernelGGL((p3_self_collection_kernel<FT, QUAD, false>), grid, block, 0, st, c, v, *quad, io, n);
+        launch<kP3BS>(p3_self_collection_kernel<FT, QUAD, false>, n, st, c, v, *quad, io, n);
     else
-        hipLaunchKernelGGL((p3_self_collection_kernel<FT, QUAD, true>), grid, block, 0, st, c, v, *quad, io, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+        launch<kP3BS>(p3_self_collection_kernel<FT, QUAD, true>, n, st, c, v, *quad, io, n);
+    return launched();
 }
 
 // ---- UT.gamma_inc / UT.gamma_inc_inv over columns (src/Utilities.jl:54-61,93-144,205-252; KA wrapper test_gamma_inc_kernel!,
@@ -493,23 +482,16 @@ __global__ __launch_bounds__(kP3BS) void gamma_inc_inv_kernel(const int64_t n, c
 }
 
 template <typename FT> static int32_t gamma_inc_entry(int64_t n, const FT *a, const FT *x, FT *P, FT *Q, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    CMX_TRY_COUNT(n);
     if (!a || !x || (!P && !Q)) return CMX_ERR_BAD_ARG;
-    hipLaunchKernelGGL((gamma_inc_kernel<FT>), dim3((unsigned)((n + kP3BS - 1) / kP3BS)), dim3(kP3BS), 0, reinterpret_cast<hipStream_t>(stream), n, a, x, P, Q);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kP3BS>(gamma_inc_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), n, a, x, P, Q);
+    return launched();
 }
 template <typename FT> static int32_t gamma_inc_inv_entry(int64_t n, const FT *a, const FT *p, const FT *q, FT *x, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    CMX_TRY_COUNT(n);
     if (!a || !p || !q || !x) return CMX_ERR_BAD_ARG;
-    hipLaunchKernelGGL((gamma_inc_inv_kernel<FT>), dim3((unsigned)((n + kP3BS - 1) / kP3BS)), dim3(kP3BS), 0, reinterpret_cast<hipStream_t>(stream), n, a, p, q,
-                       x);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kP3BS>(gamma_inc_inv_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), n, a, p, q, x);
+    return launched();
 }
 
 // ---- size-distribution helpers over columns (src/DistributionTools.jl:44-151, src/Microphysics2M.jl:270-354) ----------------------------
@@ -638,32 +620,23 @@ __global__ __launch_bounds__(kP3BS) void sb2006_size_distribution_kernel(const P
 }
 
 template <typename FT> static int32_t generalized_gamma_entry(FT nu, FT mu, int64_t n, const FT *B, const FT *Y, const FT *x, FT *quantile, FT *cdf, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    CMX_TRY_COUNT(n);
     if (!B || (!quantile && !cdf) || (quantile && !Y) || (cdf && !x)) return CMX_ERR_BAD_ARG;
-    hipLaunchKernelGGL((generalized_gamma_kernel<FT>), dim3((unsigned)((n + kP3BS - 1) / kP3BS)), dim3(kP3BS), 0, reinterpret_cast<hipStream_t>(stream), nu, mu, n,
-                       B, Y, x, quantile, cdf);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kP3BS>(generalized_gamma_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), nu, mu, n, B, Y, x, quantile, cdf);
+    return launched();
 }
 template <typename FT> static int32_t exponential_distribution_entry(int64_t n, const FT *D_mean, const FT *Y, const FT *D, FT *quantile, FT *cdf, void *stream) {
-    if (n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    CMX_TRY_COUNT(n);
     if (!D_mean || (!quantile && !cdf) || (quantile && !Y) || (cdf && !D)) return CMX_ERR_BAD_ARG;
-    hipLaunchKernelGGL((exponential_distribution_kernel<FT>), dim3((unsigned)((n + kP3BS - 1) / kP3BS)), dim3(kP3BS), 0, reinterpret_cast<hipStream_t>(stream), n,
-                       D_mean, Y, D, quantile, cdf);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kP3BS>(exponential_distribution_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), n, D_mean, Y, D, quantile, cdf);
+    return launched();
 }
 template <typename FT, typename PC, typename PR>
 static int32_t sb2006_size_distribution_entry(const PC *pdf_c, const PR *pdf_r, uint32_t flags, FT p, int64_t n, const FT *q, const FT *rho, const FT *N,
                                               const FT *D, FT *n_D, FT *D_min, FT *D_max, void *stream) {
     const bool cloud = flags & CMX_PSD_CLOUD, limited = flags & CMX_SB2006_LIMITED;
-    if (n < 0 || (flags & ~(uint32_t)(CMX_PSD_CLOUD | CMX_SB2006_LIMITED)) || (cloud ? !pdf_c : !pdf_r)) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
+    if ((flags & ~(uint32_t)(CMX_PSD_CLOUD | CMX_SB2006_LIMITED)) || (cloud ? !pdf_c : !pdf_r)) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q || !rho || !N || (!n_D && !D_min && !D_max) || (n_D && !D)) return CMX_ERR_BAD_ARG;
     // the limited rain PSD clamps with its limiter pairs: a struct of the NOT-limited variant (limiters all zero, cmx.h) passed with the flag set
     // would clamp N0 and λ to 0 and return Inf / NaN silently — the same rule as the rate and column entries (sb_limiters_ok)
@@ -678,13 +651,11 @@ static int32_t sb2006_size_distribution_entry(const PC *pdf_c, const PR *pdf_r, 
         k.lam_max = pdf_r->lambda_max; k.rho_w_r = pdf_r->rho_w;
     }
     k.p = p;
-    const dim3 grid((unsigned)((n + kP3BS - 1) / kP3BS)), block(kP3BS);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (cloud) hipLaunchKernelGGL((sb2006_size_distribution_kernel<FT, true, false>), grid, block, 0, st, k, n, q, rho, N, D, n_D, D_min, D_max);
-    else if (limited) hipLaunchKernelGGL((sb2006_size_distribution_kernel<FT, false, true>), grid, block, 0, st, k, n, q, rho, N, D, n_D, D_min, D_max);
-    else hipLaunchKernelGGL((sb2006_size_distribution_kernel<FT, false, false>), grid, block, 0, st, k, n, q, rho, N, D, n_D, D_min, D_max);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    if (cloud) launch<kP3BS>(sb2006_size_distribution_kernel<FT, true, false>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
+    else if (limited) launch<kP3BS>(sb2006_size_distribution_kernel<FT, false, true>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
+    else launch<kP3BS>(sb2006_size_distribution_kernel<FT, false, false>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
+    return launched();
 }
 
 CMX_P3_CONTRACT_END

@@ -280,12 +280,12 @@ template <typename FT, int VEC>
 static void launch_column(bool limited, int vel, bool cloud, bool intpow, const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, const SbColIO<FT> &io,
                           int64_t first, int64_t nvec, hipStream_t s) {
     if (nvec <= 0) return;
-    const int64_t grid = (nvec + (kColBS - 1) - 1) / (kColBS - 1);      // tiles overlap by one lane (sb2006_column_kernel)
+    const dim3 grid((unsigned)((nvec + (kColBS - 1) - 1) / (kColBS - 1))), block(kColBS);      // tiles overlap by one lane (sb2006_column_kernel)
     // intpow: the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
 #define CMX_LAUNCH(L, V, C)                                                                                                                          \
     do {                                                                                                                                             \
-        if (intpow) CMX_LAUNCH_FRONT((sb2006_column_kernel<FT, L, V, C, VEC, kColBS, true>), dim3((unsigned)grid), dim3(kColBS), 0, s, c, cv, io, first, nvec); \
-        else CMX_LAUNCH_FRONT((sb2006_column_kernel<FT, L, V, C, VEC, kColBS>), dim3((unsigned)grid), dim3(kColBS), 0, s, c, cv, io, first, nvec);   \
+        if (intpow) launch_grid(sb2006_column_kernel<FT, L, V, C, VEC, kColBS, true>, grid, block, 0, s, c, cv, io, first, nvec); \
+        else launch_grid(sb2006_column_kernel<FT, L, V, C, VEC, kColBS>, grid, block, 0, s, c, cv, io, first, nvec);   \
     } while (0)
 #define CMX_PICK(L, V) do { if (cloud) CMX_LAUNCH(L, V, true); else CMX_LAUNCH(L, V, false); } while (0)
     if (limited) {
@@ -332,8 +332,7 @@ static int32_t column_entry(const WR *wr, const TH *tps, const VL *vel, const ST
         constexpr int V = decltype(vec_tag)::value;
         launch_column<FT, V>(limited, velk, cloud, intpow, c, cv, io, lo, count / V, s);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 }  // namespace cmx

@@ -31,15 +31,12 @@ template <typename FT, int VEC>
 static void launch_tendencies(bool limited, int vel, bool intpow, const SbConsts<FT> &c, const SbIn<FT> &in, const SbOut<FT> &out,
                               int64_t nvec, hipStream_t s) {
     // one short-lived workgroup per tile of kTendBS lanes (see the kernel's header comment)
-    const int64_t grid = (nvec + kTendBS - 1) / kTendBS;
-#define CMX_LAUNCH(L, V)                                                                                                                   \
-    do {                                                                                                                                   \
-        if (intpow && CMX_SB_INTPOW)                                                                                                       \
-            CMX_LAUNCH_FRONT((sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS, 1, true, true>), dim3((unsigned)grid), dim3(kTendBS), 0, s, c, in, \
-                               out, nvec);                                                                                                 \
-        else                                                                                                                               \
-            CMX_LAUNCH_FRONT((sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS>), dim3((unsigned)grid), dim3(kTendBS), 0, s, c, in, out,  \
-                               nvec);                                                                                                      \
+#define CMX_LAUNCH(L, V)                                                                                              \
+    do {                                                                                                              \
+        if (intpow && CMX_SB_INTPOW)                                                                                  \
+            launch<kTendBS>(sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS, 1, true, true>, nvec, s, c, in, out, nvec); \
+        else                                                                                                          \
+            launch<kTendBS>(sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS>, nvec, s, c, in, out, nvec);              \
     } while (0)
     if (limited) {
         if (vel == VEL_NONE) CMX_LAUNCH(true, VEL_NONE);
@@ -60,9 +57,8 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
                                 const FT *T, const FT *q_tot, const FT *q_lcl, const FT *n_lcl, const FT *q_rai,
                                 const FT *n_rai, FT *dq_lcl, FT *dn_lcl, FT *dq_rai, FT *dn_rai, FT *vt_n, FT *vt_m,
                                 void *stream) {
-    if (!wr || !tps || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!wr || !tps) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!rho || !T || !q_tot || !q_lcl || !n_lcl || !q_rai || !n_rai || !dq_lcl || !dn_lcl || !dq_rai || !dn_rai)
         return CMX_ERR_BAD_ARG;
     const bool want_vel = vt_n || vt_m;
@@ -82,12 +78,10 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
         SbIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, n_lcl + lo, q_rai + lo, n_rai + lo};
-        SbOut<FT> out{dq_lcl + lo, dn_lcl + lo, dq_rai + lo, dn_rai + lo, vt_n ? vt_n + lo : nullptr,
-                      vt_m ? vt_m + lo : nullptr};
+        SbOut<FT> out{dq_lcl + lo, dn_lcl + lo, dq_rai + lo, dn_rai + lo, shift(vt_n, lo), shift(vt_m, lo)};
         launch_tendencies<FT, V>(limited, velk, intpow, c, in, out, count / V, s);
     });
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // cmx_sb2006_warm_rain_tendencies_fields_*: segmented (ClimaCore field) columns in, segmented columns or the reference's
@@ -112,9 +106,8 @@ template <typename FT, typename WR, typename TH, typename VL>
 static int32_t process_entry(const WR *wr, const TH *tps, const VL *vel, uint32_t flags, int64_t n, const FT *q_tot,
                              const FT *q_lcl, const FT *q_rai, const FT *N_lcl, const FT *N_rai, const FT *rho,
                              const FT *T, FT *const out[CMX_SB2006_NPROC], void *stream) {
-    if (!wr || !tps || !out || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!wr || !tps || !out) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q_tot || !q_lcl || !q_rai || !N_lcl || !N_rai || !rho || !T) return CMX_ERR_BAD_ARG;
     const bool want_vel = out[CMX_SB_RAI_VEL_N] || out[CMX_SB_RAI_VEL_M];
     int velk = decode_vel(flags, want_vel);
@@ -126,10 +119,8 @@ static int32_t process_entry(const WR *wr, const TH *tps, const VL *vel, uint32_
     SbProcOut<FT> o;
     for (int k = 0; k < CMX_SB2006_NPROC; ++k) o.col[k] = out[k];
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int grid = grid_for(n);
-#define CMX_LAUNCH(L, V)                                                                                        \
-    CMX_LAUNCH_FRONT((sb2006_process_kernel<FT, L, V>), dim3(grid), dim3(kBlock), 0, s, c, q_tot, q_lcl, q_rai, \
-                       N_lcl, N_rai, rho, T, o, n)
+    const dim3 grid(grid_for(n));
+#define CMX_LAUNCH(L, V) launch_grid(sb2006_process_kernel<FT, L, V>, grid, dim3(kBlock), 0, s, c, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, o, n)
     if (limited) {
         if (velk == VEL_NONE) CMX_LAUNCH(true, VEL_NONE);
         else if (velk == VEL_SB) CMX_LAUNCH(true, VEL_SB);
@@ -142,8 +133,7 @@ static int32_t process_entry(const WR *wr, const TH *tps, const VL *vel, uint32_
         else CMX_LAUNCH(false, VEL_CHEN_GEN);
     }
 #undef CMX_LAUNCH
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    return launched();
 }
 
 // CM2.cloud_terminal_velocity — Microphysics2M.jl:647-664 (point function and constants: cmx_sb2006.hpp).  20 B/point (f32), one point per lane.
@@ -163,15 +153,12 @@ __global__ __launch_bounds__(kBlock) void sb2006_cloud_velocity_kernel(const Clo
 template <typename FT, typename PDF, typename VEL>
 static int32_t cloud_velocity_entry(const PDF *pdf, const VEL *vel, int64_t n, const FT *q_liq, const FT *rho, const FT *N_liq, FT *vt_n,
                                     FT *vt_m, void *stream) {
-    if (!pdf || !vel || n < 0) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
-    if (n == 0) return CMX_OK;
+    if (!pdf || !vel) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT(n);
     if (!q_liq || !rho || !N_liq) return CMX_ERR_BAD_ARG;
     const CloudVelConsts<FT> c = make_cloud_vel_consts<FT>(*pdf, *vel);
-    hipLaunchKernelGGL((sb2006_cloud_velocity_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), c, q_liq, rho, N_liq, vt_n, vt_m, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(sb2006_cloud_velocity_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, q_liq, rho, N_liq, vt_n, vt_m, n);
+    return launched();
 }
 
 // ---- bulk 2M cloud → rain conversion of KK2000 / B1994 / TC1980 / LD2004 — Microphysics2M.jl:920-1003 -------------------
@@ -251,8 +238,8 @@ template <typename FT, typename SC>
 static int32_t bulk_2m_entry(const SC *p, uint32_t scheme, int64_t n, const FT *q_lcl, const FT *q_rai, const FT *rho, const FT *N_d,
                              FT *acnv, FT *accr, void *stream) {
     const uint32_t sch = scheme & 0xffu;
-    if (!p || n < 0 || sch > CMX_2M_LD2004 || (scheme & ~(0xffu | CMX_2M_SMOOTH_TRANSITION))) return CMX_ERR_BAD_ARG;
-    if (n > kMaxPoints) return CMX_ERR_UNSUPPORTED;      // one launch cannot express the grid (cmx_launch.hpp)
+    if (!p || sch > CMX_2M_LD2004 || (scheme & ~(0xffu | CMX_2M_SMOOTH_TRANSITION))) return CMX_ERR_BAD_ARG;
+    CMX_TRY_COUNT_LIMIT(n);
     if (sch == CMX_2M_LD2004 && accr) return CMX_ERR_BAD_ARG;
     if (n == 0) return CMX_OK;
     if (!q_lcl || !rho || (acnv && !N_d) || (accr && !q_rai) || (!acnv && !accr)) return CMX_ERR_BAD_ARG;
@@ -268,10 +255,8 @@ static int32_t bulk_2m_entry(const SC *p, uint32_t scheme, int64_t n, const FT *
     c.t_thr_c = (FT)((double)p->tc1980.acnv_m0_liq_coeff * std::pow((double)p->tc1980.acnv_r_0, (double)p->tc1980.acnv_me_liq));
     c.l_rvol_c = (FT)(3.0 / 4.0 / pi / (double)p->ld2004.rho_w * 1e18);
     c.l_E_0 = p->ld2004.E_0; c.l_R_6C_0 = p->ld2004.R_6C_0; c.l_k = p->ld2004.k;
-    hipLaunchKernelGGL((bulk_2m_cloud_to_rain_kernel<FT>), dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       reinterpret_cast<hipStream_t>(stream), c, q_lcl, q_rai, rho, N_d, acnv, accr, n);
-    CMX_HIP_TRY(hipGetLastError());
-    return CMX_OK;
+    launch<kBlock>(bulk_2m_cloud_to_rain_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, q_lcl, q_rai, rho, N_d, acnv, accr, n);
+    return launched();
 }
 
 }  // namespace cmx

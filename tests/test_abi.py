@@ -4,6 +4,7 @@ ctypes struct mirror matches the C layout; argument validation returns the docum
 import ctypes as C
 import re
 import subprocess
+import warnings
 from pathlib import Path
 
 import pytest
@@ -138,6 +139,91 @@ def test_argument_validation_without_gpu():
     assert g(2, (C.c_void_p * 2)(4096, 4096), 8, C.c_void_p(8192), None, None) == _abi.CMX_ERR_BAD_ARG   # … and so is a missing workspace
     assert g(17, (C.c_void_p * 17)(*[4096] * 17), 8, C.c_void_p(8192), C.c_void_p(16384), None) == _abi.CMX_ERR_BAD_ARG     # more than CMX_COLUMN_SUMS_MAX_COLS
     assert g(0, None, 0, None, None, None) == _abi.CMX_OK
+
+
+def _default_structs(ft):
+    """Every parameter struct (and nested struct) that a public builder of cmx.parameters makes with its defaults, by type."""
+    found = {}
+
+    def walk(c):
+        if type(c) not in found:
+            found[type(c)] = c
+            for name, _ in c._fields_:
+                if isinstance(getattr(c, name), C.Structure):
+                    walk(getattr(c, name))
+    for name, builder in list(vars(P).items()):
+        if name.startswith("_") or not callable(builder):
+            continue
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", P.UnpinnedParameterWarning)
+                obj = builder(ft)
+        except Exception:        # builders that need more than the float type, classes that are not builders
+            continue
+        if isinstance(getattr(obj, "c", obj), C.Structure):
+            walk(getattr(obj, "c", obj))
+    return found
+
+
+# Entries whose (n = -1, n = kMaxPoints + 1, n = 0) statuses differ from the count rule's (BAD_ARG, UNSUPPORTED, OK) with the
+# arguments below, because they check something else first: recorded from the implementation, so that the order of checks stays put.
+_BAD, _UNS, _OK = _abi.CMX_ERR_BAD_ARG, _abi.CMX_ERR_UNSUPPORTED, _abi.CMX_OK
+_COUNT_STATUS_EXCEPTIONS = {
+    "cmx_arg2000_total_activated": (_BAD, _BAD, _BAD),         # no output column, checked before the parameters
+    "cmx_h2so4_solution": (_BAD, _BAD, _BAD),                  # no output column, checked with the parameters
+    "cmx_mohler2006_deposition": (_BAD, _BAD, _BAD),           # no output column, checked with the parameters
+    "cmx_p3_terminal_velocities": (_BAD, _UNS, _BAD),          # quadrature checked between the count limit and n == 0
+    "cmx_p3_shape_terminal_velocities": (_BAD, _UNS, _BAD),
+    "cmx_p3_ice_melt": (_BAD, _UNS, _BAD),
+    "cmx_cloud_diagnostics": (_BAD, _UNS, _BAD),               # no output column, checked before n == 0
+    "cmx_aerosol_nucleation_rates": (_BAD, _UNS, _BAD),
+    "cmx_nucleation_rates_prescribed": (_BAD, _UNS, _BAD),
+    "cmx_apparent_nucleation_rate": (_BAD, _UNS, _BAD),
+    "cmx_p3_ice_nucleation_counts": (_BAD, _UNS, _BAD),
+    "cmx_column_sums": (_BAD, _BAD, _BAD),                     # no count limit; a NULL column is refused first
+}
+
+
+def test_point_count_statuses_without_gpu():
+    """Every entry point with a point count n, f32 and f64: n < 0, n > kMaxPoints (cmx_launch.hpp) and n = 0 with default parameters,
+    in-range scalars and NULL columns.  Each of these calls returns before any HIP runtime call."""
+    lib = _lib.lib()
+    entries = []
+    for name, params in re.findall(r"^int32_t\s+(cmx_\w+_f(?:32|64))\s*\(([^;]*?)\);", HEADER, flags=re.M | re.S):
+        params = [a.strip() for a in re.sub(r"/\*.*?\*/", "", params, flags=re.S).split(",")]
+        k = [i for i, a in enumerate(params) if re.fullmatch(r"int64_t\s+n", a)]
+        if k:
+            entries.append((name, k[0]))
+    assert len(entries) == 84
+    structs = {ft: _default_structs(ft) for ft in ("f32", "f64")}
+    huge = 16 * 0x7fffffff + 1
+    for name, k in entries:
+        fn = getattr(lib, name)
+        args = []
+        for t in fn.argtypes:
+            target = getattr(t, "_type_", None)
+            if isinstance(target, type) and issubclass(target, C.Structure):
+                s = structs[name[-3:]].get(target)
+                if s is None:                  # built only from more than the float type (aerosol modes, dust): in-range by hand
+                    s = target()
+                    if hasattr(s, "n_modes"):
+                        s.n_modes = 1
+                args.append(C.pointer(s))
+            elif target is C.c_void_p:         # an array of column pointers: present, every column NULL
+                args.append((C.c_void_p * 16)())
+            elif t in (C.c_float, C.c_double):
+                args.append(0.5)
+            elif t is C.c_int32:
+                args.append(1)
+            elif t is C.c_uint32:
+                args.append(0)
+            else:
+                args.append(None)
+        got = []
+        for n in (-1, huge, 0):
+            args[k] = n
+            got.append(fn(*args))
+        assert tuple(got) == _COUNT_STATUS_EXCEPTIONS.get(name[:-4], (_BAD, _UNS, _OK)), name
 
 
 def test_product_never_imports_the_oracle():
