@@ -123,8 +123,8 @@ static void launch_arg(const ArgConsts<FT> &c, const ArgIO<FT> &io0, int64_t n, 
         io.S_max = shift(io.S_max, lo); io.N_tot = shift(io.N_tot, lo); io.M_tot = shift(io.M_tot, lo);
         for (int j = 0; j < CMX_ARG_MAX_MODES; ++j) { io.N_act[j] = shift(io.N_act[j], lo); io.M_act[j] = shift(io.M_act[j], lo); }
         const int64_t nv = count / V;
-        if (io.want_N && !io.want_M) launch<kArgBS>(arg_activation_kernel<FT, NM, SINKS, V, true>, nv, s, c, io, nv);
-        else launch<kArgBS>(arg_activation_kernel<FT, NM, SINKS, V, false>, nv, s, c, io, nv);
+        dispatch([&](auto N_ONLY) { launch<kArgBS>(arg_activation_kernel<FT, NM, SINKS, V, decltype(N_ONLY)::value>, nv, s, c, io, nv); },
+                 flag(io.want_N && !io.want_M));
     });
 }
 
@@ -150,17 +150,9 @@ static int32_t arg_entry(const AP *ap, const AD *ad, const AI *aip, const TH *tp
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const bool sinks = N_liq || N_ice;
-#define CMX_ARG_CASE(NM)                                                             \
-    case NM:                                                                         \
-        if (sinks) launch_arg<FT, NM, true>(c, io, n, ptrs, np, s);                  \
-        else launch_arg<FT, NM, false>(c, io, n, ptrs, np, s);                       \
-        break;
-    switch (ad->n_modes) {
-        CMX_ARG_CASE(1) CMX_ARG_CASE(2) CMX_ARG_CASE(3) CMX_ARG_CASE(4)
-        CMX_ARG_CASE(5) CMX_ARG_CASE(6) CMX_ARG_CASE(7) CMX_ARG_CASE(8)
-        default: return CMX_ERR_BAD_ARG;
-    }
-#undef CMX_ARG_CASE
+    if (!dispatch([&](auto NM, auto S) { launch_arg<FT, decltype(NM)::value, decltype(S)::value>(c, io, n, ptrs, np, s); },
+                  one_of<1, 2, 3, 4, 5, 6, 7, 8>(ad->n_modes), flag(sinks)))
+        return CMX_ERR_BAD_ARG;      // unreachable: n_modes was checked above
     return launched();
 }
 
@@ -295,8 +287,8 @@ static void launch_arg_columns(const ArgConsts<FT> &c, const ArgColPar<FT> &par,
             mc.r_dry[j] += lo; mc.stdev[j] += lo; mc.N[j] += lo; mc.hyg[j] += lo; mc.mmix[j] = shift(mc.mmix[j], lo);
         }
         const int64_t nv = count / V;
-        if (!io.want_M) launch<kArgColBS<FT>>(arg_activation_columns_kernel<FT, NM, SINKS, V, true>, nv, s, c, par, io, mc, nv);
-        else launch<kArgColBS<FT>>(arg_activation_columns_kernel<FT, NM, SINKS, V, false>, nv, s, c, par, io, mc, nv);
+        dispatch([&](auto N_ONLY) { launch<kArgColBS<FT>>(arg_activation_columns_kernel<FT, NM, SINKS, V, decltype(N_ONLY)::value>, nv, s, c, par, io, mc, nv); },
+                 flag(!io.want_M));
     });
 }
 
@@ -330,17 +322,9 @@ static int32_t arg_columns_entry(const AP *ap, const AI *aip, const TH *tps, int
     const bool sinks = N_liq || N_ice;
     const double l2e = 1.4426950408889634074;
     const ArgColPar<FT> par{(FT)std::log2((double)ap->f1), (FT)((double)ap->f2 * l2e), (FT)ap->g1, (FT)ap->g2};
-#define CMX_ARGC_CASE(NM)                                                                     \
-    case NM:                                                                                  \
-        if (sinks) launch_arg_columns<FT, NM, true>(c, par, io, mc, n, ptrs, np, s);          \
-        else launch_arg_columns<FT, NM, false>(c, par, io, mc, n, ptrs, np, s);               \
-        break;
-    switch (n_modes) {
-        CMX_ARGC_CASE(1) CMX_ARGC_CASE(2) CMX_ARGC_CASE(3) CMX_ARGC_CASE(4)
-        CMX_ARGC_CASE(5) CMX_ARGC_CASE(6) CMX_ARGC_CASE(7) CMX_ARGC_CASE(8)
-        default: return CMX_ERR_BAD_ARG;
-    }
-#undef CMX_ARGC_CASE
+    if (!dispatch([&](auto NM, auto S) { launch_arg_columns<FT, decltype(NM)::value, decltype(S)::value>(c, par, io, mc, n, ptrs, np, s); },
+                  one_of<1, 2, 3, 4, 5, 6, 7, 8>(n_modes), flag(sinks)))
+        return CMX_ERR_BAD_ARG;      // unreachable: n_modes was checked above
     return launched();
 }
 

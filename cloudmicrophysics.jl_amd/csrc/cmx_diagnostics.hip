@@ -181,8 +181,7 @@ static int32_t cloud_diagnostics_entry(const RN *rain, const PC *pdf_c, const PR
         const DiagIO<FT> io{rho + lo, shift(q_lcl, lo), shift(q_rai, lo), shift(N_lcl, lo), shift(N_rai, lo), shift(Z_1m, lo), shift(Z_2m, lo),
                             shift(reff_2m, lo), shift(reff_lh97, lo)};
         const int64_t nvec = count / V;
-        if (limited) launch<kBlock>(cloud_diagnostics_kernel<FT, V, true>, nvec, s, c, io, lh_defaults, nvec);
-        else launch<kBlock>(cloud_diagnostics_kernel<FT, V, false>, nvec, s, c, io, lh_defaults, nvec);
+        dispatch([&](auto L) { launch<kBlock>(cloud_diagnostics_kernel<FT, V, decltype(L)::value>, nvec, s, c, io, lh_defaults, nvec); }, flag(limited));
     });
     return launched();
 }

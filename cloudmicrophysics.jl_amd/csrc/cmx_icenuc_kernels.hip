@@ -207,20 +207,18 @@ static int32_t icenuc_entry(const TH *tps, const DU *dust, const KO *koop, const
     constexpr int VEC = Math<FT>::VEC;
     const void *ptrs[] = {T, a_w, r, delta_a_w, J_het, J_hom, rate_het, rate_hom};
     const bool linear = flags & CMX_ICENUC_HOM_LINEAR;
+    // three modes, not the product from_x × rates_only: the solution-droplet input mode has one instantiation per homogeneous-rate form
+    enum : int { ICENUC_ALL, ICENUC_RATES_ONLY, ICENUC_FROM_X };
+    const bool rates_only = !delta_a_w && !J_het && !J_hom && rate_het && rate_hom;
+    const int mode = from_x ? ICENUC_FROM_X : rates_only ? ICENUC_RATES_ONLY : ICENUC_ALL;
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
         IceNucIO<FT> io{T + lo, a_w + lo, shift(r, lo), shift(delta_a_w, lo), shift(J_het, lo), shift(J_hom, lo),
                         shift(rate_het, lo), shift(rate_hom, lo), reinterpret_cast<unsigned long long *>(n_domain_errors)};
         const int64_t nv = count / V;
-        const bool rates_only = !delta_a_w && !J_het && !J_hom && rate_het && rate_hom;
-        if (from_x) {   // the solution-droplet input mode: one instantiation per homogeneous-rate form
-            if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V, false, true>, nv, s, c, io, nv);
-            else launch<kBlock>(ice_nucleation_kernel<FT, false, V, false, true>, nv, s, c, io, nv);
-        } else if (rates_only) {
-            if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V, true>, nv, s, c, io, nv);
-            else launch<kBlock>(ice_nucleation_kernel<FT, false, V, true>, nv, s, c, io, nv);
-        } else if (linear) launch<kBlock>(ice_nucleation_kernel<FT, true, V>, nv, s, c, io, nv);
-        else launch<kBlock>(ice_nucleation_kernel<FT, false, V>, nv, s, c, io, nv);
+        dispatch([&](auto LIN, auto M) {
+            launch<kBlock>(ice_nucleation_kernel<FT, decltype(LIN)::value, V, decltype(M)::value == ICENUC_RATES_ONLY, decltype(M)::value == ICENUC_FROM_X>, nv, s, c, io, nv);
+        }, flag(linear), one_of<ICENUC_ALL, ICENUC_RATES_ONLY, ICENUC_FROM_X>(mode));
     });
     return launched();
 }

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "../../include/cmx.h"
+#include "cmx_dispatch.hpp"
 #include "cmx_split.hpp"
 
 namespace cmx {
@@ -40,6 +41,8 @@ inline int32_t launched() {
 // tile_grid; `grid_for` (capped, grid-stride) sizes sb2006_process_kernel only.  A geometry of their own have the column-sum
 // reduction (fixed 2-D grid, cmx_common.hip), the column kernels (tiles that overlap by one lane, cmx_*_column.hip) and the P3
 // collision kernels (collision_geometry with dynamic LDS, cmx_p3_collisions.hip).
+// Who picks which instantiation: the entry, with dispatch() (cmx_dispatch.hpp) — run-time flags and modes become the kernel's template arguments
+// inside one generic lambda whose body is the launch; for_each_range below adds the vector width of each range.
 constexpr int kBlock = 256;
 
 struct DeviceInfo { int cus; int blocks_per_cu; };

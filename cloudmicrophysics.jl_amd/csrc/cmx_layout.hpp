@@ -182,22 +182,14 @@ static int32_t launch_layout(const typename POLICY::Consts &c, int64_t n_seg, in
     for (int k = 0; k < NIN; ++k) io.idx32 = io.idx32 && io.in_stride[k] < ((int64_t)1 << 32);
     for (int k = 0; k < NOUT && out; ++k) io.idx32 = io.idx32 && io.out_stride[k] < ((int64_t)1 << 32);
     io.seg_div = make_fastdiv((uint32_t)(io.idx32 ? seg_len : 1));
-    const bool seg = n_seg > 1;
-    auto launch = [&](auto vec_tag) {
-        constexpr int V = decltype(vec_tag)::value;
+    // vector width (VEC, or 1 where a column or a stride does not allow it) × segmented input × array-of-structs output
+    dispatch([&](auto W, auto SEG, auto AOS) {
+        constexpr int V = decltype(W)::value;
         const int64_t nvec = n / V;
         const dim3 grid((unsigned)tile_grid(nvec, kLayoutBS)), block(kLayoutBS);
         const size_t lds = aos ? sizeof(FT) * (size_t)kLayoutBS * (V * NAOS + 16 / sizeof(FT)) : 0;
-        if (seg) {
-            if (aos) launch_grid(tendencies_layout_kernel<FT, POLICY, V, true, true>, grid, block, lds, s, c, io, nvec);
-            else launch_grid(tendencies_layout_kernel<FT, POLICY, V, true, false>, grid, block, lds, s, c, io, nvec);
-        } else {
-            if (aos) launch_grid(tendencies_layout_kernel<FT, POLICY, V, false, true>, grid, block, lds, s, c, io, nvec);
-            else launch_grid(tendencies_layout_kernel<FT, POLICY, V, false, false>, grid, block, lds, s, c, io, nvec);
-        }
-    };
-    if (vec_ok) launch(std::integral_constant<int, VEC>{});
-    else launch(std::integral_constant<int, 1>{});
+        launch_grid(tendencies_layout_kernel<FT, POLICY, V, decltype(SEG)::value, decltype(AOS)::value, kLayoutBS>, grid, block, lds, s, c, io, nvec);
+    }, one_of<VEC, 1>(vec_ok ? VEC : 1), flag(n_seg > 1), flag(aos != nullptr));
     return launched();
 }
 

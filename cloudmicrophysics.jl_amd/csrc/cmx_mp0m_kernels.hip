@@ -50,10 +50,9 @@ static int32_t mp0m_entry(const PR *p, int64_t n, const FT *q_lcl, const FT *q_i
         constexpr int V = decltype(vec_tag)::value;
         const Mp0mIO<FT> io{q_lcl + lo, q_icl + lo, shift(q_vap_sat, lo), dq_tot_dt + lo, shift(ddq_dq_tot, lo)};
         const int64_t nvec = count / V;
-#define CMX_LAUNCH(S, D) launch<kBlock>(mp0m_tendencies_kernel<FT, V, S, D>, nvec, s, p->tau_precip, p->qc_0, p->S_0, io, nvec)
-        if (q_vap_sat) { if (ddq_dq_tot) CMX_LAUNCH(true, true); else CMX_LAUNCH(true, false); }
-        else           { if (ddq_dq_tot) CMX_LAUNCH(false, true); else CMX_LAUNCH(false, false); }
-#undef CMX_LAUNCH
+        dispatch([&](auto S, auto D) {
+            launch<kBlock>(mp0m_tendencies_kernel<FT, V, decltype(S)::value, decltype(D)::value>, nvec, s, p->tau_precip, p->qc_0, p->S_0, io, nvec);
+        }, flag(q_vap_sat != nullptr), flag(ddq_dq_tot != nullptr));
     });
     return launched();
 }

@@ -21,6 +21,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "cmx_dispatch.hpp"
 #include "../../include/cmx.h"
 #include "cmx_math.hpp"
 
@@ -74,6 +75,11 @@ template <typename CT> inline bool mp1m_default_exponents(const CT &c) {
     return CMX_1M_DEFEXP && c.vt_e_rai == 0.5 && c.acc_e_rai == 3.5 && c.sink_e == 6.5 && c.rs_dp1_rai == 4 && c.ven_e_rai == 0.75 && c.vt_e_sno == 0.25 &&
            c.acc_e_sno == 3.25 && c.rs_dp1_sno == 3 && c.ven_e_sno == 0.625 &&
            c.ka_qthr >= c.eps_1m && c.ks_qthr >= c.eps_1m;   // … and regular autoconversion thresholds (logistic_rate)
+}
+// the compile-time FLAGS of a call, as a selector of dispatch(): the default-options instantiation or the run-time-flags one
+constexpr uint32_t kDefaultFlags = CMX_1M_DEFAULT_OPTIONS | kDefExpBit;
+template <typename CT> inline auto flags_1m(uint32_t flags, const CT &c) {
+    return one_of<kDefaultFlags, kRuntimeFlags>(flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(c) ? kDefaultFlags : kRuntimeFlags);
 }
 
 template <typename FT, typename MP, typename TH>

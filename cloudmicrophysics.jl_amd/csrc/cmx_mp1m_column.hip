@@ -72,29 +72,8 @@ __global__ __launch_bounds__(BS) void mp1m_column_shaped_kernel(const Mp1mColSha
 #endif
 constexpr int kColBS1m = CMX_COLUMN1M_BS;
 
-template <typename FT, int VEC>
-static void launch_column_1m(bool def, bool lin, bool general, const Mp1mColKernArgs<FT> &a, const Mp1mColIO<FT> &io, int64_t first, int64_t nvec,
-                             hipStream_t s) {
-    if (nvec <= 0) return;
-    const dim3 grid((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))), block(kColBS1m);      // tiles overlap by one lane
-    constexpr uint32_t DEF = CMX_1M_DEFAULT_OPTIONS | kDefExpBit;
-#define CMX_L(FL, LN, GG) launch_grid(mp1m_column_kernel<FT, FL, LN, GG, VEC, kColBS1m>, grid, block, 0, s, a, io, first, nvec)
-#define CMX_G(FL, LN) do { if (general) CMX_L(FL, LN, true); else CMX_L(FL, LN, false); } while (0)
-    if (def) { if (lin) CMX_G(DEF, true); else CMX_G(DEF, false); }
-    else { if (lin) CMX_G(kRuntimeFlags, true); else CMX_G(kRuntimeFlags, false); }
-#undef CMX_G
-#undef CMX_L
-}
-template <typename FT, int VEC>
-static void launch_column_1m_shaped(bool lin, bool general, const Mp1mColShapeKernArgs<FT> &a, const Mp1mColIO<FT> &io, int64_t first, int64_t nvec,
-                                    hipStream_t s) {
-    if (nvec <= 0) return;
-    const dim3 grid((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))), block(kColBS1m);      // tiles overlap by one lane
-#define CMX_L(LN, GG) launch_grid(mp1m_column_shaped_kernel<FT, LN, GG, VEC, kColBS1m>, grid, block, 0, s, a, io, first, nvec)
-    if (lin) { if (general) CMX_L(true, true); else CMX_L(true, false); }
-    else { if (general) CMX_L(false, true); else CMX_L(false, false); }
-#undef CMX_L
-}
+// the grid of one range of nvec lanes: tiles overlap by one lane
+static dim3 column_1m_grid(int64_t nvec) { return dim3((unsigned)((nvec + (kColBS1m - 1) - 1) / (kColBS1m - 1))); }
 
 template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
 static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, FT q_min, FT dt,
@@ -125,7 +104,6 @@ static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, co
     for (int j = 0; j < 7; ++j) { if (!in[j]) return CMX_ERR_BAD_ARG; io.in[j] = in[j]; ptrs[j] = in[j]; }
     for (int j = 0; j < 4; ++j) { if (!out[j]) return CMX_ERR_BAD_ARG; io.out[j] = out[j]; ptrs[7 + j] = out[j]; }
     io.inv_dz = inv_dz; io.precip_rai = precip_rai; io.precip_sno = precip_sno; io.n = n; io.n_lev = n_lev; io.inv_n_lev = 1.0 / (double)n_lev; io.lev_div = make_fastdiv((uint32_t)n_lev);
-    const bool def = flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(k.c);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;     // Float64: one point per lane, as in the pointwise kernel
     // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches
@@ -136,12 +114,16 @@ static int32_t column_1m_entry(const MP *mp, const TH *tps, const ST *stokes, co
         as.vc = make_snow_shape_consts<FT>(*mp, chen_rain, stokes, *chen_ice, snow_shape);
         for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
             constexpr int V = decltype(vec_tag)::value;
-            launch_column_1m_shaped<FT, V>(lin, general, as, io, lo, count / V, s);
+            dispatch([&](auto LN, auto GG) {
+                launch_grid(mp1m_column_shaped_kernel<FT, decltype(LN)::value, decltype(GG)::value, V, kColBS1m>, column_1m_grid(count / V), dim3(kColBS1m), 0, s, as, io, lo, count / V);
+            }, flag(lin), flag(general));
         });
     } else {
         for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
             constexpr int V = decltype(vec_tag)::value;
-            launch_column_1m<FT, V>(def, lin, general, a, io, lo, count / V, s);
+            dispatch([&](auto FL, auto LN, auto GG) {
+                launch_grid(mp1m_column_kernel<FT, decltype(FL)::value, decltype(LN)::value, decltype(GG)::value, V, kColBS1m>, column_1m_grid(count / V), dim3(kColBS1m), 0, s, a, io, lo, count / V);
+            }, flags_1m(flags, k.c), flag(lin), flag(general));
         });
     }
     return launched();

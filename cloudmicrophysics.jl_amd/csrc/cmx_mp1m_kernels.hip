@@ -222,10 +222,7 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
         Mp1mIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo};
         Mp1mOut<FT> out{dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo};
         const int64_t nv = count / V;
-        if (flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(c))
-            launch<kBlock1m<FT>>(mp1m_tendencies_kernel<FT, V, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, c, in, out, nv);
-        else
-            launch<kBlock1m<FT>>(mp1m_tendencies_kernel<FT, V>, nv, s, c, in, out, nv);
+        dispatch([&](auto FL) { launch<kBlock1m<FT>>(mp1m_tendencies_kernel<FT, V, decltype(FL)::value>, nv, s, c, in, out, nv); }, flags_1m(flags, c));
     });
     return launched();
 }
@@ -257,9 +254,9 @@ static int32_t fields_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int6
     if (const int32_t st = check_flags_1m(flags)) return st;
     const Mp1mConsts<FT> c = make_mp1m_consts<FT>(*mp, *tps, flags, (double)Math<FT>::eps_1m());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(c))
-        return launch_layout<FT, Mp1mLayoutPolicy<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-    return launch_layout<FT, Mp1mLayoutPolicy<FT, kRuntimeFlags>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto FL) {
+        return launch_layout<FT, Mp1mLayoutPolicy<FT, decltype(FL)::value>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    }, flags_1m(flags, c));
 }
 
 template <typename FT, typename MP, typename TH>
@@ -281,7 +278,6 @@ static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
     if (n == 0) return CMX_OK;
     if (!rho || !T || !q_tot || !q_lcl || !q_icl || !q_rai || !q_sno || !dq_lcl || !dq_icl || !dq_rai || !dq_sno) return CMX_ERR_BAD_ARG;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool def = flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(k.c);
     // Float32: pairs of points in packed arithmetic (8-byte body), the rest one point per lane — the same per-point operations, so the
     // result does not depend on the alignment split (cmx_split.hpp)
     constexpr int VEC = (sizeof(FT) == 4 && CMX_1M_LIN_PACKED) ? 2 : 1;
@@ -290,15 +286,14 @@ static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
         constexpr int V = decltype(vec_tag)::value;
         Mp1mLinIO<FT> io{{rho + lo, T + lo, q_tot + lo, q_lcl + lo, q_icl + lo, q_rai + lo, q_sno + lo}, {dq_lcl + lo, dq_icl + lo, dq_rai + lo, dq_sno + lo}};
         const int64_t nv = count / V;
-        if constexpr (V == 2) {
-            if constexpr (sizeof(FT) == 4) {      // always true here (VEC above); discards the Float32-only kernel from the Float64 entry
-                if (def) launch<kBlockLin>(mp1m_linearized_pair_kernel<CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, k, io, nv);
-                else launch<kBlockLin>(mp1m_linearized_pair_kernel<kRuntimeFlags>, nv, s, k, io, nv);
+        dispatch([&](auto FL) {
+            if constexpr (V == 2) {
+                // always true here (VEC above); discards the Float32-only kernel from the Float64 entry
+                if constexpr (sizeof(FT) == 4) launch<kBlockLin>(mp1m_linearized_pair_kernel<decltype(FL)::value>, nv, s, k, io, nv);
+            } else {
+                launch<kBlockLin>(mp1m_linearized_kernel<FT, decltype(FL)::value>, nv, s, k, io, nv);
             }
-        } else {
-            if (def) launch<kBlockLin>(mp1m_linearized_kernel<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>, nv, s, k, io, nv);
-            else launch<kBlockLin>(mp1m_linearized_kernel<FT>, nv, s, k, io, nv);
-        }
+        }, flags_1m(flags, k.c));
     });
     return launched();
 }
@@ -309,9 +304,9 @@ static int32_t linearized_fields_1m_entry(const MP *mp, const TH *tps, uint32_t 
     Mp1mLinKernArgs<FT> k{};
     if (const int32_t st = make_lin_kernargs<FT>(mp, tps, flags, q_min, dt, nsub, k)) return st;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(k.c))
-        return launch_layout<FT, Mp1mLinLayoutPolicy<FT, CMX_1M_DEFAULT_OPTIONS | kDefExpBit>>(k, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-    return launch_layout<FT, Mp1mLinLayoutPolicy<FT, kRuntimeFlags>>(k, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto FL) {
+        return launch_layout<FT, Mp1mLinLayoutPolicy<FT, decltype(FL)::value>>(k, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    }, flags_1m(flags, k.c));
 }
 
 template <typename FT, typename MP, typename TH>
@@ -333,8 +328,7 @@ static int32_t sources_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int
 
 // the Chen-2022 rain table selects the instantiation: polynomial Γ on its window (fast) or run-time Γ for any exponent (general)
 template <typename FT> static void launch_velocity(bool general_gamma, const Vel1mConsts<FT> &c, const Vel1mIO<FT> &io, int64_t n, void *stream) {
-    if (general_gamma) launch<kBlock>(mp1m_velocity_kernel<FT, true>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
-    else launch<kBlock>(mp1m_velocity_kernel<FT, false>, n, reinterpret_cast<hipStream_t>(stream), c, io, n);
+    dispatch([&](auto GG) { launch<kBlock>(mp1m_velocity_kernel<FT, decltype(GG)::value>, n, reinterpret_cast<hipStream_t>(stream), c, io, n); }, flag(general_gamma));
 }
 
 template <typename FT, typename MP, typename CH>

@@ -624,6 +624,45 @@ static P3VelConsts<FT> make_p3_vel_consts(const PR &pr, const VR &vel, double p)
     v.p_lo = (FT)p; v.p_hi = (FT)(1.0 - p);
     return v;
 }
+// … of the collision integrals: their quantile levels are FT numbers, p = FT(0.00001) (P3_processes.jl:546)
+template <typename FT, typename PR, typename VR>
+static P3VelConsts<FT> make_p3_collision_vel_consts(const PR &pr, const VR &vel) {
+    P3VelConsts<FT> v = make_p3_vel_consts<FT>(pr, vel, 1e-5);
+    v.p_lo = FT(0.00001); v.p_hi = FT(1) - v.p_lo;
+    return v;
+}
+
+// Host constants that more than one constants struct holds under the same member names, filled by one function each (K: the struct).
+// ice_melt (P3_processes.jl:64-94): ventilation F_v = vent_a + vent_bc √(D v), 4 K_therm, L_f(T) = LH_f0 + dcp_f (T − T_0)
+template <typename K, typename VT, typename AP, typename TH> inline void fill_melt_consts(K &k, const VT &vent, const AP &aps, const TH &tps) {
+    using FT = decltype(k.vent_a);
+    k.vent_a = (FT)vent.a;
+    k.vent_bc = (FT)((double)vent.b * std::cbrt((double)aps.nu_air / (double)aps.D_vapor) / std::sqrt((double)aps.nu_air));
+    k.K4 = (FT)(4.0 * (double)aps.K_therm);
+    k.LH_f0 = (FT)((double)tps.LH_s0 - (double)tps.LH_v0); k.dcp_f = (FT)((double)tps.cp_l - (double)tps.cp_i);
+    k.T_0 = (FT)tps.T_0;
+}
+// saturation vapour pressure over ice: p_sat = press_tr (T/T_tr)^ps_pow exp(ps_b (1/T_tr − 1/T))
+template <typename K, typename TH> inline void fill_ice_saturation_consts(K &k, const TH &tps) {
+    using FT = decltype(k.ps_pow);
+    const double dcp_i = (double)tps.cp_v - (double)tps.cp_i, Rv = tps.R_v;
+    k.ps_pow = (FT)(dcp_i / Rv); k.ps_b = (FT)(((double)tps.LH_s0 - dcp_i * (double)tps.T_0) / Rv); k.inv_T_tr = (FT)(1.0 / (double)tps.T_triple);
+    k.press_tr = tps.press_triple; k.R_v = tps.R_v;
+}
+
+// the flags of the entries that take a P3 state
+constexpr uint32_t kP3StateFlags = CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO;
+
+// The common prologue of the P3 entries, in their order of checks: parameter structs and flag mask, the count rule (cmx_launch.hpp),
+// quadrature order and — where the entry takes one (p non-null) — the quantile level, then n == 0.  proceed = false: the entry returns status.
+struct P3Checked { int32_t status; bool proceed; };
+template <typename FT, typename QUAD>
+inline P3Checked p3_entry_checks(bool have_params, const QUAD *quad, uint32_t flags, uint32_t allowed, int64_t n, const FT *p) {
+    if (!have_params || !quad || (flags & ~allowed)) return {CMX_ERR_BAD_ARG, false};
+    if (const int32_t st = count_limit_status(n)) return {st, false};
+    if (quad->n < 1 || quad->n > CMX_QUAD_MAX || (p && !(*p > FT(0) && *p < FT(0.5)))) return {CMX_ERR_BAD_ARG, false};
+    return {CMX_OK, n != 0};
+}
 
 // UT._gamma_inc_inv — Utilities.jl:205-252 (Halley on P − p or Q − q, ≤ 15 iterations)
 template <typename FT> __device__ FT gamma_inc_inv_dev(FT a, FT p, FT q) {

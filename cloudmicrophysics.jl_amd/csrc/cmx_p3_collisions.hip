@@ -102,7 +102,7 @@ static P3ColConsts<FT> make_p3col_consts(const IP &ip, const AP &aps, const TH &
     k.log_zq_lo = (FT)std::log(host_gamma_inc_inv(zq, (double)p_lo));
     k.log_zq_hi = (FT)std::log(host_gamma_inc_inv(zq, (double)p_hi));
     const auto &pr = ip.rain_pdf;
-    k.xr_min = pr.xr_min; k.xr_max = pr.xr_max; k.N0_min = pr.N0_min; k.N0_max = pr.N0_max; k.lam_min = pr.lambda_min; k.lam_max = pr.lambda_max;
+    fill_rain_pdf_limiters(k, pr);
     k.pi_rho_w = (FT)(pi * (double)pr.rho_w);
     k.k_lo = (FT)(-std::log1p(-(double)p_lo)); k.k_hi = (FT)(-std::log1p(-(double)p_hi));
     k.limited = (flags & CMX_P3_RAIN_PDF_LIMITED) != 0;
@@ -111,22 +111,19 @@ static P3ColConsts<FT> make_p3col_consts(const IP &ip, const AP &aps, const TH &
     k.rime_rho8 = (FT)((double)rl.a + 8.0 * (double)rl.b + 64.0 * (double)rl.c);
     k.K_therm = aps.K_therm; k.D_vapor = aps.D_vapor; k.cp_l = tps.cp_l;
     k.LH_v0 = tps.LH_v0; k.dcp_v = (FT)((double)tps.cp_v - (double)tps.cp_l);
-    k.LH_f0 = (FT)((double)tps.LH_s0 - (double)tps.LH_v0); k.dcp_f = (FT)((double)tps.cp_l - (double)tps.cp_i);
-    k.T_0 = tps.T_0; k.T_freeze_tps = tps.T_freeze;
+    fill_melt_consts(k, ip.vent, aps, tps);      // vent_a, vent_bc, K4, LH_f0, dcp_f, T_0
+    k.T_freeze_tps = tps.T_freeze;
+    fill_ice_saturation_consts(k, tps);           // ps_pow, ps_b, inv_T_tr, press_tr, R_v
     const double dcp_i = (double)tps.cp_v - (double)tps.cp_i, Rv = tps.R_v, Ttr = tps.T_triple;
-    k.ps_pow = (FT)(dcp_i / Rv); k.ps_b = (FT)(((double)tps.LH_s0 - dcp_i * (double)tps.T_0) / Rv); k.inv_T_tr = (FT)(1.0 / Ttr);
-    k.press_tr = tps.press_triple; k.R_v = tps.R_v;
     const double Tf = tps.T_freeze;
     const double ps_frz = (double)tps.press_triple * std::pow(Tf / Ttr, dcp_i / Rv) * std::exp(((double)tps.LH_s0 - dcp_i * (double)tps.T_0) / Rv * (1 / Ttr - 1 / Tf));
     k.qsi_frz = (FT)(ps_frz / (Rv * Tf));
-    k.vent_a = ip.vent.a;
-    k.vent_bc = (FT)((double)ip.vent.b * std::cbrt((double)aps.nu_air / (double)aps.D_vapor) / std::sqrt((double)aps.nu_air));
     k.T_freeze_p3 = ip.scheme.T_freeze;
     k.m_fac = (FT)((double)pc.rho_w * pi / 6.0);
     k.tau_wet = ip.scheme.tau_wet; k.rho_i = ip.scheme.rho_i;
     k.inv_m_shd = (FT)(1.0 / ((double)pc.rho_w * 1e-9 * pi / 6.0));      // 1/m_liq(D_shd = 1 mm)
     k.brent_iters = sizeof(FT) == 4 ? 8 : 10;
-    k.p_lo_m = (FT)1e-6; k.p_hi_m = (FT)(1.0 - 1e-6); k.K4 = (FT)(4.0 * (double)aps.K_therm);
+    k.p_lo_m = (FT)1e-6; k.p_hi_m = (FT)(1.0 - 1e-6);
     return k;
 }
 
@@ -216,9 +213,8 @@ static PointwiseConsts<FT> make_pointwise_consts(const WR &wr, const IP &ip, con
     k.m_nuc = (FT)((double)ip.scheme.rho_i * (1e-15 * pi / 6.0));                       // ρ_i · volume_sphere_D(10 µm) — BMT:999-1000
     k.T_dep = (FT)((double)fr.T_freeze - 15.0); k.S_thresh = (FT)0.05;
     k.rf_a = ip.rain_freezing.het_a; k.rf_B = ip.rain_freezing.het_B; k.T_bigg = (FT)((double)tps.T_freeze - 4.0);
-    const double dcp_i = (double)tps.cp_v - (double)tps.cp_i, Rv = tps.R_v;
-    k.ps_pow = (FT)(dcp_i / Rv); k.ps_b = (FT)(((double)tps.LH_s0 - dcp_i * (double)tps.T_0) / Rv); k.inv_T_tr = (FT)(1.0 / (double)tps.T_triple);
-    k.press_tr = tps.press_triple; k.R_v = tps.R_v; k.LH_s0 = tps.LH_s0; k.dcp_s = (FT)dcp_i; k.T_0 = tps.T_0;
+    fill_ice_saturation_consts(k, tps);      // ps_pow, ps_b, inv_T_tr, press_tr, R_v
+    k.LH_s0 = tps.LH_s0; k.dcp_s = (FT)((double)tps.cp_v - (double)tps.cp_i); k.T_0 = tps.T_0;
     k.cp_d = tps.cp_d; k.cpm_qt = (FT)((double)tps.cp_v - (double)tps.cp_d); k.cpm_ql = (FT)((double)tps.cp_l - (double)tps.cp_v);
     k.cpm_qi = (FT)((double)tps.cp_i - (double)tps.cp_v); k.T_freeze_tps = tps.T_freeze;
     k.tau_subdep = wr.subdep_tau_relax;
@@ -230,7 +226,7 @@ static PointwiseConsts<FT> make_pointwise_consts(const WR &wr, const IP &ip, con
     k.k3 = (FT)(-3.0 / muD); k.k6 = (FT)(-6.0 / muD);
     k.V1 = (FT)(pi / 6.0); k.rho_w_V1sq = (FT)((double)pc.rho_w * (pi / 6.0) * (pi / 6.0));
     const auto &pr = ip.rain_pdf;
-    k.xr_min = pr.xr_min; k.xr_max = pr.xr_max; k.N0_min = pr.N0_min; k.N0_max = pr.N0_max; k.lam_min = pr.lambda_min; k.lam_max = pr.lambda_max;
+    fill_rain_pdf_limiters(k, pr);
     k.pi_rho_w = (FT)(pi * (double)pr.rho_w);
     k.inv_rho_i = (FT)(1.0 / (double)ip.scheme.rho_i);
     return k;
@@ -973,34 +969,29 @@ static int32_t launch_collision_kernel(const P3Consts<FT> &c, const P3VelConsts<
     dim3 grid, block;
     size_t lds;
     if (!collision_geometry<FT>(group, quad.n, n, grid, block, lds)) return CMX_ERR_UNSUPPORTED;
-    auto go = [&](auto kern) -> int32_t {
-        if (lds > 48 * 1024) CMX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        launch_grid(kern, grid, block, lds, st, c, v, k, quad, io, n, ex);
-        return launched();
-    };
-    if (group == 8)
-        return aspect ? go(&p3_collision_kernel<FT, QUAD, true, FUSED, 8, EXTRA>) : go(&p3_collision_kernel<FT, QUAD, false, FUSED, 8, EXTRA>);
-    // 16 lanes per state: rules of order >= 48 (collision_group) — never a QuadSmall rule (order <= 32), so the one-launch form has no such
-    // instantiation
-    if constexpr (std::is_same_v<QUAD, QuadSmall<FT>>) return CMX_ERR_BAD_ARG;
-    else return aspect ? go(&p3_collision_kernel<FT, QUAD, true, FUSED, 16, EXTRA>) : go(&p3_collision_kernel<FT, QUAD, false, FUSED, 16, EXTRA>);
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto A, auto G) -> int32_t {
+        // 16 lanes per state: rules of order >= 48 (collision_group) — never a QuadSmall rule (order <= 32), so the one-launch form has no such
+        // instantiation
+        if constexpr (decltype(G)::value == 16 && std::is_same_v<QUAD, QuadSmall<FT>>) return CMX_ERR_BAD_ARG;
+        else {
+            const auto kern = &p3_collision_kernel<FT, QUAD, decltype(A)::value, FUSED, decltype(G)::value, EXTRA>;
+            if (lds > 48 * 1024) CMX_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            launch_grid(kern, grid, block, lds, st, c, v, k, quad, io, n, ex);
+            return launched();
+        }
+    }, flag(aspect), one_of<8, 16>(group));
 }
 
 template <typename FT, typename IP, typename AP, typename TH, typename QUAD>
 static int32_t p3_collision_entry(const IP *ip, const AP *aps, const TH *tps, const QUAD *quad, uint32_t flags, int64_t n, const FT *rho_q,
                                   const FT *rho_n, const FT *x3, const FT *x4, const FT *L_c, const FT *N_c, const FT *L_r, const FT *N_r,
                                   const FT *rho_a, const FT *T, const FT *loglam, FT *const *sources, FT *const *rates, void *stream) {
-    if (!ip || !aps || !tps || !quad ||
-        (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED)))
-        return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (quad->n < 1 || quad->n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked ck = p3_entry_checks(ip && aps && tps, quad, flags, kP3StateFlags | CMX_P3_RAIN_PDF_LIMITED, n, (const FT *)nullptr); !ck.proceed)
+        return ck.status;
     if (!rho_q || !rho_n || !x3 || !x4 || !L_c || !N_c || !L_r || !N_r || !rho_a || !T || !loglam || (!sources && !rates)) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(ip->scheme, flags);
     c.brent_iters = 0;
-    P3VelConsts<FT> v = make_p3_vel_consts<FT>(ip->scheme, ip->vel_ice, 1e-5);
-    v.p_lo = FT(0.00001); v.p_hi = FT(1) - v.p_lo;
+    const P3VelConsts<FT> v = make_p3_collision_vel_consts<FT>(ip->scheme, ip->vel_ice);
     const P3ColConsts<FT> k = make_p3col_consts<FT>(*ip, *aps, *tps, flags);
     P3ColIO<FT> io{};
     io.rho_q = rho_q; io.rho_n = rho_n; io.x3 = x3; io.x4 = x4; io.L_c = L_c; io.N_c = N_c; io.L_r = L_r; io.N_r = N_r;
@@ -1037,9 +1028,11 @@ static int32_t liquid_freezing_entry(const IP *ip, const TH *tps, uint32_t flags
     WR wr{};
     const PointwiseConsts<FT> k = make_pointwise_consts<FT>(wr, *ip, *tps);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_FREEZE_CLOUD_PSD) launch<kBlock>(liquid_freezing_kernel<FT, true, true>, n, st, k, q, rho, N, T, dn, dq, n);
-    else if (flags & CMX_P3_RAIN_PDF_LIMITED) launch<kBlock>(liquid_freezing_kernel<FT, false, true>, n, st, k, q, rho, N, T, dn, dq, n);
-    else launch<kBlock>(liquid_freezing_kernel<FT, false, false>, n, st, k, q, rho, N, T, dn, dq, n);
+    // three distributions: the cloud PSD is compiled as <CLOUD, LIMITED> = <true, true> only
+    enum : int { FRZ_CLOUD, FRZ_RAIN_LIMITED, FRZ_RAIN };
+    dispatch([&](auto M) {
+        launch<kBlock>(liquid_freezing_kernel<FT, decltype(M)::value == FRZ_CLOUD, decltype(M)::value != FRZ_RAIN>, n, st, k, q, rho, N, T, dn, dq, n);
+    }, one_of<FRZ_CLOUD, FRZ_RAIN_LIMITED, FRZ_RAIN>((flags & CMX_FREEZE_CLOUD_PSD) ? FRZ_CLOUD : (flags & CMX_P3_RAIN_PDF_LIMITED) ? FRZ_RAIN_LIMITED : FRZ_RAIN));
     return launched();
 }
 
@@ -1047,10 +1040,10 @@ template <typename FT, typename WR, typename IP, typename TH>
 static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T, const FT *q_tot,
                              const FT *q_lcl, const FT *n_lcl, const FT *q_rai, const FT *n_rai, const FT *q_ice, const FT *n_ice, const FT *q_rim,
                              const FT *b_rim, const FT *loglam, const FT *shift, FT *const *out, void *stream, const SegLayout *lay = nullptr) {
-    if (!wr || !ip || !tps || (flags & ~(CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED))) return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (ip->quad.n < 1 || ip->quad.n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked ck = p3_entry_checks(wr && tps, ip ? &ip->quad : nullptr, flags, CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED, n,
+                                             (const FT *)nullptr);
+        !ck.proceed)
+        return ck.status;
     if (!rho || !T || !q_tot || !q_lcl || !n_lcl || !q_rai || !n_rai || !q_ice || !n_ice || !q_rim || !b_rim || !loglam || !out) return CMX_ERR_BAD_ARG;
     for (int q = 0; q < 8; ++q) if (!out[q]) return CMX_ERR_BAD_ARG;
     const bool limited = (flags & CMX_P3_RAIN_PDF_LIMITED) != 0;
@@ -1063,8 +1056,7 @@ static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const bool intpow = sb_integer_exponents(*wr) && CMX_SB_INTPOW_P3;   // the same warm-rain instantiation as cmx_sb2006_warm_rain_tendencies_* picks
     // ice processes
-    P3VelConsts<FT> v = make_p3_vel_consts<FT>(ip->scheme, ip->vel_ice, 1e-5);
-    v.p_lo = FT(0.00001); v.p_hi = FT(1) - v.p_lo;
+    const P3VelConsts<FT> v = make_p3_collision_vel_consts<FT>(ip->scheme, ip->vel_ice);
     const P3ColConsts<FT> k = make_p3col_consts<FT>(*ip, wr->air_properties, *tps, flags);
     P3ColIO<FT> io{};
     io.rho_a = rho; io.T = T; io.loglam = loglam;
@@ -1081,25 +1073,19 @@ static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t
         qs.n = ip->quad.n;
         for (int j = 0; j < qs.n; ++j) { qs.node[j] = ip->quad.node[j]; qs.weight[j] = ip->quad.weight[j]; }
         const bool aspect = !(flags & CMX_P3_NO_ASPECT_RATIO);
-        auto go = [&](auto ex) -> int32_t {
+        return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) {
+            PointwiseExtra<FT, decltype(L)::value, decltype(I)::value> ex{};
             ex.sc = sc; ex.pk = pk; ex.q_tot = q_tot; ex.shift = shift;
             return launch_collision_kernel<FT, QuadSmall<FT>, true, decltype(ex)>(c, v, k, qs, io, n, aspect, st, ex);
-        };
-        if (limited) return intpow ? go(PointwiseExtra<FT, true, true>{}) : go(PointwiseExtra<FT, true, false>{});
-        return intpow ? go(PointwiseExtra<FT, false, true>{}) : go(PointwiseExtra<FT, false, false>{});
+        }, flag(limited), flag(intpow));
     }
     // TWO launches (quadrature rules above order 32 — the kernel-argument segment is 4 KiB): pointwise kernel, then the collision kernel
     // read-modify-writes the eight columns
     FusedIO<FT> fio{rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, shift, {}};
     for (int q = 0; q < 8; ++q) fio.out[q] = out[q];
     if (lay) fio.lay = *lay;
-    if (intpow) {
-        if (limited) launch<kBlock>(mp2m_p3_pointwise_kernel<FT, true, true>, n, st, sc, c, pk, fio, n);
-        else launch<kBlock>(mp2m_p3_pointwise_kernel<FT, false, true>, n, st, sc, c, pk, fio, n);
-    } else {
-        if (limited) launch<kBlock>(mp2m_p3_pointwise_kernel<FT, true>, n, st, sc, c, pk, fio, n);
-        else launch<kBlock>(mp2m_p3_pointwise_kernel<FT, false>, n, st, sc, c, pk, fio, n);
-    }
+    dispatch([&](auto L, auto I) { launch<kBlock>(mp2m_p3_pointwise_kernel<FT, decltype(L)::value, decltype(I)::value>, n, st, sc, c, pk, fio, n); },
+             flag(limited), flag(intpow));
     if (const int32_t e = launched()) return e;      // the pointwise launch, before the collision kernel's
     return launch_collision_kernel<FT, QUAD, true>(c, v, k, ip->quad, io, n, !(flags & CMX_P3_NO_ASPECT_RATIO), st);
 }

@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "cmx_p3.hpp"
+#include "cmx_sb2006.hpp"
 
 namespace cmx {
 CMX_P3_CONTRACT_BEGIN      // the whole translation unit is P3 quadrature / solver code (cmx_p3.hpp)
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(kP3BS) void p3_shape_kernel(const P3Consts<FT> c, c
 template <typename FT, typename PR>
 static int32_t p3_entry(const PR *params, uint32_t flags, int32_t brent_iters, int64_t n, const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4,
                         const FT *guess, FT *F_rim, FT *rho_rim, FT *loglam, FT *D_m, FT *logN0, void *stream) {
-    if (!params || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO))) return CMX_ERR_BAD_ARG;
+    if (!params || (flags & ~kP3StateFlags)) return CMX_ERR_BAD_ARG;
     CMX_TRY_COUNT(n);
     if (!rho_q || !rho_n || !x3 || !x4) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
@@ -269,21 +270,14 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_velocity_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, FT p, int64_t n, const FT *rho_q,
                                  const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *loglam, FT *v_n, FT *v_m,
                                  void *stream) {
-    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
-        return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked k = p3_entry_checks(params && vel, quad, flags, kP3StateFlags, n, &p); !k.proceed) return k.status;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !loglam) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
     c.brent_iters = 0;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, (double)p);
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, v_n, v_m, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_P3_NO_ASPECT_RATIO)
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false>, n, st, c, v, *quad, io, n);
-    else
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true>, n, st, c, v, *quad, io, n);
+    dispatch([&](auto A) { launch<kP3BS>(p3_velocity_kernel<FT, QUAD, decltype(A)::value, false, false>, n, st, c, v, *quad, io, n); }, flag(!(flags & CMX_P3_NO_ASPECT_RATIO)));
     return launched();
 }
 
@@ -292,21 +286,14 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_shape_velocity_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, int32_t brent_iters, FT p, int64_t n,
                                        const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *guess,
                                        FT *loglam, FT *D_m, FT *v_n, FT *v_m, void *stream) {
-    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
-        return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked k = p3_entry_checks(params && vel, quad, flags, kP3StateFlags, n, &p); !k.proceed) return k.status;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
     c.brent_iters = brent_iters > 0 ? brent_iters : PM<FT>::kBrent;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, (double)p);
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, nullptr, v_n, v_m, nullptr, nullptr, nullptr, guess, loglam, D_m};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_P3_NO_ASPECT_RATIO)
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false, false, true>, n, st, c, v, *quad, io, n);
-    else
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true, false, true>, n, st, c, v, *quad, io, n);
+    dispatch([&](auto A) { launch<kP3BS>(p3_velocity_kernel<FT, QUAD, decltype(A)::value, false, true>, n, st, c, v, *quad, io, n); }, flag(!(flags & CMX_P3_NO_ASPECT_RATIO)));
     return launched();
 }
 
@@ -314,27 +301,16 @@ template <typename FT, typename PR, typename VR, typename AP, typename TH, typen
 static int32_t p3_melt_entry(const PR *params, const VR *vel, const AP *aps, const TH *tps, const VT *vent, const QUAD *quad, uint32_t flags,
                              FT p, int64_t n, const FT *rho_q, const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *T,
                              const FT *loglam, FT *dNdt, FT *dLdt, void *stream) {
-    if (!params || !vel || !aps || !tps || !vent || !quad ||
-        (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
-        return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (quad->n < 1 || quad->n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked k = p3_entry_checks(params && vel && aps && tps && vent, quad, flags, kP3StateFlags, n, &p); !k.proceed) return k.status;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !T || !loglam) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
     c.brent_iters = 0;
     P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, (double)p);
-    v.vent_a = (FT)vent->a;
-    v.vent_bc = (FT)((double)vent->b * std::cbrt((double)aps->nu_air / (double)aps->D_vapor) / std::sqrt((double)aps->nu_air));
-    v.K4 = (FT)(4.0 * (double)aps->K_therm);
-    v.LH_f0 = (FT)((double)tps->LH_s0 - (double)tps->LH_v0); v.dcp_f = (FT)((double)tps->cp_l - (double)tps->cp_i);
-    v.T_0 = (FT)tps->T_0; v.T_freeze = (FT)params->T_freeze;
+    fill_melt_consts(v, *vent, *aps, *tps);
+    v.T_freeze = (FT)params->T_freeze;
     P3VelIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, nullptr, nullptr, T, dNdt, dLdt, nullptr, nullptr, nullptr};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_P3_NO_ASPECT_RATIO)
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, false, true>, n, st, c, v, *quad, io, n);
-    else
-        launch<kP3BS>(p3_velocity_kernel<FT, QUAD, true, true>, n, st, c, v, *quad, io, n);
+    dispatch([&](auto A) { launch<kP3BS>(p3_velocity_kernel<FT, QUAD, decltype(A)::value, true, false>, n, st, c, v, *quad, io, n); }, flag(!(flags & CMX_P3_NO_ASPECT_RATIO)));
     return launched();
 }
 
@@ -438,21 +414,14 @@ template <typename FT, typename PR, typename VR, typename QUAD>
 static int32_t p3_self_collection_entry(const PR *params, const VR *vel, const QUAD *quad, uint32_t flags, int64_t n, const FT *rho_q,
                                         const FT *rho_n, const FT *x3, const FT *x4, const FT *rho_a, const FT *loglam, FT *dNdt,
                                         void *stream) {
-    if (!params || !vel || !quad || (flags & ~(CMX_P3_INPUT_IS_STATE | CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO)))
-        return CMX_ERR_BAD_ARG;
-    CMX_TRY_COUNT_LIMIT(n);
-    if (quad->n < 1 || quad->n > CMX_QUAD_MAX) return CMX_ERR_BAD_ARG;
-    if (n == 0) return CMX_OK;
+    if (const P3Checked k = p3_entry_checks(params && vel, quad, flags, kP3StateFlags, n, (const FT *)nullptr); !k.proceed) return k.status;
     if (!rho_q || !rho_n || !x3 || !x4 || !rho_a || !loglam || !dNdt) return CMX_ERR_BAD_ARG;
     P3Consts<FT> c = make_p3_consts<FT>(*params, flags);
     c.brent_iters = 0;
     const P3VelConsts<FT> v = make_p3_vel_consts<FT>(*params, *vel, 1e-6);
     P3SelfIO<FT, QUAD> io{rho_q, rho_n, x3, x4, rho_a, loglam, dNdt};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (flags & CMX_P3_NO_ASPECT_RATIO)
-        launch<kP3BS>(p3_self_collection_kernel<FT, QUAD, false>, n, st, c, v, *quad, io, n);
-    else
-        launch<kP3BS>(p3_self_collection_kernel<FT, QUAD, true>, n, st, c, v, *quad, io, n);
+    dispatch([&](auto A) { launch<kP3BS>(p3_self_collection_kernel<FT, QUAD, decltype(A)::value>, n, st, c, v, *quad, io, n); }, flag(!(flags & CMX_P3_NO_ASPECT_RATIO)));
     return launched();
 }
 
@@ -640,21 +609,17 @@ static int32_t sb2006_size_distribution_entry(const PC *pdf_c, const PR *pdf_r, 
     if (!q || !rho || !N || (!n_D && !D_min && !D_max) || (n_D && !D)) return CMX_ERR_BAD_ARG;
     // the limited rain PSD clamps with its limiter pairs: a struct of the NOT-limited variant (limiters all zero, cmx.h) passed with the flag set
     // would clamp N0 and λ to 0 and return Inf / NaN silently — the same rule as the rate and column entries (sb_limiters_ok)
-    if (!cloud && limited &&
-        !(pdf_r->xr_min > 0 && pdf_r->xr_min <= pdf_r->xr_max && pdf_r->N0_min > 0 && pdf_r->N0_min <= pdf_r->N0_max && pdf_r->lambda_min > 0 &&
-          pdf_r->lambda_min <= pdf_r->lambda_max))
-        return CMX_ERR_BAD_ARG;
+    if (!cloud && limited && !rain_pdf_limiters_ok(*pdf_r)) return CMX_ERR_BAD_ARG;
     PsdPar<FT> k{};
     if (cloud) { k.nu_c = pdf_c->nu_c; k.mu_c = pdf_c->mu_c; k.rho_w_c = pdf_c->rho_w; k.lg_z1 = pdf_c->loggamma_z1; k.lg_z2 = pdf_c->loggamma_z2; }
-    else {
-        k.xr_min = pdf_r->xr_min; k.xr_max = pdf_r->xr_max; k.N0_min = pdf_r->N0_min; k.N0_max = pdf_r->N0_max; k.lam_min = pdf_r->lambda_min;
-        k.lam_max = pdf_r->lambda_max; k.rho_w_r = pdf_r->rho_w;
-    }
+    else { fill_rain_pdf_limiters(k, *pdf_r); k.rho_w_r = pdf_r->rho_w; }
     k.p = p;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (cloud) launch<kP3BS>(sb2006_size_distribution_kernel<FT, true, false>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
-    else if (limited) launch<kP3BS>(sb2006_size_distribution_kernel<FT, false, true>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
-    else launch<kP3BS>(sb2006_size_distribution_kernel<FT, false, false>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
+    // three distributions, not cloud × limited: the cloud PSD has no limited form
+    enum : int { PSD_CLOUD, PSD_RAIN_LIMITED, PSD_RAIN };
+    dispatch([&](auto M) {
+        launch<kP3BS>(sb2006_size_distribution_kernel<FT, decltype(M)::value == PSD_CLOUD, decltype(M)::value == PSD_RAIN_LIMITED>, n, st, k, n, q, rho, N, D, n_D, D_min, D_max);
+    }, one_of<PSD_CLOUD, PSD_RAIN_LIMITED, PSD_RAIN>(cloud ? PSD_CLOUD : limited ? PSD_RAIN_LIMITED : PSD_RAIN));
     return launched();
 }
 

@@ -70,9 +70,13 @@ template <typename FT> struct SbConsts {
 
 // The limited rain PSD clamps with v_med3 (clamp_ordered): every (min, max) pair of the limiters must be ordered and positive.
 // Entry points return CMX_ERR_BAD_ARG otherwise (Base.clamp with lo > hi is not a clamp either).
-template <typename WR> inline bool sb_limiters_ok(const WR &wr) {
-    const auto &p = wr.seifert_beheng.pdf_r;
+template <typename PR> inline bool rain_pdf_limiters_ok(const PR &p) {      // p: the rain-PDF struct (cmx_rain_pdf_sb2006_*)
     return p.xr_min > 0 && p.xr_min <= p.xr_max && p.N0_min > 0 && p.N0_min <= p.N0_max && p.lambda_min > 0 && p.lambda_min <= p.lambda_max;
+}
+template <typename WR> inline bool sb_limiters_ok(const WR &wr) { return rain_pdf_limiters_ok(wr.seifert_beheng.pdf_r); }
+// the limiter pairs of the rain PDF into a constants struct that clamps with them (members xr_min … lam_max)
+template <typename K, typename PR> inline void fill_rain_pdf_limiters(K &k, const PR &p) {
+    k.xr_min = p.xr_min; k.xr_max = p.xr_max; k.N0_min = p.N0_min; k.N0_max = p.N0_max; k.lam_min = p.lambda_min; k.lam_max = p.lambda_max;
 }
 
 template <typename FT, typename WR, typename TH, typename VL>

@@ -276,29 +276,16 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(sizeof(FT) =
 #endif
 constexpr int kColBS = CMX_COLUMN_BS;
 
+// sizes the grid of one range and picks the instantiation; false for a velocity kind the column step has no kernel for (VEL_NONE)
 template <typename FT, int VEC>
-static void launch_column(bool limited, int vel, bool cloud, bool intpow, const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, const SbColIO<FT> &io,
+static bool launch_column(bool limited, int vel, bool cloud, bool intpow, const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, const SbColIO<FT> &io,
                           int64_t first, int64_t nvec, hipStream_t s) {
-    if (nvec <= 0) return;
+    if (nvec <= 0) return true;
     const dim3 grid((unsigned)((nvec + (kColBS - 1) - 1) / (kColBS - 1))), block(kColBS);      // tiles overlap by one lane (sb2006_column_kernel)
-    // intpow: the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
-#define CMX_LAUNCH(L, V, C)                                                                                                                          \
-    do {                                                                                                                                             \
-        if (intpow) launch_grid(sb2006_column_kernel<FT, L, V, C, VEC, kColBS, true>, grid, block, 0, s, c, cv, io, first, nvec); \
-        else launch_grid(sb2006_column_kernel<FT, L, V, C, VEC, kColBS>, grid, block, 0, s, c, cv, io, first, nvec);   \
-    } while (0)
-#define CMX_PICK(L, V) do { if (cloud) CMX_LAUNCH(L, V, true); else CMX_LAUNCH(L, V, false); } while (0)
-    if (limited) {
-        if (vel == VEL_SB) CMX_PICK(true, VEL_SB);
-        else if (vel == VEL_CHEN) CMX_PICK(true, VEL_CHEN);
-        else CMX_PICK(true, VEL_CHEN_GEN);
-    } else {
-        if (vel == VEL_SB) CMX_PICK(false, VEL_SB);
-        else if (vel == VEL_CHEN) CMX_PICK(false, VEL_CHEN);
-        else CMX_PICK(false, VEL_CHEN_GEN);
-    }
-#undef CMX_PICK
-#undef CMX_LAUNCH
+    // I: the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
+    return dispatch([&](auto L, auto K, auto C, auto I) {
+        launch_grid(sb2006_column_kernel<FT, decltype(L)::value, decltype(K)::value, decltype(C)::value, VEC, kColBS, decltype(I)::value>, grid, block, 0, s, c, cv, io, first, nvec);
+    }, flag(limited), one_of<VEL_SB, VEL_CHEN, VEL_CHEN_GEN>(vel), flag(cloud), flag(intpow));
 }
 
 template <typename FT, typename WR, typename TH, typename VL, typename ST>
@@ -328,10 +315,12 @@ static int32_t column_entry(const WR *wr, const TH *tps, const VL *vel, const ST
     // compose exactly
     const void *ptrs[] = {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dq_lcl, dn_lcl, dq_rai, dn_rai};
     const bool cloud = cloud_vel != nullptr;
+    bool known = true;
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        launch_column<FT, V>(limited, velk, cloud, intpow, c, cv, io, lo, count / V, s);
+        known &= launch_column<FT, V>(limited, velk, cloud, intpow, c, cv, io, lo, count / V, s);
     });
+    if (!known) return CMX_ERR_BAD_ARG;      // unreachable: velk is VEL_SB or what chen_vel_kind gives
     return launched();
 }
 

@@ -27,31 +27,6 @@ constexpr int kTendBS = CMX_TEND_BS;   // lanes per workgroup of the fused tende
 #ifndef CMX_SB_INTPOW
 #define CMX_SB_INTPOW 1      // A/B switch for the integer-exponent instantiations (cmx_sb2006.hpp INTPOW)
 #endif
-template <typename FT, int VEC>
-static void launch_tendencies(bool limited, int vel, bool intpow, const SbConsts<FT> &c, const SbIn<FT> &in, const SbOut<FT> &out,
-                              int64_t nvec, hipStream_t s) {
-    // one short-lived workgroup per tile of kTendBS lanes (see the kernel's header comment)
-#define CMX_LAUNCH(L, V)                                                                                              \
-    do {                                                                                                              \
-        if (intpow && CMX_SB_INTPOW)                                                                                  \
-            launch<kTendBS>(sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS, 1, true, true>, nvec, s, c, in, out, nvec); \
-        else                                                                                                          \
-            launch<kTendBS>(sb2006_tendencies_kernel<FT, L, V, VEC, kTendBS>, nvec, s, c, in, out, nvec);              \
-    } while (0)
-    if (limited) {
-        if (vel == VEL_NONE) CMX_LAUNCH(true, VEL_NONE);
-        else if (vel == VEL_SB) CMX_LAUNCH(true, VEL_SB);
-        else if (vel == VEL_CHEN) CMX_LAUNCH(true, VEL_CHEN);
-        else CMX_LAUNCH(true, VEL_CHEN_GEN);
-    } else {
-        if (vel == VEL_NONE) CMX_LAUNCH(false, VEL_NONE);
-        else if (vel == VEL_SB) CMX_LAUNCH(false, VEL_SB);
-        else if (vel == VEL_CHEN) CMX_LAUNCH(false, VEL_CHEN);
-        else CMX_LAUNCH(false, VEL_CHEN_GEN);
-    }
-#undef CMX_LAUNCH
-}
-
 template <typename FT, typename WR, typename TH, typename VL>
 static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint32_t flags, int64_t n, const FT *rho,
                                 const FT *T, const FT *q_tot, const FT *q_lcl, const FT *n_lcl, const FT *q_rai,
@@ -68,7 +43,8 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
     const bool limited = flags & CMX_SB2006_LIMITED;
     if ((flags & CMX_SB2006_LIMITED) && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
-    const bool intpow = sb_integer_exponents(*wr);        // b = 3, c = 4, d = −5: the integer-power instantiation (cmx_sb2006.hpp)
+    const bool intpow = sb_integer_exponents(*wr) && CMX_SB_INTPOW;        // b = 3, c = 4, d = −5: the integer-power instantiation (cmx_sb2006.hpp)
+    bool known = true;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // Float64: one point per lane (8-byte loads).  The kernel is VALU-bound there and the two-points-per-lane variant spends 14 % of
     // its instructions on SGPR spill traffic (60 Float64 constants = 120 SGPRs): 1307 vs 1048 VALU instructions per point.
@@ -79,8 +55,13 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
         constexpr int V = decltype(vec_tag)::value;
         SbIn<FT> in{rho + lo, T + lo, q_tot + lo, q_lcl + lo, n_lcl + lo, q_rai + lo, n_rai + lo};
         SbOut<FT> out{dq_lcl + lo, dn_lcl + lo, dq_rai + lo, dn_rai + lo, shift(vt_n, lo), shift(vt_m, lo)};
-        launch_tendencies<FT, V>(limited, velk, intpow, c, in, out, count / V, s);
+        const int64_t nvec = count / V;
+        // one short-lived workgroup per tile of kTendBS lanes (see the kernel's header comment)
+        known &= dispatch([&](auto L, auto K, auto I) {
+            launch<kTendBS>(sb2006_tendencies_kernel<FT, decltype(L)::value, decltype(K)::value, V, kTendBS, 1, true, decltype(I)::value>, nvec, s, c, in, out, nvec);
+        }, flag(limited), one_of<VEL_NONE, VEL_SB, VEL_CHEN, VEL_CHEN_GEN>(velk), flag(intpow));
     });
+    if (!known) return CMX_ERR_BAD_ARG;      // unreachable: decode_vel and chen_vel_kind give listed kinds only
     return launched();
 }
 
@@ -94,12 +75,10 @@ static int32_t fields_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, (const std::conditional_t<std::is_same_v<FT, float>, cmx_rain_vel_f32, cmx_rain_vel_f64> *)nullptr,
                                               (double)Math<FT>::eps_1m());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (sb_integer_exponents(*wr) && CMX_SB_INTPOW) {     // the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
-        if (flags & CMX_SB2006_LIMITED) return launch_layout<FT, Sb2006LayoutPolicy<FT, true, true>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-        return launch_layout<FT, Sb2006LayoutPolicy<FT, false, true>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-    }
-    if (flags & CMX_SB2006_LIMITED) return launch_layout<FT, Sb2006LayoutPolicy<FT, true>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-    return launch_layout<FT, Sb2006LayoutPolicy<FT, false>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    // I: the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) {
+        return launch_layout<FT, Sb2006LayoutPolicy<FT, decltype(L)::value, decltype(I)::value>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
+    }, flag(flags & CMX_SB2006_LIMITED), flag(sb_integer_exponents(*wr) && CMX_SB_INTPOW));
 }
 
 template <typename FT, typename WR, typename TH, typename VL>
@@ -120,19 +99,10 @@ static int32_t process_entry(const WR *wr, const TH *tps, const VL *vel, uint32_
     for (int k = 0; k < CMX_SB2006_NPROC; ++k) o.col[k] = out[k];
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(grid_for(n));
-#define CMX_LAUNCH(L, V) launch_grid(sb2006_process_kernel<FT, L, V>, grid, dim3(kBlock), 0, s, c, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, o, n)
-    if (limited) {
-        if (velk == VEL_NONE) CMX_LAUNCH(true, VEL_NONE);
-        else if (velk == VEL_SB) CMX_LAUNCH(true, VEL_SB);
-        else if (velk == VEL_CHEN) CMX_LAUNCH(true, VEL_CHEN);
-        else CMX_LAUNCH(true, VEL_CHEN_GEN);
-    } else {
-        if (velk == VEL_NONE) CMX_LAUNCH(false, VEL_NONE);
-        else if (velk == VEL_SB) CMX_LAUNCH(false, VEL_SB);
-        else if (velk == VEL_CHEN) CMX_LAUNCH(false, VEL_CHEN);
-        else CMX_LAUNCH(false, VEL_CHEN_GEN);
-    }
-#undef CMX_LAUNCH
+    if (!dispatch([&](auto L, auto K) {
+            launch_grid(sb2006_process_kernel<FT, decltype(L)::value, decltype(K)::value>, grid, dim3(kBlock), 0, s, c, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, o, n);
+        }, flag(limited), one_of<VEL_NONE, VEL_SB, VEL_CHEN, VEL_CHEN_GEN>(velk)))
+        return CMX_ERR_BAD_ARG;      // unreachable: decode_vel and chen_vel_kind give listed kinds only
     return launched();
 }
 
