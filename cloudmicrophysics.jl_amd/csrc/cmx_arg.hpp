@@ -130,13 +130,10 @@ template <typename VT> __device__ __forceinline__ VT erfc_f32(VT x) {
     const VT e = (q * t) * M::exp2((ax * ax) * VT(-1.4426950408889634f));
     return x >= VT(0.0f) ? e : VT(2.0f) - e;
 }
-#ifndef CMX_ARG_LEAN_ERFC
-#define CMX_ARG_LEAN_ERFC 1      // 0: OCML erfc (A/B switch)
-#endif
 // erfc_dev: the activated NUMBER.  Float64: the table-driven lean::erfc (cmx_lean_f64.hpp: relative error ≤ (2 + x²)·2e-16 up to 6.5; the
 // reference's ½(1 − erf u) is exactly 0 beyond u = 5.9) — 45 instructions against OCML's 135, five calls per state
 template <typename VT> __device__ __forceinline__ VT erfc_dev(VT x) {
-    if constexpr (sizeof(typename Math<VT>::Scalar) == 8) return CMX_ARG_LEAN_ERFC ? lean::erfc(x) : ::erfc(x);
+    if constexpr (sizeof(typename Math<VT>::Scalar) == 8) return lean::erfc(x);
     else return erfc_f32<VT>(x);
 }
 // erfc_rel_dev: the activated MASS (relative accuracy over the whole range: the reference evaluates erfc itself).  Float64: OCML
@@ -145,17 +142,9 @@ template <typename VT> __device__ __forceinline__ VT erfc_rel_dev(VT x) {
     else return erfc_f32<VT>(x);
 }
 
-#ifndef CMX_ARG_P2_ROOTS
-#define CMX_ARG_P2_ROOTS 1      // A/B switch for the p2 = ¾ path of the Float64 S_max sum (arg_point)
-#endif
 // y^(−¾) for the p2 = ¾ path of the Float64 S_max sum
 __device__ __forceinline__ double arg_pow_m34(double y) {
-#if CMX_F64_FINITE_FORMS
     return lean::pow_m34_pos(y);
-#else
-    const double t = lean::rsqrt(y);
-    return t * lean::sqrt(t);
-#endif
 }
 
 template <typename VT, int NM> struct ArgOut { VT smax; VT n[NM]; VT m[NM]; };
@@ -279,7 +268,7 @@ __device__ __forceinline__ ArgOut<VT, NM> arg_point(const C &c, VT T, VT p, VT w
     const ArgPre<VT> s = arg_pre<VT, SINKS>(c, T, p, w, q_tot, q_liq, q_ice, N_liq, N_ice);
     // per mode one FMA, one log2, one multiply, one exp2 and one accumulating FMA; Σ c1_i is a constant of the distribution
     VT sum2 = VT(0);
-    const bool p2_34 = sizeof(S) == 8 && CMX_ARG_P2_ROOTS && c.p2 == S(0.75);
+    const bool p2_34 = sizeof(S) == 8 && c.p2 == S(0.75);
 #pragma unroll
     // (a multiply and an add per mode, not an fma: the reference sums separately rounded terms, so its totals do not depend on the ORDER of two modes —
     // test/aerosol_activation_tests.jl:222-234 asserts that with `==` — and a + b = b + a holds for rounded products, not for fma(c, p, a))
@@ -297,7 +286,7 @@ __device__ __forceinline__ ArgOut<VT, NM> arg_point(const C &c, VT T, VT p, VT w
         // LDS reads hoisted (422 VGPRs for 5 modes × 2 states: one wave per SIMD).  The asm pins the mode's result here and, with its
         // memory clobber, keeps the next mode's table reads behind it.
 #if !defined(CMX_HOST_BUILD)
-        if constexpr (sizeof(S) == 8 && CMX_ARG_LEAN_ERFC) asm volatile("" : "+v"(o.n[k]) : : "memory");
+        if constexpr (sizeof(S) == 8) asm volatile("" : "+v"(o.n[k]) : : "memory");
 #endif
         o.m[k] = want_M ? cm[k].half_M * erfc_rel_dev<VT>(u - cm[k].fac) : VT(0); // M/2 erfc(u − fac)    AA:319
     }

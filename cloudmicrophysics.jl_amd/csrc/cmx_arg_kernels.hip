@@ -36,9 +36,6 @@ template <typename FT> struct ArgIO {
 #ifndef CMX_ARG_BS
 #define CMX_ARG_BS 128
 #endif
-#ifndef CMX_ARG_F32_PACKED
-#define CMX_ARG_F32_PACKED 1     // 0: one state at a time (A/B switch)
-#endif
 constexpr int kArgBS = CMX_ARG_BS;   // lanes per workgroup of the activation kernel: 128 (same-box A/B, f32: 256 → 0.650 ms, 128 → 0.638, 512 → 0.637–0.655; f64 indifferent)
 template <typename FT, int NM, bool SINKS, int VEC, bool N_ONLY = false>
 __global__ __launch_bounds__(kArgBS) void arg_activation_kernel(const ArgConsts<FT> c, const ArgIO<FT> io, const int64_t nvec) {
@@ -53,13 +50,13 @@ __global__ __launch_bounds__(kArgBS) void arg_activation_kernel(const ArgConsts<
             if (io.N_ice) load_col<FT, VEC>(io.N_ice, i, Ni);
         }
     }
-    if constexpr (sizeof(FT) == 8 && CMX_ARG_LEAN_ERFC) lean::erfc_tab_fill();   // published by the barrier inside prepare()
+    if constexpr (sizeof(FT) == 8) lean::erfc_tab_fill();   // published by the barrier inside prepare()
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
     if (i >= nvec) return;
     FT sm[VEC], na[NM][VEC], ma[NM][VEC];
     // one value of the value type VT at a time: a state, or — Float32 with four states per lane — a PAIR of states in packed arithmetic (cmx_math.hpp f32x2):
     // the same IEEE operations in the same order, so the one-state launches of an unaligned head / tail give the same bits
-    constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_HAVE_PACKED && CMX_ARG_F32_PACKED) ? 2 : 1;
+    constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_HAVE_PACKED) ? 2 : 1;
     using VT = std::conditional_t<L == 2, f32x2, FT>;
     const bool want_smax = io.S_max != nullptr;
 #pragma unroll
@@ -196,11 +193,11 @@ __global__ __launch_bounds__(kArgColBS<FT>) void arg_activation_columns_kernel(c
             if (io.N_ice) load_col_wg<FT, VEC>(at(io.N_ice), lane, Ni);
         }
     }
-    if constexpr (sizeof(FT) == 8 && CMX_ARG_LEAN_ERFC) lean::erfc_tab_fill();   // published by the barrier inside prepare()
+    if constexpr (sizeof(FT) == 8) lean::erfc_tab_fill();   // published by the barrier inside prepare()
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly; no-op for Float32
     if (i >= nvec) return;
     const FT ln2 = FT(0.6931471805599453);
-    const bool p2_34 = sizeof(FT) == 8 && CMX_ARG_P2_ROOTS && c.p2 == FT(0.75);
+    const bool p2_34 = sizeof(FT) == 8 && c.p2 == FT(0.75);
     ArgPre<FT> pre[VEC];
     FT sum1[VEC], sum2[VEC];
 #pragma unroll
@@ -260,7 +257,7 @@ __global__ __launch_bounds__(kArgColBS<FT>) void arg_activation_columns_kernel(c
             const FT ls = k_ls[k][v];
             const FT u = FT(0.3267527144895157) * M::rcp(ls) * (k_l2sm[k][v] + dl0[v]);   // 2 ln2/(3√2 ln σ) · log2(Sm_k/S_max)   AA:255
             na[v] = FT(0.5) * k_N[k][v] * erfc_dev<FT>(u);                                  // N ½ (1 − erf u)   AA:257
-            if constexpr (sizeof(FT) == 8 && CMX_ARG_LEAN_ERFC) asm volatile("" : "+v"(na[v]) : : "memory");
+            if constexpr (sizeof(FT) == 8) asm volatile("" : "+v"(na[v]) : : "memory");
             if constexpr (!N_ONLY) ma[v] = FT(0.5) * k_mm[k][v] * erfc_rel_dev<FT>(u - FT(2.121320343559643) * ls);   // M/2 erfc(u − 3 ln σ √2/2)   AA:319
         }
         if (io.N_act[k]) store_col_wg<FT, VEC>(at(io.N_act[k]), lane, na);

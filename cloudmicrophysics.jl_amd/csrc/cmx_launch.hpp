@@ -100,10 +100,6 @@ inline void launch(void (*kernel)(P...), int64_t lanes, hipStream_t stream, cons
 // VALU-bound, not HBM-bound, and the two-points-per-lane variants spend VALU instructions on SGPR-spill traffic for the 2-SGPR
 // Float64 constants (SB2006: 1307 vs 1048 instructions per point in round 1; 1-moment 4.60 → 4.36 ms per 1e8 points in a same-box
 // A/B, round 2).  The lighter ones keep two points per lane (same A/B: ARG 3.25 vs 3.50 ms, ice nucleation 0.73 vs 0.88 with one).
-// A/B switch for the 1-moment kernel: -DCMX_F64_ONE_POINT_PER_LANE=0.
-#ifndef CMX_F64_ONE_POINT_PER_LANE
-#define CMX_F64_ONE_POINT_PER_LANE 1
-#endif
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

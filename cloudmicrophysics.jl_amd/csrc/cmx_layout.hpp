@@ -41,12 +41,6 @@ template <typename P> struct layout_packable<P, std::enable_if_t<P::PACKABLE>> :
 // kernel-argument pointer like the Float64 kernels do (cmx_math.hpp front_consts ALSO) — as by-value arguments 32 of them were spilled to VGPR lanes
 template <typename P, typename = void> struct layout_phase_consts : std::false_type {};
 template <typename P> struct layout_phase_consts<P, std::enable_if_t<P::PHASE_CONSTS>> : std::true_type {};
-#ifndef CMX_F32_PACKED_LAYOUT
-#define CMX_F32_PACKED_LAYOUT 1          // A/B switch: 0 = one point at a time
-#endif
-#ifndef CMX_F32_PACKED_LAYOUT_PHASE
-#define CMX_F32_PACKED_LAYOUT_PHASE 1    // the packed instantiations read their constants phase by phase (cmx_sb2006_kernels.hpp CMX_F32_PACKED_PHASE_CONSTS)
-#endif
 #ifndef CMX_LAYOUT_F64_VEC
 #define CMX_LAYOUT_F64_VEC 1     // A/B switch (2: 16-byte accesses for Float64 as well)
 #endif
@@ -93,14 +87,15 @@ __global__ __launch_bounds__(BS) void tendencies_layout_kernel(const typename PO
     }
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
     if (active) {
-        // Float32 with four points per lane and a policy whose point function takes the packed pair type: two PAIRS of points (cmx_math.hpp f32x2)
-        if constexpr (layout_packable<POLICY>::value && sizeof(FT) == 4 && VEC % 2 == 0 && CMX_F32_PACKED_LAYOUT) {
+        // Float32 with four points per lane and a policy whose point function takes the packed pair type: two PAIRS of points (cmx_math.hpp f32x2),
+        // which read their constants phase by phase (a packed instruction takes no literal: cmx_math.hpp, above lanes_of)
+        if constexpr (layout_packable<POLICY>::value && sizeof(FT) == 4 && VEC % 2 == 0) {
 #pragma unroll
             for (int k = 0; k < VEC; k += 2) {
                 f32x2 xi[NIN], yi[NOUT];
 #pragma unroll
                 for (int q = 0; q < NIN; ++q) xi[q] = f32x2{x[q][k], x[q][k + 1]};
-                POLICY::point(front_consts<FT, (bool)CMX_F32_PACKED_LAYOUT_PHASE>(c), xi, yi);
+                POLICY::point(front_consts<FT, true>(c), xi, yi);
 #pragma unroll
                 for (int q = 0; q < NOUT; ++q) { y[k][q] = yi[q].x; y[k + 1][q] = yi[q].y; }
             }

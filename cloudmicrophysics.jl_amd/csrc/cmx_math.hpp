@@ -104,18 +104,17 @@ template <> struct Math<double> {
     static __device__ __forceinline__ double rcp(double x) { return lean::rcp(x); }
     // exp2_fin: the argument is finite or NaN (never ±Inf); rcp_nz: the argument is finite and non-zero, or NaN.  They drop the clamp /
     // NaN select (5 instructions) resp. the second Newton step and the 0 / Inf fix-up (5 instructions; 2⁻⁴⁸ relative instead of ≤ 1 ulp)
-    // of the full forms; NaN still propagates.  Every call site states why its argument qualifies; CMX_F64_FINITE_FORMS=0
-    // (cmx_lean_f64.hpp) maps them back to the full forms for A/B runs.
+    // of the full forms; NaN still propagates.  Every call site states why its argument qualifies.
     static __device__ __forceinline__ double exp2_fin(double x) { return lean::exp2_fin(x); }
-    static __device__ __forceinline__ double rcp_nz(double x) { return CMX_F64_FINITE_FORMS ? lean::rcp_nz(x) : lean::rcp(x); }
+    static __device__ __forceinline__ double rcp_nz(double x) { return lean::rcp_nz(x); }
     // rcp_nz1: the same contract at ≤ 1 ulp (two Newton steps, no 0 / Inf fix-up) — where the reciprocal is amplified afterwards, e.g.
     // the determinants of the implicit step, whose result enters a difference quotient (q_new − q)/Δt
-    static __device__ __forceinline__ double rcp_nz1(double x) { return CMX_F64_FINITE_FORMS ? lean::rcp_finite(x) : lean::rcp(x); }
+    static __device__ __forceinline__ double rcp_nz1(double x) { return lean::rcp_finite(x); }
     static __device__ __forceinline__ double sqrt(double x) { return lean::sqrt(x); }
     static __device__ __forceinline__ double rsqrt(double x) { return lean::rsqrt(x); }
     // positive finite argument (or NaN): no 0 / Inf fix-ups
-    static __device__ __forceinline__ double sqrt_pos(double x) { return CMX_F64_FINITE_FORMS ? lean::sqrt_pos(x) : lean::sqrt(x); }
-    static __device__ __forceinline__ double rsqrt_pos(double x) { return CMX_F64_FINITE_FORMS ? lean::rsqrt_pos(x) : lean::rsqrt(x); }
+    static __device__ __forceinline__ double sqrt_pos(double x) { return lean::sqrt_pos(x); }
+    static __device__ __forceinline__ double rsqrt_pos(double x) { return lean::rsqrt_pos(x); }
     static __device__ __forceinline__ double div(double a, double b) { return a * lean::rcp(b); }
     static __device__ __forceinline__ double fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
     static __device__ __forceinline__ double max(double a, double b) { return __builtin_fmax(a, b); }
@@ -195,17 +194,10 @@ __device__ __forceinline__ bool m_and(bool a, bool b) { return a && b; }
 __device__ __forceinline__ i32x2 m_and(i32x2 a, i32x2 b) { return a & b; }
 #endif
 template <typename B, typename... R> __device__ __forceinline__ B m_and(B a, B b, R... r) { return m_and(m_and(a, b), r...); }
-// CMX_F32_PACKED: the Float32 instantiations with four points per lane evaluate two PAIRS of points in packed arithmetic (cmx_math.hpp f32x2); 0 = one
-// point at a time as in rounds 1–4 (A/B switch)
-#ifndef CMX_F32_PACKED
-#define CMX_F32_PACKED 1
-#endif
-// CMX_F32_PACKED_PHASE_CONSTS: a packed instruction takes no literal, so the ≈ 30 literal constants of the point function occupy SGPRs next to the 95 kernel
-// constants — more than the file holds (84 v_writelane + 84 v_readlane per 4 points appeared).  The packed instantiations therefore read the constants
-// through the kernel-argument pointer, phase by phase, like the Float64 kernels do (cmx_math.hpp consts_after).
-#ifndef CMX_F32_PACKED_PHASE_CONSTS
-#define CMX_F32_PACKED_PHASE_CONSTS 1
-#endif
+// The Float32 instantiations with four points per lane evaluate two PAIRS of points in packed arithmetic (f32x2 above; rounds 1–4: one point at a time).
+// A packed instruction takes no literal, so the ≈ 30 literal constants of the point function occupy SGPRs next to the 95 kernel constants — more than the
+// file holds (84 v_writelane + 84 v_readlane per 4 points appeared).  The packed column and layout-adapter instantiations therefore read the constants through the
+// kernel-argument pointer, phase by phase, like the Float64 kernels do (consts_after below).
 // the scalar type and the points per value of a value type
 template <typename VT> struct lanes_of { static constexpr int value = 1; };
 #if CMX_HAVE_PACKED
@@ -224,11 +216,8 @@ template <> struct lanes_of<f32x2> { static constexpr int value = 2; };
 // in its cost model) — per point, 3–4 branches in the SB2006 kernel.  A lane owns 4 independent points whose instruction streams
 // should interleave; every branch ends a basic block, costs 4–6 scalar instructions and a pipeline bubble, and in a wave of 64
 // different states both sides run anyway.  The empty asm makes the value opaque at this point, so it cannot be sunk behind the gate.
-#ifndef CMX_KEEP
-#define CMX_KEEP 1
-#endif
 template <typename FT> __device__ __forceinline__ FT keep(FT x) {
-#if CMX_KEEP && !defined(CMX_HOST_BUILD)
+#if !defined(CMX_HOST_BUILD)
     asm volatile("" : "+v"(x));
 #endif
     return x;
@@ -389,15 +378,12 @@ template <typename FT> __device__ __forceinline__ FT clampv(FT x, FT lo, FT hi) 
 // not need that, returns 0 for a NaN like v_max does (the NaN rule is applied separately), and its result counts as canonical.
 // (Written as an inline-asm v_med3_f32 so that the optimiser cannot turn it back into canonicalize + v_max — it does in the 1-moment
 // kernels — it measured no faster there and 6 % slower in the LinearizedAverage kernel, round 2: the builtin stays.)
-// Round 3 (CMX_MAX0_INT, default on): as ONE integer instruction instead — for a float, max(0, x) is v_max_i32 on the bits (negative
+// Round 3: as ONE integer instruction instead — for a float, max(0, x) is v_max_i32 on the bits (negative
 // floats, −0 and sign-bit NaNs are negative integers → +0; positive floats, +Inf and the other NaNs pass).  No canonicalisation is
 // emitted for an integer operation, and a NaN input is poisoned by the kernels' own rule either way.  Same-box A/B (3 interleaved
 // runs, ms per 1e8 Float32 points): 1-moment tendencies 0.788–0.804 → 0.782–0.793, LinearizedAverage 1.79 → 1.76, SB2006 unchanged.
-#ifndef CMX_MAX0_INT
-#define CMX_MAX0_INT 1
-#endif
 __device__ __forceinline__ float max0(float x) {
-#if CMX_MAX0_INT && !defined(CMX_HOST_BUILD)
+#if !defined(CMX_HOST_BUILD)
     const int i = __builtin_bit_cast(int, x);
     return __builtin_bit_cast(float, i > 0 ? i : 0);
 #else
@@ -433,23 +419,10 @@ __device__ __forceinline__ f32x2 clamp_ordered(f32x2 x, f32x2 lo, f32x2 hi) { re
 // constant-address-space pointer to the kernel-argument segment (front_consts) and pass it through consts_after(c, x) at the phase
 // boundaries of the point function: an empty asm that makes the pointer depend on a value the previous phase computed, so the
 // scalar loads of a phase cannot be hoisted above it and only that phase's constants are live.  Float32 (95 SGPRs) needs none of it.
-#ifndef CMX_PHASE_CONSTS
-#define CMX_PHASE_CONSTS 1
-#endif
-// CMX_PHASE_DEP(late, early): the value a phase's constants wait for — the LAST value of the previous phase (only one phase's
-// constants live), or with CMX_PHASE_PREFETCH an EARLY value of the previous phase (the loads overlap that phase's arithmetic; two
-// phases' constants live).
-#ifndef CMX_PHASE_PREFETCH
-#define CMX_PHASE_PREFETCH 0
-#endif
-#if CMX_PHASE_PREFETCH
-#define CMX_PHASE_DEP(late, early) early
-#else
-#define CMX_PHASE_DEP(late, early) late
-#endif
+// The value a phase's constants wait for is the LAST value of the previous phase, so only one phase's constants are live.  Waiting for an
+// EARLY value instead (the loads overlap the previous phase's arithmetic, two phases' constants live) measured slower in round 2
+// (SB2006 Float64 3.23 → 3.68 ms per 1e8 points).  The host build has no kernel-argument segment: its constants are a plain reference.
 #if defined(CMX_HOST_BUILD)
-#undef CMX_PHASE_CONSTS
-#define CMX_PHASE_CONSTS 0
 template <typename T> using KernArg = const T;
 template <typename T> struct is_kernarg { static constexpr bool value = false; };
 #else
@@ -464,7 +437,7 @@ template <typename FT, bool ALSO = false, typename CT> inline const CT &front_co
 template <typename C, typename FT> inline const C &consts_after(const C &c, FT) { return c; }
 #else
 template <typename FT, bool ALSO = false, typename CT> __device__ __forceinline__ decltype(auto) front_consts(const CT &c) {
-    if constexpr ((sizeof(FT) == 8 || ALSO) && CMX_PHASE_CONSTS) return (*(KernArg<CT> *)__builtin_amdgcn_kernarg_segment_ptr());
+    if constexpr (sizeof(FT) == 8 || ALSO) return (*(KernArg<CT> *)__builtin_amdgcn_kernarg_segment_ptr());
     else return (c);
 }
 // (a plain reference passes through: laundering the address of a by-value kernel argument would force a private copy of the struct)
@@ -481,11 +454,8 @@ template <typename C, typename FT> __device__ __forceinline__ const C &consts_af
 // NaN inputs.  The reference sanitises with Julia's max(0, x), which returns NaN for a NaN x, and its arithmetic then carries the NaN to
 // the tendencies; the hardware v_max returns the other operand and would hide it.  The bulk-tendency kernels therefore poison every output
 // of a point whose inputs hold a NaN: one unordered compare per pair of inputs.
-#ifndef CMX_NAN_POISON
-#define CMX_NAN_POISON 1
-#endif
-template <typename FT> __device__ __forceinline__ bool any_nan(FT a) { return CMX_NAN_POISON && a != a; }
-template <typename FT> __device__ __forceinline__ bool any_nan(FT a, FT b) { return CMX_NAN_POISON && __builtin_isunordered(a, b); }
+template <typename FT> __device__ __forceinline__ bool any_nan(FT a) { return a != a; }
+template <typename FT> __device__ __forceinline__ bool any_nan(FT a, FT b) { return __builtin_isunordered(a, b); }
 template <typename FT, typename... R> __device__ __forceinline__ bool any_nan(FT a, FT b, R... r) {
     return (bool)((int)any_nan(a, b) | (int)any_nan(r...));   // bitwise on purpose: no branch
 }

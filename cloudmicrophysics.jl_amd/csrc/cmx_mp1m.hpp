@@ -68,11 +68,8 @@ template <typename FT> struct Mp1mConsts {
 constexpr uint32_t kRuntimeFlags = 0xffffffffu;
 constexpr uint32_t kDefExpBit = 0x40000000u;   // internal (not an ABI flag): set in the compile-time FLAGS of the default instantiation
 static_assert((CMX_1M_DEFAULT_OPTIONS & kDefExpBit) == 0, "internal bit collides with an option flag");
-#ifndef CMX_1M_DEFEXP
-#define CMX_1M_DEFEXP 1      // A/B switch
-#endif
 template <typename CT> inline bool mp1m_default_exponents(const CT &c) {
-    return CMX_1M_DEFEXP && c.vt_e_rai == 0.5 && c.acc_e_rai == 3.5 && c.sink_e == 6.5 && c.rs_dp1_rai == 4 && c.ven_e_rai == 0.75 && c.vt_e_sno == 0.25 &&
+    return c.vt_e_rai == 0.5 && c.acc_e_rai == 3.5 && c.sink_e == 6.5 && c.rs_dp1_rai == 4 && c.ven_e_rai == 0.75 && c.vt_e_sno == 0.25 &&
            c.acc_e_sno == 3.25 && c.rs_dp1_sno == 3 && c.ven_e_sno == 0.625 &&
            c.ka_qthr >= c.eps_1m && c.ks_qthr >= c.eps_1m;   // … and regular autoconversion thresholds (logistic_rate)
 }
@@ -425,21 +422,6 @@ template <typename FT> __device__ __forceinline__ void mp1m_aggregate(const Mp1m
     const FT to_sno = p.is_warm ? -(p.S_sno_rai + melted) : p.S_lcl_sno + p.S_rai_sno;
     dr = ((((p.acnv_lcl_rai + p.accr_lcl_rai) - p.freeze_icl_rai) + to_rai) + p.vap_rai) + p.melt_sno;
     ds = (((((p.acnv_icl_sno + p.accr_icl_rai) + p.freeze_icl_rai) + p.accr_icl_sno) + to_sno) + p.vap_sno) - p.melt_sno;
-}
-
-// A lane of the Float32 vector kernels evaluates 4 points.  An instruction reads at most one SGPR, so every `a·x + b` with both a and b
-// kernel constants costs a v_mov_b32 of b per POINT (the compiler rematerialises it rather than keep a VGPR live: 12 of the 266
-// instructions of a point).  CMX_1M_HOIST (default on) parks those additive constants in VGPRs once per lane: 70 → 76 VGPRs, same-box
-// A/B with CMX_MAX0_INT 0.782–0.793 → 0.778–0.779 ms per 1e8 points.
-#ifndef CMX_1M_HOIST
-#define CMX_1M_HOIST 1
-#endif
-template <typename FT> __device__ __forceinline__ void mp1m_hoist_consts(Mp1mConsts<FT> &c) {
-#if CMX_1M_HOIST
-    c.ps_c0 = keep(c.ps_c0); c.LH_v0 = keep(c.LH_v0); c.LH_s0 = keep(c.LH_s0); c.LH_f0 = keep(c.LH_f0); c.cp_d = keep(c.cp_d);
-    c.lam_b_icl = keep(c.lam_b_icl); c.lamp_b_rai = keep(c.lamp_b_rai); c.lamp_b_sno = keep(c.lamp_b_sno); c.sno_l2_mu = keep(c.sno_l2_mu);
-    c.ka_omemk = keep(c.ka_omemk); c.ks_omemk = keep(c.ks_omemk); c.ven_a_rai = keep(c.ven_a_rai); c.ven_a_sno = keep(c.ven_a_sno);
-#endif
 }
 
 // bulk_microphysics_tendencies(Instantaneous(), Microphysics1Moment(), …) of one point — BMT:505-514.  NaN in → NaN out (cmx_math.hpp any_nan)

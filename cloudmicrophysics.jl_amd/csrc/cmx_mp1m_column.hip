@@ -47,9 +47,6 @@ template <typename FT> struct Mp1mColKernArgs { Mp1mLinKernArgs<FT> k; Vel1mCons
 // … of the step with a snow shape (CMX_1M_SED_SNOW_*): the fall-speed constants with the shaped snow terms (cmx_mp1m_vel.hpp Vel1mShapeConsts)
 template <typename FT> struct Mp1mColShapeKernArgs { Mp1mLinKernArgs<FT> k; Vel1mShapeConsts<FT> vc; };
 
-#ifndef CMX_1M_COLUMN_PACKED
-#define CMX_1M_COLUMN_PACKED 1      // A/B switch: 0 = one point at a time (rounds 3–4)
-#endif
 template <typename FT, uint32_t FLAGS, bool LIN, bool GENERAL_GAMMA, int VEC, int BS>
 __global__ __launch_bounds__(BS) void mp1m_column_kernel(const Mp1mColKernArgs<FT> a0, const Mp1mColIO<FT> io, const int64_t first, const int64_t nvec) {
     constexpr bool SHAPED = false;

@@ -52,7 +52,7 @@
         FT t[VEC][4];
         // one value of the value type VT at a time: a point, or — Float32 with four points per lane — a PAIR of points in packed arithmetic (cmx_math.hpp f32x2;
         // not the run-time-Γ instantiation: an OCML call per lane, nothing to pack)
-        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_1M_COLUMN_PACKED && !GENERAL_GAMMA) ? 2 : 1;
+        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && !GENERAL_GAMMA) ? 2 : 1;
         using VT = std::conditional_t<L == 2, f32x2, FT>;
         using MV = Math<VT>;
         if constexpr (L == 1) {      // (kept verbatim from rounds 3–4: routing the one-point case through the generic form below doubled its registers)

@@ -37,9 +37,6 @@ template <typename FT> constexpr int kBlock1m = CMX_1M_BLOCK;
 #else
 template <typename FT> constexpr int kBlock1m = sizeof(FT) == 4 ? 64 : 256;
 #endif
-#ifndef CMX_1M_PACKED
-#define CMX_1M_PACKED 1      // A/B switch: 0 = one point at a time (rounds 1–4)
-#endif
 template <typename FT, int VEC, uint32_t FLAGS = kRuntimeFlags>
 __global__ __launch_bounds__(kBlock1m<FT>) void mp1m_tendencies_kernel(const Mp1mConsts<FT> c, const Mp1mIn<FT> in,
                                                                        const Mp1mOut<FT> out, const int64_t nvec) {
@@ -53,9 +50,12 @@ __global__ __launch_bounds__(kBlock1m<FT>) void mp1m_tendencies_kernel(const Mp1
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
     if (i >= nvec) return;
     FT dl[VEC], di[VEC], dr[VEC], ds[VEC];
-    if constexpr (CMX_1M_PACKED && sizeof(FT) == 4 && VEC == 4) {
+    if constexpr (sizeof(FT) == 4 && VEC == 4) {
         // Float32, four points per lane: two PAIRS of points in packed arithmetic (cmx_math.hpp f32x2); the constants are read phase by phase through the
-        // kernel-argument pointer (a packed instruction takes no literal: the point function's literals occupy SGPRs next to the constants)
+        // kernel-argument pointer (a packed instruction takes no literal: the point function's literals occupy SGPRs next to the constants).
+        // Rounds 1–4 evaluated one point at a time here; round 3 parked the additive constants of every `a·x + b` in VGPRs once per lane for
+        // them (an instruction reads one SGPR: 12 of a point's 266 instructions were v_mov_b32 of b; 70 → 76 VGPRs, 0.782–0.793 → 0.778–0.779 ms
+        // per 1e8 points) — the packed form took over every instantiation that did.
 #pragma unroll
         for (int k = 0; k < VEC; k += 2) {
             f32x2 l, ic, r, sn;
@@ -64,12 +64,6 @@ __global__ __launch_bounds__(kBlock1m<FT>) void mp1m_tendencies_kernel(const Mp1
                                                 f32x2{q_sno[k], q_sno[k + 1]}, l, ic, r, sn);
             dl[k] = l.x; dl[k + 1] = l.y; di[k] = ic.x; di[k + 1] = ic.y; dr[k] = r.x; dr[k + 1] = r.y; ds[k] = sn.x; ds[k + 1] = sn.y;
         }
-    } else if constexpr (CMX_1M_HOIST && sizeof(FT) == 4 && VEC == 4 && FLAGS != kRuntimeFlags) {
-        Mp1mConsts<FT> ch = c;
-        mp1m_hoist_consts<FT>(ch);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k)
-            mp1m_tendencies_point<FT, FLAGS>(ch, rho[k], T[k], q_tot[k], q_lcl[k], q_icl[k], q_rai[k], q_sno[k], dl[k], di[k], dr[k], ds[k]);
     } else {
 #pragma unroll
         for (int k = 0; k < VEC; ++k)
@@ -112,9 +106,6 @@ __global__ __launch_bounds__(kBlockLin) void mp1m_linearized_kernel(const Mp1mLi
 
 // Float32, round 5: TWO consecutive points per lane as one packed pair (cmx_math.hpp f32x2) — 8-byte loads and stores, the substep loop in packed
 // arithmetic.  Needs 8-byte-aligned columns; `npair` pairs.  (The host launches the one-point kernel for an odd last point or misaligned columns.)
-#ifndef CMX_1M_LIN_PACKED
-#define CMX_1M_LIN_PACKED 1      // A/B switch
-#endif
 template <uint32_t FLAGS = kRuntimeFlags>
 __global__ __launch_bounds__(kBlockLin) void mp1m_linearized_pair_kernel(const Mp1mLinKernArgs<float> k0, const Mp1mLinIO<float> io, const int64_t npair) {
     const int64_t i = (int64_t)blockIdx.x * kBlockLin + threadIdx.x;
@@ -215,7 +206,7 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
     if (!rho || !T || !q_tot || !q_lcl || !q_icl || !q_rai || !q_sno || !dq_lcl || !dq_icl || !dq_rai || !dq_sno) return CMX_ERR_BAD_ARG;
     const Mp1mConsts<FT> c = make_mp1m_consts<FT>(*mp, *tps, flags, (double)Math<FT>::eps_1m());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    constexpr int VEC = (sizeof(FT) == 8 && CMX_F64_ONE_POINT_PER_LANE) ? 1 : Math<FT>::VEC;
+    constexpr int VEC = sizeof(FT) == 8 ? 1 : Math<FT>::VEC;      // Float64: one point per lane (cmx_launch.hpp)
     const void *ptrs[] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dq_lcl, dq_icl, dq_rai, dq_sno};
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {      // alignment split: cmx_split.hpp
         constexpr int V = decltype(vec_tag)::value;
@@ -231,7 +222,7 @@ static int32_t tendencies_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
 template <typename FT, uint32_t FLAGS> struct Mp1mLayoutPolicy {
     static constexpr int NIN = 7, NOUT = 4, NAOS = 4;   // rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno → (dq_lcl_dt, dq_icl_dt, dq_rai_dt, dq_sno_dt)
     using Consts = Mp1mConsts<FT>;
-    static constexpr bool PACKABLE = CMX_1M_PACKED;      // point() also takes the packed pair type (cmx_layout.hpp)
+    static constexpr bool PACKABLE = true;      // point() also takes the packed pair type (cmx_layout.hpp)
     template <typename C, typename VT> static __device__ __forceinline__ void point(const C &c, const VT (&x)[NIN], VT (&y)[NOUT]) {
         mp1m_tendencies_point<VT, FLAGS>(c, x[0], x[1], x[2], x[3], x[4], x[5], x[6], y[0], y[1], y[2], y[3]);
     }
@@ -240,7 +231,7 @@ template <typename FT, uint32_t FLAGS> struct Mp1mLayoutPolicy {
 template <typename FT, uint32_t FLAGS> struct Mp1mLinLayoutPolicy {
     static constexpr int NIN = 7, NOUT = 4, NAOS = 4;
     using Consts = Mp1mLinKernArgs<FT>;
-    static constexpr bool PACKABLE = CMX_1M_LIN_PACKED;
+    static constexpr bool PACKABLE = true;
     static constexpr bool PHASE_CONSTS = FLAGS == kRuntimeFlags;
     template <typename C, typename VT> static __device__ __forceinline__ void point(const C &k, const VT (&x)[NIN], VT (&y)[NOUT]) {
         mp1m_linearized_point<VT, FLAGS>(k.c, [&](VT dep) -> decltype(auto) { return (consts_after(k, dep).a); }, k.a.nsub, x[0], x[1], x[2], x[3], x[4], x[5],
@@ -280,7 +271,7 @@ static int32_t linearized_1m_entry(const MP *mp, const TH *tps, uint32_t flags, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // Float32: pairs of points in packed arithmetic (8-byte body), the rest one point per lane — the same per-point operations, so the
     // result does not depend on the alignment split (cmx_split.hpp)
-    constexpr int VEC = (sizeof(FT) == 4 && CMX_1M_LIN_PACKED) ? 2 : 1;
+    constexpr int VEC = sizeof(FT) == 4 ? 2 : 1;
     const void *ptrs[] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dq_lcl, dq_icl, dq_rai, dq_sno};
     for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;

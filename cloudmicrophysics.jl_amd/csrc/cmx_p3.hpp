@@ -17,14 +17,10 @@
 // 1e6 / 1e7 states: 2M + P3 Float64 20.7 → 19.1, shape + fall speeds 26.8 → 24.5, self-collection 50.7 → 46.1; Float32 6.7 → 6.2, 8.0 → 7.1, 16.1 → 14.7).
 // The pragma brackets exactly that code: this header's device functions and the P3 kernels of cmx_p3_kernels.hip / cmx_p3_collisions.hip.  The pointwise
 // part of the 2M + P3 entry (mp2m_p3_point → sb2006_point) stays outside — it is bit-identical to the warm-rain entry, and tested so.
-// -DCMX_P3_FP_CONTRACT=0: no contraction anywhere (A/B switch).
-#ifndef CMX_P3_FP_CONTRACT
-#define CMX_P3_FP_CONTRACT 1
-#endif
 // The bracket acts in the DEVICE pass only: the host pass of the same sources holds the entry functions that fold the kernel constants
 // (make_p3_consts, the collision entry), which the Python and oracle mirrors reproduce operation by operation — an FMA-capable host build must not contract
-// them.  With CMX_P3_FP_CONTRACT=0 both macros are empty, so the translation unit's own default stays in force.
-#if CMX_P3_FP_CONTRACT && defined(__HIP_DEVICE_COMPILE__)
+// them.  There both macros are empty, so the translation unit's own default stays in force.
+#if defined(__HIP_DEVICE_COMPILE__)
 #define CMX_P3_CONTRACT_BEGIN _Pragma("clang fp contract(fast)")
 #define CMX_P3_CONTRACT_END _Pragma("clang fp contract(off)")
 #else
@@ -42,23 +38,15 @@ template <> struct PM<double> {
     // one-argument forms (the shape solver's dozen call sites around the incomplete-gamma loops; the quadrature loops use the
     // register-pinned lean forms below): the table-driven lean routines where the translation unit keeps their polynomial coefficients
     // as SGPR literals (cmx_lean_f64.hpp CMX_LEAN_COEFS_IN_LDS = 0: 253 VGPRs, 2 waves per SIMD like the OCML build, 10 % fewer
-    // instructions — shape + fall speeds 41.7 → 38.5 ms per 1e7 columns, 2M + P3 27.9 → 26.7 ms per 1e6 states, same-box A/B round 2);
-    // OCML where the coefficients live in LDS (there the inlined lean routines cost 286 VGPRs — 1 wave per SIMD, 24 → 30 ms).
-#ifndef CMX_P3_LEAN_ONEARG
-#define CMX_P3_LEAN_ONEARG (!CMX_LEAN_COEFS_IN_LDS)
+    // instructions — shape + fall speeds 41.7 → 38.5 ms per 1e7 columns, 2M + P3 27.9 → 26.7 ms per 1e6 states, same-box A/B round 2).
+    // With the coefficients in LDS the inlined lean routines cost 286 VGPRs — 1 wave per SIMD, 24 → 30 ms (OCML served there): both
+    // translation units that include this header are in the Makefile's LITCOEF list, and must stay there.
+#if CMX_LEAN_COEFS_IN_LDS      // (defined in the device pass only)
+#error "cmx_p3.hpp: the P3 translation units keep the lean Float64 coefficients as SGPR literals (csrc/Makefile LITCOEF); with them in LDS the shape solver needs 286 VGPRs"
 #endif
-#if CMX_P3_LEAN_ONEARG
     static __device__ __forceinline__ double log(double x) { return lean::log(x); }
     static __device__ __forceinline__ double exp(double x) { return lean::exp(x); }
-#else
-    static __device__ __forceinline__ double log(double x) { return ::log(x); }
-    static __device__ __forceinline__ double exp(double x) { return ::exp(x); }
-#endif
-#if CMX_P3_LEAN_ONEARG
     static __device__ __forceinline__ double lgamma(double x) { return lean::lgamma_pos(x); }   // every argument here is > 0 (μ + 1, μ + b + n + 1, 1 + b_j)
-#else
-    static __device__ __forceinline__ double lgamma(double x) { return ::lgamma(x); }
-#endif
     static __device__ __forceinline__ double expm1(double x) { return ::expm1(x); }
     static __device__ __forceinline__ double log1p(double x) { return ::log1p(x); }
     static __device__ __forceinline__ double pow(double x, double y) { return ::pow(x, y); }
@@ -69,11 +57,8 @@ template <> struct PM<double> {
     // 1/d to ≈1 ulp: v_rcp_f64 (≈2⁻²⁴ relative) + two Newton steps — no div_scale / div_fmas / div_fixup sequence.
     // Only for finite, normal d (the incomplete-gamma loops: d = a + k, or a rescaled continued-fraction denominator).
     static __device__ __forceinline__ double rcp(double d) { return lean::rcp_finite(d); }
-    // hot-loop variants with register-pinned constants (cmx_lean_f64.hpp): table-driven (round 2; -DCMX_P3_TABLE_MATH=0 restores the
-    // round-1 polynomial forms for A/B runs).  The kernels call Math<FT>::prepare() first (tables → LDS).
-#ifndef CMX_P3_TABLE_MATH
-#define CMX_P3_TABLE_MATH 1
-#endif
+    // hot-loop variants with register-pinned constants (cmx_lean_f64.hpp): table-driven since round 2 (round 1: table-free polynomial
+    // forms, 29 pinned values).  The kernels call Math<FT>::prepare() first (tables → LDS).
 #ifndef CMX_P3_SCALAR_COEFS
 #define CMX_P3_SCALAR_COEFS 0      // 1: the hot loops call the one-argument forms with SGPR-literal coefficients (needs CMX_LEAN_COEFS_IN_LDS=0)
 #endif
@@ -86,40 +71,23 @@ template <> struct PM<double> {
     static __device__ __forceinline__ double log(double x, const Coefs &) { return lean::log(x); }
     static __device__ __forceinline__ double log_pos(double x, const Coefs &) { return lean::log_pos(x); }   // positive normal finite x
 #else
-#if CMX_P3_TABLE_MATH
     using Coefs = lean::TabCoefs;
     static __device__ __forceinline__ Coefs coefs() { return lean::tab_coefs(); }
-#else
-    using Coefs = lean::PinnedCoefs;
-    static __device__ __forceinline__ Coefs coefs() { return lean::pinned_coefs(); }
-#endif
     static __device__ __forceinline__ double exp(double x, const Coefs &k) { return lean::exp_fin(x, k); }   // integrand form: see above
     static __device__ __forceinline__ double log(double x, const Coefs &k) { return lean::log(x, k); }
     static __device__ __forceinline__ double log_pos(double x, const Coefs &k) { return lean::log_pos(x, k); }
 #endif
     // Constants pinned in registers for ONE phase of a kernel built with the scalar forms (round 5): the phase with register slack pays for them, the phase
-    // at the kernel's register limit (the collision sweep) keeps the scalar forms.  CMX_P3_LOCAL_COEFS = 2 (default): all eighteen constants of the
-    // table-driven exp / log (lean::tab_coefs — volatile pins, so they are born where coefs_local() is called and not before); = 1: only the second
-    // polynomial coefficient of each (exp_fin_c1 / log_pos_c1: no v_mov_b64 in front of the first Horner step; the asm depends on `dep`, a value born
-    // in that phase); = 0: the scalar forms everywhere (A/B switch; profiles/r05_ab_sessions.txt session 9: 21.2 / 21.0 / 20.7 ms for 0 / 1 / 2).
-#ifndef CMX_P3_LOCAL_COEFS
-#define CMX_P3_LOCAL_COEFS 2
-#endif
-#if CMX_P3_SCALAR_COEFS && CMX_P3_LOCAL_COEFS == 2
+    // at the kernel's register limit (the collision sweep) keeps the scalar forms.  Pinned are all eighteen constants of the table-driven exp / log
+    // (lean::tab_coefs — volatile pins, so they are born where coefs_local() is called and not before).  Measured against pinning only the second
+    // polynomial coefficient of each (no v_mov_b64 in front of the first Horner step) and against the scalar forms everywhere
+    // (profiles/r05_ab_sessions.txt session 9): 20.7 ms against 21.0 and 21.2.
+#if CMX_P3_SCALAR_COEFS
     // every constant of the table-driven exp / log in registers for the phase (18 pairs, the TabCoefs of the translation units that are not at a register limit)
     using LocalCoefs = lean::TabCoefs;
     static __device__ __forceinline__ LocalCoefs coefs_local(double) { return lean::tab_coefs(); }
     static __device__ __forceinline__ double exp(double x, const LocalCoefs &k) { return lean::exp_fin(x, k); }
     static __device__ __forceinline__ double log_pos(double x, const LocalCoefs &k) { return lean::log_pos(x, k); }
-#elif CMX_P3_SCALAR_COEFS && CMX_P3_LOCAL_COEFS
-    struct LocalCoefs { double e1, l1; };
-    static __device__ __forceinline__ LocalCoefs coefs_local(double dep) {
-        LocalCoefs k{lean::coefs().ee[1], lean::coefs().ln[1]};
-        asm volatile("" : "+v"(k.e1), "+v"(k.l1) : "v"(dep));
-        return k;
-    }
-    static __device__ __forceinline__ double exp(double x, const LocalCoefs &k) { return lean::exp_fin_c1(x, k.e1); }
-    static __device__ __forceinline__ double log_pos(double x, const LocalCoefs &k) { return lean::log_pos_c1(x, k.l1); }
 #else
     using LocalCoefs = Coefs;
     static __device__ __forceinline__ LocalCoefs coefs_local(double) { return coefs(); }
@@ -147,32 +115,16 @@ template <> struct PM<float> {
     using LocalCoefs = Coefs;
     static __device__ __forceinline__ LocalCoefs coefs_local(float) { return {}; }
     static __device__ __forceinline__ void pin(float &) {}
-    // the incomplete-gamma prefactor e^(a ln x − x − ln Γ(a)) — eight per residual evaluation of the shape solver: CMX_P3_F32_FAST_PREFACTOR=1
-    // takes the hardware forms there too (A/B switch)
-#ifndef CMX_P3_F32_FAST_PREFACTOR
-#define CMX_P3_F32_FAST_PREFACTOR 1
-#endif
-#if CMX_P3_F32_FAST_PREFACTOR
+    // the incomplete-gamma prefactor e^(a ln x − x − ln Γ(a)) — eight per residual evaluation of the shape solver — takes the hardware forms too
+    // (OCML's expf / logf before)
     static __device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
     static __device__ __forceinline__ float log_fast(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-#else
-    static __device__ __forceinline__ float exp_fast(float x) { return ::expf(x); }
-    static __device__ __forceinline__ float log_fast(float x) { return ::logf(x); }
-#endif
     // hot-loop forms (quadrature integrands): the hardware v_exp_f32 / v_log_f32 with one multiply — 2 instructions instead of OCML's 15
     // (expf) and 14 (logf), which spend the rest on the last ulp and on subnormals; the product x·log₂e is rounded once, so the
     // relative error is ≈ 6e-8·(1 + |x| log₂e) (1e-5 at |x| = 100) — an integrand weight, well inside the 1e-3 Float32 bound.  The shape
-    // solver and the set-up code keep the one-argument OCML forms.  A/B switch: -DCMX_P3_F32_FAST_LOOPS=0.
-#ifndef CMX_P3_F32_FAST_LOOPS
-#define CMX_P3_F32_FAST_LOOPS 1
-#endif
-#if CMX_P3_F32_FAST_LOOPS
+    // solver and the set-up code keep the one-argument OCML forms.
     static __device__ __forceinline__ float exp(float x, const Coefs &) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
     static __device__ __forceinline__ float log(float x, const Coefs &) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
-#else
-    static __device__ __forceinline__ float exp(float x, const Coefs &) { return ::expf(x); }
-    static __device__ __forceinline__ float log(float x, const Coefs &) { return ::logf(x); }
-#endif
     static __device__ __forceinline__ float log_pos(float x, const Coefs &k) { return log(x, k); }      // Float32: the hardware form handles every class
     static __device__ __forceinline__ float rcp(float d) {
         const float r = __builtin_amdgcn_rcpf(d);
@@ -270,27 +222,13 @@ template <typename FT, typename PR> static P3Consts<FT> make_p3_consts(const PR 
 //     recurrence A_n = b_n A_{n−1} + a_n A_{n−2} — the value modified Lentz produces with two divisions per term —
 //     rescaled every kRescale terms; one reciprocal at the end.
 // `gamma_series` / `gamma_cf` return the bracketed sums WITHOUT the prefactor x^a e^{−x}/Γ(a).
-#ifndef CMX_P3_CF_EARLY_EXIT
-#define CMX_P3_CF_EARLY_EXIT 1      // A/B switch
-#endif
-#ifndef CMX_P3_SERIES_FWD_F32
-#define CMX_P3_SERIES_FWD_F32 1      // A/B switch
-#endif
-#ifndef CMX_P3_CF_INCREMENT
-#define CMX_P3_CF_INCREMENT 2      // Float64: continued fraction from the tail inwards (2) / forwards (1) with its coefficients by differences, series denominators by decrement (gamma_cf_value; A/B switch)
-#endif
-#ifndef CMX_P3_SERIES_NODIV
-#define CMX_P3_SERIES_NODIV 1      // 0: term-by-term with one reciprocal per term (round 1; A/B switch)
-#endif
 template <typename FT> __device__ __forceinline__ FT gamma_series_sum(FT a, FT x) {
     using P = PM<FT>;
-#if CMX_P3_SERIES_NODIV
     // Σ_{k=0}^{K} x^k/(a(a+1)…(a+k)) = T₁/a with T_k = 1 + x T_{k+1}/(a+k), T_{K+1} = 1, carried as a fraction p/q from the last term
     // inwards: p ← q(a+k) + x p, q ← q(a+k) — three instructions per term and NO reciprocal (the term-by-term form spends one per
     // term: 8 instructions + a quarter-rate v_rcp in Float64), rescaled every kSeriesRescale terms ((a+k) ≤ 60: 6e17 / 8e8 growth).
     constexpr int R = sizeof(FT) == 8 ? 10 : 5;
     static_assert(P::kGammaIters % R == 0, "rescale period must divide the term count");
-#if CMX_P3_SERIES_FWD_F32
     if constexpr (sizeof(FT) == 4) {
         // Float32: forwards, S_k = M_k/D_k with M_k = M_{k−1}(a+k) + x^k, D_k = D_{k−1}(a+k) — four instructions per term, but the
         // terms fall monotonically (x < a + 1), so the wave can stop once the remaining tail is ≤ eps·S_k for all of its lanes in this loop
@@ -315,16 +253,15 @@ template <typename FT> __device__ __forceinline__ FT gamma_series_sum(FT a, FT x
         }
         return M;       // D == 1
     }
-#endif
+    // Float64
     FT p = FT(1), q = FT(1);
-    FT ak = a + FT(P::kGammaIters);      // a + k carried downwards: one subtraction per term instead of an integer conversion and an addition (CMX_P3_CF_INCREMENT)
+    FT ak = a + FT(P::kGammaIters);      // a + k carried downwards: one subtraction per term instead of an integer conversion and an addition
 #pragma unroll 1
     for (int k0 = P::kGammaIters; k0 > 0; k0 -= R) {
 #pragma unroll
         for (int j = 0; j < R; ++j) {
-            FT qa;
-            if constexpr (sizeof(FT) == 8 && CMX_P3_CF_INCREMENT) { qa = q * ak; ak -= FT(1); }
-            else qa = q * (a + FT(k0 - j));
+            const FT qa = q * ak;
+            ak -= FT(1);
             p = Math<FT>::fma(x, p, qa);
             q = qa;
         }
@@ -332,24 +269,19 @@ template <typename FT> __device__ __forceinline__ FT gamma_series_sum(FT a, FT x
         q = FT(1);
     }
     return p * P::rcp(a);
-#else
-    FT term = P::rcp(a), sum = term;
-#pragma unroll 2
-    for (int k = 1; k <= P::kGammaIters; ++k) { term *= x * P::rcp(a + FT(k)); sum += term; }
-    return sum;
-#endif
 }
 template <typename FT> __device__ __forceinline__ FT gamma_cf_value(FT a, FT x) {
     using P = PM<FT>;
     static_assert(P::kGammaIters % P::kRescale == 0, "rescale period must divide the term count");
     // h₀ = 1/b₀:  A₀ = 1, B₀ = b₀;  A₋₁ = 0, B₋₁ = 1
     const FT b0 = x + FT(1) - a;
-    if constexpr (sizeof(FT) == 8 && CMX_P3_CF_INCREMENT >= 2) {
+    if constexpr (sizeof(FT) == 8) {
         // Float64 (round 5): the SAME convergent h_N, evaluated from the tail inwards.  t_N = b_N, t_{k−1} = b_{k−1} + a_k/t_k, h_N = 1/t_0, with t carried as a
         // fraction p/q:  p ← b_{k−1} p + a_k q,  q ← p  — one multiply and one fused multiply-add per term where the forward (Wallis) recurrence above runs
         // two of each (A and B), and no convergent is formed on the way: Float64 never took the early exit (it reaches eps only near the full count).  The
         // coefficients by differences (a_{k−1} − a_k = 2k − 1 − a, b_{k−1} − b_k = −2: three additions per term); rescaled every kRescale terms by 1/p.
-        // 8.5 → 6 instructions per term; -DCMX_P3_CF_INCREMENT=1: the forward recurrence with difference coefficients, =0: with closed-form coefficients.
+        // 8.5 → 6 instructions per term against the forward recurrence with difference coefficients.  The accumulated rounding of a_k is ≤ k ulp of a
+        // number of size k² (1e-14 relative at the 30th term, against the 1e-6 of the parity bound and the 1e-11 the shape solve reaches).
         constexpr int N = P::kGammaIters;
         FT bk = b0 + FT(2 * N);                      // b_N
         FT ak = -FT(N) * (FT(N) - a);                // a_N
@@ -368,33 +300,20 @@ template <typename FT> __device__ __forceinline__ FT gamma_cf_value(FT a, FT x) 
         }
         return q;
     }
+    // Float32: the forward recurrence with closed-form coefficients
     FT Am = FT(0), Bm = FT(1), A = FT(1), B = b0;
-#if CMX_P3_CF_EARLY_EXIT
     FT A_prev = FT(0);
-#endif
-    // Float64 (round 5): the coefficients by differences — a_{k+1} − a_k = a − (2k + 1), b_{k+1} − b_k = 2 — three additions per term instead of an
-    // integer conversion, a subtraction, a multiply and an addition; the accumulated rounding of a_k is ≤ k ulp of a number of size k² (1e-14 relative at
-    // the 30th term, against the 1e-6 of the parity bound and the 1e-11 the shape solve reaches).  -DCMX_P3_CF_INCREMENT=0: the closed forms (A/B switch).
-    constexpr bool INCR = sizeof(FT) == 8 && CMX_P3_CF_INCREMENT == 1;
-    FT ak_i = a - FT(1), dk_i = a - FT(3), bk_i = b0 + FT(2);      // a_1 = −1·(1 − a), a_2 − a_1, b_1
 #pragma unroll 1
     for (int k0 = 0; k0 < P::kGammaIters; k0 += P::kRescale) {
 #pragma unroll
         for (int j = 1; j <= P::kRescale; ++j) {
-            FT ak, bk;
-            if constexpr (INCR) {
-                ak = ak_i; bk = bk_i;
-                ak_i += dk_i; dk_i -= FT(2); bk_i += FT(2);
-            } else {
-                const FT kk = FT(k0 + j);
-                ak = -kk * (kk - a); bk = b0 + FT(2) * kk;
-            }
+            const FT kk = FT(k0 + j);
+            const FT ak = -kk * (kk - a), bk = b0 + FT(2) * kk;
             const FT An = bk * A + ak * Am, Bn = bk * B + ak * Bm;
             Am = A; Bm = B; A = An; B = Bn;
         }
         const FT r = P::rcp(B);
         A *= r; Am *= r; Bm *= r; B = FT(1);
-#if CMX_P3_CF_EARLY_EXIT
         // the reference's 20 / 30 terms are an upper bound: stop once the convergent no longer moves for ANY lane of the wave that is in
         // this loop (after a rescale A IS the convergent; a NaN compares unequal forever and runs the full count)
         // Float32 only (same-box A/B, shape + fall speeds per 1e7 columns: 13.1 → 11.75 ms; Float64 reaches eps only near the full count:
@@ -403,7 +322,6 @@ template <typename FT> __device__ __forceinline__ FT gamma_cf_value(FT a, FT x) 
             if (__all(P::abs(A - A_prev) <= P::eps() * P::abs(A))) break;
             A_prev = A;
         }
-#endif
     }
     return A;
 }

@@ -268,9 +268,6 @@ __device__ __forceinline__ void bigg_rain(const KC &k, FT J_bigg, FT rho, FT q_r
     }
 }
 
-#ifndef CMX_SB_INTPOW_P3
-#define CMX_SB_INTPOW_P3 1
-#endif
 template <typename FT> struct FusedIO {
     const FT *rho, *T, *q_tot, *q_lcl, *n_lcl, *q_rai, *n_rai, *q_ice, *n_ice, *q_rim, *b_rim, *shift;
     FT *out[8];
@@ -791,11 +788,11 @@ __global__ __launch_bounds__(kBlock, CMX_COL_WAVES) void p3_collision_kernel(con
     FT acc_sc = FT(0), acc_m = FT(0);
     if constexpr (FUSED) {
         const FT D_lo_sc = Sv[20], D_hi_sc = Sv[21];
-        // these two sweeps run far below the kernel's register count (≈ 107 of 163–168 VGPRs): their integrands read the second polynomial coefficient
+        // these two sweeps run far below the kernel's register count (≈ 107 of 163–168 VGPRs): their integrands read the constants
         // of exp / log from register pairs pinned HERE (cmx_p3.hpp coefs_local) — 5 v_mov_b64 fewer per inner node of the self-collection integral
         const typename P::LocalCoefs kl = P::coefs_local(D_lo_sc);
         IceK ikp = ik0;
-        if constexpr (CMX_P3_LOCAL_COEFS) { P::pin(ikp.half_sigma); P::pin(ikp.sqrt_gamma_pi); P::pin(ikp.pi_4); P::pin(ikp.gamma_area); P::pin(ikp.g0); P::pin(ikp.g1); P::pin(ikp.bnd1); }
+        P::pin(ikp.half_sigma); P::pin(ikp.sqrt_gamma_pi); P::pin(ikp.pi_4); P::pin(ikp.gamma_area); P::pin(ikp.g0); P::pin(ikp.g1); P::pin(ikp.bnd1);
         if (present) {
             FT bs[5];
             bs[0] = D_lo_sc; bs[4] = D_hi_sc;
@@ -921,7 +918,7 @@ __global__ __launch_bounds__(kBlock, CMX_COL_WAVES) void p3_collision_kernel(con
 #pragma unroll
             for (int kk = 0; kk < 11; ++kk) in[kk] = p2.at_tab(col[kk], seg_tab, kk);
             const FT shift = ex.shift ? p2.at_tab(ex.shift, seg_tab, SEG_SHIFT) : FT(0);
-            if constexpr (sizeof(FT) == 8 && CMX_PHASE_CONSTS) {
+            if constexpr (sizeof(FT) == 8) {
                 // Float64: the pointwise constants (≈ 150 doubles) are read THROUGH the kernel-argument segment and only now — taken from the by-value
                 // argument the compiler loads them in the entry block and parks them in VGPR lanes across all the sweeps (cmx_math.hpp consts_after)
                 // (its offset comes from THIS kernel's parameter list — kernarg_offset_of_last, cmx_launch.hpp — not from a hand-kept mirror struct)
@@ -1054,7 +1051,7 @@ static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t
     c.brent_iters = 0;
     const PointwiseConsts<FT> pk = make_pointwise_consts<FT>(*wr, *ip, *tps);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const bool intpow = sb_integer_exponents(*wr) && CMX_SB_INTPOW_P3;   // the same warm-rain instantiation as cmx_sb2006_warm_rain_tendencies_* picks
+    const bool intpow = sb_integer_exponents(*wr);   // the same warm-rain instantiation as cmx_sb2006_warm_rain_tendencies_* picks
     // ice processes
     const P3VelConsts<FT> v = make_p3_collision_vel_consts<FT>(ip->scheme, ip->vel_ice);
     const P3ColConsts<FT> k = make_p3col_consts<FT>(*ip, wr->air_properties, *tps, flags);
@@ -1064,10 +1061,7 @@ static int32_t mp2m_p3_entry(const WR *wr, const IP *ip, const TH *tps, uint32_t
     for (int q = 0; q < 8; ++q) io.out[q] = out[q];
     if (lay) io.lay = *lay;
     using QUAD = std::remove_cv_t<std::remove_reference_t<decltype(ip->quad)>>;
-#ifndef CMX_MP2M_P3_ONE_LAUNCH
-#define CMX_MP2M_P3_ONE_LAUNCH 1      // 0: always the two launches (A/B switch)
-#endif
-    if (CMX_MP2M_P3_ONE_LAUNCH && ip->quad.n <= 32) {
+    if (ip->quad.n <= 32) {
         // ONE launch: the collision kernel's epilogue evaluates the pointwise part too (PointwiseExtra) — each tendency column is written once
         QuadSmall<FT> qs{};
         qs.n = ip->quad.n;

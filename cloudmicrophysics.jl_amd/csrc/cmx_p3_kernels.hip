@@ -29,9 +29,6 @@ CMX_P3_CONTRACT_BEGIN      // the whole translation unit is P3 quadrature / solv
 #ifndef CMX_P3_BS
 #define CMX_P3_BS 256
 #endif
-#ifndef CMX_P3_F32_PACKED_NODES
-#define CMX_P3_F32_PACKED_NODES 1      // Float32 fall-speed / melting node loops two nodes at a time in packed arithmetic (0: one node at a time, A/B switch)
-#endif
 constexpr int kP3BS = CMX_P3_BS;      // lanes per workgroup of the kernels of this file, one state per lane (A/B switch)
 
 
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(kP3BS) void p3_velocity_kernel(const P3Consts<FT> c
             };
             int j = 0;
 #if CMX_HAVE_PACKED
-            if constexpr (sizeof(FT) == 4 && CMX_P3_F32_PACKED_NODES) {
+            if constexpr (sizeof(FT) == 4) {      // Float32: two nodes at a time in packed arithmetic (cmx_p3.hpp PM<f32x2>)
                 f32x2 rn2 = f32x2(0.0f), rm2 = f32x2(0.0f);
                 for (; j + 1 < quad.n; j += 2) {
                     const f32x2 xn = f32x2{quad.node[j], quad.node[j + 1]}, wn = f32x2{quad.weight[j], quad.weight[j + 1]};

@@ -25,9 +25,6 @@ namespace cmx {
 // VEL_CHEN: the density-dependent coefficients of the Chen-2022 terms from host-fitted polynomials in ρ (cmx_math.hpp ChenLog); VEL_CHEN_GEN: run-time Γ for
 // parameter sets the fit cannot represent (make_chen_log false)
 enum : int { VEL_NONE = 0, VEL_SB = 1, VEL_CHEN = 2, VEL_CHEN_GEN = 3 };
-#ifndef CMX_SB_TSTAR_RCP
-#define CMX_SB_TSTAR_RCP 1        // A/B switch of the evaporation's t* (below)
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // Host-folded constants.  Plain FT members only (kernel argument → SGPRs).
@@ -435,7 +432,7 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
     const FT one_m_tau = sq_lcl * inv_qsum;
     const FT l2_tau = M::log2(tau);
     {   // autoconversion CM2:396-427
-        const C &c = consts_after(c0, CMX_PHASE_DEP(G, inv_T));
+        const C &c = consts_after(c0, G);
         const FT x_lcl = M::min(c.x_star, x_lcl_raw);
         const FT tau_a = M::exp2_fin(c.acnv_a * l2_tau);                  // τ ∈ [eps², 1]: l2_tau finite
         FT pow_b;
@@ -454,7 +451,7 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
         r.au_dN_lcl = FT(-2) * r.au_dN_rai;
     }
     {   // cloud_liquid_self_collection CM2:488-501 (raw L_lcl = ρ q_lcl)
-        const C &c = consts_after(c0, CMX_PHASE_DEP(G, inv_T));
+        const C &c = consts_after(c0, G);
         const FT Lr = rho * q_lcl;
         const FT sc = -c.ksc * inv_rho * (Lr * Lr) - r.au_dN_lcl;
         r.lsc = no_q_lcl ? FT(0) : sc;
@@ -462,7 +459,7 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
         r.lsc_plus_au = no_q_lcl ? FT(0) : -c.ksc * inv_rho * (Lr * Lr);
     }
     {   // accretion CM2:445-470
-        const C &c = consts_after(c0, CMX_PHASE_DEP(G, inv_T));
+        const C &c = consts_after(c0, G);
         FT pow_c;
         if constexpr (INTPOW) { const FT t = tau * M::rcp_nz(tau + c.tau_0), t2 = t * t; pow_c = t2 * t2; }
         else pow_c = M::exp2_fin(c.accr_c * (l2_tau - M::log2(tau + c.tau_0)));
@@ -477,14 +474,14 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
     }
 
     // ---- rain PSD parameters, once (CM2:67-110), from the safe values ----------
-    const C &c_psd = consts_after(c0, CMX_PHASE_DEP(r.ac_dN_lcl, l2_tau));
+    const C &c_psd = consts_after(c0, r.ac_dN_lcl);
     const SbRainPsd<FT> psd = sb2006_rain_psd<FT, LIMITED>(c_psd, L_rai, sN_rai);
     const FT l2_xr = psd.l2_xr, l2_lam = psd.l2_lam;
     const FT l2_Dr = (l2_xr + c_psd.l2_Drc) * FT(1.0 / 3.0);
     const FT Dr = M::exp2_fin(l2_Dr);                      // ∛(6 x̄_r/(π ρw)): CM2:588 and :809
     const B no_N_rai = N_rai < eps;
     {   // rain_self_collection CM2:545-560 + rain_breakup CM2:579-601
-        const C &c = consts_after(c0, CMX_PHASE_DEP(r.ac_dN_lcl, l2_tau));
+        const C &c = consts_after(c0, r.ac_dN_lcl);
         // 1/Br = ∛(x̄_r/6) = Dr·∛(π ρw/36): κ_rr/Br = kappa_rr_K·Dr
         FT pw;
         if constexpr (INTPOW) { const FT r1 = M::rcp_nz(M::fma(c.kappa_rr_K, Dr, FT(1))), r2 = r1 * r1; pw = r2 * r2 * r1; }
@@ -498,13 +495,13 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
         r.rbr = gate ? FT(0) : -(phi_br + FT(1)) * r.rsc;
     }
     {   // rain_evaporation CM2:780-828
-        const C &c = consts_after(c0, CMX_PHASE_DEP(r.rbr, l2_xr));
+        const C &c = consts_after(c0, r.rbr);
         const FT l2_t = (c.l2_6xstar - l2_xr) * FT(1.0 / 3.0);            // t* = ∛(6 x*/x̄_r)
         // Float64 (round 5): t*·Dr is a constant of the parameter set, so t* is one Newton reciprocal of the Dr already at hand (≈ 7 instruction
         // slots) instead of a table-driven exponential (≈ 14); Float32 keeps the exponential (v_exp_f32 and v_rcp_f32 cost the same).  Dr > 0 and finite:
         // the exponential of a finite log2.  2⁻⁴⁸ relative on t*, which enters e^{−t*} (absolute exponent error t*·2⁻⁴⁸) and nothing else.
         FT t_star;
-        if constexpr (M::IS_F64 && CMX_SB_TSTAR_RCP) t_star = c.tstar_Dr * M::rcp_nz(Dr);
+        if constexpr (M::IS_F64) t_star = c.tstar_Dr * M::rcp_nz(Dr);
         else t_star = M::exp2_fin(l2_t);
         // e^{−t*}/x̄_r in one exponential: both factors enter the number tendency only (Γ_incl does not appear in the mass one);
         // the ventilation coefficients a_vent_0, b_vent_0·∛Sc are folded into the Γ_incl denominators on the host
@@ -525,14 +522,14 @@ __device__ __forceinline__ SbRates<FT> sb2006_point(const C &c0, FT rho, FT T, F
         r.evq = gate_q ? FT(0) : dq;
     }
     {   // number_tendency_from_mass_limits CM2:882-891 (cloud: xc_min/xc_max, rain: xr_min/xr_max)
-        const C &c = consts_after(c0, CMX_PHASE_DEP(r.evq, Dr));
+        const C &c = consts_after(c0, r.evq);
         const FT tl = no_q_lcl ? FT(0) : clampv(n_lcl, q_lcl * c.inv_xc_max, q_lcl * c.inv_xc_min);
         r.na_lcl = (tl - n_lcl) * c.inv_tau_na;
         const FT tr = no_q_rai ? FT(0) : clampv(n_rai, q_rai * c.inv_xr_max, q_rai * c.inv_xr_min);
         r.na_rai = (tr - n_rai) * c.inv_tau_na;
     }
     // ---- rain terminal velocity (optional columns) ----------------------------------------------
-    sb2006_rain_velocity<FT, LIMITED, VEL>(consts_after(c0, CMX_PHASE_DEP(r.evq, Dr)), rho, rs_rho, l2_lam, no_N_rai, no_q_rai, r.vt_n, r.vt_m);
+    sb2006_rain_velocity<FT, LIMITED, VEL>(consts_after(c0, r.evq), rho, rs_rho, l2_lam, no_N_rai, no_q_rai, r.vt_n, r.vt_m);
     return r;
 }
 

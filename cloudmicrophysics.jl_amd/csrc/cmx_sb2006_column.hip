@@ -79,13 +79,10 @@ __device__ __forceinline__ SedFlux<FT> sed_fluxes_of_point(const C &c, const Clo
     return f;
 }
 
-#ifndef CMX_F32_PACKED_COLUMN
-#define CMX_F32_PACKED_COLUMN 1        // A/B switch: 0 = one point at a time (rounds 2–4)
-#endif
 // waves per SIMD the Float32 instantiation is compiled for: 5 (96 VGPRs) for the one-point form of rounds 2–4; the packed form holds two points' intermediates in
 // register pairs and spills at 96 (2–25 VGPRs to scratch in the SB2006 / Chen instantiations): 4 (128 VGPRs)
 #ifndef CMX_COL_F32_WAVES
-#define CMX_COL_F32_WAVES (CMX_F32_PACKED_COLUMN ? 4 : 5)
+#define CMX_COL_F32_WAVES 4
 #endif
 #ifndef CMX_COL_F64_WAVES
 #define CMX_COL_F64_WAVES 2      // A/B switch: waves per SIMD the Float64 instantiation is compiled for
@@ -151,7 +148,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(sizeof(FT) =
         }
         int32_t lv = lev;
         // one value of the value type VT at a time: a point, or — Float32 with four points per lane — a PAIR of points in packed arithmetic (cmx_math.hpp f32x2)
-        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_F32_PACKED_COLUMN && VEL != VEL_CHEN_GEN) ? 2 : 1;    // (the run-time Γ of the general Chen instantiation is an OCML call per lane: nothing to pack, 100 spilled VGPRs)
+        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && VEL != VEL_CHEN_GEN) ? 2 : 1;    // (the run-time Γ of the general Chen instantiation is an OCML call per lane: nothing to pack, 100 spilled VGPRs)
         if constexpr (L == 1) {      // one point at a time — rounds 2–4 verbatim (see sb2006_tendencies_kernel)
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -192,7 +189,7 @@ __global__ __launch_bounds__(BS) __attribute__((amdgpu_waves_per_eu(sizeof(FT) =
                 const VT r_ = max0(rho_k), qt = max0(qt_k), ql = max0(ql_k);
                 const VT qr = max0(qr_k), nl = max0(nl_k), nr = max0(nr_k);
                 const typename MV::Mask poisoned = nan_mask(rho_k, qt_k, ql_k, nl_k, qr_k, nr_k, T_k);
-                const SbRates<VT> p = sb2006_point<VT, LIMITED, VEL, false, INTPOW>(front_consts<FT, (L == 2 && CMX_F32_PACKED_PHASE_CONSTS)>(c), r_, T_k, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
+                const SbRates<VT> p = sb2006_point<VT, LIMITED, VEL, false, INTPOW>(front_consts<FT, (L == 2)>(c), r_, T_k, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
                 SedFlux<VT> Fk = sed_fluxes<VT, CLOUD>(cv, r_, ql, nl, qr, nr, p.vt_n, p.vt_m);
                 VT gk;                                                             // 1/(ρ_k Δz_k)
                 if constexpr (L == 2) {

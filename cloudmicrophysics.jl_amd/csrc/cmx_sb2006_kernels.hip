@@ -24,9 +24,6 @@ constexpr int kTendBS = CMX_TEND_BS;   // lanes per workgroup of the fused tende
                                        // 263-instruction point function, 1e8 f32 points, three runs on one box: 128 → 0.883–0.885 ms, 64 → 0.887–0.902,
                                        // 512 → 0.894–0.923, 256 → 0.915–0.962 (256 was the optimum of the 350-instruction version)
 
-#ifndef CMX_SB_INTPOW
-#define CMX_SB_INTPOW 1      // A/B switch for the integer-exponent instantiations (cmx_sb2006.hpp INTPOW)
-#endif
 template <typename FT, typename WR, typename TH, typename VL>
 static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint32_t flags, int64_t n, const FT *rho,
                                 const FT *T, const FT *q_tot, const FT *q_lcl, const FT *n_lcl, const FT *q_rai,
@@ -43,7 +40,7 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
     const bool limited = flags & CMX_SB2006_LIMITED;
     if ((flags & CMX_SB2006_LIMITED) && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
-    const bool intpow = sb_integer_exponents(*wr) && CMX_SB_INTPOW;        // b = 3, c = 4, d = −5: the integer-power instantiation (cmx_sb2006.hpp)
+    const bool intpow = sb_integer_exponents(*wr);        // b = 3, c = 4, d = −5: the integer-power instantiation (cmx_sb2006.hpp)
     bool known = true;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // Float64: one point per lane (8-byte loads).  The kernel is VALU-bound there and the two-points-per-lane variant spends 14 % of
@@ -78,7 +75,7 @@ static int32_t fields_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t
     // I: the integer-exponent instantiation of the point function (cmx_sb2006.hpp INTPOW)
     return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) {
         return launch_layout<FT, Sb2006LayoutPolicy<FT, decltype(L)::value, decltype(I)::value>>(c, n_seg, seg_len, in, in_stride, out, out_stride, aos, s);
-    }, flag(flags & CMX_SB2006_LIMITED), flag(sb_integer_exponents(*wr) && CMX_SB_INTPOW));
+    }, flag(flags & CMX_SB2006_LIMITED), flag(sb_integer_exponents(*wr)));
 }
 
 template <typename FT, typename WR, typename TH, typename VL>

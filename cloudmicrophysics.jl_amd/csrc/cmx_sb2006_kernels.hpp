@@ -14,10 +14,6 @@
 #include "cmx_layout.hpp"
 #include "cmx_sb2006.hpp"
 
-#ifndef CMX_POINT_FENCE
-#define CMX_POINT_FENCE 0      // A/B switch (round 2): a scheduling fence between the points of a lane did not pay (0.89 vs 0.86 ms)
-#endif
-
 namespace cmx {
 
 template <typename FT> struct SbIn { const FT *rho, *T, *q_tot, *q_lcl, *n_lcl, *q_rai, *n_rai; };
@@ -35,6 +31,7 @@ template <typename FT> struct SbProcOut { FT *col[CMX_SB2006_NPROC]; };
 // walking 4 or 8 tiles in a loop, tile t+1's loads issued before tile t is computed, the table copy paid once — was measured in round
 // 2 and rejected: the loop carries the prefetched columns and hoisted invariants, 167–198 VGPRs against 125, 2–3 waves per SIMD
 // instead of 4, 3.50 ms against 3.06 (tools/valu_probe: a dependent v_fma_f64 issues every 11 cycles; what hides that is waves).
+// A scheduling fence between the points of a lane did not pay either (round 2: 0.89 vs 0.86 ms).
 // CMX_SB_WAVES (A/B switch, default 1 = no request): waves per SIMD the register allocator is asked to keep for the instantiations without a Chen-2022
 // velocity (they sit at 124–136 VGPRs, on either side of the 128-register step between four and three waves; the Chen variants need 200+ and are left alone)
 #ifndef CMX_SB_WAVES
@@ -71,7 +68,7 @@ void sb2006_tendencies_kernel(const SbConsts<FT> c, const SbIn<FT> in,
         // Packed for the Chen-2022 instantiation only (same-box A/B, round 5, profiles/r05_ab_sessions.txt session 3, ms per 1e8 points: Chen 0.955 → 0.93 packed,
         // 0.922 with the constants left in SGPRs; the SB2006-velocity instantiation — the north star — is bound by its 13 HBM streams, not by issue: 0.856 one point
         // at a time, 0.862 packed at four waves per SIMD, 0.93 packed at three).  Not the general Chen instantiation: its run-time Γ is an OCML call per lane.
-        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && CMX_F32_PACKED && (VEL == VEL_CHEN || CMX_F32_PACKED > 1)) ? 2 : 1;
+        constexpr int L = (sizeof(FT) == 4 && VEC % 2 == 0 && VEL == VEL_CHEN) ? 2 : 1;
         if constexpr (L == 1) {      // one point at a time — rounds 1–4 verbatim (routing it through the generic form below costs the compiler 20–60 registers)
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
@@ -98,9 +95,6 @@ void sb2006_tendencies_kernel(const SbConsts<FT> c, const SbIn<FT> in,
                 // branch-free: x + NaN = NaN, x + 0 = x (a −0 result becomes +0, the same in every variant of this kernel)
                 const FT poison = poisoned ? Math<FT>::nan() : FT(0);
                 dq_lcl[k] += poison; dn_lcl[k] += poison; dq_rai[k] += poison; dn_rai[k] += poison; vt_n[k] += poison; vt_m[k] += poison;
-#if CMX_POINT_FENCE
-                __builtin_amdgcn_sched_barrier(0);
-#endif
             }
         } else {
             using VT = std::conditional_t<L == 2, f32x2, FT>;
@@ -122,7 +116,7 @@ void sb2006_tendencies_kernel(const SbConsts<FT> c, const SbIn<FT> in,
                 // a NaN in any input column poisons every output of the point (cmx_math.hpp any_nan)
                 const typename MV::Mask poisoned = nan_mask(rho_k, qt_k, ql_k, nl_k, qr_k, nr_k, T_k);
                 // N = ρ n — BMT:718-719
-                const SbRates<VT> p = sb2006_point<VT, LIMITED, VEL, false, INTPOW>(front_consts<FT, (L == 2 && CMX_F32_PACKED_PHASE_CONSTS > 1)>(c), r_, T_k, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
+                const SbRates<VT> p = sb2006_point<VT, LIMITED, VEL, false, INTPOW>(front_consts<FT>(c), r_, T_k, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
                 // sums of warm_rain_tendencies_2m — BMT:738-779.  The per-m³ number rates are added first and divided by ρ once (the
                 // reference divides each term: same value to rounding, five multiplies fewer); autoconversion's −2·dN_rai cancels
                 // against the same term inside cloud self-collection (CM2:499), so their sum is formed directly.
@@ -142,9 +136,6 @@ void sb2006_tendencies_kernel(const SbConsts<FT> c, const SbIn<FT> in,
                     else a[k] = x;
                 };
                 put(dq_lcl, o[0]); put(dn_lcl, o[1]); put(dq_rai, o[2]); put(dn_rai, o[3]); put(vt_n, o[4]); put(vt_m, o[5]);
-#if CMX_POINT_FENCE
-                __builtin_amdgcn_sched_barrier(0);
-#endif
             }
         }
         store_col<FT, VEC, NT>(out.dq_lcl, i, dq_lcl);

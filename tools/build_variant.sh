@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libcmx.so for same-box A/B runs (tools/ab_bench.sh):
-#   [LITCOEF_EXTRA="cmx_x.o …"] tools/build_variant.sh <tag> [extra hipcc flags, e.g. -DCMX_PHASE_CONSTS=0]   →  cloudmicrophysics.jl_amd/csrc/libcmx_<tag>.so
+#   [LITCOEF_EXTRA="cmx_x.o …"] tools/build_variant.sh <tag> [extra hipcc flags, e.g. -DCMX_TEND_BS=256]   →  cloudmicrophysics.jl_amd/csrc/libcmx_<tag>.so
 set -e
 tag=$1; shift
 src=$(cd "$(dirname "$0")/../cloudmicrophysics.jl_amd/csrc" && pwd)
