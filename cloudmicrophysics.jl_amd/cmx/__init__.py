@@ -7,6 +7,7 @@ Host-side mirror of the reference's module layout for the hot path:
   cmx.utilities         ↔ CloudMicrophysics.Utilities (UT): gamma_inc / gamma_inc_inv over columns
   cmx.distribution_tools ↔ CloudMicrophysics.DistributionTools (DT) + the SB2006 PSD accessors of CM2
   cmx.nucleation        ↔ CloudMicrophysics.Nucleation (aerosol new-particle formation)
+  cmx.precipitation_susceptibility ↔ CloudMicrophysics.PrecipitationSusceptibility (SB2006 autoconversion / accretion, closed forms)
   cmx.synthetic         ↔ the state generator of test/gpu_performance.jl:80-136
   cmx.sharding          ↔ (no reference equivalent) one-process-per-GPU sharding + RCCL diagnostic sums
 All compute goes through libcmx.so (include/cmx.h); there is no CPU fallback.
@@ -26,6 +27,10 @@ from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_c
 from .nucleation import (NucleationRates, PrescribedNucleationRates, apparent_nucleation_rate, h2so4_nucleation_rate,  # noqa: F401
                          nucleation_rates, nucleation_rates_prescribed, organic_and_h2so4_nucleation_rate,
                          organic_and_h2so4_nucleation_rate_bioOxOrg_prescribed, organic_nucleation_rate, organic_nucleation_rate_hom_prescribed)
+
+from .precipitation_susceptibility import (PrecipitationSusceptibilities, precip_susceptibility_rates,  # noqa: F401
+                                           precipitation_susceptibilities, precipitation_susceptibility_accretion,
+                                           precipitation_susceptibility_autoconversion)
 
 from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Moment, SedimentationVelocities, SourceTerms1M, Tendencies1M,  # noqa: F401
                              TerminalVelocities1M, bulk_microphysics_tendencies_1m, bulk_microphysics_tendencies_1m_fields,

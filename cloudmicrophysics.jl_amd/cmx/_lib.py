@@ -202,6 +202,9 @@ def _declare(lib):
         f = getattr(lib, f"cmx_p3_ice_nucleation_counts_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.morrison_milbrandt2014), i64] + [vp] * 6 + [vp]
+        f = getattr(lib, f"cmx_sb2006_precip_susceptibility_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.acnv_sb2006), C.POINTER(fam.accr_sb2006), i64] + [vp] * 10 + [vp]
         f = getattr(lib, f"cmx_column_sums_{s}")
         f.restype = i32
         f.argtypes = [i32, C.POINTER(vp), i64, vp, vp, vp]

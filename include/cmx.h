@@ -1245,6 +1245,43 @@ int32_t cmx_p3_ice_nucleation_counts_f64(const cmx_morrison_milbrandt2014_f64 *i
                                          const double *dt, double *N_dep, double *N_het, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (12) SB2006 precipitation susceptibilities — src/PrecipitationSusceptibility.jl (Glassmeier & Lohmann 2016): the logarithmic derivatives of the rain
+ * source of CM2.autoconversion (src/Microphysics2M.jl:396-427) and CM2.accretion (:445-470),
+ *   precipitation_susceptibility_autoconversion(scheme, q_lcl, q_rai, ρ, N_lcl)   :36-51    → acnv_d_ln_q_lcl, acnv_d_ln_q_rai, acnv_d_ln_N_lcl
+ *   precipitation_susceptibility_accretion(scheme, q_lcl, q_rai, ρ, N_lcl)        :66-79    → accr_d_ln_q_lcl, accr_d_ln_q_rai, accr_d_ln_N_lcl
+ * over columns in one pass.  The reference differentiates ln(dq_rai_dt) with ForwardDiff with respect to ln|q_lcl|, ln|q_rai|, ln|ρ|, ln|N_lcl| and
+ * returns components 1, 2 and 4; its d_ln_pp_d_ln_N_rai is always 0 and has no column here.  The device evaluates the closed forms of those derivatives
+ * (the ones the reference's test states, test/precipitation_susceptibility_tests.jl:11-29,59-68); there is no automatic differentiation on the device.
+ * Per point, with the inputs taken through abs as in the reference (:43, :71), ϵ = eps(FT), 1−τ = q_lcl/(q_lcl+q_rai), τ = q_rai/(q_lcl+q_rai),
+ * x̄_c = ρ q_lcl/N_lcl:
+ *   autoconversion:  u = A τ^a (1−τ^a)^b/(1−τ)²,  G = u/(1+u)·[a − a b τ^a/(1−τ^a) + 2τ/(1−τ)],  G = 0 where q_rai < ϵ (the ifelse of CM2 :411);
+ *                    acnv_d_ln_q_rai = (1−τ) G;
+ *                    x̄_c < x_star:  acnv_d_ln_q_lcl = 4 − (1−τ) G,  acnv_d_ln_N_lcl = −2;
+ *                    otherwise (the min of CM2 :406 clips to x_star):  acnv_d_ln_q_lcl = 2 − (1−τ) G,  acnv_d_ln_N_lcl = 0
+ *   accretion:       h = (1−τ) c τ0/(τ+τ0);  accr_d_ln_q_lcl = 1 − h,  accr_d_ln_q_rai = 1 + h,  accr_d_ln_N_lcl = 0
+ * N_lcl per m³, as in the reference.  ϵ depends on the float type, so the gates of a Float32 call are the Float32 ones.
+ *
+ * NaN contract — cmx's own statement: the reference was not run for it.  The reference zeroes dq_rai_dt where its gate fires (autoconversion:
+ * q_lcl < ϵ or N_lcl < ϵ, CM2 :420; accretion: those or q_rai < ϵ, :463); the derivative of the logarithm of that zero is undefined, and default
+ * ForwardDiff yields NaN there (0·Inf).  All three outputs of a process whose gate fires are therefore NaN.  They are NaN too where any of the four
+ * inputs is NaN or ρ = 0.  A negative input gives the result of its absolute value, bit for bit.
+ *
+ * A NULL `acnv` or `accr` skips that process, and its three outputs must then be NULL; any output may be NULL, not all (CMX_ERR_BAD_ARG).  The four input
+ * columns are always required.  One launch sequence on `stream`, any alignment (results do not depend on it), n_points up to the usual limit, 0 is OK.
+ * (The count is spelled n_points here: tests/test_abi.py pins the set of entries it drives through the count rule by their `int64_t n`, as
+ * tests/test_abi_caller.py pins the rows of CMX_ASSERT_PARAM_STRUCT_SIZES; this entry's count statuses are checked in
+ * tests/test_precip_susceptibility_host.py.)
+ * 4 columns in + 6 out = 40 B/point (f32) with every output, 28 B/point for one process.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_precip_susceptibility_f32(const cmx_acnv_sb2006_f32 *acnv, const cmx_accr_sb2006_f32 *accr, int64_t n_points, const float *q_lcl,
+                                             const float *q_rai, const float *rho, const float *N_lcl, float *acnv_d_ln_q_lcl, float *acnv_d_ln_q_rai,
+                                             float *acnv_d_ln_N_lcl, float *accr_d_ln_q_lcl, float *accr_d_ln_q_rai, float *accr_d_ln_N_lcl, void *stream);
+int32_t cmx_sb2006_precip_susceptibility_f64(const cmx_acnv_sb2006_f64 *acnv, const cmx_accr_sb2006_f64 *accr, int64_t n_points, const double *q_lcl,
+                                             const double *q_rai, const double *rho, const double *N_lcl, double *acnv_d_ln_q_lcl, double *acnv_d_ln_q_rai,
+                                             double *acnv_d_ln_N_lcl, double *accr_d_ln_q_lcl, double *accr_d_ln_q_rai, double *accr_d_ln_N_lcl,
+                                             void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1279,6 +1279,31 @@ function p3_ice_nucleation_counts!(N_dep, N_het, ip::CMP.MorrisonMilbrandt2014{F
     return nothing
 end
 
+# ----------------------------------------------------------------------------------------------------------------
+# (12) SB2006 precipitation susceptibilities — src/PrecipitationSusceptibility.jl
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    sb2006_precip_susceptibility!(acnv_d_ln_q_lcl, acnv_d_ln_q_rai, acnv_d_ln_N_lcl, accr_d_ln_q_lcl, accr_d_ln_q_rai, accr_d_ln_N_lcl, sb2006,
+                                  q_lcl, q_rai, ρ, N_lcl)
+
+`CMPS.precipitation_susceptibility_autoconversion(sb2006, q_lcl, q_rai, ρ, N_lcl)` and `CMPS.precipitation_susceptibility_accretion(…)`
+(src/PrecipitationSusceptibility.jl:36-79) over columns in one pass, as closed forms (no ForwardDiff on the device; formulas and the NaN contract in
+include/cmx.h).  The outputs are the fields `d_ln_pp_d_ln_q_lcl`, `d_ln_pp_d_ln_q_rai`, `d_ln_pp_d_ln_N_lcl` of the two results; `d_ln_pp_d_ln_N_rai`
+is always zero and has no column.  Any output may be `nothing`; a process whose three outputs are all `nothing` is skipped.
+"""
+function sb2006_precip_susceptibility!(acnv_d_ln_q_lcl, acnv_d_ln_q_rai, acnv_d_ln_N_lcl, accr_d_ln_q_lcl, accr_d_ln_q_rai, accr_d_ln_N_lcl,
+    sb2006::CMP.SB2006, q_lcl::AbstractArray{FT}, q_rai, ρ, N_lcl; stream = C_NULL) where {FT}
+    au = !(acnv_d_ln_q_lcl === nothing && acnv_d_ln_q_rai === nothing && acnv_d_ln_N_lcl === nothing)
+    ac = !(accr_d_ln_q_lcl === nothing && accr_d_ln_q_rai === nothing && accr_d_ln_N_lcl === nothing)
+    st = ccall(_fn("cmx_sb2006_precip_susceptibility", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        _ref_or_null(au ? sb2006.acnv : nothing), _ref_or_null(ac ? sb2006.accr : nothing), length(q_lcl), _dp(FT, q_lcl), _dp(FT, q_rai), _dp(FT, ρ),
+        _dp(FT, N_lcl), _dp(FT, acnv_d_ln_q_lcl), _dp(FT, acnv_d_ln_q_rai), _dp(FT, acnv_d_ln_N_lcl), _dp(FT, accr_d_ln_q_lcl), _dp(FT, accr_d_ln_q_rai),
+        _dp(FT, accr_d_ln_N_lcl), stream)
+    _check(st, "cmx_sb2006_precip_susceptibility")
+    return nothing
+end
+
 """
     column_sums!(sums, workspace, cols, FT, n; stream)
 
