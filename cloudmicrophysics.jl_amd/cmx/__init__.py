@@ -8,6 +8,7 @@ Host-side mirror of the reference's module layout for the hot path:
   cmx.distribution_tools ↔ CloudMicrophysics.DistributionTools (DT) + the SB2006 PSD accessors of CM2
   cmx.nucleation        ↔ CloudMicrophysics.Nucleation (aerosol new-particle formation)
   cmx.precipitation_susceptibility ↔ CloudMicrophysics.PrecipitationSusceptibility (SB2006 autoconversion / accretion, closed forms)
+  cmx.parcel            ↔ the reference's parcel/ (adiabatic parcel model): run_parcel / parcel_model over an ensemble, the time loop on the device
   cmx.synthetic         ↔ the state generator of test/gpu_performance.jl:80-136
   cmx.sharding          ↔ (no reference equivalent) one-process-per-GPU sharding + RCCL diagnostic sums
 All compute goes through libcmx.so (include/cmx.h); there is no CPU fallback.
@@ -31,6 +32,9 @@ from .nucleation import (NucleationRates, PrescribedNucleationRates, apparent_nu
 from .precipitation_susceptibility import (PrecipitationSusceptibilities, precip_susceptibility_rates,  # noqa: F401
                                            precipitation_susceptibilities, precipitation_susceptibility_accretion,
                                            precipitation_susceptibility_autoconversion)
+
+from . import parcel  # noqa: F401
+from .parcel import ParcelSolution, ParcelTendencies, parcel_params, parcel_tendencies, run_parcel  # noqa: F401
 
 from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Moment, SedimentationVelocities, SourceTerms1M, Tendencies1M,  # noqa: F401
                              TerminalVelocities1M, bulk_microphysics_tendencies_1m, bulk_microphysics_tendencies_1m_fields,

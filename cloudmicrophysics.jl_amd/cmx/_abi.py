@@ -72,6 +72,43 @@ MP1M_SOURCE_COLUMNS = (
 )
 CMX_MP1M_NSRC = len(MP1M_SOURCE_COLUMNS)
 
+# the parcel model (include/cmx.h §13): one field of the flags word per member of the reference's parcel_params
+CMX_PARCEL_AERO_ACT = 1 << 0
+CMX_PARCEL_DEP_MASK = 7 << 4
+CMX_PARCEL_DEP_MOHLER_AF = 1 << 4
+CMX_PARCEL_DEP_MOHLER_RATE = 2 << 4
+CMX_PARCEL_DEP_ABDINM = 3 << 4
+CMX_PARCEL_DEP_P3 = 4 << 4
+CMX_PARCEL_HET_MASK = 7 << 8
+CMX_PARCEL_HET_ABIFM = 1 << 8
+CMX_PARCEL_HET_P3 = 2 << 8
+CMX_PARCEL_HET_FROSTENBERG_RANDOM = 3 << 8
+CMX_PARCEL_HET_FROSTENBERG_MEAN = 4 << 8
+CMX_PARCEL_HET_FROSTENBERG_STOCHASTIC = 5 << 8
+CMX_PARCEL_HOM_MASK = 3 << 12
+CMX_PARCEL_HOM_ABHOM = 1 << 12
+CMX_PARCEL_HOM_P3 = 2 << 12
+CMX_PARCEL_COND_MASK = 3 << 16
+CMX_PARCEL_COND_CONDENSATION = 1 << 16
+CMX_PARCEL_COND_NONEQ_SIMPLE = 2 << 16
+CMX_PARCEL_COND_NONEQ = 3 << 16
+CMX_PARCEL_DEPGROWTH_MASK = 3 << 20
+CMX_PARCEL_DEPGROWTH_DEPOSITION = 1 << 20
+CMX_PARCEL_DEPGROWTH_NONEQ_SIMPLE = 2 << 20
+CMX_PARCEL_DEPGROWTH_NONEQ = 3 << 20
+CMX_PARCEL_LIQ_MASK = 3 << 24
+CMX_PARCEL_LIQ_GAMMA = 1 << 24
+CMX_PARCEL_LIQ_MONODISPERSE_MIX = 2 << 24
+CMX_PARCEL_ICE_GAMMA = 1 << 26
+CMX_PARCEL_PRESCRIBED_THERMODYNAMICS = 1 << 28
+CMX_PARCEL_NSTATE = 9
+CMX_PARCEL_NCOEF = 6
+CMX_PARCEL_NPROC = 6
+CMX_PARCEL_MAX_STEPS_PER_LAUNCH = 256
+PARCEL_STATE_COLUMNS = ("S_l", "p_air", "T", "q_vap", "q_liq", "q_ice", "N_aer", "N_liq", "N_ice")
+PARCEL_PROCESS_COLUMNS = ("dN_liq_act", "dN_ice_dep", "dN_ice_imm", "dN_ice_hom", "dq_liq_ce", "dq_ice_ds")
+PARCEL_COEFFICIENT_COLUMNS = ("deposition_m", "deposition_c", "ABIFM_m", "ABIFM_c", "linear_c1", "linear_c2")
+
 CMX_OK = 0
 CMX_ERR_BAD_ARG = -1
 CMX_ERR_HIP = -2
@@ -204,6 +241,12 @@ def _family(ft, sfx):
         ("vel_rain", ns.chen2022_rain_vel), ("vel_ice", ns.chen2022_ice_vel), ("cloud_pdf", ns.cloud_pdf_sb2006),
         ("rain_pdf", ns.rain_pdf_sb2006), ("ice_nucleation", ns.frostenberg2023), ("rain_freezing", ns.rain_freezing),
         ("tau_act", ft), ("quad", ns.quadrature)])
+    # ---- the parcel model (parcel/ParcelModel.jl:12-43)
+    ns.parcel_params = _struct(f"cmx_parcel_params_{sfx}", [
+        ("tps", ns.thermo), ("aps", ns.air_properties), ("aap", ns.aerosol_activation_params), ("homogeneous", ns.koop2000),
+        ("deposition", ns.mohler2006), ("p3", ns.morrison_milbrandt2014), ("ip", ns.frostenberg2023), ("aerosol_abifm", ns.abifm_dust),
+        ("aerosol_deposition", ns.deposition_dust), ("aerosol_mohler", ns.mohler_dust)] + s(
+        "const_dt", "r_nuc", "A_aer", "aero_sigma_g", "aero_N", "aero_M", "aero_kappa", "grav", "rho_w", "rho_i", "tau_relax_liq", "tau_relax_ice"))
     return ns
 
 

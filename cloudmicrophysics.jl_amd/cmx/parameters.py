@@ -956,6 +956,14 @@ def Sulfate(FT):
     return _AerosolSpecies(_td(FT), "sulfate")
 
 
+class WaterProperties:
+    """CMP.WaterProperties(FT): ρw, ρi (src/parameters/Water.jl) — the two densities the parcel model reads."""
+
+    def __init__(self, FT):
+        td = _td(FT)
+        self.rho_w, self.rho_i = td["density_liquid_water"], td["density_ice_water"]
+
+
 def rain_vel_params(FT):
     """Both rain terminal-velocity parameter sets in the C layout `cmx_rain_vel`."""
     td = _td(FT)

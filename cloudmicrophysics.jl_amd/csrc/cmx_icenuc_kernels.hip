@@ -20,78 +20,12 @@
 #include <cmath>
 #include <type_traits>
 
+#include "cmx_icenuc.hpp"
 #include "cmx_launch.hpp"
 #include "cmx_math.hpp"
 #include "cmx_lean_eval.hpp"
 
 namespace cmx {
-
-template <typename FT> struct IceNucConsts {
-    // log2 a_w_ice(T) = d0 + da·log2(T/T_tr) + db·(1/T_tr − 1/T)
-    FT aw_d0, aw_da, aw_db, inv_T_tr;
-    // log2 p_sat,liq(T) = c0 + a·log2(T/T_tr) + b·(1/T_tr − 1/T)   (a_w_eT)
-    FT ps_c0, ps_a, ps_b;
-    FT abifm_m_l2, abifm_c_l2;        // (m Δ + c + 4)·log2(10)
-    double c1, c2, c3, c4;            // Koop cubic, evaluated in double
-    FT lin_c1_l2, lin_c2_l2;          // (linear_c2 Δ + linear_c1 + 6)·log2(10)
-    FT d_min, d_max;
-    FT l2_four_pi, l2_four_thirds_pi;
-    // H2SO4 solution (Common.jl:188-220): log2 p_sol[Pa] = hp1(x) + hp2(x)/T,  hp1 = Σ hp1[m] x^m (m ≤ 3), hp2 = Σ hp2[m] x^m (m ≤ 2)
-    FT hp1[4], hp2[3];
-};
-
-template <typename FT, typename HS> static void add_h2so4_consts(IceNucConsts<FT> &c, const HS &h) {
-    const double l2e = 1.4426950408889634074, w2 = h.w_2;
-    c.hp1[0] = (FT)((double)h.c1 * l2e + std::log2(100.0));   // ·100: mbar → Pa
-    c.hp1[1] = (FT)(-(double)h.c2 * l2e);
-    c.hp1[2] = (FT)((double)h.c3 * w2 * l2e);                  // c3 x w_h, w_h = w_2 x
-    c.hp1[3] = (FT)(-(double)h.c4 * w2 * w2 * l2e);            // −c4 x w_h²
-    c.hp2[0] = (FT)((double)h.c5 * l2e);
-    c.hp2[1] = (FT)((double)h.c6 * l2e);
-    c.hp2[2] = (FT)(-(double)h.c7 * w2 * l2e);                 // −c7 x w_h
-}
-// log2 of CO.H2SO4_soln_saturation_vapor_pressure(prs, x, T) [Pa]
-template <typename FT> __device__ __forceinline__ FT l2_p_sol_dev(const IceNucConsts<FT> &c, FT x, FT inv_T) {
-    using M = Math<FT>;
-    const FT p1 = M::fma(M::fma(M::fma(c.hp1[3], x, c.hp1[2]), x, c.hp1[1]), x, c.hp1[0]);
-    const FT p2 = M::fma(M::fma(c.hp2[2], x, c.hp2[1]), x, c.hp2[0]);
-    return M::fma(p2, inv_T, p1);
-}
-template <typename FT> __device__ __forceinline__ FT l2_p_sat_liq_dev(const IceNucConsts<FT> &c, FT T, FT inv_T) {
-    using M = Math<FT>;
-    return M::fma(c.ps_a, M::log2(T * c.inv_T_tr), M::fma(c.ps_b, c.inv_T_tr - inv_T, c.ps_c0));
-}
-
-template <typename FT, typename TH, typename DU, typename KO>
-static IceNucConsts<FT> make_icenuc_consts(const TH &tp, const DU *dust, const KO *koop) {
-    IceNucConsts<FT> c{};
-    const double l2e = 1.4426950408889634074, l2_10 = 3.3219280948873623479, pi = 3.14159265358979323846;
-    const double Rv = tp.R_v, Ttr = tp.T_triple, T0 = tp.T_0;
-    const double dcp_l = (double)tp.cp_v - (double)tp.cp_l, dcp_i = (double)tp.cp_v - (double)tp.cp_i;
-    const double a_l = dcp_l / Rv, a_i = dcp_i / Rv;
-    const double b_l = ((double)tp.LH_v0 - dcp_l * T0) / Rv * l2e, b_i = ((double)tp.LH_s0 - dcp_i * T0) / Rv * l2e;
-    c.aw_d0 = (FT)0;                                   // same triple-point pressure for both phases
-    c.aw_da = (FT)(a_i - a_l);
-    c.aw_db = (FT)(b_i - b_l);
-    c.inv_T_tr = (FT)(1.0 / Ttr);
-    c.ps_c0 = (FT)std::log2((double)tp.press_triple);
-    c.ps_a = (FT)a_l;
-    c.ps_b = (FT)b_l;
-    if (dust) {
-        c.abifm_m_l2 = (FT)((double)dust->ABIFM_m * l2_10);
-        c.abifm_c_l2 = (FT)(((double)dust->ABIFM_c + 4.0) * l2_10);
-    }
-    if (koop) {
-        c.c1 = koop->c1; c.c2 = koop->c2; c.c3 = koop->c3; c.c4 = koop->c4;
-        c.lin_c1_l2 = (FT)(((double)koop->linear_c1 + 6.0) * l2_10);
-        c.lin_c2_l2 = (FT)((double)koop->linear_c2 * l2_10);
-        c.d_min = (FT)koop->delta_a_w_min;
-        c.d_max = (FT)koop->delta_a_w_max;
-    }
-    c.l2_four_pi = (FT)std::log2(4.0 * pi);
-    c.l2_four_thirds_pi = (FT)std::log2(4.0 / 3.0 * pi);
-    return c;
-}
 
 template <typename FT> struct IceNucIO {
     const FT *T, *a_w, *r;
@@ -99,10 +33,6 @@ template <typename FT> struct IceNucIO {
     unsigned long long *n_err;
 };
 
-template <typename FT> __device__ __forceinline__ FT a_w_ice_dev(const IceNucConsts<FT> &c, FT T, FT inv_T) {
-    using M = Math<FT>;
-    return M::exp2(M::fma(c.aw_da, M::log2(T * c.inv_T_tr), M::fma(c.aw_db, c.inv_T_tr - inv_T, c.aw_d0)));
-}
 
 // RATES_ONLY: only the per-droplet rates J·4πr² / J·4⁄3πr³ are requested (the BASELINE configuration): the two exp2 for the bare
 // rate coefficients are then dead code — as a compile-time fact (with run-time nullable pointers they are always evaluated)
@@ -130,11 +60,11 @@ __global__ __launch_bounds__(kBlock) void ice_nucleation_kernel(const IceNucCons
             const FT inv_T = M::rcp(T[k]);
             if constexpr (FROM_X) aw[k] = M::exp2(l2_p_sol_dev<FT>(c, aw[k], inv_T) - l2_p_sat_liq_dev<FT>(c, T[k], inv_T));   // a_w_xT  Common.jl:235-246
             d[k] = aw[k] - a_w_ice_dev<FT>(c, T[k], inv_T);                        // Δa_w
-            const FT l2_jh = M::fma(c.abifm_m_l2, d[k], c.abifm_c_l2);            // ABIFM_J  IceNucleation.jl:124-134
+            const FT l2_jh = l2_activity_J_dev<FT>(c.abifm_m_l2, c.abifm_c_l2, d[k]);   // ABIFM_J  IceNucleation.jl:124-134
             FT l2_jo;
             bool ok = true;
             if constexpr (LINEAR) {
-                l2_jo = M::fma(c.lin_c2_l2, d[k], c.lin_c1_l2);                   // homogeneous_J_linear :581-584
+                l2_jo = l2_activity_J_dev<FT>(c.lin_c2_l2, c.lin_c1_l2, d[k]);         // homogeneous_J_linear :581-584
             } else {
                 const double dd = (double)d[k];
                 const double logJ = __builtin_fma(dd, __builtin_fma(dd, __builtin_fma(dd, c.c4, -c.c3), c.c2), c.c1);
@@ -189,7 +119,7 @@ __global__ __launch_bounds__(kBlock) void water_activity_kernel(const IceNucCons
     const FT T = io.T[i], inv_T = M::rcp(T);
     if (io.a_w_ice) io.a_w_ice[i] = a_w_ice_dev<FT>(c, T, inv_T);                  // Common.jl:267-271
     if (io.a_w_eT) {                                                               // Common.jl:250-253
-        const FT l2_ps = M::fma(c.ps_a, M::log2(T * c.inv_T_tr), M::fma(c.ps_b, c.inv_T_tr - inv_T, c.ps_c0));
+        const FT l2_ps = l2_p_sat_liq_dev<FT>(c, T, inv_T);
         io.a_w_eT[i] = io.e[i] * M::exp2(-l2_ps);
     }
 }
@@ -249,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void p3_het_nucleation_kernel(const IceNucC
     if (i >= n) return;
     const FT Ti = T[i];
     const FT d = RH[i] - a_w_ice_dev<FT>(c, Ti, M::rcp(Ti));
-    const FT J = M::exp2(M::fma(c.abifm_m_l2, d, c.abifm_c_l2));              // ABIFM_J  IceNucleation.jl:124-134 [1/m²/s]
+    const FT J = activity_J_dev<FT>(c.abifm_m_l2, c.abifm_c_l2, d);            // ABIFM_J  IceNucleation.jl:124-134 [1/m²/s]
     const FT JA = (J - J == FT(0)) ? J * FT(1e-10) : FT(0);                    // isfinite(J) ? J·A_aer : 0
     if (dNdt) dNdt[i] = M::max(FT(0), JA * N_lcl[i]);
     if (dLdt) dLdt[i] = M::max(FT(0), JA * q_lcl[i] * rho[i]);
@@ -284,7 +214,6 @@ __global__ __launch_bounds__(kBlock) void h2so4_solution_kernel(const IceNucCons
 }
 
 // CMI_het.dust_activated_number_fraction / MohlerDepositionRate — IceNucleation.jl:44-79
-template <typename FT> struct MohlerConsts { FT S_i_max, T_thr, S0_warm, S0_cold, a_warm_l2e, a_cold_l2e, a_warm, a_cold; };
 template <typename FT>
 __global__ __launch_bounds__(kBlock) void mohler_deposition_kernel(const MohlerConsts<FT> c, const FT *__restrict__ S_i, const FT *__restrict__ T,
                                                                   const FT *__restrict__ dSi_dt, const FT *__restrict__ N_aer,
@@ -299,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void mohler_deposition_kernel(const MohlerC
         const bool warm = T[i] > c.T_thr;
         bad = !(Si < c.S_i_max);                                  // the reference's @assert Si < ip.Sᵢ_max
         if (act_frac) {
-            const FT f = M::max(FT(0), M::exp2((warm ? c.a_warm_l2e : c.a_cold_l2e) * (Si - (warm ? c.S0_warm : c.S0_cold))) - FT(1));
+            const FT f = mohler_activated_fraction_dev<FT>(c, Si, warm);
             act_frac[i] = bad ? M::nan() : f;
         }
         if (dep_rate) {
@@ -318,11 +247,10 @@ template <typename FT>
 __global__ __launch_bounds__(kBlock) void deposition_J_kernel(const FT m_l2, const FT c_l2, const FT *__restrict__ d, FT *__restrict__ J, const int64_t n) {
     Math<FT>::prepare();
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) J[i] = Math<FT>::exp2(Math<FT>::fma(m_l2, d[i], c_l2));
+    if (i < n) J[i] = activity_J_dev<FT>(m_l2, c_l2, d[i]);
 }
 
 // CMI_het.INP_concentration_frequency — IceNucleation.jl:219-226 with INP_concentration_mean :250-253
-template <typename FT> struct InpFreqConsts { FT T_freeze, b10, log_a, ln2, inv_2s2_l2e, inv_norm; };
 template <typename FT>
 __global__ __launch_bounds__(kBlock) void inp_frequency_kernel(const InpFreqConsts<FT> c, const FT *__restrict__ INPC, const FT *__restrict__ T,
                                                               FT *__restrict__ freq, const int64_t n) {
@@ -331,8 +259,7 @@ __global__ __launch_bounds__(kBlock) void inp_frequency_kernel(const InpFreqCons
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const FT Ti = T[i];
-    const FT Tc = M::min(Ti - c.T_freeze, FT(0));
-    const FT mu = M::fma(FT(9) * c.ln2, M::log2(-(c.b10 * Tc)), -c.log_a);          // 9 log(−b T_c/10) − log a
+    const FT mu = inp_concentration_mean_dev<FT>(c, Ti);
     const FT dl = M::fma(c.ln2, M::log2(INPC[i]), -mu);                              // log(INPC) − μ
     const FT f = M::exp2(-(dl * dl) * c.inv_2s2_l2e) * c.inv_norm;                   // exp(−(…)²/2σ²)/√(2πσ²)
     freq[i] = Ti >= c.T_freeze ? FT(0) : f;
@@ -355,9 +282,7 @@ static int32_t mohler_entry(const DU *dust, const IP *ip, int64_t n, const FT *S
     if (!dust || !ip || (!act_frac && !dep_rate)) return CMX_ERR_BAD_ARG;
     CMX_TRY_COUNT(n);
     if (!S_i || !T || (dep_rate && (!dSi_dt || !N_aer))) return CMX_ERR_BAD_ARG;
-    const double l2e = 1.4426950408889634074;
-    const MohlerConsts<FT> c{(FT)ip->S_i_max, (FT)ip->T_thr, (FT)dust->S0_warm, (FT)dust->S0_cold, (FT)((double)dust->a_warm * l2e),
-                             (FT)((double)dust->a_cold * l2e), (FT)dust->a_warm, (FT)dust->a_cold};
+    const MohlerConsts<FT> c = make_mohler_consts<FT>(*dust, *ip);
     launch<kBlock>(mohler_deposition_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream),
                    c, S_i, T, dSi_dt, N_aer, act_frac, dep_rate, reinterpret_cast<unsigned long long *>(n_err), n);
     return launched();
@@ -375,9 +300,7 @@ template <typename FT, typename IP> static int32_t inp_frequency_entry(const IP 
     if (!ip) return CMX_ERR_BAD_ARG;
     CMX_TRY_COUNT(n);
     if (!INPC || !T || !freq) return CMX_ERR_BAD_ARG;
-    const double l2e = 1.4426950408889634074, pi = 3.14159265358979323846, two_s2 = 2.0 * (double)ip->sigma * (double)ip->sigma;
-    const InpFreqConsts<FT> c{(FT)ip->T_freeze, (FT)((double)ip->b / 10.0), (FT)ip->log_a, (FT)0.69314718055994530942, (FT)(l2e / two_s2),
-                              (FT)(1.0 / std::sqrt(pi * two_s2))};
+    const InpFreqConsts<FT> c = make_inp_consts<FT>(*ip);
     launch<kBlock>(inp_frequency_kernel<FT>, n, reinterpret_cast<hipStream_t>(stream), c, INPC, T, freq, n);
     return launched();
 }

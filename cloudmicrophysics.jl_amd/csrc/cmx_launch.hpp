@@ -75,6 +75,15 @@ inline int32_t count_limit_status(int64_t n) { return n < 0 ? CMX_ERR_BAD_ARG : 
         if ((n) == 0) return CMX_OK;                                              \
     } while (0)
 
+// Steps of ONE launch of the parcel-run kernel (cmx_parcel_kernels.hip); cmx_parcel_run_* splits a longer integration into consecutive launches on
+// the caller's stream, which is exact: the nine state values pass through memory between launches as they are.  Every other kernel here finishes in
+// milliseconds whatever its arguments; this one loops n_steps times per lane, and a launch that runs for seconds holds the device against everything
+// else queued on it.  256 steps, from the timing of tools/time_parcel.py on an MI355X (1e6 parcels, 600 steps, median of 5): one 256-step launch takes
+// 1.4 ms (Float32, every option off), 1.9 ms (Float32, ABIFM + Condensation + Deposition), 3.4 ms and 5.0 ms (Float64, the same two), i.e. 5.3 / 7.4 /
+// 13.2 / 19.6 ps per parcel-step, linear in the parcels; the listing (626 / 1539 static VALU instructions with every option's branch counted,
+// tools/isa_cost.py) had put it at 4 / 11 ms.  The split costs one read and write of the state per launch, 0.03–0.06 ms of the above.
+constexpr int kParcelMaxStepsPerLaunch = CMX_PARCEL_MAX_STEPS_PER_LAUNCH;
+
 // Workgroups for `lanes` lanes at `bs` each.  launch() passes at most kMaxPoints lanes (the count rule) at bs ≥ 16, which stays within HIP's
 // 2^31 − 1 workgroups in x.
 inline int64_t tile_grid(int64_t lanes, int64_t bs) { return (lanes + bs - 1) / bs; }

@@ -349,7 +349,27 @@ typedef enum cmx_status {
         cmx_rain_freezing_##SFX rain_freezing;                                                 \
         FT tau_act;                                                                            \
         cmx_quadrature_##SFX quad;                                                             \
-    } cmx_p3_ice_params_##SFX;
+    } cmx_p3_ice_params_##SFX;                                                                 \
+    /* parcel_params — parcel/ParcelModel.jl:12-43 — as the constructors of run_parcel read it  */ \
+    /* (:230-366): tps, aps, aap, ips.homogeneous / .deposition / .p3, ip, the coefficients of   */ \
+    /* the `aerosol` member (ABIFM, deposition_J, Mohler: zero-filled where the aerosol type has */ \
+    /* none), then the scalars.  grav = TDI.grav(tps), rho_w / rho_i = wps.ρw / wps.ρi,          */ \
+    /* aero_N = pp.Nₐ, aero_M / aero_kappa = aerosol.M / aerosol.κ (AeroAct),                    */ \
+    /* tau_relax_liq / tau_relax_ice = MNE.τ_relax(liquid) / (ice) of the NonEq _simple options  */ \
+    typedef struct cmx_parcel_params_##SFX {                                                   \
+        cmx_thermo_##SFX tps;                                                                  \
+        cmx_air_properties_##SFX aps;                                                          \
+        cmx_aerosol_activation_params_##SFX aap;                                               \
+        cmx_koop2000_##SFX homogeneous;                                                        \
+        cmx_mohler2006_##SFX deposition;                                                       \
+        cmx_morrison_milbrandt2014_##SFX p3;                                                   \
+        cmx_frostenberg2023_##SFX ip;                                                          \
+        cmx_abifm_dust_##SFX aerosol_abifm;                                                    \
+        cmx_deposition_dust_##SFX aerosol_deposition;                                          \
+        cmx_mohler_dust_##SFX aerosol_mohler;                                                  \
+        FT const_dt, r_nuc, A_aer, aero_sigma_g, aero_N, aero_M, aero_kappa;                   \
+        FT grav, rho_w, rho_i, tau_relax_liq, tau_relax_ice;                                   \
+    } cmx_parcel_params_##SFX;
 
 #define CMX_ARG_MAX_MODES 8
 #define CMX_QUAD_MAX 128
@@ -434,6 +454,12 @@ CMX_ASSERT_PARAM_STRUCT_SIZES(double, f64)
     CMX_STATIC_ASSERT((sizeof(cmx_mixed_nucleation_##SFX) == 3 * sizeof(FT)), "cmx_mixed_nucleation");
 CMX_ASSERT_NUCLEATION_STRUCT_SIZES(float, f32)
 CMX_ASSERT_NUCLEATION_STRUCT_SIZES(double, f64)
+/* … and for the parcel-model struct: 13 + 3 + 12 + 8 + 2 + 6 + 5 + 2 + 2 + 4 nested values and 12 scalars (a row of its own spelling: the rows of the
+ * two lists above are pinned by tests/test_abi_caller.py and tests/test_nucleation_host.py; tests/test_parcel_host.py checks this one) */
+#define CMX_ASSERT_PARCEL_STRUCT_SIZES(FT, SFX) \
+    CMX_STATIC_ASSERT( sizeof(cmx_parcel_params_##SFX) == 69 * sizeof(FT) , "cmx_parcel_params");
+CMX_ASSERT_PARCEL_STRUCT_SIZES(float, f32)
+CMX_ASSERT_PARCEL_STRUCT_SIZES(double, f64)
 
 /* ---------------------------------------------------------------------------
  * Library / device queries
@@ -1280,6 +1306,104 @@ int32_t cmx_sb2006_precip_susceptibility_f64(const cmx_acnv_sb2006_f64 *acnv, co
                                              const double *q_rai, const double *rho, const double *N_lcl, double *acnv_d_ln_q_lcl, double *acnv_d_ln_q_rai,
                                              double *acnv_d_ln_N_lcl, double *accr_d_ln_q_lcl, double *accr_d_ln_q_rai, double *accr_d_ln_N_lcl,
                                              void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (13) The adiabatic parcel model — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl, ParcelCommon.jl — over an ENSEMBLE of parcels,
+ * one parcel per lane: calibration ensembles (test/ice_nucleation_calibration.jl, papers/ice_nucleation_2024/calibration.jl) and the sweeps over updraft
+ * speed and initial state of parcel/Example_*.jl.
+ *   cmx_parcel_tendencies_*   the right-hand side parcel_model(dY, Y, p, t) (ParcelModel.jl:54-187) as a pointwise map
+ *   cmx_parcel_run_*          run_parcel (:230-366): n_steps forward-Euler steps Y ← Y + const_dt·dY inside ONE kernel (ODE.Euler with dt = const_dt is this
+ *                             recurrence), the nine state values in registers from the first step to the last
+ * State columns, in the reference's order: S_l, p_air, T, q_vap, q_liq, q_ice, N_aer, N_liq, N_ice (rows 1–9 of Y), plus the updraft speed w per parcel.
+ * Row 10, ln_INPC, matters to the stochastic Frostenberg option only, which is not built: it is no column of this ABI.
+ *
+ * Options: `flags` holds one field per member of parcel_params, the values below; every other parameter is in cmx_parcel_params_*.  Not built, refused
+ * with CMX_ERR_UNSUPPORTED: deposition MohlerRate (it reads dY[1] before the call has written it, ParcelTendencies.jl:73: its value depends on the
+ * solver's buffer reuse), heterogeneous Frostenberg_random / Frostenberg_stochastic (random draws), NonEq_Condensation / NonEq_Deposition (a mock
+ * 1-moment parameter set), MonodisperseMix (two more state variables), prescribed_thermodynamics (AIDA profiles).  A value outside a field's list, or a
+ * bit outside every field, is CMX_ERR_BAD_ARG.
+ *
+ * Per-parcel coefficients: `coefficients` is NULL or an array of CMX_PARCEL_NCOEF column pointers (each NULL-able) that override, per parcel, the
+ * coefficient pair of the activity-based schemes — deposition_m, deposition_c (ABDINM), ABIFM_m, ABIFM_c (ABIFM), linear_c1, linear_c2 (ABHOM).  A NULL
+ * column means the struct's value for every parcel; a column filled with that value gives the same bits.
+ *
+ * Semantics kept from the reference: the clip of rows 4–9 only; the N == 0 || q == 0 branch of distribution_moments; the number sinks
+ * dq < 0 && 0 < q < 1e-6; r_act with its eps(FT) gates and min(1e-6, …); every min(…, N/const_dt) limiter; S_i ≥ S_i_max → AF = 0 (the reference
+ * also logs a warning there; the device does not report it).  eps(FT) is the float type's.  min / max propagate NaN as Julia's do, and a parcel with a
+ * NaN in any of its ten inputs (or in a coefficient it reads) has NaN in ALL its outputs — the library's NaN rule; the reference's own arithmetic
+ * carries a NaN only to the tendencies that read it.  Division by zero and overflow follow IEEE.
+ *
+ * cmx_parcel_tendencies: nine NULL-able tendency columns dY (same order as the state) and `process_rates`, NULL or an array of CMX_PARCEL_NPROC
+ * NULL-able columns: dN_liq_act, dN_ice_dep, dN_ice_imm, dN_ice_hom, dq_liq_ce, dq_ice_ds (cmx_parcel_process_column).  At least one output.
+ *
+ * cmx_parcel_run: `state_out` = nine columns, all required; each may be the matching input column (in place), no other overlap.  n_steps ≥ 0 steps of
+ * pp->const_dt.  `trajectory` is NULL or a buffer of (1 + n_steps / save_every) records × 9 variables × n_parcels values, layout
+ * [record][variable][parcel]: record 0 is the initial state, record j the state after j·save_every steps; NULL or save_every = 0 skips it.
+ * A run of a + b steps equals a run of a steps followed by a run of b steps on its result, bit for bit; the entry itself splits n_steps into launches of
+ * at most CMX_PARCEL_MAX_STEPS_PER_LAUNCH steps (cmx_launch.hpp states the launch time that cap corresponds to), all on `stream`, no host
+ * synchronisation: graph-capturable like every other entry.
+ *
+ * Status order: pp NULL / flags → BAD_ARG or UNSUPPORTED; n_parcels < 0 → BAD_ARG, > the point limit → UNSUPPORTED; n_steps < 0 or save_every < 0 →
+ * BAD_ARG; n_parcels = 0 → OK; then the columns.  (The count is spelled n_parcels: tests/test_abi.py pins the entries it drives by `int64_t n`.)
+ * ------------------------------------------------------------------------- */
+#define CMX_PARCEL_AERO_ACT                  (1u << 0)    /* aerosol_act = "AeroAct"                          ParcelTendencies.jl:20-41   */
+#define CMX_PARCEL_DEP_MASK                  (7u << 4)    /* deposition                                                                   */
+#define CMX_PARCEL_DEP_MOHLER_AF             (1u << 4)    /*   "MohlerAF"                                     :48-66                      */
+#define CMX_PARCEL_DEP_MOHLER_RATE           (2u << 4)    /*   "MohlerRate" — CMX_ERR_UNSUPPORTED             :68-90                      */
+#define CMX_PARCEL_DEP_ABDINM                (3u << 4)    /*   "ABDINM"                                       :92-105                     */
+#define CMX_PARCEL_DEP_P3                    (4u << 4)    /*   "P3_dep"                                       :107-113                    */
+#define CMX_PARCEL_HET_MASK                  (7u << 8)    /* heterogeneous                                                                */
+#define CMX_PARCEL_HET_ABIFM                 (1u << 8)    /*   "ABIFM"                                        :120-133                    */
+#define CMX_PARCEL_HET_P3                    (2u << 8)    /*   "P3_het"                                       :135-141                    */
+#define CMX_PARCEL_HET_FROSTENBERG_RANDOM    (3u << 8)    /*   "Frostenberg_random" — CMX_ERR_UNSUPPORTED     :143-154                    */
+#define CMX_PARCEL_HET_FROSTENBERG_MEAN      (4u << 8)    /*   "Frostenberg_mean"                             :156-162                    */
+#define CMX_PARCEL_HET_FROSTENBERG_STOCHASTIC (5u << 8)   /*   "Frostenberg_stochastic" — CMX_ERR_UNSUPPORTED :169-187                    */
+#define CMX_PARCEL_HOM_MASK                  (3u << 12)   /* homogeneous                                                                  */
+#define CMX_PARCEL_HOM_ABHOM                 (1u << 12)   /*   "ABHOM"                                        :194-205                    */
+#define CMX_PARCEL_HOM_P3                    (2u << 12)   /*   "P3_hom"                                       :207-213                    */
+#define CMX_PARCEL_COND_MASK                 (3u << 16)   /* condensation_growth                                                          */
+#define CMX_PARCEL_COND_CONDENSATION         (1u << 16)   /*   "Condensation"                                 :220-232                    */
+#define CMX_PARCEL_COND_NONEQ_SIMPLE         (2u << 16)   /*   "NonEq_Condensation_simple"                    :234-246                    */
+#define CMX_PARCEL_COND_NONEQ                (3u << 16)   /*   "NonEq_Condensation" — CMX_ERR_UNSUPPORTED     :248-276                    */
+#define CMX_PARCEL_DEPGROWTH_MASK            (3u << 20)   /* deposition_growth                                                            */
+#define CMX_PARCEL_DEPGROWTH_DEPOSITION      (1u << 20)   /*   "Deposition"                                   :283-296                    */
+#define CMX_PARCEL_DEPGROWTH_NONEQ_SIMPLE    (2u << 20)   /*   "NonEq_Deposition_simple"                      :298-311                    */
+#define CMX_PARCEL_DEPGROWTH_NONEQ           (3u << 20)   /*   "NonEq_Deposition" — CMX_ERR_UNSUPPORTED       :313-342                    */
+#define CMX_PARCEL_LIQ_MASK                  (3u << 24)   /* liq_size_distribution ("Monodisperse" = 0)       ParcelDistributions.jl      */
+#define CMX_PARCEL_LIQ_GAMMA                 (1u << 24)   /*   "Gamma"                                        :54-74                      */
+#define CMX_PARCEL_LIQ_MONODISPERSE_MIX      (2u << 24)   /*   "MonodisperseMix" — CMX_ERR_UNSUPPORTED        :25-52                      */
+#define CMX_PARCEL_ICE_GAMMA                 (1u << 26)   /* ice_size_distribution = "Gamma" ("Monodisperse" = 0)                         */
+#define CMX_PARCEL_PRESCRIBED_THERMODYNAMICS (1u << 28)   /* prescribed_thermodynamics = true — CMX_ERR_UNSUPPORTED                       */
+#define CMX_PARCEL_NSTATE 9
+#define CMX_PARCEL_NCOEF 6
+#define CMX_PARCEL_NPROC 6
+#define CMX_PARCEL_MAX_STEPS_PER_LAUNCH 256               /* == kParcelMaxStepsPerLaunch, cmx_launch.hpp                                  */
+typedef enum cmx_parcel_process_column {
+    CMX_PARCEL_PROC_DN_LIQ_ACT = 0,
+    CMX_PARCEL_PROC_DN_ICE_DEP = 1,
+    CMX_PARCEL_PROC_DN_ICE_IMM = 2,
+    CMX_PARCEL_PROC_DN_ICE_HOM = 3,
+    CMX_PARCEL_PROC_DQ_LIQ_CE = 4,
+    CMX_PARCEL_PROC_DQ_ICE_DS = 5
+} cmx_parcel_process_column;
+typedef enum cmx_parcel_coefficient_column {
+    CMX_PARCEL_COEF_DEPOSITION_M = 0,
+    CMX_PARCEL_COEF_DEPOSITION_C = 1,
+    CMX_PARCEL_COEF_ABIFM_M = 2,
+    CMX_PARCEL_COEF_ABIFM_C = 3,
+    CMX_PARCEL_COEF_LINEAR_C1 = 4,
+    CMX_PARCEL_COEF_LINEAR_C2 = 5
+} cmx_parcel_coefficient_column;
+int32_t cmx_parcel_tendencies_f32(const cmx_parcel_params_f32 *pp, uint32_t flags, int64_t n_parcels, const float *const *state, const float *w,
+                                  const float *const *coefficients, float *const *tendencies, float *const *process_rates, void *stream);
+int32_t cmx_parcel_tendencies_f64(const cmx_parcel_params_f64 *pp, uint32_t flags, int64_t n_parcels, const double *const *state, const double *w,
+                                  const double *const *coefficients, double *const *tendencies, double *const *process_rates, void *stream);
+int32_t cmx_parcel_run_f32(const cmx_parcel_params_f32 *pp, uint32_t flags, int64_t n_parcels, int64_t n_steps, int64_t save_every,
+                           const float *const *state, const float *w, const float *const *coefficients, float *const *state_out, float *trajectory,
+                           void *stream);
+int32_t cmx_parcel_run_f64(const cmx_parcel_params_f64 *pp, uint32_t flags, int64_t n_parcels, int64_t n_steps, int64_t save_every,
+                           const double *const *state, const double *w, const double *const *coefficients, double *const *state_out, double *trajectory,
+                           void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

@@ -124,6 +124,32 @@ const CMX_SNOW_SHAPE_OBLATE = UInt32(1)
 const CMX_SNOW_SHAPE_PROLATE = UInt32(2)
 const CMX_1M_SED_SNOW_OBLATE = UInt32(1) << 17
 const CMX_1M_SED_SNOW_PROLATE = UInt32(1) << 18
+const CMX_PARCEL_AERO_ACT = UInt32(1) << 0
+const CMX_PARCEL_DEP_MOHLER_AF = UInt32(1) << 4
+const CMX_PARCEL_DEP_MOHLER_RATE = UInt32(2) << 4
+const CMX_PARCEL_DEP_ABDINM = UInt32(3) << 4
+const CMX_PARCEL_DEP_P3 = UInt32(4) << 4
+const CMX_PARCEL_HET_ABIFM = UInt32(1) << 8
+const CMX_PARCEL_HET_P3 = UInt32(2) << 8
+const CMX_PARCEL_HET_FROSTENBERG_RANDOM = UInt32(3) << 8
+const CMX_PARCEL_HET_FROSTENBERG_MEAN = UInt32(4) << 8
+const CMX_PARCEL_HET_FROSTENBERG_STOCHASTIC = UInt32(5) << 8
+const CMX_PARCEL_HOM_ABHOM = UInt32(1) << 12
+const CMX_PARCEL_HOM_P3 = UInt32(2) << 12
+const CMX_PARCEL_COND_CONDENSATION = UInt32(1) << 16
+const CMX_PARCEL_COND_NONEQ_SIMPLE = UInt32(2) << 16
+const CMX_PARCEL_COND_NONEQ = UInt32(3) << 16
+const CMX_PARCEL_DEPGROWTH_DEPOSITION = UInt32(1) << 20
+const CMX_PARCEL_DEPGROWTH_NONEQ_SIMPLE = UInt32(2) << 20
+const CMX_PARCEL_DEPGROWTH_NONEQ = UInt32(3) << 20
+const CMX_PARCEL_LIQ_GAMMA = UInt32(1) << 24
+const CMX_PARCEL_LIQ_MONODISPERSE_MIX = UInt32(2) << 24
+const CMX_PARCEL_ICE_GAMMA = UInt32(1) << 26
+const CMX_PARCEL_PRESCRIBED_THERMODYNAMICS = UInt32(1) << 28
+const CMX_PARCEL_NSTATE = 9
+const CMX_PARCEL_NCOEF = 6
+const CMX_PARCEL_NPROC = 6
+const CMX_PARCEL_MAX_STEPS_PER_LAUNCH = 256
 const CMX_SB2006_NPROC = 19
 const CMX_MP1M_NSRC = 18
 const CMX_ARG_MAX_MODES = 8
@@ -1301,6 +1327,125 @@ function sb2006_precip_susceptibility!(acnv_d_ln_q_lcl, acnv_d_ln_q_rai, acnv_d_
         _dp(FT, N_lcl), _dp(FT, acnv_d_ln_q_lcl), _dp(FT, acnv_d_ln_q_rai), _dp(FT, acnv_d_ln_N_lcl), _dp(FT, accr_d_ln_q_lcl), _dp(FT, accr_d_ln_q_rai),
         _dp(FT, accr_d_ln_N_lcl), stream)
     _check(st, "cmx_sb2006_precip_susceptibility")
+    return nothing
+end
+
+# ----------------------------------------------------------------------------------------------------------------
+# (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
+# ----------------------------------------------------------------------------------------------------------------
+struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
+    tps::CmxThermo{FT}
+    aps::AP
+    aap::AA
+    homogeneous::KO
+    deposition::MO
+    p3::MM
+    ip::CmxFrostenberg{FT}
+    aerosol_abifm::CmxDust{FT}
+    aerosol_deposition::CmxDepositionDust{FT}
+    aerosol_mohler::CmxMohlerDust{FT}
+    const_dt::FT
+    r_nuc::FT
+    A_aer::FT
+    aero_sigma_g::FT
+    aero_N::FT
+    aero_M::FT
+    aero_kappa::FT
+    grav::FT
+    rho_w::FT
+    rho_i::FT
+    tau_relax_liq::FT
+    tau_relax_ice::FT
+end
+
+# the coefficient structs of the `aerosol` member: an aerosol type without the coefficients of a scheme has J = 10^(0·Δa_w − Inf) = 0 there, which is what
+# `CMI_het.ABIFM_J(::CMP.AerosolType, Δa_w)` and `CMI_het.deposition_J(::CMP.AerosolType, Δa_w)` return for it
+_parcel_abifm(::Type{FT}, d) where {FT} = hasproperty(d, :ABIFM_m) ? CmxDust(FT(d.ABIFM_m), FT(d.ABIFM_c)) : CmxDust(zero(FT), FT(-Inf))
+_parcel_deposition(::Type{FT}, d) where {FT} =
+    hasproperty(d, :deposition_m) ? CmxDepositionDust(FT(d.deposition_m), FT(d.deposition_c)) : CmxDepositionDust(zero(FT), FT(-Inf))
+_parcel_mohler(::Type{FT}, d) where {FT} =
+    hasproperty(d, :a_warm) ? CmxMohlerDust(FT(d.S₀_warm), FT(d.S₀_cold), FT(d.a_warm), FT(d.a_cold)) : CmxMohlerDust(zero(FT), zero(FT), zero(FT), zero(FT))
+_parcel_M(::Type{FT}, d) where {FT} = hasproperty(d, :M) ? FT(d.M) : zero(FT)
+_parcel_kappa(::Type{FT}, d) where {FT} = hasproperty(d, :κ) ? FT(d.κ) : zero(FT)
+
+const PARCEL_OPTION_BITS = (
+    aerosol_act = ("None" => UInt32(0), "AeroAct" => CMX_PARCEL_AERO_ACT),
+    deposition = ("None" => UInt32(0), "MohlerAF" => CMX_PARCEL_DEP_MOHLER_AF, "MohlerRate" => CMX_PARCEL_DEP_MOHLER_RATE,
+        "ABDINM" => CMX_PARCEL_DEP_ABDINM, "P3_dep" => CMX_PARCEL_DEP_P3),
+    heterogeneous = ("None" => UInt32(0), "ABIFM" => CMX_PARCEL_HET_ABIFM, "P3_het" => CMX_PARCEL_HET_P3,
+        "Frostenberg_random" => CMX_PARCEL_HET_FROSTENBERG_RANDOM, "Frostenberg_mean" => CMX_PARCEL_HET_FROSTENBERG_MEAN,
+        "Frostenberg_stochastic" => CMX_PARCEL_HET_FROSTENBERG_STOCHASTIC),
+    homogeneous = ("None" => UInt32(0), "ABHOM" => CMX_PARCEL_HOM_ABHOM, "P3_hom" => CMX_PARCEL_HOM_P3),
+    condensation_growth = ("None" => UInt32(0), "Condensation" => CMX_PARCEL_COND_CONDENSATION,
+        "NonEq_Condensation_simple" => CMX_PARCEL_COND_NONEQ_SIMPLE, "NonEq_Condensation" => CMX_PARCEL_COND_NONEQ),
+    deposition_growth = ("None" => UInt32(0), "Deposition" => CMX_PARCEL_DEPGROWTH_DEPOSITION,
+        "NonEq_Deposition_simple" => CMX_PARCEL_DEPGROWTH_NONEQ_SIMPLE, "NonEq_Deposition" => CMX_PARCEL_DEPGROWTH_NONEQ),
+    liq_size_distribution = ("Monodisperse" => UInt32(0), "Gamma" => CMX_PARCEL_LIQ_GAMMA, "MonodisperseMix" => CMX_PARCEL_LIQ_MONODISPERSE_MIX),
+    ice_size_distribution = ("Monodisperse" => UInt32(0), "Gamma" => CMX_PARCEL_ICE_GAMMA),
+)
+
+"""
+    parcel_flags(pp)
+
+The option word of `cmx_parcel_*` from the option strings of a `parcel_params` (parcel/ParcelModel.jl:12-43); an unknown string throws as
+`run_parcel` does.  Options the library does not build are encoded too: the entry refuses them with "unsupported request".
+"""
+function parcel_flags(pp)
+    bits = pp.prescribed_thermodynamics ? CMX_PARCEL_PRESCRIBED_THERMODYNAMICS : UInt32(0)
+    for (name, table) in pairs(PARCEL_OPTION_BITS)
+        value = getproperty(pp, name)
+        k = findfirst(p -> first(p) == value, table)
+        k === nothing && throw("Unrecognized $(name) option: $(value)")
+        bits |= last(table[k])
+    end
+    return bits
+end
+
+"""
+    pack_parcel(pp, FT; τ_relax_liquid, τ_relax_ice)
+
+`parcel_params{FT}` → `cmx_parcel_params_*` (69 FT), as the constructors of `run_parcel` read it.  The two relaxation timescales of the
+`NonEq_*_simple` options are `MNE.τ_relax(pp.liquid)` and `MNE.τ_relax(pp.ice)`.
+"""
+function pack_parcel(pp, ::Type{FT}; τ_relax_liquid = FT(10), τ_relax_ice = FT(10)) where {FT}
+    tps, ips, aer = pp.tps, pp.ips, pp.aerosol
+    return CmxParcelParams(CmxThermo(tps), pp.aps, pp.aap, ips.homogeneous, ips.deposition, ips.p3, CmxFrostenberg(pp.ip),
+        _parcel_abifm(FT, aer), _parcel_deposition(FT, aer), _parcel_mohler(FT, aer), FT(pp.const_dt), FT(pp.r_nuc), FT(pp.A_aer),
+        FT(pp.aero_σ_g), FT(pp.Nₐ), _parcel_M(FT, aer), _parcel_kappa(FT, aer), FT(TDP.grav(tps)), FT(pp.wps.ρw), FT(pp.wps.ρi),
+        FT(τ_relax_liquid), FT(τ_relax_ice))
+end
+
+"""
+    parcel_tendencies!(dY, process_rates, pp, flags, Y, w; coefficients = nothing, stream)
+
+`parcel_model(dY, Y, p, t)` (parcel/ParcelModel.jl:54-187) over an ensemble of parcels: `Y` = nine device columns Sₗ, p_air, T, qᵥ, qₗ, qᵢ, Nₐ, Nₗ, Nᵢ,
+`w` a column, `dY` nine columns (any may be `nothing`), `process_rates` six columns dNₗ_act, dNᵢ_dep, dNᵢ_imm, dNᵢ_hom, dqₗ_ce, dqᵢ_ds or `nothing`.
+`pp = pack_parcel(…)`, `flags = parcel_flags(…)`.  `coefficients` = six columns (or `nothing` each) overriding deposition_m, deposition_c, ABIFM_m,
+ABIFM_c, linear_c1, linear_c2 per parcel.
+"""
+function parcel_tendencies!(dY, process_rates, pp::CmxParcelParams, flags::UInt32, Y, w::AbstractArray{FT}; coefficients = nothing,
+    stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_parcel_tendencies", FT), Int32,
+        (Ptr{Cvoid}, UInt32, Int64, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pp), flags, length(w), _ptrs(FT, Y), _dp(FT, w), _opt_ptrs(FT, coefficients), _opt_ptrs(FT, dY), _opt_ptrs(FT, process_rates), stream)
+    _check(st, "cmx_parcel_tendencies")
+    return nothing
+end
+
+"""
+    run_parcel!(Y_out, trajectory, pp, flags, Y, w, n_steps; save_every = 0, coefficients = nothing, stream)
+
+`run_parcel(IC, t_0, t_end, pp)` (parcel/ParcelModel.jl:230-366: `ODE.Euler()`, `dt = const_dt`) over an ensemble: `n_steps = (t_end − t_0)/const_dt`
+forward-Euler steps inside one kernel, one parcel per lane.  `Y_out` = nine columns (each may be the matching column of `Y`); `trajectory` = `nothing`
+or a device array of `(1 + n_steps ÷ save_every) · 9 · n` values, layout [record][variable][parcel], record 0 = the initial state.
+"""
+function run_parcel!(Y_out, trajectory, pp::CmxParcelParams, flags::UInt32, Y, w::AbstractArray{FT}, n_steps::Integer; save_every::Integer = 0,
+    coefficients = nothing, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_parcel_run", FT), Int32,
+        (Ptr{Cvoid}, UInt32, Int64, Int64, Int64, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pp), flags, length(w), n_steps, save_every, _ptrs(FT, Y), _dp(FT, w), _opt_ptrs(FT, coefficients), _ptrs(FT, Y_out), _dp(FT, trajectory),
+        stream)
+    _check(st, "cmx_parcel_run")
     return nothing
 end
 
