@@ -217,9 +217,10 @@ def bulk_microphysics_tendencies_fields(scheme, mp, tps, rho, T, q_tot, q_lcl, n
     return r if aos else WarmRainTendencies2M(*r, None, None)
 
 
-def sb2006_process_rates(mp, tps, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, *, vel=SB2006VelType, stream=None):
+def sb2006_process_rates(mp, tps, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, *, vel=SB2006VelType, vel_params=None, stream=None):
     """The individual SB2006 process rates over columns — the reference's SB2006_2M_kernel
-    (test/gpu_tests.jl:220-235) + cond/evap (NonEq:117-140).  N_* are per m³ (CM2 convention)."""
+    (test/gpu_tests.jl:220-235) + cond/evap (NonEq:117-140).  N_* are per m³ (CM2 convention).
+    `vel_params` = a `cmx_rain_vel` struct with non-default fall-speed parameters (default: `parameters.rain_vel_params(FT)`)."""
     wr = _warm_rain(mp)
     cols = (q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T)
     ref = _check_cols(cols, ("q_tot", "q_lcl", "q_rai", "N_lcl", "N_rai", "rho", "T"))
@@ -233,7 +234,9 @@ def sb2006_process_rates(mp, tps, q_tot, q_lcl, q_rai, N_lcl, N_rai, rho, T, *, 
         outs[_abi.SB2006_PROCESS_COLUMNS.index("rain_vel_m")] = None
     arr = (C.c_void_p * _abi.CMX_SB2006_NPROC)(*[o.data_ptr() if o is not None else None for o in outs])
     flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | vflag
-    velp = rain_vel_params(fam.sfx) if vflag else None
+    velp = (vel_params if vel_params is not None else rain_vel_params(fam.sfx)) if vflag else None
+    if velp is not None and not isinstance(velp, fam.rain_vel):
+        raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
     _lib.call("cmx_sb2006_process_rates", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp) if velp is not None else None, flags,
               ref.numel(), *[_ptr(t) for t in cols], arr, stream=stream)
     return SB2006ProcessRates(*outs)
@@ -281,7 +284,7 @@ def cloud_terminal_velocity(pdf_c, vel, q_liq, rho, N_liq, *, stream=None) -> Cl
 ColumnTendencies2M = namedtuple("ColumnTendencies2M", ["dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "precip_flux"])
 
 
-def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, *, vel=SB2006VelType, cloud_vel=None,
+def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, *, vel=SB2006VelType, vel_params=None, cloud_vel=None,
                                     want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None,
                                     stream=None) -> ColumnTendencies2M:
     """SURVEY §8f-4 — the fused column step behind `cmx_sb2006_column_tendencies_sedimentation_*`: per column of `n_lev`
@@ -292,7 +295,8 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
 
     plus the host model's first-order upwind sedimentation flux divergence ∂χ/∂t += (F_{k+1} − F_k)/(ρ_k Δz_k), F = ρ χ w
     (the flux scheme is the host model's, not the reference's: include/cmx.h).  `inv_dz`: the n_lev values 1/Δz_k.
-    `cloud_vel` = parameters.StokesRegimeVelType(FT) adds cloud-droplet sedimentation of q_lcl / n_lcl."""
+    `cloud_vel` = parameters.StokesRegimeVelType(FT) adds cloud-droplet sedimentation of q_lcl / n_lcl; `vel_params` = a `cmx_rain_vel` struct
+    with non-default fall-speed parameters (default: `parameters.rain_vel_params(FT)`)."""
     wr = _warm_rain(mp)
     cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
     ref = _check_cols(cols, ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai"))
@@ -313,7 +317,9 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
     else:
         _check_cols([ref, *out[:4]], ["rho", *ColumnTendencies2M._fields[:4]])
     flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | flag
-    velp = rain_vel_params(fam.sfx)
+    velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
+    if not isinstance(velp, fam.rain_vel):
+        raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
     _lib.call("cmx_sb2006_column_tendencies_sedimentation", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
               C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev, _ptr(inv_dz), *[_ptr(t) for t in cols],
               *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)

@@ -149,7 +149,7 @@ def microphysics_source_terms_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_
 
 def terminal_velocity_1m(mp, rho, q_rai=None, q_sno=None, *, chen=False, stream=None) -> TerminalVelocities1M:
     """Mass-weighted 1M fall speeds — CM1.terminal_velocity (CM1:223-270): Blk1M rain (needs q_rai), Blk1M snow
-    (needs q_sno) and, with `chen=True`, Chen-2022 rain."""
+    (needs q_sno) and, with `chen=True`, Chen-2022 rain (Table B1; or `chen` = a Chen2022VelTypeRain struct with another table)."""
     if not isinstance(mp, Microphysics1MParams):
         raise TypeError("mp must be Microphysics1MParams")
     cols = [c for c in (rho, q_rai, q_sno) if c is not None]
@@ -160,8 +160,10 @@ def terminal_velocity_1m(mp, rho, q_rai=None, q_sno=None, *, chen=False, stream=
     if chen and q_rai is None:
         raise ValueError("the Chen-2022 rain velocity needs q_rai")
     mk = lambda on: torch.empty_like(ref) if on else None  # noqa: E731
-    out = TerminalVelocities1M(mk(q_rai is not None), mk(q_sno is not None), mk(chen))
-    ch = Chen2022VelTypeRain(fam.sfx) if chen else None
+    out = TerminalVelocities1M(mk(q_rai is not None), mk(q_sno is not None), mk(bool(chen)))
+    ch = (Chen2022VelTypeRain(fam.sfx) if chen is True else chen) if chen else None
+    if ch is not None and not isinstance(ch, fam.chen2022_rain_vel):
+        raise TypeError("chen must be True or the Chen2022VelTypeRain struct of the state's float type")
     _lib.call("cmx_mp1m_terminal_velocity", fam, ref.device, C.byref(mp.c), C.byref(ch) if ch is not None else None, ref.numel(), _ptr(rho),
               _ptr(q_rai), _ptr(q_sno), *[_ptr(o) for o in out], stream=stream)
     return out

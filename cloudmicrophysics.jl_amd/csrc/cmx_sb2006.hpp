@@ -71,6 +71,10 @@ template <typename PR> inline bool rain_pdf_limiters_ok(const PR &p) {      // p
     return p.xr_min > 0 && p.xr_min <= p.xr_max && p.N0_min > 0 && p.N0_min <= p.N0_max && p.lambda_min > 0 && p.lambda_min <= p.lambda_max;
 }
 template <typename WR> inline bool sb_limiters_ok(const WR &wr) { return rain_pdf_limiters_ok(wr.seifert_beheng.pdf_r); }
+// The SB2006 fall speed of the NOT-limited rain PSD integrates from r_c = −log(aR/bR)/(2 cR), the radius below which aR − bR e^{−2 cR r} is
+// negative (CM2:720-739): that needs aR < bR.  With aR ≥ bR the reference's exp(−2 r_c λ) overflows for q_rai → 0 (λ → ∞) and its fall speeds
+// are Inf − Inf = NaN; the entry points return CMX_ERR_BAD_ARG instead.  The limited PSD does not truncate at r_c and takes any aR, bR.
+template <typename VL> inline bool sb_rain_vel_ok(const VL &vel, bool limited) { return limited || vel.sb2006.aR < vel.sb2006.bR; }
 // the limiter pairs of the rain PDF into a constants struct that clamps with them (members xr_min … lam_max)
 template <typename K, typename PR> inline void fill_rain_pdf_limiters(K &k, const PR &p) {
     k.xr_min = p.xr_min; k.xr_max = p.xr_max; k.N0_min = p.N0_min; k.N0_max = p.N0_max; k.lam_min = p.lambda_min; k.lam_max = p.lambda_max;

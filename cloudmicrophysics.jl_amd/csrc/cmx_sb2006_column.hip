@@ -299,6 +299,7 @@ static int32_t column_entry(const WR *wr, const TH *tps, const VL *vel, const ST
     if (!inv_dz || !rho || !T || !q_tot || !q_lcl || !n_lcl || !q_rai || !n_rai || !dq_lcl || !dn_lcl || !dq_rai || !dn_rai)
         return CMX_ERR_BAD_ARG;
     if ((flags & CMX_SB2006_LIMITED) && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
+    if (sbv && !sb_rain_vel_ok(*vel, (flags & CMX_SB2006_LIMITED) != 0)) return CMX_ERR_BAD_ARG;      // the not-limited SB2006 fall speed needs aR < bR
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
     const bool intpow = sb_integer_exponents(*wr);
     CloudVelConsts<FT> cv{};

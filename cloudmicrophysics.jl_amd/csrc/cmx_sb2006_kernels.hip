@@ -39,6 +39,7 @@ static int32_t tendencies_entry(const WR *wr, const TH *tps, const VL *vel, uint
     if (velk == VEL_CHEN) velk = chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1), or the general instantiation (cmx_math.hpp ChenGamma)
     const bool limited = flags & CMX_SB2006_LIMITED;
     if ((flags & CMX_SB2006_LIMITED) && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
+    if (velk == VEL_SB && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;          // the not-limited SB2006 fall speed needs aR < bR
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
     const bool intpow = sb_integer_exponents(*wr);        // b = 3, c = 4, d = −5: the integer-power instantiation (cmx_sb2006.hpp)
     bool known = true;
@@ -91,6 +92,7 @@ static int32_t process_entry(const WR *wr, const TH *tps, const VL *vel, uint32_
     if (velk == VEL_CHEN) velk = chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1), or the general instantiation (cmx_math.hpp ChenGamma)
     const bool limited = flags & CMX_SB2006_LIMITED;
     if ((flags & CMX_SB2006_LIMITED) && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
+    if (velk == VEL_SB && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;          // the not-limited SB2006 fall speed needs aR < bR
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
     SbProcOut<FT> o;
     for (int k = 0; k < CMX_SB2006_NPROC; ++k) o.col[k] = out[k];

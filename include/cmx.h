@@ -31,6 +31,12 @@
  *    return a non-finite value wherever the reference does and may return NaN for an output the reference still evaluates (their
  *    finite-argument elementary functions assume ρ > 0; the Float64 1-moment entries return NaN in EVERY output of such a point;
  *    tests/test_nan_inputs_gpu.py::test_zero_and_negative_air_density);
+ *  - parameter domain of the SB2006 rain fall speed (CMX_VEL_SB2006): with the NOT-limited rain PSD the speeds integrate from the radius
+ *    r_c = −log(aR/bR)/(2 cR), which exists only for aR < bR.  With aR ≥ bR that radius is zero or negative, the truncation means nothing, and the reference's
+ *    Float64 result is NaN where q_rai → 0 at large N_rai (exp(−2 r_c λ_r) overflows: Inf − Inf; src/Microphysics2M.jl:685-739); the entries that evaluate this fall speed
+ *    (cmx_sb2006_warm_rain_tendencies_*, cmx_sb2006_process_rates_*, cmx_sb2006_column_tendencies_sedimentation_*) return CMX_ERR_BAD_ARG for
+ *    such a struct and launch nothing.  The limited PSD (CMX_SB2006_LIMITED) takes any aR, bR;
+ *    tests/test_param_sweep_gpu.py::test_sb2006_fall_speed_needs_aR_below_bR;
  *  - `_f32` entry points compute in float with the reference's Float32
  *    thresholds (eps(Float32), cbrt(floatmin(Float32)) — src/Utilities.jl:318-340),
  *    `_f64` ones in double with the Float64 thresholds.
@@ -1031,7 +1037,11 @@ int32_t cmx_p3_shape_terminal_velocities_f64(const cmx_p3_params_f64 *params, co
  * dL/dt = max(0, 4 K_therm / L_f(T) · (T − T_freeze) ∫ ∂m/∂D · F_v(D) · N′(D)/D dD) over the same bounds / segments as the fall
  * speeds, F_v = a_v + b_v ∛(ν/D_v) √(D v(D)/ν) (CO.ventilation_factor, src/Common.jl:506-514; vent = params.vent, the SB2006
  * ventilation coefficients); dN/dt = N/L · dL/dt.  Points with ρn_ice or ρq_ice < eps(FT) give 0 (the reference calls
- * ice_melt only where ice is present, BMT:966). */
+ * ice_melt only where ice is present, BMT:966).
+ * Parameter domain: the Chen-2022 ice tables must give a non-negative particle fall speed v(D) over the integration range, as the published tables do.
+ * Where v(D) < 0 the reference takes the square root of a negative Reynolds number (DomainError on the CPU, NaN in a kernel); this entry clamps the
+ * Reynolds number at 0 there (F_v = a_v) and returns a finite rate — it does not reproduce that failure
+ * (tests/param_sweep.py DOMAIN, "P3 ventilation factor": the six one-entry changes of Table B3's E and F that reach it). */
 int32_t cmx_p3_ice_melt_f32(const cmx_p3_params_f32 *params, const cmx_chen2022_ice_vel_f32 *vel, const cmx_air_properties_f32 *aps,
                             const cmx_thermo_f32 *tps, const cmx_ventilation_f32 *vent, const cmx_quadrature_f32 *quad, uint32_t flags,
                             float p, int64_t n, const float *rho_q_ice, const float *rho_n_ice, const float *x3, const float *x4,

@@ -118,7 +118,8 @@ int32_t sb2006_host(const WR *wr, const TH *tps, const VL *vel, uint32_t flags, 
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
     const bool limited = flags & CMX_SB2006_LIMITED, chen = flags & CMX_VEL_CHEN2022, intpow = sb_integer_exponents(*wr);
     if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;
-    if (chen && chen_vel_kind<FT>(vel->chen2022) != VEL_CHEN) return CMX_ERR_UNSUPPORTED;      // (the general-Γ instantiation is not built here)
+    if (!chen && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;
+    const int velk = chen ? chen_vel_kind<FT>(vel->chen2022) : VEL_SB;      // the instantiation the entry points pick: fitted Γ, or the general (run-time Γ) one
     auto run = [&](auto lim, auto vk, auto ip) {
         constexpr bool L = decltype(lim)::value, I = decltype(ip)::value;
         constexpr int V = decltype(vk)::value;
@@ -143,9 +144,13 @@ int32_t sb2006_host(const WR *wr, const TH *tps, const VL *vel, uint32_t flags, 
         }
     };
     auto pick_ip = [&](auto lim, auto vk) { if (intpow) run(lim, vk, std::true_type{}); else run(lim, vk, std::false_type{}); };
-    auto pick_v = [&](auto lim) { if (chen) pick_ip(lim, std::integral_constant<int, VEL_CHEN>{}); else pick_ip(lim, std::integral_constant<int, VEL_SB>{}); };
+    auto pick_v = [&](auto lim) {
+        if (velk == VEL_CHEN_GEN) pick_ip(lim, std::integral_constant<int, VEL_CHEN_GEN>{});
+        else if (velk == VEL_CHEN) pick_ip(lim, std::integral_constant<int, VEL_CHEN>{});
+        else pick_ip(lim, std::integral_constant<int, VEL_SB>{});
+    };
     if (limited) pick_v(std::true_type{}); else pick_v(std::false_type{});
-    return intpow ? 1 : 0;
+    return (intpow ? 1 : 0) | (velk == VEL_CHEN_GEN ? 2 : 0);      // bit 0: integer-exponent instantiation, bit 1: general Chen-2022 instantiation
 }
 
 #if CMX_HAVE_PACKED

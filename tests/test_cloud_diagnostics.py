@@ -98,19 +98,7 @@ def test_device_reproduces_the_reference_kats(dev, ft):
     assert CD.effective_radius_const(mp.c.cloud_liquid) == float(NPF[ft](c["cloud_liquid_m"])) and CD.effective_radius_const(mp.c.cloud_ice) == float(NPF[ft](c["cloud_ice_m"]))
 
 
-def _random_state(n, seed):
-    rng = np.random.default_rng(seed)
-    rho = rng.uniform(0.3, 1.3, n)
-    present = lambda p: rng.random(n) < p  # noqa: E731
-    q_lcl = np.where(present(0.8), 10 ** rng.uniform(-8, -2.5, n), 0.0)
-    q_rai = np.where(present(0.8), 10 ** rng.uniform(-9, -2.5, n), 0.0)
-    N_lcl = np.where(present(0.9), 10 ** rng.uniform(5, 9.5, n), 0.0)
-    N_rai = np.where(present(0.9), 10 ** rng.uniform(0, 6.5, n), 0.0)
-    # tiny values around the gates (eps(FT) and far below), as in the reference's "small numbers" case
-    k = n // 20
-    q_lcl[:k] = 10 ** rng.uniform(-30, -6, k); N_lcl[:k] = 10 ** rng.uniform(-15, 3, k)
-    q_rai[k:2 * k] = 10 ** rng.uniform(-30, -6, k); N_rai[k:2 * k] = 10 ** rng.uniform(-20, 1, k)
-    return rho, q_lcl, q_rai, N_lcl, N_rai
+from param_sweep import cloud_diagnostics_state as _random_state  # noqa: E402  (shared with the parameter sweep)
 
 
 @pytest.mark.gpu

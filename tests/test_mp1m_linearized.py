@@ -85,13 +85,7 @@ def test_reference_property_tests(oracle):
     assert all(np.isfinite(t[k][0]) for k in NAMES)
 
 
-def _random_state(n, seed=11):
-    rng = np.random.default_rng(seed)
-    rho, T = rng.uniform(0.3, 1.3, n), rng.uniform(235, 300, n)
-    q = lambda: np.where(rng.random(n) < 0.25, 0.0, 10 ** rng.uniform(-7, -2.7, n))  # noqa: E731
-    q_lcl, q_icl, q_rai, q_sno = q(), q(), q(), q()
-    q_tot = q_lcl + q_icl + q_rai + q_sno + 10 ** rng.uniform(-5, -1.8, n)
-    return rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno
+from param_sweep import mp1m_linearized_state as _random_state  # noqa: E402  (shared with the parameter sweep)
 
 
 def test_mass_budget_and_nonnegativity_on_random_states(oracle):

@@ -38,13 +38,7 @@ def params(ft):
         return P.H2S04NucleationParameters(ft), P.OrganicNucleationParameters(ft), P.MixedNucleationParameters(ft)
 
 
-def random_states(n, seed):
-    """Physical ranges — T 190–320 K; concentrations log-uniform over the CLOUD-chamber ranges and beyond (per m³): h2so4 1e8–1e16, nh3 1e8–1e18,
-    negative ions 1e6–1e10, monoterpenes 1e12–1e18, O3 1e16–1e19, OH 1e9–1e14; condensation sink 1e-5–1e-1 s⁻¹."""
-    g = np.random.default_rng(seed)
-    lu = lambda lo, hi: 10.0 ** g.uniform(lo, hi, n)  # noqa: E731
-    return {"h2so4": lu(8, 16), "nh3": lu(8, 18), "negative_ion": lu(6, 10), "monoterpene": lu(12, 18), "O3": lu(16, 19), "OH": lu(9, 14),
-            "temp": g.uniform(190, 320, n), "condensation_sink": lu(-5, -1)}
+from param_sweep import nucleation_state as random_states  # noqa: E402  (shared with the parameter sweep)
 
 
 def special_states(seed=3, ft="f64"):
