@@ -19,7 +19,8 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
                               SB2006VelType, Tendencies2MP3, WarmRainTendencies2M, bulk_microphysics_tendencies,
                               bulk_microphysics_tendencies_fields, bulk_microphysics_tendencies_2m_p3_fields,
                               bulk_2m_cloud_to_rain, cloud_terminal_velocity, column_sums, sb2006_process_rates,
-                              ColumnTendencies2M, column_tendencies_sedimentation)
+                              ColumnTendencies2M, column_tendencies_sedimentation, ColumnTendencies2MP3,
+                              column_tendencies_sedimentation_2m_p3)
 
 from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_count,  # noqa: F401
                              ice_nucleation_rates, liquid_freezing_rate, h2so4_solution, mohler2006_deposition, MohlerDeposition, deposition_J,

@@ -24,6 +24,8 @@ CMX_P3_SLOPE_CONSTANT = 1 << 1
 CMX_P3_NO_ASPECT_RATIO = 1 << 2
 CMX_P3_RAIN_PDF_LIMITED = 1 << 3
 CMX_FREEZE_CLOUD_PSD = 1 << 4
+CMX_P3COL_VEL_SB2006 = 1 << 8      # cmx_mp2m_p3_column_tendencies_sedimentation_*: the rain fall-speed scheme (bits 1, 2 are P3 flags there)
+CMX_P3COL_VEL_CHEN2022 = 1 << 9
 CMX_QUAD_MAX = 128
 CMX_PSD_CLOUD = 1 << 5
 CMX_COLUMN_SUMS_MAX_COLS = 16

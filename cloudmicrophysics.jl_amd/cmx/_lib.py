@@ -172,6 +172,10 @@ def _declare(lib):
         f.restype = i32
         f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.p3_ice_params), C.POINTER(fam.thermo), u32, i64, i64, C.POINTER(vp), C.POINTER(i64),
                       C.POINTER(vp), C.POINTER(i64), vp]
+        f = getattr(lib, f"cmx_mp2m_p3_column_tendencies_sedimentation_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.p3_ice_params), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel),
+                      C.POINTER(fam.stokes_vel), u32, i32, fam.ft, i64, i32, vp, C.POINTER(vp), C.POINTER(vp)] + [vp] * 5 + [vp]
         f = getattr(lib, f"cmx_gamma_inc_{s}")
         f.restype = i32
         f.argtypes = [i64, vp, vp, vp, vp, vp]

@@ -326,6 +326,75 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
     return out
 
 
+ColumnTendencies2MP3 = namedtuple(
+    "ColumnTendencies2MP3",
+    ["dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dn_ice_dt", "dq_rim_dt", "db_rim_dt", "log_lambda", "v_ice_n", "v_ice_m",
+     "precip_rai", "precip_ice"])
+
+# the rain fall-speed scheme in the flag word of the 2M + P3 column step (bits 1 and 2 are P3 flags there: include/cmx.h (9b))
+_P3COL_VEL = {_abi.CMX_VEL_SB2006: _abi.CMX_P3COL_VEL_SB2006, _abi.CMX_VEL_CHEN2022: _abi.CMX_P3COL_VEL_CHEN2022}
+
+
+def column_tendencies_sedimentation_2m_p3(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, *,
+                                          log_lambda_guess=None, inpc_log_shift=None, vel=SB2006VelType, vel_params=None, cloud_vel=None,
+                                          p: float = 1e-6, brent_iters: int = 0, aspect_ratio: bool = True, want_precip_flux: bool = False,
+                                          out: Optional[ColumnTendencies2MP3] = None, stream=None) -> ColumnTendencies2MP3:
+    """The 2M + P3 column step behind `cmx_mp2m_p3_column_tendencies_sedimentation_*` — one call per time step of a mixed-phase host model.
+    Per column of `n_lev` contiguous levels (state tensors of shape (n_col, n_lev), level 0 = lowest), in this order:
+
+        p3_shape_and_terminal_velocities(mp.ice.scheme…, ρ, ρ q_ice, ρ n_ice, ρ q_rim, ρ b_rim; log_lambda_guess, brent_iters, p, quad = mp.ice's)
+        bulk_microphysics_tendencies(Microphysics2Moment(), mp, tps, ρ, …, b_rim, log_lambda, inpc_log_shift)            BMT:898-1083
+        CM2.rain_terminal_velocity(sb, vel, q_rai, ρ, ρ n_rai)  [+ CM2.cloud_terminal_velocity iff `cloud_vel`]          CM2:685-719, 647-664
+
+    plus the host model's first-order upwind sedimentation flux divergence ∂χ/∂t += (F_{k+1} − F_k)/(ρ_k Δz_k), F = ρ χ w, of q_rai, n_rai
+    (rain speeds), q_ice, q_rim, b_rim (v_ice_m), n_ice (v_ice_n) and — with `cloud_vel` — q_lcl, n_lcl (the flux scheme is the host model's,
+    not the reference's: include/cmx.h).  `inv_dz`: the n_lev values 1/Δz_k.  Returns `ColumnTendencies2MP3`: the eight tendencies,
+    `log_lambda` (cache it: it is the next step's `log_lambda_guess`), the ice fall speeds, and — `want_precip_flux` — the surface
+    fluxes of q_rai and q_ice per column.  Points without ice: log λ = −Inf, speeds 0."""
+    if not (isinstance(mp, Microphysics2MParams) and mp.ice is not None):
+        raise TypeError("mp must be Microphysics2MParams(FT, with_ice=True)")
+    names = ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai", "q_ice", "n_ice", "q_rim", "b_rim")
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim)
+    ref = _check_cols(cols, names)
+    if ref.dim() != 2:
+        raise ValueError("state columns must have shape (n_col, n_lev)")
+    n_col, n_lev = ref.shape
+    fam = _fam_of(ref)
+    if fam is not mp.fam or fam is not mp.ice.fam or not isinstance(tps, fam.thermo) or \
+            (cloud_vel is not None and not isinstance(cloud_vel, fam.stokes_vel)):
+        raise TypeError("parameter float type does not match the state columns")
+    if mp.ice.is_limited != mp.warm_rain.is_limited:
+        raise ValueError("warm_rain and ice must use the same rain PSD variant (is_limited)")
+    if inv_dz.dtype != ref.dtype or inv_dz.device != ref.device or inv_dz.numel() != n_lev or not inv_dz.is_contiguous():
+        raise ValueError("inv_dz must be a contiguous device vector of n_lev values of the state dtype")
+    flag = _vel_flag(vel)
+    if not flag:
+        raise ValueError("the column step needs a rain fall-speed scheme (SB2006VelType or Chen2022VelTypeRain)")
+    for t, nm in ((log_lambda_guess, "log_lambda_guess"), (inpc_log_shift, "inpc_log_shift")):
+        if t is not None:
+            _check_cols([ref, t], ["rho", nm])
+    if out is None:
+        mk = lambda: torch.empty_like(ref)  # noqa: E731
+        pf = lambda: torch.empty(n_col, dtype=ref.dtype, device=ref.device) if want_precip_flux else None  # noqa: E731
+        out = ColumnTendencies2MP3(*[mk() for _ in range(11)], pf(), pf())
+    else:
+        _check_cols([ref, *out[:11]], ["rho", *ColumnTendencies2MP3._fields[:11]])
+        for t, nm in zip(out[11:], ColumnTendencies2MP3._fields[11:]):
+            if t is not None and (t.dtype != ref.dtype or t.device != ref.device or t.numel() != n_col or not t.is_contiguous()):
+                raise ValueError(f"{nm} must be a contiguous device vector of n_col values of the state dtype")
+    velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
+    if not isinstance(velp, fam.rain_vel):
+        raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
+    flags = mp.ice.flags | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO) | _P3COL_VEL[flag]
+    in_p = (C.c_void_p * 13)(*[t.data_ptr() for t in cols], log_lambda_guess.data_ptr() if log_lambda_guess is not None else None,
+                             inpc_log_shift.data_ptr() if inpc_log_shift is not None else None)
+    out_p = (C.c_void_p * 8)(*[t.data_ptr() for t in out[:8]])
+    _lib.call("cmx_mp2m_p3_column_tendencies_sedimentation", fam, ref.device, C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), C.byref(velp),
+              C.byref(cloud_vel) if cloud_vel is not None else None, flags, int(brent_iters), p, n_col, n_lev, _ptr(inv_dz), in_p, out_p,
+              _ptr(out.log_lambda), _ptr(out.v_ice_n), _ptr(out.v_ice_m), _ptr(out.precip_rai), _ptr(out.precip_ice), stream=stream)
+    return out
+
+
 _SCHEMES_2M = {"KK2000": _abi.CMX_2M_KK2000, "B1994": _abi.CMX_2M_B1994, "TC1980": _abi.CMX_2M_TC1980, "LD2004": _abi.CMX_2M_LD2004}
 CloudToRain2M = namedtuple("CloudToRain2M", ["acnv", "accr"])
 

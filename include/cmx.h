@@ -82,6 +82,7 @@ extern "C" {
  *        cmx_snow_terminal_velocity (the snow fall speed with CM1.Oblate / CM1.Prolate) and the CMX_1M_SED_SNOW_* bits of the column step.
  *        cmx_aerosol_nucleation_rates, cmx_nucleation_rates_prescribed, cmx_apparent_nucleation_rate (Nucleation.jl) with the new structs cmx_h2so4_nucleation /
  *        cmx_organic_nucleation / cmx_mixed_nucleation, and cmx_p3_ice_nucleation_counts (CMI_het.P3_deposition_N_i / P3_het_N_i).
+ *        cmx_mp2m_p3_column_tendencies_sedimentation (the 2M + P3 column step, (9b)) with the flag bits CMX_P3COL_VEL_*.
  *        julia/CMXExt.jl (the reference-side binding) checks this number. */
 #define CMX_VERSION_MAJOR 0
 #define CMX_VERSION_MINOR 5
@@ -1144,6 +1145,53 @@ int32_t cmx_microphysics_2m_p3_tendencies_fields_f32(const cmx_warm_rain_2m_f32 
 int32_t cmx_microphysics_2m_p3_tendencies_fields_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_p3_ice_params_f64 *ice, const cmx_thermo_f64 *tps,
                                                      uint32_t flags, int64_t n_seg, int64_t seg_len, const double *const *in,
                                                      const int64_t *in_seg_stride, double *const *out, const int64_t *out_seg_stride, void *stream);
+
+/* (9b) The 2M + P3 COLUMN step — the third fused column step, next to cmx_sb2006_column_tendencies_sedimentation_* (2b) and
+ * cmx_mp1m_column_tendencies_sedimentation_*: what a mixed-phase host model evaluates once per time step, as one call.  Layout as there:
+ * n_col columns of n_lev contiguous levels, flat index i = col·n_lev + k, level 0 lowest, inv_dz = n_lev values 1/Δz_k [1/m].
+ *   in[13]        = HOST array of device columns (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, log_lambda_guess,
+ *                   inpc_log_shift); the last two may be NULL
+ *   tendencies[8] = HOST array of device columns in the order of cmx_microphysics_2m_p3_tendencies_*, all required
+ *   log_lambda, v_ice_n, v_ice_m = n_col·n_lev values each, all required: the caller caches log λ as the next step's warm start and wants the
+ *                   speeds for its CFL check — and, the library being stateless and allocating nothing, they are the hand-off between the launches
+ *   precip_rai, precip_ice = n_col values each, optional: F_0 of q_rai and of q_ice, the surface mass fluxes [kg m⁻² s⁻¹]
+ * Per point, in this order:
+ *   1. cmx_p3_shape_terminal_velocities_* on (ρ q_ice, ρ n_ice, ρ q_rim, ρ b_rim) with ice->scheme, ice->vel_ice, ice->quad, the caller's p and
+ *      brent_iters (0 = the reference's budget) and log_lambda_guess as the warm start (a non-finite guess is ignored, as without one)
+ *      → log_lambda, v_ice_n, v_ice_m, bit for bit that entry's.  Points without ice: log λ = −Inf, speeds 0.
+ *   2. cmx_microphysics_2m_p3_tendencies_* with that log λ → tendencies, bit for bit that entry's.  It reads log λ only where ice is present, so
+ *      the −Inf of the other points is passed as it is; the tendencies there are what that entry returns for any log λ (0, say).
+ *   3. (w_n, w_m) = CM2.rain_terminal_velocity(sb, rain_vel, q_rai, ρ, ρ n_rai) on the clamped state (CM2:685-719), with cloud_vel != NULL also
+ *      (c_n, c_m) = CM2.cloud_terminal_velocity(sb.pdf_c, cloud_vel, q_lcl, ρ, ρ n_lcl) (CM2:647-664), then the host model's first-order upwind
+ *      ("right-biased") flux divergence of (2b),
+ *          F_k = ρ_k χ_k w_k,   ∂χ_k/∂t += (F_{k+1} − F_k) · inv_dz[k] / ρ_k,   F_{n_lev} = 0,
+ *      for χ = q_rai (w_m), n_rai (w_n), q_ice, q_rim, b_rim (v_ice_m), n_ice (v_ice_n) and — with cloud_vel — q_lcl (c_m), n_lcl (c_n).
+ *      The flux scheme is the host model's, NOT part of the reference package: "parity unpinned" for the flux step, as for (2b); the tendencies
+ *      and fall speeds it consumes are pinned by their own entries.
+ * flags: CMX_P3_RAIN_PDF_LIMITED, CMX_P3_SLOPE_CONSTANT, CMX_P3_NO_ASPECT_RATIO as for cmx_microphysics_2m_p3_tendencies_*, and exactly one of
+ * CMX_P3COL_VEL_SB2006 / CMX_P3COL_VEL_CHEN2022: the rain fall-speed scheme of step 3.  (CMX_VEL_SB2006 / CMX_VEL_CHEN2022 are bits 1 and 2 — the
+ * bits of CMX_P3_SLOPE_CONSTANT / CMX_P3_NO_ASPECT_RATIO — so the choice has bits of its own in this word.)
+ * Results do not depend on tile boundaries or pointer alignment.  A NaN in ρ or in any column of a species gives a NaN flux of that species and a
+ * NaN tendency in the cell below; the four ice species share the two fall speeds and hence their NaN fate, as the two rain moments do.
+ * A pure sequence of launches on `stream` (products → shape + fall speeds → tendencies → sedimentation): no allocation, no synchronisation, no host
+ * read-back — capturable in a HIP graph.  The four products are parked in tendencies[4..7] until step 2 overwrites them, so the tendency
+ * columns must not alias an input column.
+ * Status, before any HIP call: n_col < 0, n_lev <= 0, both or neither velocity flag, an unknown flag → CMX_ERR_BAD_ARG; n_col·n_lev > 16·(2^31 − 1),
+ * or above the 4·(2^31 − 8) states of the collision kernel's smallest tile → CMX_ERR_UNSUPPORTED; n_col = 0 → CMX_OK; then a NULL required column,
+ * disordered limiters, a quadrature order outside 1…CMX_QUAD_MAX or p outside (0, ½) → CMX_ERR_BAD_ARG.
+ * cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup). */
+#define CMX_P3COL_VEL_SB2006    (1u << 8)   /* cmx_mp2m_p3_column_tendencies_sedimentation_* only: rain fall speeds as with CMX_VEL_SB2006   */
+#define CMX_P3COL_VEL_CHEN2022  (1u << 9)   /* cmx_mp2m_p3_column_tendencies_sedimentation_* only: rain fall speeds as with CMX_VEL_CHEN2022 */
+int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_p3_ice_params_f32 *ice, const cmx_thermo_f32 *tps,
+                                                        const cmx_rain_vel_f32 *rain_vel, const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags,
+                                                        int32_t brent_iters, float p, int64_t n_col, int32_t n_lev, const float *inv_dz,
+                                                        const float *const *in, float *const *tendencies, float *log_lambda, float *v_ice_n,
+                                                        float *v_ice_m, float *precip_rai, float *precip_ice, void *stream);
+int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_p3_ice_params_f64 *ice, const cmx_thermo_f64 *tps,
+                                                        const cmx_rain_vel_f64 *rain_vel, const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags,
+                                                        int32_t brent_iters, double p, int64_t n_col, int32_t n_lev, const double *inv_dz,
+                                                        const double *const *in, double *const *tendencies, double *log_lambda, double *v_ice_n,
+                                                        double *v_ice_m, double *precip_rai, double *precip_ice, void *stream);
 
 /* UT.gamma_inc(a, x) = (P, Q) and UT.gamma_inc_inv(a, p, q) over columns — src/Utilities.jl:54-61,93-144 and :205-252 (KA wrapper
  * test_gamma_inc_kernel!, test/gpu_tests.jl:456-461; CPU test test/gamma_inc_tests.jl): the reference's fast regularised incomplete gamma

@@ -101,6 +101,8 @@ const CMX_P3_SLOPE_CONSTANT = UInt32(1) << 1
 const CMX_P3_NO_ASPECT_RATIO = UInt32(1) << 2
 const CMX_P3_RAIN_PDF_LIMITED = UInt32(1) << 3
 const CMX_FREEZE_CLOUD_PSD = UInt32(1) << 4
+const CMX_P3COL_VEL_SB2006 = UInt32(1) << 8
+const CMX_P3COL_VEL_CHEN2022 = UInt32(1) << 9
 const CMX_PSD_CLOUD = UInt32(1) << 5
 const CMX_1M_CLOUD_LIQUID_FORMATION = UInt32(1) << 0
 const CMX_1M_CLOUD_ICE_FORMATION_CONST = UInt32(1) << 1
@@ -1144,6 +1146,32 @@ function bulk_microphysics_tendencies!(out, ::BMT.Microphysics2Moment, mp::CMP.M
         _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai), _dp(FT, q_ice), _dp(FT, n_ice), _dp(FT, q_rim), _dp(FT, b_rim), _dp(FT, logλ),
         _dp(FT, inpc_log_shift), _ptrs(FT, out), stream)
     _check(st, "cmx_microphysics_2m_p3_tendencies")
+    return out
+end
+
+"""
+    column_tendencies_sedimentation!(out, BMT.Microphysics2Moment(), mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+                                     q_ice, n_ice, q_rim, b_rim, logλ, v_ice_n, v_ice_m; logλ_guess, inpc_log_shift, p, brent_iters, precip_rai, precip_ice, stream)
+
+The 2M + P3 column step (include/cmx.h (9b)), `mp::Microphysics2MParams{WR, <:P3IceParams}`: shape solve and ice fall speeds on
+(ρ q_ice, ρ n_ice, ρ q_rim, ρ b_rim) → `logλ`, `v_ice_n`, `v_ice_m` (outputs; cache `logλ` as the next step's `logλ_guess`), the eight 2M + P3
+tendencies into `out`, then the rain (`vel`, required) and — `cloud_vel = CMP.StokesRegimeVelType(FT)` — cloud fall speeds and the first-order upwind
+sedimentation of the eight falling species.
+"""
+function column_tendencies_sedimentation!(out, ::BMT.Microphysics2Moment, mp::CMP.Microphysics2MParams{WR, <:CMP.P3IceParams}, tps, vel, cloud_vel,
+    n_col::Integer, n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, logλ, v_ice_n, v_ice_m;
+    logλ_guess = nothing, inpc_log_shift = nothing, p = 1e-6, brent_iters::Integer = 0, precip_rai = nothing, precip_ice = nothing,
+    stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    length(out) == 8 || error("out: the eight tendency columns")
+    flags = p3_flags(_ice(mp)) | (_vel_flag(vel) == CMX_VEL_SB2006 ? CMX_P3COL_VEL_SB2006 : CMX_P3COL_VEL_CHEN2022)
+    in = _ptrs(FT, (ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, logλ_guess, inpc_log_shift))
+    st = ccall(_fn("cmx_mp2m_p3_column_tendencies_sedimentation", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int32, FT, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(_warm_rain(mp))), Ref(pack(_ice(mp))), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, brent_iters, FT(p),
+        n_col, n_lev, _dp(FT, inv_dz), in, _ptrs(FT, out), _dp(FT, logλ), _dp(FT, v_ice_n), _dp(FT, v_ice_m), _dp(FT, precip_rai), _dp(FT, precip_ice), stream)
+    _check(st, "cmx_mp2m_p3_column_tendencies_sedimentation")
     return out
 end
 
