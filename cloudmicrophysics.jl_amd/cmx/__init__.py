@@ -3,7 +3,7 @@
 Host-side mirror of the reference's module layout for the hot path:
   cmx.parameters        ↔ CloudMicrophysics.Parameters (CMP)
   cmx.microphysics0m    ↔ CloudMicrophysics.Microphysics0M (CM0) + the 0M methods of BMT
-  cmx.bulk_tendencies   ↔ CloudMicrophysics.BulkMicrophysicsTendencies (BMT) + per-process CM2 rates
+  cmx.bulk_tendencies   ↔ CloudMicrophysics.BulkMicrophysicsTendencies (BMT) + per-process CM2 rates + the warm-rain Jacobian (forward-mode duals)
   cmx.utilities         ↔ CloudMicrophysics.Utilities (UT): gamma_inc / gamma_inc_inv over columns
   cmx.distribution_tools ↔ CloudMicrophysics.DistributionTools (DT) + the SB2006 PSD accessors of CM2
   cmx.nucleation        ↔ CloudMicrophysics.Nucleation (aerosol new-particle formation)
@@ -20,7 +20,7 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
                               bulk_microphysics_tendencies_fields, bulk_microphysics_tendencies_2m_p3_fields,
                               bulk_2m_cloud_to_rain, cloud_terminal_velocity, column_sums, sb2006_process_rates,
                               ColumnTendencies2M, column_tendencies_sedimentation, ColumnTendencies2MP3,
-                              column_tendencies_sedimentation_2m_p3)
+                              column_tendencies_sedimentation_2m_p3, WarmRainJacobian2M, warm_rain_jacobian_2m)
 
 from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_count,  # noqa: F401
                              ice_nucleation_rates, liquid_freezing_rate, h2so4_solution, mohler2006_deposition, MohlerDeposition, deposition_J,

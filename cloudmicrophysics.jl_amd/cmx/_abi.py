@@ -130,6 +130,13 @@ SB2006_PROCESS_COLUMNS = (
 )
 CMX_SB2006_NPROC = len(SB2006_PROCESS_COLUMNS)
 
+# cmx_sb2006_jac_out, cmx_sb2006_jac_wrt (include/cmx.h §14): jac[o * CMX_SB2006_JAC_NWRT + i] = ∂out_o/∂in_i
+SB2006_JAC_OUT = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt")
+SB2006_JAC_WRT = ("T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai")
+CMX_SB2006_JAC_NOUT = len(SB2006_JAC_OUT)
+CMX_SB2006_JAC_NWRT = len(SB2006_JAC_WRT)
+CMX_SB2006_JAC_NCOL = CMX_SB2006_JAC_NOUT * CMX_SB2006_JAC_NWRT
+
 
 def _struct(name, fields):
     return type(name, (C.Structure,), {"_fields_": fields})

@@ -1464,6 +1464,55 @@ int32_t cmx_parcel_run_f64(const cmx_parcel_params_f64 *pp, uint32_t flags, int6
                            void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (14) The Jacobian of the SB2006 warm-rain tendencies — the derivatives the reference obtains with ForwardDiff through
+ * BMT.bulk_microphysics_tendencies(Microphysics2Moment(), mp{WR, Nothing}, …) (test/ad_compat_tests.jl:106-175): what an implicit time step or a
+ * calibration gradient of the host model consumes.  Per point the four tendencies of cmx_sb2006_warm_rain_tendencies_* (cmx_sb2006_jac_out) are
+ * differentiated with respect to six of its seven inputs (cmx_sb2006_jac_wrt): T, q_tot, q_lcl, n_lcl, q_rai, n_rai; the air density ρ is held fixed.
+ *   jac[o * CMX_SB2006_JAC_NWRT + i] = the column ∂out_o/∂in_i   (a host array of 24 device column pointers, any of them NULL)
+ *   tendencies[o]                    = the tendency itself (NULL, or an array of 4 NULL-able columns): bit-identical to what
+ *                                      cmx_sb2006_warm_rain_tendencies_* writes for the same points and parameters
+ * The device runs the SAME point function as the tendencies entry on forward-mode dual numbers (a value and K tangents, csrc/cmx_dual.hpp): no finite
+ * difference, no second statement of the physics.  Tangents follow the analytic rules; min / max / clamp and the conditional carry the tangents of the
+ * operand whose value they return (ForwardDiff's rule), so at a kink the one-sided derivative of the branch taken is returned; the input clamps max(0, x)
+ * (BMT:828-837) are part of the differentiated function (a negative input has zero derivative); a gate is a select, so a gated-off process contributes
+ * exactly zero and a non-finite tangent behind a closed gate is discarded.  With the integer exponents of the published scheme (b = 3, c = 4, d = −5) the
+ * integer-power instantiation runs, otherwise the general one — the choice the tendencies entry makes for the same struct.
+ *
+ * An input whose four columns are all NULL is not differentiated; the others are carried K at a time through ⌈n/K⌉ evaluations of the point function
+ * inside ONE kernel (the inputs are read once).  The value of a column does not depend on which other columns are requested, bit for bit.
+ * At least one column of `jac` or `tendencies` must be non-NULL (CMX_ERR_BAD_ARG).  flags: CMX_SB2006_LIMITED only; any other bit is CMX_ERR_BAD_ARG.
+ * Statuses as for cmx_sb2006_warm_rain_tendencies_*, in its order: NULL parameters; the count rule (n_points = 0 is CMX_OK before anything else is looked
+ * at); a NULL input column; no output; flags; unordered limiter pairs under CMX_SB2006_LIMITED.  A NaN in any of the seven inputs of a point gives NaN in
+ * every output of that point.  A pure launch sequence on `stream`: no allocation, no synchronisation, graph-capturable; any alignment.
+ * 7 columns in + up to 28 out: 140 B/point (f32) for the full Jacobian with the tendencies.
+ * ------------------------------------------------------------------------- */
+#define CMX_SB2006_JAC_NOUT 4
+#define CMX_SB2006_JAC_NWRT 6
+#define CMX_SB2006_JAC_NCOL 24               /* NOUT * NWRT */
+typedef enum cmx_sb2006_jac_out {
+    CMX_SB2006_JAC_DQ_LCL_DT = 0,
+    CMX_SB2006_JAC_DN_LCL_DT = 1,
+    CMX_SB2006_JAC_DQ_RAI_DT = 2,
+    CMX_SB2006_JAC_DN_RAI_DT = 3
+} cmx_sb2006_jac_out;
+typedef enum cmx_sb2006_jac_wrt {
+    CMX_SB2006_JAC_WRT_T = 0,
+    CMX_SB2006_JAC_WRT_Q_TOT = 1,
+    CMX_SB2006_JAC_WRT_Q_LCL = 2,
+    CMX_SB2006_JAC_WRT_N_LCL = 3,
+    CMX_SB2006_JAC_WRT_Q_RAI = 4,
+    CMX_SB2006_JAC_WRT_N_RAI = 5
+} cmx_sb2006_jac_wrt;
+int32_t cmx_sb2006_warm_rain_jacobian_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                          const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                          float *const jac[CMX_SB2006_JAC_NCOL], float *const tendencies[CMX_SB2006_JAC_NOUT],
+                                          void *stream);
+int32_t cmx_sb2006_warm_rain_jacobian_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                          const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                          const double *n_rai, double *const jac[CMX_SB2006_JAC_NCOL],
+                                          double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1359,6 +1359,36 @@ function sb2006_precip_susceptibility!(acnv_d_ln_q_lcl, acnv_d_ln_q_rai, acnv_d_
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (14) the Jacobian of the SB2006 warm-rain tendencies — test/ad_compat_tests.jl:106-175
+# ----------------------------------------------------------------------------------------------------------------
+const CMX_SB2006_JAC_NOUT = 4
+const CMX_SB2006_JAC_NWRT = 6
+const CMX_SB2006_JAC_NCOL = 24
+
+"""
+    warm_rain_jacobian_2m!(jac, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai; stream = C_NULL)
+
+What `ForwardDiff.jacobian` gives through `BMT.bulk_microphysics_tendencies(BMT.Microphysics2Moment(), mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)`
+with respect to (T, q_tot, q_lcl, n_lcl, q_rai, n_rai), over columns: the device evaluates the same point function on forward-mode dual numbers.
+`jac` = `CMX_SB2006_JAC_NCOL` (24) device columns or `nothing`s, `jac[o * 6 + i + 1]` = ∂out_o/∂in_i with out = (dq_lcl_dt, dn_lcl_dt, dq_rai_dt,
+dn_rai_dt) and in as above (0-based o, i: the order of `cmx_sb2006_jac_out` / `cmx_sb2006_jac_wrt`); an input whose four columns are all `nothing` is
+not differentiated.  `tendencies` = `nothing` or 4 columns (or `nothing`s): the tendencies themselves, bit-identical to `bulk_microphysics_tendencies!`.
+"""
+function warm_rain_jacobian_2m!(jac, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl, q_rai,
+    n_rai; stream = C_NULL) where {WR, FT}
+    length(jac) == CMX_SB2006_JAC_NCOL || error("jac: $(CMX_SB2006_JAC_NCOL) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = ccall(_fn("cmx_sb2006_warm_rain_jacobian", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), _ptrs(FT, jac), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_jacobian")
+    return jac
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params

@@ -1,0 +1,213 @@
+"""The SB2006 warm-rain Jacobian without a GPU (include/cmx.h §(14), cmx.warm_rain_jacobian_2m):
+
+  * the dual instantiation of the device point function (csrc/cmx_dual.hpp, csrc/cmx_sb2006_jacobian.hpp) compiled by g++ for the host
+    (tests/native/jacobian_host.cpp) against central differences of the Float64 oracle — tests/jacobian_cases.py has the states, the reference and the
+    measure — at the reference's own bound 1e-5 (test/ad_compat_tests.jl:163) in Float64 and the project's Float32 bound 1e-3 in every row in Float32 —
+    except dn_rai_dt with the perturbed parameter set, which misses it at ONE state (2.2e-3 here, 2.3e-3 on the device) and is held entry by entry to the
+    bound its evaporation share earns from the oracle's own Float32-against-Float64 spread of the evaporation rate (jacobian_cases.float32_bound);
+  * the value parts against the plain instantiation, bit for bit; the columns against the tangent width K, bit for bit;
+  * finiteness at the reference's boundary state and on every present / absent combination of the four species;
+  * the argument statuses of the two entries and the Python wrapper's errors.
+
+The host build proves the derivative RULES (its transcendentals are libm's, not the hardware's); tests/test_sb2006_jacobian_gpu.py repeats the parity
+assertions on the device."""
+import ctypes as C
+import itertools
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+import jacobian_cases as JC
+import cmx
+from cmx import _abi, _lib, synthetic
+from cmx import parameters as P
+
+REPO = Path(__file__).resolve().parent.parent
+NPT = {"f32": np.float32, "f64": np.float64}
+CT = {"f32": C.c_float, "f64": C.c_double}
+
+
+@pytest.fixture(scope="module")
+def host():
+    out = REPO / "tests" / "native" / "_build"
+    out.mkdir(exist_ok=True)
+    so = out / "libjacobian_host.so"
+    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(REPO / "tests" / "native" / "jacobian_host.cpp")],
+                   check=True)
+    return C.CDLL(str(so))
+
+
+def _arr(ft, cols):
+    return (C.POINTER(CT[ft]) * len(cols))(*[c.ctypes.data_as(C.POINTER(CT[ft])) if c is not None else None for c in cols])
+
+
+def host_jacobian(host, ft, wr, limited, cols, wrt=JC.WRT, k=0, with_tendencies=True):
+    """([4, len(wrt), n] Jacobian, [4, n] tendencies, status) of the host build; wrt: names in any order."""
+    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
+    n = x[0].size
+    jac = np.full((4, len(wrt), n), np.nan, dtype=NPT[ft])
+    tend = np.full((4, n), np.nan, dtype=NPT[ft]) if with_tendencies else None
+    slots = [None] * _abi.CMX_SB2006_JAC_NCOL
+    for kk, name in enumerate(wrt):
+        for o in range(4):
+            slots[o * 6 + JC.WRT.index(name)] = jac[o, kk]
+    fn = getattr(host, f"host_sb2006_jacobian_{ft}")
+    fn.restype = C.c_int32
+    rc = fn(C.byref(wr.c), C.byref(P.ThermodynamicsParameters(ft)), C.c_uint32(_abi.CMX_SB2006_LIMITED if limited else 0), C.c_int(k), C.c_int64(n),
+            _arr(ft, x), _arr(ft, slots), _arr(ft, list(tend)) if tend is not None else None)
+    return jac, tend, rc
+
+
+def host_plain(host, ft, wr, limited, cols):
+    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
+    y = np.empty((4, x[0].size), dtype=NPT[ft])
+    fn = getattr(host, f"host_sb2006_plain_{ft}")
+    fn.restype = C.c_int32
+    rc = fn(C.byref(wr.c), C.byref(P.ThermodynamicsParameters(ft)), C.c_uint32(_abi.CMX_SB2006_LIMITED if limited else 0), C.c_int64(x[0].size),
+            _arr(ft, x), _arr(ft, list(y)))
+    return y, rc
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return bool(np.all((a.view(np.uint8) == b.view(np.uint8)).reshape(a.shape + (-1,)).all(axis=-1) | (np.isnan(a) & np.isnan(b))))
+
+
+# ---- parity against the finite-difference reference ---------------------------------------------------------------------------------------------
+CASES = [(True, False), (False, False), (True, True)]        # (limited, perturbed exponents → the general-exponent instantiation)
+
+
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("limited,perturbed", CASES)
+def test_host_jacobian_matches_central_differences_of_the_oracle(host, oracle, ft, limited, perturbed):
+    """Float64: every row of every kept state within the reference's own 1e-5.  Float32, same Float64 reference: every row within 1e-3, except dn_rai_dt
+    with the perturbed parameter set, held entry by entry to jacobian_cases.float32_bound (worst values observed: DESIGN.md §6)."""
+    wr = JC.warm_rain_params(ft, limited, JC.perturbed_overrides() if perturbed else None)
+    for which in ("interior", "points"):
+        J, _, rc = host_jacobian(host, ft, wr, limited, JC.reference(limited, perturbed, which)[0])
+        assert rc == (0 if perturbed else 1)                 # which instantiation ran: the one sb_integer_exponents selects
+        JC.assert_parity(ft, J, limited, perturbed, which, "host")
+
+
+# ---- the primal ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("limited", [True, False])
+def test_value_parts_are_the_plain_instantiation_bit_for_bit(host, oracle, ft, limited):
+    wr = JC.warm_rain_params(ft, limited)
+    dt = {"f32": torch.float32, "f64": torch.float64}[ft]
+    for cols in (JC.reference(limited)[0], [c.numpy() for c in synthetic.sb2006_state(4096, dtype=dt, seed=321)]):
+        plain, rc = host_plain(host, ft, wr, limited, cols)
+        assert rc == 1
+        for wrt in (JC.WRT, ("q_rai",), ()):
+            _, tend, _ = host_jacobian(host, ft, wr, limited, cols, wrt=wrt)
+            assert _same_bits(tend, plain), wrt
+
+
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+def test_columns_do_not_depend_on_the_tangent_width_or_the_selection(host, oracle, ft):
+    """Each tangent is computed by the same operations whatever K is and whichever other inputs are seeded: K = 1, 2, 3, 4, 6, subsets in any order."""
+    wr = JC.warm_rain_params(ft, True)
+    cols = [c[:512] for c in JC.reference(True)[0]]
+    full, _, _ = host_jacobian(host, ft, wr, True, cols)
+    for k in (1, 2, 3, 4, 6):
+        J, _, rc = host_jacobian(host, ft, wr, True, cols, k=k)
+        assert rc == 1 and _same_bits(J, full), k
+    for wrt in (("n_rai", "T"), ("q_lcl",), ("q_rai", "q_tot", "n_lcl", "T", "q_lcl")):
+        J, _, _ = host_jacobian(host, ft, wr, True, cols, wrt=wrt)
+        for kk, name in enumerate(wrt):
+            assert _same_bits(J[:, kk], full[:, JC.WRT.index(name)]), (wrt, name)
+
+
+# ---- finiteness ---------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("limited", [True, False])
+def test_jacobian_is_finite_at_the_zero_rain_boundary(host, ft, limited):
+    """ad_compat_tests.jl:167-174: Φ_au(τ) ∝ τ^0.7 has a vertical tangent at exactly zero rain with cloud present; the ϵ-gate keeps the Jacobian finite."""
+    J, tend, _ = host_jacobian(host, ft, JC.warm_rain_params(ft, limited), limited, JC.points(JC.BOUNDARY))
+    assert np.all(np.isfinite(J)) and np.all(np.isfinite(tend))
+
+
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("limited", [True, False])
+def test_jacobian_is_finite_with_absent_species(host, oracle, ft, limited):
+    """The 16 present / absent combinations of (q_lcl, n_lcl, q_rai, n_rai) ∈ {0, interior value} at ρ = 1, T = 285, sub- and super-saturated: every entry
+    is finite, and the column of an absent species is exactly zero — the input clamp max(0, x) passes no tangent at x = 0 and every gate behind it is a
+    select."""
+    qs = float(JC.q_sat(oracle, np.array([285.0]), np.array([1.0]))[0])
+    states = []
+    for sat in (0.7, 1.03):
+        for present in itertools.product((0, 1), repeat=4):
+            ql, nl, qr, nr = (v * p for v, p in zip((1e-3, 1e8, 5e-4, 1e4), present))
+            states.append((1.0, 285.0, ql + qr + sat * qs, ql, nl, qr, nr))
+    cols = JC.points(*states)
+    J, tend, _ = host_jacobian(host, ft, JC.warm_rain_params(ft, limited), limited, cols)
+    assert np.all(np.isfinite(J)) and np.all(np.isfinite(tend))
+    for name in ("q_lcl", "n_lcl", "q_rai", "n_rai"):
+        j = JC.WRT.index(name)
+        absent = cols[j + 1] == 0
+        assert absent.sum() == 16 and np.all(J[:, j, absent] == 0), name
+
+
+def test_a_nan_input_poisons_every_output_of_its_point(host, oracle):
+    for ft in ("f64", "f32"):
+        cols = [np.array(c[:16], dtype=NPT[ft]) for c in JC.reference(True)[0]]
+        clean, ctend, _ = host_jacobian(host, ft, JC.warm_rain_params(ft, True), True, cols)
+        for j in range(7):
+            bad = [c.copy() for c in cols]
+            bad[j][5] = np.nan
+            J, tend, _ = host_jacobian(host, ft, JC.warm_rain_params(ft, True), True, bad)
+            assert np.all(np.isnan(J[:, :, 5])) and np.all(np.isnan(tend[:, 5]))
+            keep = np.arange(16) != 5
+            assert _same_bits(J[:, :, keep], clean[:, :, keep]) and _same_bits(tend[:, keep], ctend[:, keep])
+
+
+# ---- statuses and the wrapper's errors ----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ft", ["f32", "f64"])
+def test_argument_statuses_without_gpu(ft):
+    """Every call below returns before any HIP runtime call."""
+    lib = _lib.lib()
+    fn = getattr(lib, f"cmx_sb2006_warm_rain_jacobian_{ft}")
+    BAD, UNS, OK = _abi.CMX_ERR_BAD_ARG, _abi.CMX_ERR_UNSUPPORTED, _abi.CMX_OK
+    wr, tps = P.WarmRainParams2M(ft, True), P.ThermodynamicsParameters(ft)
+    seven = [C.c_void_p(4096 + 64 * k) for k in range(7)]
+    jac = (C.c_void_p * _abi.CMX_SB2006_JAC_NCOL)(*[8192 + 64 * k for k in range(_abi.CMX_SB2006_JAC_NCOL)])
+    tend = (C.c_void_p * 4)(*[16384 + 64 * k for k in range(4)])
+    nojac, notend = (C.c_void_p * _abi.CMX_SB2006_JAC_NCOL)(), (C.c_void_p * 4)()
+    huge = 16 * 0x7fffffff + 1
+
+    def call(flags=_abi.CMX_SB2006_LIMITED, n=8, cols=seven, j=jac, t=tend, w=wr, th=tps):
+        return fn(C.byref(w.c) if w is not None else None, C.byref(th) if th is not None else None, flags, n, *cols, j, t, None)
+    assert call(w=None) == BAD and call(th=None) == BAD                                   # no parameters
+    assert call(n=-1) == BAD and call(n=huge) == UNS and call(n=0) == OK                   # the count rule
+    assert call(n=0, cols=[None] * 7, j=None, t=None) == OK                                # n = 0 returns before the columns matter …
+    assert call(n=0, flags=1 << 7) == OK                                                   # … and before the flags, like the tendencies entry
+    for k in range(7):                                                                     # a NULL input column
+        assert call(cols=seven[:k] + [None] + seven[k + 1:]) == BAD, k
+    assert call(j=None, t=None) == BAD and call(j=nojac, t=None) == BAD and call(j=nojac, t=notend) == BAD and call(j=None, t=notend) == BAD    # no output
+    for bit in (_abi.CMX_VEL_SB2006, _abi.CMX_VEL_CHEN2022, 1 << 3, 1 << 31):              # CMX_SB2006_LIMITED is the only flag
+        assert call(flags=bit) == BAD and call(flags=bit | _abi.CMX_SB2006_LIMITED) == BAD, hex(bit)
+    bad_wr = P.WarmRainParams2M(ft, True)
+    bad_wr.c.seifert_beheng.pdf_r.xr_min, bad_wr.c.seifert_beheng.pdf_r.xr_max = bad_wr.c.seifert_beheng.pdf_r.xr_max, bad_wr.c.seifert_beheng.pdf_r.xr_min
+    assert call(w=bad_wr) == BAD                                                           # unordered limiter pair under CMX_SB2006_LIMITED
+
+
+def test_python_wrapper_errors():
+    wr, tps = P.WarmRainParams2M("f64", True), P.ThermodynamicsParameters("f64")
+    cols = [torch.ones(4, dtype=torch.float64) for _ in range(7)]
+    with pytest.raises(ValueError, match="unknown input 'rho'"):
+        cmx.warm_rain_jacobian_2m(wr, tps, *cols, wrt=("T", "rho"))
+    with pytest.raises(ValueError, match="unknown input"):
+        cmx.warm_rain_jacobian_2m(wr, tps, *cols, wrt=("q_vap",))
+    with pytest.raises(ValueError, match="listed twice"):
+        cmx.warm_rain_jacobian_2m(wr, tps, *cols, wrt=("T", "T"))
+    with pytest.raises(ValueError, match="nothing to compute"):
+        cmx.warm_rain_jacobian_2m(wr, tps, *cols, wrt=())
+    with pytest.raises(TypeError, match="mp must be"):
+        cmx.warm_rain_jacobian_2m(object(), tps, *cols)
+    with pytest.raises(ValueError, match="resident on the GPU"):          # there is no CPU path
+        cmx.warm_rain_jacobian_2m(wr, tps, *cols)
+    assert cmx.bulk_tendencies.JACOBIAN_WRT == _abi.SB2006_JAC_WRT == ("T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai")
+    assert cmx.WarmRainJacobian2M._fields == ("jac", "tendencies", "wrt")
