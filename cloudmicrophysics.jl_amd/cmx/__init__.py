@@ -40,7 +40,8 @@ from .parcel import ParcelSolution, ParcelTendencies, parcel_params, parcel_tend
 from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Moment, SedimentationVelocities, SourceTerms1M, Tendencies1M,  # noqa: F401
                              TerminalVelocities1M, bulk_microphysics_tendencies_1m, bulk_microphysics_tendencies_1m_fields,
                              microphysics_source_terms_1m, sedimentation_velocities, terminal_velocity_1m, ColumnStep1M,
-                             column_tendencies_sedimentation_1m, AbstractSnowShape, Oblate, Prolate, snow_terminal_velocity)
+                             column_tendencies_sedimentation_1m, AbstractSnowShape, Oblate, Prolate, snow_terminal_velocity, Jacobian1M,
+                             JACOBIAN_WRT_1M, JACOBIAN_OUTPUTS_1M, jacobian_1m)
 
 from .microphysics0m import (Microphysics0Moment, bulk_microphysics_tendencies_0m, d_remove_precipitation_d_q_tot,  # noqa: F401
                              remove_precipitation)

@@ -137,6 +137,13 @@ CMX_SB2006_JAC_NOUT = len(SB2006_JAC_OUT)
 CMX_SB2006_JAC_NWRT = len(SB2006_JAC_WRT)
 CMX_SB2006_JAC_NCOL = CMX_SB2006_JAC_NOUT * CMX_SB2006_JAC_NWRT
 
+# cmx_mp1m_jac_out, cmx_mp1m_jac_wrt (include/cmx.h §15): jac[o * CMX_MP1M_JAC_NWRT + i] = ∂out_o/∂in_i
+MP1M_JAC_OUT = ("dq_lcl_dt", "dq_icl_dt", "dq_rai_dt", "dq_sno_dt")
+MP1M_JAC_WRT = ("T", "q_tot", "q_lcl", "q_icl", "q_rai", "q_sno")
+CMX_MP1M_JAC_NOUT = len(MP1M_JAC_OUT)
+CMX_MP1M_JAC_NWRT = len(MP1M_JAC_WRT)
+CMX_MP1M_JAC_NCOL = CMX_MP1M_JAC_NOUT * CMX_MP1M_JAC_NWRT
+
 
 def _struct(name, fields):
     return type(name, (C.Structure,), {"_fields_": fields})

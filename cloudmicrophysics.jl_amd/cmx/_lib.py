@@ -212,6 +212,9 @@ def _declare(lib):
         f = getattr(lib, f"cmx_sb2006_warm_rain_jacobian_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.POINTER(vp), C.POINTER(vp), vp]
+        f = getattr(lib, f"cmx_mp1m_jacobian_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.POINTER(vp), C.POINTER(vp), vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

@@ -107,6 +107,64 @@ def bulk_microphysics_tendencies_1m(mode, scheme, mp, tps, rho, T, q_tot, q_lcl,
     return out
 
 
+Jacobian1M = namedtuple("Jacobian1M", ["jac", "tendencies", "wrt"])
+
+JACOBIAN_OUTPUTS_1M = _abi.MP1M_JAC_OUT
+JACOBIAN_WRT_1M = _abi.MP1M_JAC_WRT
+
+
+def jacobian_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, wrt=JACOBIAN_WRT_1M, with_tendencies=False, *, out=None, stream=None) -> Jacobian1M:
+    """The Jacobian of the 1-moment tendencies `bulk_microphysics_tendencies_1m(Instantaneous(), …)` (BMT:505-514 → :141-252) with respect to the state,
+    behind `cmx_mp1m_jacobian_*`: the same point function, evaluated on forward-mode dual numbers in one kernel — the true derivatives, not the donor-based
+    linearization inside LinearizedAverage (BMT:269-379).
+
+    `wrt`: the inputs to differentiate, any subset of `JACOBIAN_WRT_1M` = ("T", "q_tot", "q_lcl", "q_icl", "q_rai", "q_sno") in any order (ρ is held
+    fixed).  Returns `Jacobian1M(jac, tendencies, wrt)`: `jac` is one contiguous tensor of shape (4, len(wrt), *rho.shape) with
+    `jac[o, k]` = ∂`JACOBIAN_OUTPUTS_1M[o]`/∂`wrt[k]` (its slices are the columns handed to the ABI; a column does not depend on which others are
+    requested); `tendencies` is a (4, *rho.shape) tensor, bit-identical to `bulk_microphysics_tendencies_1m(Instantaneous(), …)` on the same columns,
+    with `with_tendencies=True`, else None.  `out=(jac, tendencies)` lets the caller provide either tensor (None: allocated here; each slice
+    `[o, k]` / `[o]` must be contiguous).  An implicit step solves (I − Δt·J) δ = Δt·f per point from these columns.
+    Asynchronous on `stream` (default: torch's current stream)."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    wrt = tuple(wrt)
+    for name in wrt:
+        if name not in JACOBIAN_WRT_1M:
+            raise ValueError(f"wrt: unknown input '{name}' (one of {JACOBIAN_WRT_1M}; rho is not differentiated)")
+    if len(set(wrt)) != len(wrt):
+        raise ValueError("wrt: an input is listed twice")
+    if not wrt and not with_tendencies:
+        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    ref, fam = _prep(mp, tps, cols)
+    nout, nwrt = _abi.CMX_MP1M_JAC_NOUT, _abi.CMX_MP1M_JAC_NWRT
+    jac, tend = out if out is not None else (None, None)
+    if jac is None:
+        jac = torch.empty((nout, len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
+    elif jac.shape != (nout, len(wrt), *ref.shape):
+        raise ValueError(f"out: jac must have shape (4, len(wrt), *rho.shape) = {(nout, len(wrt), *ref.shape)}")
+    if with_tendencies:
+        if tend is None:
+            tend = torch.empty((nout, *ref.shape), dtype=ref.dtype, device=ref.device)
+        elif tend.shape != (nout, *ref.shape):
+            raise ValueError(f"out: tendencies must have shape (4, *rho.shape) = {(nout, *ref.shape)}")
+    elif tend is not None:
+        raise ValueError("out: a tendencies tensor was given but with_tendencies is False")
+    if wrt:
+        _check_cols([ref] + [jac[o, k] for o in range(nout) for k in range(len(wrt))], ["rho"] + ["jac"] * (nout * len(wrt)))
+    if tend is not None:
+        _check_cols([ref] + [tend[o] for o in range(nout)], ["rho"] + ["tendencies"] * nout)
+    ptrs = [None] * _abi.CMX_MP1M_JAC_NCOL
+    for k, name in enumerate(wrt):
+        for o in range(nout):
+            ptrs[o * nwrt + JACOBIAN_WRT_1M.index(name)] = jac[o, k].data_ptr()
+    jac_p = (C.c_void_p * _abi.CMX_MP1M_JAC_NCOL)(*ptrs)
+    tend_p = (C.c_void_p * nout)(*[tend[o].data_ptr() for o in range(nout)]) if tend is not None else None
+    _lib.call("cmx_mp1m_jacobian", fam, ref.device, C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols], jac_p, tend_p,
+              stream=stream)
+    return Jacobian1M(jac, tend, wrt)
+
+
 def bulk_microphysics_tendencies_1m_fields(mode, scheme, mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt=None, nsub=1, *, q_min=None, out=None,
                                            aos=False, stream=None):
     """The 1-moment tendencies — Instantaneous, or LinearizedAverage with `dt` [, `nsub`] — on the host model's own storage (SURVEY §8f-3,

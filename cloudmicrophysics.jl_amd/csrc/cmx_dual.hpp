@@ -205,6 +205,34 @@ template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> clamp_order
     CMX_DUAL_FOR r.d[k] = pass ? x.d[k] : FT(0);
     return r;
 }
+// lo ≤ hi with bounds that are duals themselves (the 1-moment cloud-ice excess is clamped to −q_icl, cmx_mp1m.hpp): the plain clamp_ordered on the values; a
+// value clamped to a bound carries THAT BOUND's tangents (ForwardDiff's rule: the operand whose value is returned), x's on a tie and inside
+template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> clamp_ordered(const Dual<FT, K> &x, const Dual<FT, K> &lo, const Dual<FT, K> &hi) {
+    Dual<FT, K> r; r.v = clamp_ordered(x.v, lo.v, hi.v);
+    const bool below = x.v < lo.v, above = !below && x.v > hi.v;
+#pragma unroll
+    CMX_DUAL_FOR r.d[k] = below ? lo.d[k] : (above ? hi.d[k] : x.d[k]);
+    return r;
+}
+template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> clamp_ordered(const Dual<FT, K> &x, const Dual<FT, K> &lo, std::enable_if_t<true, FT> hi) {
+    return clamp_ordered(x, lo, Dual<FT, K>(hi));
+}
+// log2 of a non-negative quantity that is ordinarily zero (cmx_math.hpp log2_floored): the value is formed exactly as there; Float64: the tangent is that of
+// the operand the max returned — the literal zeros of the floor for an absent species; Float32: the logarithm's own rule (an absent species has −Inf with a
+// non-finite tangent, which the floor of the slope parameter or the gate q > ϵ behind it discards)
+template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> log2_floored(const Dual<FT, K> &x) {
+    using MD = Math<Dual<FT, K>>;
+    if constexpr (MD::IS_F64) return MD::log2_pn(MD::max(x, FT(2.2250738585072014e-308)));
+    else return MD::log2(x);
+}
+// a value that is constant wherever `gate` holds (cmx_math.hpp flat_where): no tangents there — the chain rule through the −Inf exponent that made it 0 would
+// give 0·Inf
+template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> flat_where(bool gate, const Dual<FT, K> &x) {
+    Dual<FT, K> r; r.v = x.v;
+#pragma unroll
+    CMX_DUAL_FOR r.d[k] = gate ? FT(0) : x.d[k];
+    return r;
+}
 // the phase boundary of the constants (cmx_math.hpp consts_after) waits for the VALUE
 template <typename C, typename FT, int K> __device__ __forceinline__ const C &consts_after(const C &c, const Dual<FT, K> &dep) { return consts_after(c, dep.v); }
 #undef CMX_DUAL_FOR

@@ -394,6 +394,10 @@ __device__ __forceinline__ double max0(double x) { return Math<double>::max(0.0,
 #if CMX_HAVE_PACKED
 __device__ __forceinline__ f32x2 max0(f32x2 x) { return f32x2{max0(x.x), max0(x.y)}; }
 #endif
+// flat_where(gate, x): x itself.  It MARKS a value that is constant in a neighbourhood wherever `gate` holds — a quantity that reached exactly 0 through a −Inf
+// exponent, say — for the value types that carry derivatives: cmx_dual.hpp drops the tangents there, where the chain rule would form 0·Inf.  No code for
+// the plain value types.
+template <typename B, typename FT> __device__ __forceinline__ FT flat_where(B, FT x) { return x; }
 // log2 of a non-negative quantity that is ORDINARILY zero — ρ·q of an absent species.  Float64: floored at the smallest normal number (−1022
 // instead of −Inf: every caller floors the slope parameter it derives far above that, or gates the result on q > ϵ) and evaluated by the
 // main path of the logarithm alone; the full form would send nearly every wave of a real field through its rescue block.  A NaN argument does

@@ -274,7 +274,7 @@ __device__ __forceinline__ Mp1mSrc<FT> mp1m_point(const C &c0, FT rho, FT T, FT 
         } else {   // TemperatureDependent — NonEq:194-224 with τ_dep = τ_relax(…) :32-50 (Frostenberg 2023 INP number, spherical crystals)
             const FT Tc = M::min(dTf, FT(0));
             const FT l2_N = M::fma(FT(9), M::log2(-(c->td_b10 * Tc)), -c->td_l2a);   // log2 of exp(INP_concentration_mean)
-            const FT N = M::exp2(l2_N);
+            const FT N = flat_where(dTf >= FT(0), M::exp2(l2_N));      // no INPs at and above freezing: exp2(−Inf) = 0, and constant there
             const FT r = N > eps ? FT(M::exp2((M::log2(c->td_c3 * q_icl) - M::max(l2_N, c->l2_eps)) * FT(1.0 / 3.0))) : FT(0);
             const FT inv_tau_dep = c->td_fourpiD * N * M::max(r, FT(1e-6));
             o.vap_icl = lim * ((ex < FT(0) ? FT(c->inv_tau_i) : inv_tau_dep) * inv_G);

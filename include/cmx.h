@@ -1513,6 +1513,52 @@ int32_t cmx_sb2006_warm_rain_jacobian_f64(const cmx_warm_rain_2m_f64 *warm_rain,
                                           double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (15) The Jacobian of the 1-moment tendencies — the derivatives of BMT.bulk_microphysics_tendencies(Instantaneous(), Microphysics1Moment(), mp, tps, …)
+ * (BMT:505-514 → :141-252) with respect to the state: what a linearly implicit step of the host model consumes in place of the donor-based
+ * approximation inside LinearizedAverage (BMT:269-379).  Per point the four tendencies of cmx_mp1m_tendencies_* (cmx_mp1m_jac_out) are differentiated with
+ * respect to six of its seven inputs (cmx_mp1m_jac_wrt): T, q_tot, q_lcl, q_icl, q_rai, q_sno; the air density ρ is held fixed.
+ *   jac[o * CMX_MP1M_JAC_NWRT + i] = the column ∂out_o/∂in_i   (a host array of 24 device column pointers, any of them NULL)
+ *   tendencies[o]                  = the tendency itself (NULL, or an array of 4 NULL-able columns): bit-identical to what cmx_mp1m_tendencies_*
+ *                                    writes for the same points and parameters
+ * The device runs the SAME point function as the tendencies entry on forward-mode dual numbers (csrc/cmx_dual.hpp), with the rules of (14): analytic
+ * tangents; min / max / clamp and the conditional carry the tangents of the operand whose value they return, so at a kink — the saturation limiters, the
+ * melting gate at T_freeze, q = ϵ — the one-sided derivative of the branch taken is returned; the input clamps max(0, x) (BMT:147-152; T is not clamped)
+ * are part of the differentiated function; a gate is a select, and a process switched off by its option contributes exactly zero.  `flags` and the
+ * parameter struct select the instantiation as for cmx_mp1m_tendencies_*: the default options with the default exponents, or the run-time-flags one.
+ *
+ * An input whose four columns are all NULL is not differentiated; the others are carried K at a time through ⌈n/K⌉ evaluations of the point function
+ * inside ONE kernel (the inputs are read once).  The value of a column does not depend on which other columns are requested, bit for bit.
+ * Statuses as for cmx_mp1m_tendencies_*, in its order: NULL parameters; the count rule; the flags (both members of an exclusive option pair, an unknown
+ * bit: CMX_ERR_BAD_ARG); n_points = 0 is CMX_OK; a NULL input column; no non-NULL column in `jac` and `tendencies` at all (CMX_ERR_BAD_ARG).
+ * A NaN in any of the seven inputs of a point gives NaN in every output of that point; in Float64 so does ρ ≤ 0.  A pure launch sequence on `stream`: no
+ * allocation, no synchronisation, graph-capturable; any alignment.  7 columns in + up to 28 out: 140 B/point (f32) for the full Jacobian with the
+ * tendencies.
+ * ------------------------------------------------------------------------- */
+#define CMX_MP1M_JAC_NOUT 4
+#define CMX_MP1M_JAC_NWRT 6
+#define CMX_MP1M_JAC_NCOL 24                 /* NOUT * NWRT */
+typedef enum cmx_mp1m_jac_out {
+    CMX_MP1M_JAC_DQ_LCL_DT = 0,
+    CMX_MP1M_JAC_DQ_ICL_DT = 1,
+    CMX_MP1M_JAC_DQ_RAI_DT = 2,
+    CMX_MP1M_JAC_DQ_SNO_DT = 3
+} cmx_mp1m_jac_out;
+typedef enum cmx_mp1m_jac_wrt {
+    CMX_MP1M_JAC_WRT_T = 0,
+    CMX_MP1M_JAC_WRT_Q_TOT = 1,
+    CMX_MP1M_JAC_WRT_Q_LCL = 2,
+    CMX_MP1M_JAC_WRT_Q_ICL = 3,
+    CMX_MP1M_JAC_WRT_Q_RAI = 4,
+    CMX_MP1M_JAC_WRT_Q_SNO = 5
+} cmx_mp1m_jac_wrt;
+int32_t cmx_mp1m_jacobian_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                              const float *T, const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                              float *const jac[CMX_MP1M_JAC_NCOL], float *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_jacobian_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                              const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                              double *const jac[CMX_MP1M_JAC_NCOL], double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1389,6 +1389,35 @@ function warm_rain_jacobian_2m!(jac, tendencies, mp::CMP.Microphysics2MParams{WR
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (15) the Jacobian of the 1-moment tendencies — src/BulkMicrophysicsTendencies.jl:141-252, 505-514 differentiated with respect to the state
+# ----------------------------------------------------------------------------------------------------------------
+const CMX_MP1M_JAC_NOUT = 4
+const CMX_MP1M_JAC_NWRT = 6
+const CMX_MP1M_JAC_NCOL = 24
+
+"""
+    jacobian_1m!(jac, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno; stream = C_NULL)
+
+What `ForwardDiff.jacobian` gives through `BMT.bulk_microphysics_tendencies(BMT.Instantaneous(), BMT.Microphysics1Moment(), mp, tps, ρ, T, q_tot, q_lcl,
+q_icl, q_rai, q_sno)` with respect to (T, q_tot, q_lcl, q_icl, q_rai, q_sno), over columns: the device evaluates the same point function on forward-mode
+dual numbers.  `jac` = `CMX_MP1M_JAC_NCOL` (24) device columns or `nothing`s, `jac[o * 6 + i + 1]` = ∂out_o/∂in_i with out = (dq_lcl_dt, dq_icl_dt,
+dq_rai_dt, dq_sno_dt) and in as above (0-based o, i: the order of `cmx_mp1m_jac_out` / `cmx_mp1m_jac_wrt`); an input whose four columns are all `nothing`
+is not differentiated.  `tendencies` = `nothing` or 4 columns (or `nothing`s): the tendencies themselves, bit-identical to
+`bulk_microphysics_tendencies!`.  Every `Microphysics1MOptions` combination is accepted (`option_bits`).
+"""
+function jacobian_1m!(jac, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno;
+    stream = C_NULL) where {FT}
+    length(jac) == CMX_MP1M_JAC_NCOL || error("jac: $(CMX_MP1M_JAC_NCOL) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_jacobian", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), _ptrs(FT, jac), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_jacobian")
+    return jac
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params

@@ -1,0 +1,131 @@
+"""States, reference and error measure shared by tests/test_mp1m_jacobian_host.py and tests/test_mp1m_jacobian_gpu.py.
+
+The reference Jacobian is the method of tests/jacobian_cases.py (the reference's own, test/ad_compat_tests.jl:143-165): central differences of the Float64
+ORACLE tendencies (oracle_binding.mp1m, _abi.F64, want_sources=False) with step h = 1e-6·|x_j|, the quotient formed with the realised x⁺ − x⁻, compared row
+by row in the scale s_i = max_j max(|J_ij|, |J^fd_ij|).  A state is KEPT only if the references at h and at 4h agree within 2e-6 in that measure: a state
+that sits on a kink of the tendency function (the saturation limiters, a min / max changing sides inside the stencil) has no derivative to compare with.  At
+most 1 % of a set may be set aside (asserted where the set is built).
+
+Sets: "cold" (T ∈ (235, 272.65)) and "warm" (T ∈ (273.65, 300)), 4096 states each with all four species present and T at least 0.5 K away from T_freeze,
+and "points", the two single states the repository pins for the 1-moment scheme.  Parameter cases: "default" (the compile-time instantiation), "alt" (the
+four alternative options: the run-time-flags instantiation) and "exponents" (default options, five size-relation parameters overridden: the run-time-flags
+instantiation with general exponents).
+
+Bounds: Float64 1e-5, the reference's own Jacobian bound (ad_compat_tests.jl:163); Float32 against the SAME Float64 reference at the project's Float32 bound
+1e-3, every row.
+"""
+import functools
+
+import numpy as np
+
+from cmx import _abi
+from cmx import parameters as P
+from jacobian_cases import scaled_error
+
+WRT = _abi.MP1M_JAC_WRT            # T, q_tot, q_lcl, q_icl, q_rai, q_sno = columns 1 … 6 of the state
+OUT = _abi.MP1M_JAC_OUT
+BOUND = {"f64": 1e-5, "f32": 1e-3}
+AGREE = 2e-6
+MAX_SET_ASIDE = 0.01
+N_STATES = 4096
+T_RANGE = {"cold": (235.0, 272.65), "warm": (273.65, 300.0)}
+
+# order rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno: the state of the plain-C caller (tests/test_abi_caller.py:152) and the reference suite's warm
+# all-species state (test/bulk_tendencies_tests.jl:919-977, tests/test_mp1m_linearized.py:52-56)
+CALLER = (1.2, 268.0, 6e-3, 5e-4, 5e-4, 5e-4, 5e-4)
+SUITE_WARM = (1.2, 273.15 + 5.0, 0.012, 5e-4, 2e-4, 3e-4, 3e-4)
+
+ALT_OPTIONS = dict(cloud_ice_formation=P.TemperatureDependent(), rain_autoconversion=P.PrescribedNd(), snow_autoconversion=P.WithSupersaturation(),
+                   snow_deposition_sublimation=P.SublimationOnly())
+EXPONENT_OVERRIDES = {"rain_terminal_velocity_size_relation_coefficient_ve": 0.47, "snow_terminal_velocity_size_relation_coefficient": 0.27,
+                      "rain_terminal_velocity_size_relation_coefficient_delv": 0.1, "snow_mass_size_relation_coefficient_delm": 0.05,
+                      "snow_flake_size_distribution_coefficient_nu": 0.6}
+CASES = ("default", "alt", "exponents")
+SETS = ("cold", "warm", "points")
+
+
+def params(ft, case):
+    """Microphysics1MParams of a parameter case."""
+    opts = ALT_OPTIONS if case == "alt" else {}
+    return P.Microphysics1MParams(P.create_toml_dict(ft, EXPONENT_OVERRIDES) if case == "exponents" else ft, **opts)
+
+
+def q_sat_liquid(oracle, T, rho):
+    tps = P.ThermodynamicsParameters("f64")
+    p = np.array([oracle.psat_liquid(_abi.F64, tps, float(t)) for t in T])
+    return p / (rho * tps.R_v * T)
+
+
+def states(oracle, which, n=N_STATES, seed=11):
+    """All four species present, T at least 0.5 K from T_freeze (the issue's recipe, drawn in this order)."""
+    lo, hi = T_RANGE[which]
+    rng = np.random.default_rng(seed)
+    rho = rng.uniform(0.4, 1.2, n)
+    T = rng.uniform(lo, hi, n)
+    q_lcl, q_icl = 10.0 ** rng.uniform(-6.0, -3.0, n), 10.0 ** rng.uniform(-6.0, -3.0, n)
+    q_rai, q_sno = 10.0 ** rng.uniform(-6.0, -2.7, n), 10.0 ** rng.uniform(-6.0, -2.7, n)
+    q_tot = (q_lcl + q_icl + q_rai + q_sno) + q_sat_liquid(oracle, T, rho) * rng.uniform(0.5, 1.05, n)
+    return [rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno]
+
+
+def points(*sts):
+    return [np.array([s[k] for s in sts], dtype=np.float64) for k in range(7)]
+
+
+def oracle_tendencies(oracle, mp64, cols):
+    r = oracle.mp1m(_abi.F64, mp64.c, P.ThermodynamicsParameters("f64"), mp64.flags, *[np.ascontiguousarray(c, dtype=np.float64) for c in cols],
+                    nthreads=8, want_sources=False)
+    return np.stack([r[k] for k in OUT])
+
+
+def fd_jacobian(oracle, mp64, cols, step=1e-6):
+    """[4, 6, n]: central differences with h = step·|x_j|, divided by the realised x⁺ − x⁻."""
+    cols = [np.asarray(c, dtype=np.float64) for c in cols]
+    J = np.empty((4, 6, cols[0].size))
+    for j in range(6):
+        x = cols[j + 1]
+        h = step * np.abs(x)
+        xp, xm = x + h, x - h
+        fp = oracle_tendencies(oracle, mp64, cols[:j + 1] + [xp] + cols[j + 2:])
+        fm = oracle_tendencies(oracle, mp64, cols[:j + 1] + [xm] + cols[j + 2:])
+        J[:, j] = (fp - fm) / (xp - xm)
+    return J
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(case, which):
+    import oracle_binding as oracle
+    oracle.lib()
+    mp64 = params("f64", case)
+    cols = points(CALLER, SUITE_WARM) if which == "points" else states(oracle, which)
+    J1, J4 = fd_jacobian(oracle, mp64, cols), fd_jacobian(oracle, mp64, cols, step=4e-6)
+    disagree = scaled_error(J1, J4).max(axis=0)
+    kept = disagree <= AGREE
+    for a in (*cols, J1, kept, disagree):
+        a.setflags(write=False)
+    return cols, J1, kept, disagree
+
+
+def reference(case, which):
+    """(cols, J_fd, kept, worst h-vs-4h disagreement) of a set, computed once and shared read-only; asserts the 1 % condition."""
+    cols, J, kept, disagree = _reference(case, which)
+    assert (~kept).sum() <= MAX_SET_ASIDE * kept.size, (case, which, int((~kept).sum()), kept.size, float(disagree.max()))
+    return cols, J, kept, float(disagree.max())
+
+
+def worst_rows(J, J_ref, kept):
+    """Worst scaled error per output row over the kept states: {row name: value}."""
+    e = scaled_error(J, J_ref)[:, kept]
+    return {name: float(e[i].max()) for i, name in enumerate(OUT)}
+
+
+def assert_parity(ft, J, case, which, what):
+    """The parity assertion of both test files: every row of every kept state inside BOUND[ft] in the per-row measure.  Prints and returns the worst scaled
+    error per row."""
+    cols, J_ref, kept, worst_fd = reference(case, which)
+    assert np.isfinite(np.asarray(J)[:, :, kept]).all(), (what, case, which)          # (a NaN would leave the row scale undefined, not large)
+    rows = worst_rows(J, J_ref, kept)
+    print(f"{what} {ft} {case} {which}: kept {int(kept.sum())}/{kept.size}, h-vs-4h {worst_fd:.3g}, worst rows " + ", ".join(f"{k} {v:.3g}" for k, v in rows.items()))
+    for name, v in rows.items():
+        assert v < BOUND[ft], (what, case, which, name, v)
+    return rows
