@@ -13,6 +13,23 @@ instantiation with general exponents).
 
 Bounds: Float64 1e-5, the reference's own Jacobian bound (ad_compat_tests.jl:163); Float32 against the SAME Float64 reference at the project's Float32 bound
 1e-3, every row.
+
+Both bounds are asserted in two measures (tests/jacobian_cases.py, "THE SECOND MEASURE"): the per-row one above and the input-scaled one,
+e_ij = |J_ij − J^ref_ij|·|x_j| / s'_i with s'_i = max_j max(|J_ij|, |J^ref_ij|)·|x_j| and x the reference's Float64 state columns, every (row, column), no
+exception.  The per-row scale is set by the q columns: the largest share of a T entry at any kept state is 2.3e-3, so the whole T column scaled by 1.1 shows
+as 7e-5 … 2.3e-4 there and passes Float32 — a T-derivative wrong by 40 % would; in the input-scaled measure it shows as 0.091.  A state is kept only if h and
+4h agree within 2e-6 in both measures; the cap of 1 % applies to the union (set aside of 4096: default 3 cold / 2 warm, alt 5 / 2, exponents 3 / 2).  That both
+measures can fail is tested in tests/test_mp1m_jacobian_host.py: every input column scaled by 1.1, zeroed or negated is rejected on every (case, set), and
+every one of the 24 entries reaches 1 % of its row in one of the measures on the cold and on the warm set (smallest share 0.03: dq_sno_dt × (q_tot, q_lcl),
+warm; 0.21 … 0.26 for dq_sno_dt × q_lcl and dq_rai_dt × q_tot, cold; every other ≥ 0.47).
+
+Worst input-scaled value per row over the three cases and three sets (column, case and set of the worst in brackets), host build | device (MI355X):
+  Float64   dq_lcl_dt 2.9e-10 | 2.9e-10 (q_lcl, alt cold)   dq_icl_dt 9.7e-8 | 9.7e-8 (T, alt cold)   dq_rai_dt 1.5e-9 | 1.5e-9 (T, default warm)   dq_sno_dt 7.9e-10 | 7.9e-10 (q_rai, default cold)
+  Float32   dq_lcl_dt 2.2e-6 | 2.6e-6 (T, default cold)   dq_icl_dt 5.0e-4 | 4.9e-4 (T, alt cold)   dq_rai_dt 6.0e-5 | 4.6e-5 (T, alt | default warm)   dq_sno_dt 6.6e-6 | 6.0e-6 (q_rai, alt cold)
+dq_icl_dt × T with the alternative options on the cold set is the one entry within a factor 2 of the Float32 bound, in the host build and on the device alike
+— 13 of 4091 kept states lie above 6e-5, all at T = 252.4 … 255.1 K, where ∂dq_icl_dt/∂T changes sign with these options and the entry is the small
+difference of terms of opposite sign (relative error of the entry itself 7e-3 at the worst state).  It meets the plain 1e-3 and is held to it like every
+other entry.  No entry has a bound of its own.
 """
 import functools
 
@@ -20,7 +37,7 @@ import numpy as np
 
 from cmx import _abi
 from cmx import parameters as P
-from jacobian_cases import scaled_error
+from jacobian_cases import assert_resolution, cells_line, disagreement, scaled_error, worst_cells  # noqa: F401
 
 WRT = _abi.MP1M_JAC_WRT            # T, q_tot, q_lcl, q_icl, q_rai, q_sno = columns 1 … 6 of the state
 OUT = _abi.MP1M_JAC_OUT
@@ -99,7 +116,7 @@ def _reference(case, which):
     mp64 = params("f64", case)
     cols = points(CALLER, SUITE_WARM) if which == "points" else states(oracle, which)
     J1, J4 = fd_jacobian(oracle, mp64, cols), fd_jacobian(oracle, mp64, cols, step=4e-6)
-    disagree = scaled_error(J1, J4).max(axis=0)
+    disagree = disagreement(J1, J4, cols[1:])
     kept = disagree <= AGREE
     for a in (*cols, J1, kept, disagree):
         a.setflags(write=False)
@@ -119,13 +136,19 @@ def worst_rows(J, J_ref, kept):
     return {name: float(e[i].max()) for i, name in enumerate(OUT)}
 
 
-def assert_parity(ft, J, case, which, what):
-    """The parity assertion of both test files: every row of every kept state inside BOUND[ft] in the per-row measure.  Prints and returns the worst scaled
-    error per row."""
+def assert_parity(ft, J, case, which, what, report=True):
+    """The parity assertion of both test files, in BOTH measures: every row of every kept state inside BOUND[ft] in the per-row measure, and every
+    (row, column) of every kept state inside the same BOUND[ft] in the input-scaled one.  Prints (report=True) and returns the worst scaled error per row
+    and the worst input-scaled error per (row, column)."""
     cols, J_ref, kept, worst_fd = reference(case, which)
     assert np.isfinite(np.asarray(J)[:, :, kept]).all(), (what, case, which)          # (a NaN would leave the row scale undefined, not large)
     rows = worst_rows(J, J_ref, kept)
-    print(f"{what} {ft} {case} {which}: kept {int(kept.sum())}/{kept.size}, h-vs-4h {worst_fd:.3g}, worst rows " + ", ".join(f"{k} {v:.3g}" for k, v in rows.items()))
+    cells = worst_cells(J, J_ref, cols[1:], kept)
+    if report:
+        print(f"{what} {ft} {case} {which}: kept {int(kept.sum())}/{kept.size}, h-vs-4h {worst_fd:.3g}, worst rows " + ", ".join(f"{k} {v:.3g}" for k, v in rows.items())
+              + f"\n  input-scaled, worst {cells.max():.3g} — " + cells_line(cells, OUT, WRT))
     for name, v in rows.items():
         assert v < BOUND[ft], (what, case, which, name, v)
-    return rows
+    for i, j in zip(*np.nonzero(~(cells < BOUND[ft]))):
+        raise AssertionError((what, case, which, "input-scaled", OUT[i], WRT[j], float(cells[i, j])))
+    return rows, cells

@@ -4,6 +4,11 @@
     (tests/native/jacobian_1m_host.cpp) against central differences of the Float64 oracle — tests/jacobian_1m_cases.py has the states, the reference and
     the measure — at the reference's own bound 1e-5 (test/ad_compat_tests.jl:163) in Float64 and the project's Float32 bound 1e-3 in every row in Float32
     (worst Float32 row in this build: 1.5e-4, dq_icl_dt with the alternative options on the cold set);
+  * the same parity in the second, input-scaled measure of tests/jacobian_cases.py (every entry weighted by |x_j|: it shows the T column, which the
+    per-row scale hides behind the q columns) at the same two bounds: host build worst 9.7e-8 in Float64; 5.0e-4 in Float32 (dq_icl_dt × T, alternative
+    options, cold set; every other entry ≤ 6.0e-5);
+  * that both measures can fail: every input column scaled by 1.1, zeroed or negated is rejected, every entry reaches 1 % of its row in one of the
+    measures on the cold and on the warm set, and every entry wrong by 0.2 % / 20 % is rejected;
   * the value parts against the plain instantiation, bit for bit; the columns against the tangent width K, bit for bit;
   * finiteness on every present / absent combination of the four species on both sides of T_freeze and on the broad synthetic set;
   * exact zeros from processes switched off by their option; the poison rules;
@@ -85,12 +90,74 @@ def _synthetic(ft):
 @pytest.mark.parametrize("ft", ["f64", "f32"])
 @pytest.mark.parametrize("case", JC.CASES)
 def test_host_jacobian_matches_central_differences_of_the_oracle(host, oracle, ft, case):
-    """Float64: every row of every kept state within the reference's own 1e-5.  Float32, same Float64 reference: every row within 1e-3."""
+    """Float64: every row of every kept state within the reference's own 1e-5.  Float32, same Float64 reference: every row within 1e-3.  Both in the
+    per-row and, every (row, column), in the input-scaled measure."""
     mp = JC.params(ft, case)
     for which in JC.SETS:
         J, _, rc = host_jacobian(host, ft, mp, JC.reference(case, which)[0])
         assert rc == (1 if case == "default" else 0)         # which instantiation ran: the one flags_1m selects
         JC.assert_parity(ft, J, case, which, "host")
+
+
+# ---- the two measures can fail ------------------------------------------------------------------------------------------------------------------
+MUTATIONS = (("scaled by 1.1", 1.1), ("zeroed", 0.0), ("negated", -1.0))
+
+
+def _rejected(ft, M, case, which):
+    try:
+        JC.assert_parity(ft, M, case, which, "mutated", report=False)
+    except AssertionError:
+        return True
+    return False
+
+
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("case", JC.CASES)
+def test_a_corrupted_column_is_rejected(host, oracle, ft, case):
+    """Each of the six input columns of the host-build Jacobian, whole, scaled by 1.1, zeroed or negated: assert_parity raises, in both float types, on
+    every set.  (The row measure alone accepts the T column scaled by 1.1 in Float32: test_the_row_measure_alone_does_not_see_the_T_column.)"""
+    mp = JC.params(ft, case)
+    for which in JC.SETS:
+        cols, J_ref, kept, _ = JC.reference(case, which)
+        J, _, _ = host_jacobian(host, ft, mp, cols)
+        assert not _rejected(ft, J, case, which)
+        for j, name in enumerate(JC.WRT):
+            assert np.any(J_ref[:, j, kept] != 0), name
+            for kind, f in MUTATIONS:
+                M = np.array(J)
+                M[:, j] *= NPT[ft](f)
+                assert _rejected(ft, M, case, which), (which, name, kind)
+
+
+@pytest.mark.parametrize("case", JC.CASES)
+def test_the_row_measure_alone_does_not_see_the_T_column(host, oracle, case):
+    """Why the second measure exists: with the T column 10 % wrong at every state the per-row measure stays inside the FLOAT32 bound on both interior
+    sets, the input-scaled one shows 0.1/1.1."""
+    for which in ("cold", "warm"):
+        cols, J_ref, kept, _ = JC.reference(case, which)
+        J, _, _ = host_jacobian(host, "f64", JC.params("f64", case), cols)
+        M = np.array(J)
+        M[:, 0] *= 1.1
+        assert max(JC.worst_rows(M, J_ref, kept).values()) < JC.BOUND["f32"], which
+        assert abs(JC.worst_cells(M, J_ref, cols[1:], kept).max() - 0.1 / 1.1) < 1e-6, which
+
+
+@pytest.mark.parametrize("case", JC.CASES)
+def test_every_entry_of_the_reference_is_resolved_by_the_interior_sets(host, oracle, case):
+    """From the reference alone: all 24 entries are non-zero on the cold and on the warm set, and each reaches at least 1 % of its row in one of the two
+    measures at some kept state (jacobian_cases.assert_resolution prints the relative error each entry is resolved to; the smallest share is 0.03,
+    dq_sno_dt × (q_tot, q_lcl) on the warm sets).  Then the same with the code under test: every entry of the host-build Jacobian wrong by 0.2 % (Float64)
+    or 20 % (Float32) at every state is rejected — twice the error the 1 % share promises to see."""
+    for which in ("cold", "warm"):
+        cols, J_ref, kept, _ = JC.reference(case, which)
+        share, nonzero = JC.assert_resolution(J_ref, cols[1:], kept, JC.OUT, JC.WRT, f"1-moment {case} {which}")
+        assert nonzero.all()
+        for ft, f in (("f64", 1.002), ("f32", 1.2)):
+            J, _, _ = host_jacobian(host, ft, JC.params(ft, case), cols)
+            for i, j in zip(*np.nonzero(nonzero)):
+                M = np.array(J)
+                M[i, j] *= NPT[ft](f)
+                assert _rejected(ft, M, case, which), (which, ft, JC.OUT[i], JC.WRT[j], float(share[i, j]))
 
 
 def test_the_exponent_overrides_leave_the_default_exponent_instantiation(host, oracle):

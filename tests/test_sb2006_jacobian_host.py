@@ -5,6 +5,10 @@
     measure — at the reference's own bound 1e-5 (test/ad_compat_tests.jl:163) in Float64 and the project's Float32 bound 1e-3 in every row in Float32 —
     except dn_rai_dt with the perturbed parameter set, which misses it at ONE state (2.2e-3 here, 2.3e-3 on the device) and is held entry by entry to the
     bound its evaporation share earns from the oracle's own Float32-against-Float64 spread of the evaporation rate (jacobian_cases.float32_bound);
+  * the same parity in the second, input-scaled measure of tests/jacobian_cases.py (every entry weighted by |x_j|: the T and number columns, which the
+    per-row scale hides behind the q columns) at the same two bounds, no exception: host build worst 2.3e-8 in Float64, 5.2e-6 in Float32;
+  * that both measures can fail: every input column scaled by 1.1, zeroed or negated is rejected, every structurally non-zero entry reaches 1 % of its
+    row in one of the measures on the interior set, and every such entry wrong by 0.2 % / 20 % is rejected;
   * the value parts against the plain instantiation, bit for bit; the columns against the tangent width K, bit for bit;
   * finiteness at the reference's boundary state and on every present / absent combination of the four species;
   * the argument statuses of the two entries and the Python wrapper's errors.
@@ -84,12 +88,93 @@ CASES = [(True, False), (False, False), (True, True)]        # (limited, perturb
 @pytest.mark.parametrize("limited,perturbed", CASES)
 def test_host_jacobian_matches_central_differences_of_the_oracle(host, oracle, ft, limited, perturbed):
     """Float64: every row of every kept state within the reference's own 1e-5.  Float32, same Float64 reference: every row within 1e-3, except dn_rai_dt
-    with the perturbed parameter set, held entry by entry to jacobian_cases.float32_bound (worst values observed: DESIGN.md §6)."""
+    with the perturbed parameter set, held entry by entry to jacobian_cases.float32_bound (worst values observed: DESIGN.md §6).  Input-scaled measure:
+    every (row, column) within the same 1e-5 / 1e-3, no exception."""
     wr = JC.warm_rain_params(ft, limited, JC.perturbed_overrides() if perturbed else None)
     for which in ("interior", "points"):
         J, _, rc = host_jacobian(host, ft, wr, limited, JC.reference(limited, perturbed, which)[0])
         assert rc == (0 if perturbed else 1)                 # which instantiation ran: the one sb_integer_exponents selects
         JC.assert_parity(ft, J, limited, perturbed, which, "host")
+
+
+# ---- the two measures can fail ------------------------------------------------------------------------------------------------------------------
+MUTATIONS = (("scaled by 1.1", 1.1), ("zeroed", 0.0), ("negated", -1.0))
+# the entries that do not exist: dq_lcl_dt does not see n_rai, dn_lcl_dt sees neither T, q_tot nor n_rai (no condensation term in the number)
+STRUCTURAL_ZEROS = {("dq_lcl_dt", "n_rai"), ("dn_lcl_dt", "T"), ("dn_lcl_dt", "q_tot"), ("dn_lcl_dt", "n_rai")}
+
+
+def _rejected(ft, M, limited, perturbed, which):
+    try:
+        JC.assert_parity(ft, M, limited, perturbed, which, "mutated", report=False)
+    except AssertionError:
+        return True
+    return False
+
+
+@pytest.mark.parametrize("ft", ["f64", "f32"])
+@pytest.mark.parametrize("limited,perturbed", CASES)
+def test_a_corrupted_column_is_rejected(host, oracle, ft, limited, perturbed):
+    """Each of the six input columns of the host-build Jacobian, whole, scaled by 1.1, zeroed or negated: assert_parity raises, in both float types, on
+    the interior set and on the pinned states.  (The row measure alone accepts the n_lcl and n_rai columns scaled, zeroed or negated in both float types
+    and the T column scaled in Float32: test_the_row_measure_alone_does_not_see_the_number_columns.)"""
+    wr = JC.warm_rain_params(ft, limited, JC.perturbed_overrides() if perturbed else None)
+    for which in ("interior", "points"):
+        cols, J_ref, kept, _ = JC.reference(limited, perturbed, which)
+        J, _, _ = host_jacobian(host, ft, wr, limited, cols)
+        assert not _rejected(ft, J, limited, perturbed, which)
+        for j, name in enumerate(JC.WRT):
+            assert np.any(J_ref[:, j, kept] != 0), name
+            for kind, f in MUTATIONS:
+                M = np.array(J)
+                M[:, j] *= NPT[ft](f)
+                assert _rejected(ft, M, limited, perturbed, which), (which, name, kind)
+
+
+@pytest.mark.parametrize("limited,perturbed", CASES)
+def test_the_row_measure_alone_does_not_see_the_number_columns(host, oracle, limited, perturbed):
+    """Why the second measure exists: with the n_lcl column 10 % wrong at every state the per-row measure stays inside the FLOAT64 bound, with the n_rai
+    column inside the Float32 one (2.5e-6 with the default parameters, 1.5e-5 with the perturbed set); the input-scaled one shows 0.1/1.1."""
+    cols, J_ref, kept, _ = JC.reference(limited, perturbed, "interior")
+    J, _, _ = host_jacobian(host, "f64", JC.warm_rain_params("f64", limited, JC.perturbed_overrides() if perturbed else None), limited, cols)
+    for name, ft in (("n_lcl", "f64"), ("n_rai", "f32")):
+        M = np.array(J)
+        M[:, JC.WRT.index(name)] *= 1.1
+        assert max(JC.worst_rows(M, J_ref, kept).values()) < JC.BOUND[ft], name
+        assert abs(JC.worst_cells(M, J_ref, cols[1:], kept).max() - 0.1 / 1.1) < 1e-6, name
+
+
+@pytest.mark.parametrize("limited,perturbed", CASES)
+def test_every_entry_of_the_reference_is_resolved_by_the_interior_set(host, oracle, limited, perturbed):
+    """From the reference alone: every structurally non-zero entry reaches at least 1 % of its row in one of the two measures at some kept state
+    (jacobian_cases.assert_resolution prints the relative error each entry is resolved to), and the entries that are zero are the four that do not
+    exist.  Then the same with the code under test: every such entry of the host-build Jacobian wrong by 0.2 % (Float64) or 20 % (Float32) at every state
+    is rejected — twice the error the 1 % share promises to see."""
+    cols, J_ref, kept, _ = JC.reference(limited, perturbed, "interior")
+    share, nonzero = JC.assert_resolution(J_ref, cols[1:], kept, JC.OUT, JC.WRT, f"SB2006 limited={limited} perturbed={perturbed} interior")
+    assert {(JC.OUT[i], JC.WRT[j]) for i, j in zip(*np.nonzero(~nonzero))} == STRUCTURAL_ZEROS
+    for ft, f in (("f64", 1.002), ("f32", 1.2)):
+        J, _, _ = host_jacobian(host, ft, JC.warm_rain_params(ft, limited, JC.perturbed_overrides() if perturbed else None), limited, cols)
+        for i, j in zip(*np.nonzero(nonzero)):
+            M = np.array(J)
+            M[i, j] *= NPT[ft](f)
+            assert _rejected(ft, M, limited, perturbed, "interior"), (ft, JC.OUT[i], JC.WRT[j], float(share[i, j]))
+
+
+def test_input_scaled_error_edges():
+    """A row with s'_i = 0 must be exactly zero; a non-finite entry gives Inf; the weights are the reference's state columns."""
+    x = [np.array([2.0, 0.0, 1.0])] + [np.array([1e-4, 1e-4, 1e-4])] * 5
+    J_ref = np.zeros((4, 6, 3))
+    J_ref[0, 0], J_ref[0, 1] = 1.0, 3e4
+    J = J_ref.copy()
+    assert np.all(JC.input_scaled_error(J, J_ref, x) == 0)
+    J[0, 0, 0] = 1.5                                     # s' = max(1.5·2, 3) = 3: error 0.5·2/3
+    J[0, 0, 1] = 1.5                                     # x_0 = 0 at state 1: invisible in this measure (the row measure sees it)
+    J[1, 0, 1] = 1e-30                                   # s' = 0 (x_0 = 0 and the reference row is zero): the row must be exactly zero
+    J[2, 3, 0] = np.nan
+    e = JC.input_scaled_error(J, J_ref, x)
+    assert e[0, 0, 0] == pytest.approx(1.0 / 3.0) and e[0, 0, 1] == 0 and e[0, 1, 0] == 0
+    assert e[1, 0, 1] == np.inf and np.all(e[1, 1:, 1] == 0) and np.all(e[1, :, [0, 2]] == 0)
+    assert e[2, 3, 0] == np.inf and np.all(e[3] == 0)
 
 
 # ---- the primal ---------------------------------------------------------------------------------------------------------------------------------
