@@ -21,7 +21,7 @@
  *              algorithm of netlib zeroin.f / Numerical Recipes zbrent) — passes that suite (worst 5e-7 at 10, 7e-4 at 8 iterations);
  *   variant 1 (rounds 1-5)             the pseudo-code of the Wikipedia article "Brent's method" (c := b every iteration: after a
  *              step that replaces `a` every proposal is refused until `b` moves) — FAILS it (1e-3 at 10, 3e-3 at 8 iterations),
- *              kept for the exposure measurement of tests/test_reference_suites.py.
+ *              kept for the exposure measurement of tests/test_reference_suites.py; tests/test_p3_shape_roots.py selects it and asserts that failure.
  */
 /* Quadrature rules beyond the ABI's struct (cmx_quadrature carries ≤ CMX_QUAD_MAX = 128 nodes; the reference's quadrature-order sweep compares
  * against order 200, test/bulk_tendencies_quadrature_tests.jl:232): a rule set here replaces the `quad` argument of every P3 integral of this

@@ -8,7 +8,10 @@ How logλ is compared.  The shape residual logLdivN(logλ) − log(L/N) is NOT m
 the oracle, so the two are compared iterate-for-iterate: every point must agree to the north-star tolerance except a
 counted handful (< 0.1 %) where a rounding-level difference flipped a Brent branch decision in a multi-root state.
 With a converged budget (brent_iters = 40) the same holds against the converged oracle, and every disagreeing point is
-certified to be a genuine root of the residual (|residual| ≤ 1e-6), i.e. another solution of the same equation."""
+certified to be a genuine root of the residual (|residual| ≤ 1e-6), i.e. another solution of the same equation.
+
+These are parity statements: device and oracle are restatements by the same hand.  The statement about CORRECTNESS of the shape
+solve — against high-precision roots of the equation, with no state set aside — is tests/test_p3_shape_roots_gpu.py."""
 import itertools
 import json
 import math
