@@ -24,6 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
+from ._jacobian import _jacobian
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -158,46 +159,9 @@ def warm_rain_jacobian_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, wr
     `[o, k]` / `[o]` must be contiguous).  An implicit step solves (I − Δt·J) δ = Δt·f per point from these columns.
     Asynchronous on `stream` (default: torch's current stream)."""
     wr = _warm_rain(mp)
-    wrt = tuple(wrt)
-    for name in wrt:
-        if name not in JACOBIAN_WRT:
-            raise ValueError(f"wrt: unknown input '{name}' (one of {JACOBIAN_WRT}; rho is not differentiated)")
-    if len(set(wrt)) != len(wrt):
-        raise ValueError("wrt: an input is listed twice")
-    if not wrt and not with_tendencies:
-        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
-    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
-    ref = _check_cols(cols, ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai"))
-    fam = _fam_of(ref)
-    if fam is not wr.fam or not isinstance(tps, fam.thermo):
-        raise TypeError("parameter float type does not match the state columns")
-    nout = _abi.CMX_SB2006_JAC_NOUT
-    jac, tend = out if out is not None else (None, None)
-    if jac is None:
-        jac = torch.empty((nout, len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
-    elif jac.shape != (nout, len(wrt), *ref.shape):
-        raise ValueError(f"out: jac must have shape (4, len(wrt), *rho.shape) = {(nout, len(wrt), *ref.shape)}")
-    if with_tendencies:
-        if tend is None:
-            tend = torch.empty((nout, *ref.shape), dtype=ref.dtype, device=ref.device)
-        elif tend.shape != (nout, *ref.shape):
-            raise ValueError(f"out: tendencies must have shape (4, *rho.shape) = {(nout, *ref.shape)}")
-    elif tend is not None:
-        raise ValueError("out: a tendencies tensor was given but with_tendencies is False")
-    if wrt:
-        _check_cols([ref] + [jac[o, k] for o in range(nout) for k in range(len(wrt))], ["rho"] + ["jac"] * (nout * len(wrt)))
-    if tend is not None:
-        _check_cols([ref] + [tend[o] for o in range(nout)], ["rho"] + ["tendencies"] * nout)
-    ptrs = [None] * _abi.CMX_SB2006_JAC_NCOL
-    for k, name in enumerate(wrt):
-        for o in range(nout):
-            ptrs[o * _abi.CMX_SB2006_JAC_NWRT + JACOBIAN_WRT.index(name)] = jac[o, k].data_ptr()
-    jac_p = (C.c_void_p * _abi.CMX_SB2006_JAC_NCOL)(*ptrs)
-    tend_p = (C.c_void_p * nout)(*[tend[o].data_ptr() for o in range(nout)]) if tend is not None else None
-    flags = _abi.CMX_SB2006_LIMITED if wr.is_limited else 0
-    _lib.call("cmx_sb2006_warm_rain_jacobian", fam, ref.device, C.byref(wr.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], jac_p, tend_p,
-              stream=stream)
-    return WarmRainJacobian2M(jac, tend, wrt)
+    return WarmRainJacobian2M(*_jacobian("cmx_sb2006_warm_rain_jacobian", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                                         (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai"), JACOBIAN_WRT,
+                                         _abi.CMX_SB2006_JAC_NOUT, wrt, with_tendencies, out, stream))
 
 
 AOS_FIELDS = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt")

@@ -18,6 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
+from ._jacobian import _jacobian
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -127,42 +128,8 @@ def jacobian_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, wrt=JACOBIAN
     Asynchronous on `stream` (default: torch's current stream)."""
     if not isinstance(mp, Microphysics1MParams):
         raise TypeError("mp must be Microphysics1MParams")
-    wrt = tuple(wrt)
-    for name in wrt:
-        if name not in JACOBIAN_WRT_1M:
-            raise ValueError(f"wrt: unknown input '{name}' (one of {JACOBIAN_WRT_1M}; rho is not differentiated)")
-    if len(set(wrt)) != len(wrt):
-        raise ValueError("wrt: an input is listed twice")
-    if not wrt and not with_tendencies:
-        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
-    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
-    ref, fam = _prep(mp, tps, cols)
-    nout, nwrt = _abi.CMX_MP1M_JAC_NOUT, _abi.CMX_MP1M_JAC_NWRT
-    jac, tend = out if out is not None else (None, None)
-    if jac is None:
-        jac = torch.empty((nout, len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
-    elif jac.shape != (nout, len(wrt), *ref.shape):
-        raise ValueError(f"out: jac must have shape (4, len(wrt), *rho.shape) = {(nout, len(wrt), *ref.shape)}")
-    if with_tendencies:
-        if tend is None:
-            tend = torch.empty((nout, *ref.shape), dtype=ref.dtype, device=ref.device)
-        elif tend.shape != (nout, *ref.shape):
-            raise ValueError(f"out: tendencies must have shape (4, *rho.shape) = {(nout, *ref.shape)}")
-    elif tend is not None:
-        raise ValueError("out: a tendencies tensor was given but with_tendencies is False")
-    if wrt:
-        _check_cols([ref] + [jac[o, k] for o in range(nout) for k in range(len(wrt))], ["rho"] + ["jac"] * (nout * len(wrt)))
-    if tend is not None:
-        _check_cols([ref] + [tend[o] for o in range(nout)], ["rho"] + ["tendencies"] * nout)
-    ptrs = [None] * _abi.CMX_MP1M_JAC_NCOL
-    for k, name in enumerate(wrt):
-        for o in range(nout):
-            ptrs[o * nwrt + JACOBIAN_WRT_1M.index(name)] = jac[o, k].data_ptr()
-    jac_p = (C.c_void_p * _abi.CMX_MP1M_JAC_NCOL)(*ptrs)
-    tend_p = (C.c_void_p * nout)(*[tend[o].data_ptr() for o in range(nout)]) if tend is not None else None
-    _lib.call("cmx_mp1m_jacobian", fam, ref.device, C.byref(mp.c), C.byref(tps), mp.flags, ref.numel(), *[_ptr(t) for t in cols], jac_p, tend_p,
-              stream=stream)
-    return Jacobian1M(jac, tend, wrt)
+    return Jacobian1M(*_jacobian("cmx_mp1m_jacobian", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M,
+                                 _abi.CMX_MP1M_JAC_NOUT, wrt, with_tendencies, out, stream))
 
 
 def bulk_microphysics_tendencies_1m_fields(mode, scheme, mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt=None, nsub=1, *, q_min=None, out=None,

@@ -9,7 +9,8 @@
 // (uniform loads), so one instantiation per float type and FLAGS serves every selection of columns, and a subset in any order computes, per column, exactly
 // the instruction sequence of the full call.  Every pass recomputes the primal and every pass's primal is the plain instantiation's, bit for bit.  Stores
 // are plain whole-column vector stores (one element per lane).  No LDS beyond the Float64 math tables every Float64 kernel of the library stages
-// (cmx_lean_f64.hpp), no inline assembly here.  The point's body is shared with the host test build (cmx_mp1m_jacobian.hpp).
+// (cmx_lean_f64.hpp), no inline assembly here.  The kernel and the point's body are the shared driver's (jacobian_kernel<Mp1mJac<FLAGS>, …>, cmx_jacobian.hpp);
+// the scheme it runs is shared with the host test build (cmx_mp1m_jacobian.hpp).
 //
 // FLAGS: the compile-time default-options / default-exponents instantiation or the run-time-flags one, chosen by flags_1m() as in cmx_mp1m_tendencies_*.
 // K per float type (kJac1mK, cmx_mp1m_jacobian.hpp) from the register counts of a cross-compiled build (tools/kernel_resources.py; DESIGN.md §9 has the
@@ -27,19 +28,6 @@ namespace cmx {
 #endif
 constexpr int kJac1mBS = CMX_JAC1M_BS;
 
-template <typename FT, int K, uint32_t FLAGS>
-__global__ __launch_bounds__(kJac1mBS) void mp1m_jacobian_kernel(const Mp1mConsts<FT> c, const Mp1mJacArgs<FT, K> a, const int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * kJac1mBS + threadIdx.x;
-    FT x[7];
-    if (i < n) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
-    }
-    Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
-    if (i >= n) return;
-    mp1m_jacobian_point<FT, K, FLAGS>(c, a, x, i);
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------
 template <typename FT, typename MP, typename TH>
 static int32_t jacobian_1m_entry(const MP *mp, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T, const FT *q_tot, const FT *q_lcl,
@@ -53,12 +41,12 @@ static int32_t jacobian_1m_entry(const MP *mp, const TH *tps, uint32_t flags, in
     constexpr int K = kJac1mK<FT>;
     Mp1mJacArgs<FT, K> a;
     const FT *const in[7] = {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno};
-    if (!make_jac1m_args<FT, K>(a, in, jac, tendencies)) return CMX_ERR_BAD_ARG;      // no output column at all
+    if (!make_jac_args(a, in, jac, tendencies)) return CMX_ERR_BAD_ARG;      // no output column at all
     const Mp1mConsts<FT> c = make_mp1m_consts<FT>(*mp, *tps, flags, (double)Math<FT>::eps_1m());
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // One point per lane with 4- / 8-byte accesses: any alignment and any n go through one launch (split_aligned with vec = 1 is the single range [0, n)
     // whatever the columns' addresses are, cmx_split.hpp)
-    dispatch([&](auto FL) { launch<kJac1mBS>(mp1m_jacobian_kernel<FT, K, decltype(FL)::value>, n, s, c, a, n); }, flags_1m(flags, c));
+    dispatch([&](auto FL) { launch<kJac1mBS>(jacobian_kernel<Mp1mJac<decltype(FL)::value>, FT, K, kJac1mBS, Mp1mConsts<FT>>, n, s, c, a, n); }, flags_1m(flags, c));
     return launched();
 }
 

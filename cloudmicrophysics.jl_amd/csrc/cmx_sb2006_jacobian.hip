@@ -9,7 +9,8 @@
 // LIMITED and INTPOW serves every selection of columns, and a subset in any order computes, per column, exactly the instruction sequence of the full call.
 // Every pass recomputes the primal — that is what forward mode costs — and every pass's primal is the plain instantiation's, bit for bit.  Stores are plain
 // whole-column vector stores (one element per lane, a wave writes 256 / 512 contiguous bytes).  No LDS beyond the Float64 math tables every Float64 kernel
-// of the library stages (cmx_lean_f64.hpp), no inline assembly here.  The point's body is shared with the host test build (cmx_sb2006_jacobian.hpp).
+// of the library stages (cmx_lean_f64.hpp), no inline assembly here.  The kernel and the point's body are the shared driver's (jacobian_kernel<SbJac<…>, …>,
+// cmx_jacobian.hpp); the scheme it runs is shared with the host test build (cmx_sb2006_jacobian.hpp).
 //
 // K per float type (kJacK, cmx_sb2006_jacobian.hpp) from the register counts of a cross-compiled build (tools/kernel_resources.py; DESIGN.md §9 has the table).
 // A translation unit of its own: no existing kernel's code changes.
@@ -26,19 +27,6 @@ namespace cmx {
 #endif
 constexpr int kJacBS = CMX_JAC_BS;
 
-template <typename FT, int K, bool LIMITED, bool INTPOW>
-__global__ __launch_bounds__(kJacBS) void sb2006_jacobian_kernel(const SbConsts<FT> c, const SbJacArgs<FT, K> a, const int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * kJacBS + threadIdx.x;
-    FT x[7];
-    if (i < n) {
-#pragma unroll
-        for (int j = 0; j < 7; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
-    }
-    Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
-    if (i >= n) return;
-    sb2006_jacobian_point<FT, K, LIMITED, INTPOW>(c, a, x, i);
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------
 template <typename FT, typename WR, typename TH>
 static int32_t jacobian_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *rho, const FT *T, const FT *q_tot, const FT *q_lcl,
@@ -50,7 +38,7 @@ static int32_t jacobian_entry(const WR *wr, const TH *tps, uint32_t flags, int64
     constexpr int K = kJacK<FT>;
     SbJacArgs<FT, K> a;
     const FT *const in[7] = {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai};
-    if (!make_jac_args<FT, K>(a, in, jac, tendencies)) return CMX_ERR_BAD_ARG;      // no output column at all
+    if (!make_jac_args(a, in, jac, tendencies)) return CMX_ERR_BAD_ARG;      // no output column at all
     if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
     const bool limited = flags & CMX_SB2006_LIMITED;
     if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
@@ -61,7 +49,7 @@ static int32_t jacobian_entry(const WR *wr, const TH *tps, uint32_t flags, int64
     // One point per lane with 4- / 8-byte accesses: any alignment and any n go through one launch.  (The alignment split of the vector kernels is the
     // identity here: split_aligned with vec = 1 is the single scalar range [0, n) whatever the columns' addresses are, cmx_split.hpp.)
     dispatch([&](auto L, auto I) {
-        launch<kJacBS>(sb2006_jacobian_kernel<FT, K, decltype(L)::value, decltype(I)::value>, n, s, c, a, n);
+        launch<kJacBS>(jacobian_kernel<SbJac<decltype(L)::value, decltype(I)::value>, FT, K, kJacBS, SbConsts<FT>>, n, s, c, a, n);
     }, flag(limited), flag(intpow));
     return launched();
 }

@@ -37,13 +37,11 @@ import numpy as np
 
 from cmx import _abi
 from cmx import parameters as P
-from jacobian_cases import assert_resolution, cells_line, disagreement, scaled_error, worst_cells  # noqa: F401
+from jacobian_cases import (AGREE, BOUND, MAX_SET_ASIDE, assert_resolution, cells_line, checked, fd_reference, points, worst_cells,  # noqa: F401
+                            worst_rows)
 
 WRT = _abi.MP1M_JAC_WRT            # T, q_tot, q_lcl, q_icl, q_rai, q_sno = columns 1 … 6 of the state
 OUT = _abi.MP1M_JAC_OUT
-BOUND = {"f64": 1e-5, "f32": 1e-3}
-AGREE = 2e-6
-MAX_SET_ASIDE = 0.01
 N_STATES = 4096
 T_RANGE = {"cold": (235.0, 272.65), "warm": (273.65, 300.0)}
 
@@ -85,28 +83,10 @@ def states(oracle, which, n=N_STATES, seed=11):
     return [rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno]
 
 
-def points(*sts):
-    return [np.array([s[k] for s in sts], dtype=np.float64) for k in range(7)]
-
-
 def oracle_tendencies(oracle, mp64, cols):
     r = oracle.mp1m(_abi.F64, mp64.c, P.ThermodynamicsParameters("f64"), mp64.flags, *[np.ascontiguousarray(c, dtype=np.float64) for c in cols],
                     nthreads=8, want_sources=False)
     return np.stack([r[k] for k in OUT])
-
-
-def fd_jacobian(oracle, mp64, cols, step=1e-6):
-    """[4, 6, n]: central differences with h = step·|x_j|, divided by the realised x⁺ − x⁻."""
-    cols = [np.asarray(c, dtype=np.float64) for c in cols]
-    J = np.empty((4, 6, cols[0].size))
-    for j in range(6):
-        x = cols[j + 1]
-        h = step * np.abs(x)
-        xp, xm = x + h, x - h
-        fp = oracle_tendencies(oracle, mp64, cols[:j + 1] + [xp] + cols[j + 2:])
-        fm = oracle_tendencies(oracle, mp64, cols[:j + 1] + [xm] + cols[j + 2:])
-        J[:, j] = (fp - fm) / (xp - xm)
-    return J
 
 
 @functools.lru_cache(maxsize=None)
@@ -115,25 +95,15 @@ def _reference(case, which):
     oracle.lib()
     mp64 = params("f64", case)
     cols = points(CALLER, SUITE_WARM) if which == "points" else states(oracle, which)
-    J1, J4 = fd_jacobian(oracle, mp64, cols), fd_jacobian(oracle, mp64, cols, step=4e-6)
-    disagree = disagreement(J1, J4, cols[1:])
-    kept = disagree <= AGREE
-    for a in (*cols, J1, kept, disagree):
+    J1, kept, worst = fd_reference(lambda c: oracle_tendencies(oracle, mp64, c), cols)
+    for a in (*cols, J1, kept):
         a.setflags(write=False)
-    return cols, J1, kept, disagree
+    return cols, J1, kept, worst
 
 
 def reference(case, which):
     """(cols, J_fd, kept, worst h-vs-4h disagreement) of a set, computed once and shared read-only; asserts the 1 % condition."""
-    cols, J, kept, disagree = _reference(case, which)
-    assert (~kept).sum() <= MAX_SET_ASIDE * kept.size, (case, which, int((~kept).sum()), kept.size, float(disagree.max()))
-    return cols, J, kept, float(disagree.max())
-
-
-def worst_rows(J, J_ref, kept):
-    """Worst scaled error per output row over the kept states: {row name: value}."""
-    e = scaled_error(J, J_ref)[:, kept]
-    return {name: float(e[i].max()) for i, name in enumerate(OUT)}
+    return checked(_reference(case, which), case, which)
 
 
 def assert_parity(ft, J, case, which, what, report=True):
@@ -142,7 +112,7 @@ def assert_parity(ft, J, case, which, what, report=True):
     and the worst input-scaled error per (row, column)."""
     cols, J_ref, kept, worst_fd = reference(case, which)
     assert np.isfinite(np.asarray(J)[:, :, kept]).all(), (what, case, which)          # (a NaN would leave the row scale undefined, not large)
-    rows = worst_rows(J, J_ref, kept)
+    rows = worst_rows(J, J_ref, kept, OUT)
     cells = worst_cells(J, J_ref, cols[1:], kept)
     if report:
         print(f"{what} {ft} {case} {which}: kept {int(kept.sum())}/{kept.size}, h-vs-4h {worst_fd:.3g}, worst rows " + ", ".join(f"{k} {v:.3g}" for k, v in rows.items())

@@ -78,7 +78,8 @@ def interior_states(oracle, n=4096, seed=7):
 
 
 def points(*states):
-    return [np.array([s[k] for s in states], dtype=np.float64) for k in range(7)]
+    """Single states → columns."""
+    return [np.array(c, dtype=np.float64) for c in zip(*states)]
 
 
 def warm_rain_params(ft, limited, overrides=None):
@@ -102,16 +103,17 @@ def oracle_tendencies(oracle, wr64, limited, cols):
     return np.stack([r[k] for k in OUT])
 
 
-def fd_jacobian(oracle, wr64, limited, cols, step=1e-6):
-    """[4, 6, n]: central differences with h = step·|x_j|, divided by the realised x⁺ − x⁻."""
+def fd_jacobian(tendencies, cols, step=1e-6):
+    """[n_out, n_wrt, n]: central differences of tendencies(cols) → [n_out, n] (the ORACLE's, Float64) with h = step·|x_j|, divided by the realised
+    x⁺ − x⁻; cols[0] = ρ is not differentiated."""
     cols = [np.asarray(c, dtype=np.float64) for c in cols]
-    J = np.empty((4, 6, cols[0].size))
-    for j in range(6):
+    J = None
+    for j in range(len(cols) - 1):
         x = cols[j + 1]
         h = step * np.abs(x)
         xp, xm = x + h, x - h
-        fp = oracle_tendencies(oracle, wr64, limited, cols[:j + 1] + [xp] + cols[j + 2:])
-        fm = oracle_tendencies(oracle, wr64, limited, cols[:j + 1] + [xm] + cols[j + 2:])
+        fp, fm = tendencies(cols[:j + 1] + [xp] + cols[j + 2:]), tendencies(cols[:j + 1] + [xm] + cols[j + 2:])
+        J = np.empty((fp.shape[0], len(cols) - 1, x.size)) if J is None else J
         J[:, j] = (fp - fm) / (xp - xm)
     return J
 
@@ -235,6 +237,20 @@ def cells_line(cells, out, wrt):
     return "; ".join(f"{row}: " + " ".join(f"{c} {cells[i, j]:.2g}" for j, c in enumerate(wrt)) for i, row in enumerate(out))
 
 
+def fd_reference(tendencies, cols):
+    """(J_fd at h, kept, worst h-vs-4h disagreement in either measure) of the states `cols`: a state is kept if the references at h and 4h agree within AGREE."""
+    J1, J4 = fd_jacobian(tendencies, cols), fd_jacobian(tendencies, cols, step=4e-6)
+    disagree = disagreement(J1, J4, cols[1:])
+    return J1, disagree <= AGREE, float(disagree.max())
+
+
+def checked(ref, *what):
+    """The first four members (cols, J_fd, kept, worst disagreement) of a cached reference, shared read-only; asserts the 1 % condition."""
+    cols, J, kept, worst = ref[:4]
+    assert (~kept).sum() <= MAX_SET_ASIDE * kept.size, (*what, int((~kept).sum()), kept.size, worst)
+    return cols, J, kept, worst
+
+
 @functools.lru_cache(maxsize=None)
 def _reference(limited, perturbed, which):
     import oracle_binding as oracle
@@ -242,20 +258,16 @@ def _reference(limited, perturbed, which):
     ov = perturbed_overrides() if perturbed else None
     wr64 = warm_rain_params("f64", limited, ov)
     cols = interior_states(oracle) if which == "interior" else points(WARM_RAIN, KAT)
-    J1, J4 = fd_jacobian(oracle, wr64, limited, cols), fd_jacobian(oracle, wr64, limited, cols, step=4e-6)
-    disagree = disagreement(J1, J4, cols[1:])
-    kept = disagree <= AGREE
+    J1, kept, worst = fd_reference(lambda c: oracle_tendencies(oracle, wr64, limited, c), cols)
     E, eps_S = evaporation_share(oracle, wr64, limited, cols), evaporation_spread_f32(oracle, limited, perturbed, cols)
     for a in (*cols, J1, kept, E, eps_S):
         a.setflags(write=False)
-    return cols, J1, kept, float(disagree.max()), E, eps_S
+    return cols, J1, kept, worst, E, eps_S
 
 
 def reference(limited, perturbed=False, which="interior"):
     """(cols, J_fd, kept, worst h-vs-4h disagreement in either measure) of a set, computed once and shared read-only; asserts the 1 % condition."""
-    cols, J, kept, worst, _, _ = _reference(bool(limited), bool(perturbed), which)
-    assert (~kept).sum() <= MAX_SET_ASIDE * kept.size, (int((~kept).sum()), kept.size, worst)
-    return cols, J, kept, worst
+    return checked(_reference(bool(limited), bool(perturbed), which))
 
 
 # the one (float type, parameter set, row) that cannot meet the plain Float32 bound and is held to `float32_bound` instead
@@ -267,9 +279,9 @@ def assert_parity(ft, J, limited, perturbed, which, what, report=True):
     1e-3 — except dn_rai_dt in Float32 with the perturbed parameter set, every entry of which is inside `float32_bound`.  Input-scaled measure: every
     (row, column) of every kept state inside the same BOUND[ft], no exception.  Prints (report=True) and returns the worst scaled error per row, the largest
     fraction of the entry bound that was used and the worst input-scaled error per (row, column)."""
-    cols, J_ref, kept, worst_fd, E, eps_S = _reference(bool(limited), bool(perturbed), which)
-    assert (~kept).sum() <= MAX_SET_ASIDE * kept.size, (int((~kept).sum()), kept.size, worst_fd)
-    rows = worst_rows(J, J_ref, kept)
+    cols, J_ref, kept, worst_fd, E, eps_S = ref = _reference(bool(limited), bool(perturbed), which)
+    checked(ref)
+    rows = worst_rows(J, J_ref, kept, OUT)
     cells = worst_cells(J, J_ref, cols[1:], kept)
     J = np.asarray(J, dtype=np.float64)
     by_entry = ENTRY_BOUND_ROWS.get((ft, bool(perturbed)), ())
@@ -294,7 +306,7 @@ def assert_parity(ft, J, limited, perturbed, which, what, report=True):
     return rows, used, cells
 
 
-def worst_rows(J, J_ref, kept):
-    """Worst scaled error per output row over the kept states: {row name: value}."""
+def worst_rows(J, J_ref, kept, out):
+    """Worst scaled error per output row over the kept states: {row name: value}; out: the row names."""
     e = scaled_error(J, J_ref)[:, kept]
-    return {name: float(e[i].max()) for i, name in enumerate(OUT)}
+    return {name: float(e[i].max()) for i, name in enumerate(out)}

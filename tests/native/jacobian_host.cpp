@@ -9,47 +9,23 @@
 #include <initializer_list>
 
 #include "../../cloudmicrophysics.jl_amd/csrc/cmx_sb2006_jacobian.hpp"
+#include "jacobian_driver_host.hpp"
 
 namespace {
 using namespace cmx;
 
-template <typename F> int32_t pick(bool limited, bool intpow, F &&run) {
-    if (limited) { if (intpow) run(std::true_type{}, std::true_type{}); else run(std::true_type{}, std::false_type{}); }
-    else { if (intpow) run(std::false_type{}, std::true_type{}); else run(std::false_type{}, std::false_type{}); }
-    return intpow ? 1 : 0;      // which instantiation ran: 1 = the integer-exponent one
-}
-
-// k: the tangents per pass (0: the kernel's own choice for the float type).  The columns do not depend on it, bit for bit: each tangent is computed by the
-// same operations whatever K is
-template <typename FT, int K, typename WR, typename TH>
-int32_t jacobian_k(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *const *x, FT *const *jac, FT *const *tend) {
-    if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
-    const bool limited = flags & CMX_SB2006_LIMITED;
-    if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;
-    SbJacArgs<FT, K> a;
-    const FT *const in[7] = {x[0], x[1], x[2], x[3], x[4], x[5], x[6]};
-    if (!make_jac_args<FT, K>(a, in, jac, tend)) return CMX_ERR_BAD_ARG;
-    const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, (const std::conditional_t<std::is_same<FT, float>::value, cmx_rain_vel_f32, cmx_rain_vel_f64> *)nullptr,
-                                              (double)Math<FT>::eps_1m());
-    return pick(limited, sb_integer_exponents(*wr), [&](auto L, auto I) {
-        for (int64_t i = 0; i < n; ++i) {
-            FT xi[7];
-            for (int j = 0; j < 7; ++j) xi[j] = a.in[j][i];
-            sb2006_jacobian_point<FT, K, decltype(L)::value, decltype(I)::value>(c, a, xi, i);
-        }
-    });
-}
+// k: the tangents per pass (jacobian_driver_host.hpp).  Returns which instantiation ran: 1 = the integer-exponent one
 template <typename FT, typename WR, typename TH>
 int32_t jacobian(const WR *wr, const TH *tps, uint32_t flags, int k, int64_t n, const FT *const *x, FT *const *jac, FT *const *tend) {
-    switch (k) {
-        case 0: return jacobian_k<FT, kJacK<FT>>(wr, tps, flags, n, x, jac, tend);
-        case 1: return jacobian_k<FT, 1>(wr, tps, flags, n, x, jac, tend);
-        case 2: return jacobian_k<FT, 2>(wr, tps, flags, n, x, jac, tend);
-        case 3: return jacobian_k<FT, 3>(wr, tps, flags, n, x, jac, tend);
-        case 4: return jacobian_k<FT, 4>(wr, tps, flags, n, x, jac, tend);
-        case 6: return jacobian_k<FT, 6>(wr, tps, flags, n, x, jac, tend);
-        default: return CMX_ERR_BAD_ARG;
-    }
+    if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
+    const bool limited = flags & CMX_SB2006_LIMITED, intpow = sb_integer_exponents(*wr);
+    if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;
+    const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, (const std::conditional_t<std::is_same<FT, float>::value, cmx_rain_vel_f32, cmx_rain_vel_f64> *)nullptr,
+                                              (double)Math<FT>::eps_1m());
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto K, auto L, auto I) -> int32_t {
+        using S = SbJac<decltype(L)::value, decltype(I)::value>;
+        return host_jacobian_points<S, FT, decltype(K)::value>(c, n, x, jac, tend) ? (int32_t)intpow : (int32_t)CMX_ERR_BAD_ARG;
+    }, tangent_width<1, 2, 3, 4, 6>(k, kJacK<FT>), flag(limited), flag(intpow));
 }
 
 // the plain instantiation: the sums of sb2006_tendencies_kernel (csrc/cmx_sb2006_kernels.hpp) around sb2006_point<FT, …, VEL_NONE, …>
@@ -59,7 +35,8 @@ int32_t plain(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *
     if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;
     const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, (const std::conditional_t<std::is_same<FT, float>::value, cmx_rain_vel_f32, cmx_rain_vel_f64> *)nullptr,
                                               (double)Math<FT>::eps_1m());
-    return pick(limited, sb_integer_exponents(*wr), [&](auto L, auto I) {
+    const bool intpow = sb_integer_exponents(*wr);
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t {
         for (int64_t i = 0; i < n; ++i) {
             const FT rho = x[0][i], T = x[1][i], q_tot = x[2][i], q_lcl = x[3][i], n_lcl = x[4][i], q_rai = x[5][i], n_rai = x[6][i];
             const FT r_ = max0(rho), qt = max0(q_tot), ql = max0(q_lcl), qr = max0(q_rai), nl = max0(n_lcl), nr = max0(n_rai);
@@ -70,7 +47,8 @@ int32_t plain(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *
             y[2][i] = ((p.evq + p.au_dq_rai) + p.ac_dq_rai) + poison;
             y[3][i] = Math<FT>::fma(((p.evN + p.au_dN_rai) + p.rsc) + p.rbr, p.inv_rho, p.na_rai) + poison;
         }
-    });
+        return intpow;
+    }, flag(limited), flag(intpow));
 }
 }  // namespace
 

@@ -18,68 +18,34 @@ The host build proves the derivative RULES (its transcendentals are libm's, not 
 assertions on the device."""
 import ctypes as C
 import itertools
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 import torch
 
 import jacobian_1m_cases as JC
+import jacobian_host_build as JH
+from jacobian_host_build import NPT, _same_bits, host_fixture
 import cmx
 from cmx import _abi, _lib, synthetic
 from cmx import parameters as P
 
-REPO = Path(__file__).resolve().parent.parent
-NPT = {"f32": np.float32, "f64": np.float64}
-CT = {"f32": C.c_float, "f64": C.c_double}
 DT = {"f32": torch.float32, "f64": torch.float64}
 T_FREEZE = 273.15
+host = host_fixture("jacobian_1m_host")
 
 
-@pytest.fixture(scope="module")
-def host():
-    out = REPO / "tests" / "native" / "_build"
-    out.mkdir(exist_ok=True)
-    so = out / "libjacobian_1m_host.so"
-    subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-o", str(so), str(REPO / "tests" / "native" / "jacobian_1m_host.cpp")],
-                   check=True)
-    return C.CDLL(str(so))
-
-
-def _arr(ft, cols):
-    return (C.POINTER(CT[ft]) * len(cols))(*[c.ctypes.data_as(C.POINTER(CT[ft])) if c is not None else None for c in cols])
+def _head(ft, mp):
+    return C.byref(mp.c), C.byref(P.ThermodynamicsParameters(ft)), C.c_uint32(mp.flags)
 
 
 def host_jacobian(host, ft, mp, cols, wrt=JC.WRT, k=0, with_tendencies=True):
     """([4, len(wrt), n] Jacobian, [4, n] tendencies, status) of the host build; wrt: names in any order."""
-    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
-    n = x[0].size
-    jac = np.full((4, len(wrt), n), np.nan, dtype=NPT[ft])
-    tend = np.full((4, n), np.nan, dtype=NPT[ft]) if with_tendencies else None
-    slots = [None] * _abi.CMX_MP1M_JAC_NCOL
-    for kk, name in enumerate(wrt):
-        for o in range(4):
-            slots[o * 6 + JC.WRT.index(name)] = jac[o, kk]
-    fn = getattr(host, f"host_mp1m_jacobian_{ft}")
-    fn.restype = C.c_int32
-    rc = fn(C.byref(mp.c), C.byref(P.ThermodynamicsParameters(ft)), C.c_uint32(mp.flags), C.c_int(k), C.c_int64(n), _arr(ft, x), _arr(ft, slots),
-            _arr(ft, list(tend)) if tend is not None else None)
-    return jac, tend, rc
+    return JH.host_jacobian(host, "mp1m_jacobian", ft, _head(ft, mp), cols, JC.WRT, wrt, k=k, with_tendencies=with_tendencies)
 
 
 def host_plain(host, ft, mp, cols):
-    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
-    y = np.empty((4, x[0].size), dtype=NPT[ft])
-    fn = getattr(host, f"host_mp1m_plain_{ft}")
-    fn.restype = C.c_int32
-    rc = fn(C.byref(mp.c), C.byref(P.ThermodynamicsParameters(ft)), C.c_uint32(mp.flags), C.c_int64(x[0].size), _arr(ft, x), _arr(ft, list(y)))
-    return y, rc
-
-
-def _same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return bool(np.all((a.view(np.uint8) == b.view(np.uint8)).reshape(a.shape + (-1,)).all(axis=-1) | (np.isnan(a) & np.isnan(b))))
+    return JH.host_plain(host, "mp1m_plain", ft, _head(ft, mp), cols)
 
 
 def _synthetic(ft):
@@ -138,7 +104,7 @@ def test_the_row_measure_alone_does_not_see_the_T_column(host, oracle, case):
         J, _, _ = host_jacobian(host, "f64", JC.params("f64", case), cols)
         M = np.array(J)
         M[:, 0] *= 1.1
-        assert max(JC.worst_rows(M, J_ref, kept).values()) < JC.BOUND["f32"], which
+        assert max(JC.worst_rows(M, J_ref, kept, JC.OUT).values()) < JC.BOUND["f32"], which
         assert abs(JC.worst_cells(M, J_ref, cols[1:], kept).max() - 0.1 / 1.1) < 1e-6, which
 
 
