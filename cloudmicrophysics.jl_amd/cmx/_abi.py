@@ -144,6 +144,10 @@ CMX_MP1M_JAC_NOUT = len(MP1M_JAC_OUT)
 CMX_MP1M_JAC_NWRT = len(MP1M_JAC_WRT)
 CMX_MP1M_JAC_NCOL = CMX_MP1M_JAC_NOUT * CMX_MP1M_JAC_NWRT
 
+# the products with the two Jacobians (include/cmx.h §16, §17): <stem>_jvp_* takes tangents[NWRT], jvp[NOUT], tendencies[NOUT]; <stem>_vjp_* takes
+# cotangents[NOUT], grad[NWRT], tendencies[NOUT]
+JACOBIAN_PRODUCT_STEMS = ("cmx_sb2006_warm_rain", "cmx_mp1m")
+
 
 def _struct(name, fields):
     return type(name, (C.Structure,), {"_fields_": fields})

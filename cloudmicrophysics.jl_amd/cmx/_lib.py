@@ -215,6 +215,11 @@ def _declare(lib):
         f = getattr(lib, f"cmx_mp1m_jacobian_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.POINTER(vp), C.POINTER(vp), vp]
+        for stem, params in (("cmx_sb2006_warm_rain", fam.warm_rain_2m), ("cmx_mp1m", fam.microphysics_1m)):
+            for product in ("jvp", "vjp"):       # (tangents[6], jvp[4], tendencies[4]) / (cotangents[4], grad[6], tendencies[4])
+                f = getattr(lib, f"{stem}_{product}_{s}")
+                f.restype = i32
+                f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

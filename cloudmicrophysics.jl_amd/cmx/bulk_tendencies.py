@@ -24,7 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _jacobian
+from ._jacobian import _jacobian, _jvp, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -162,6 +162,41 @@ def warm_rain_jacobian_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, wr
     return WarmRainJacobian2M(*_jacobian("cmx_sb2006_warm_rain_jacobian", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
                                          (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai"), JACOBIAN_WRT,
                                          _abi.CMX_SB2006_JAC_NOUT, wrt, with_tendencies, out, stream))
+
+
+WarmRainJvp2M = namedtuple("WarmRainJvp2M", ["jvp", "tendencies"])
+WarmRainVjp2M = namedtuple("WarmRainVjp2M", ["grad", "tendencies", "wrt"])
+_NAMES_2M = ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai")
+
+
+def warm_rain_jvp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, tangents, with_tendencies=False, *, out=None, stream=None) -> WarmRainJvp2M:
+    """J v of the 2-moment warm-rain tendencies behind `cmx_sb2006_warm_rain_jvp_*`: the directional derivative of the four tendencies along `tangents`,
+    one evaluation of the point function on dual numbers seeded with the tangent — what a Jacobian-free Newton–Krylov matvec needs — without the 24
+    columns of `warm_rain_jacobian_2m`.
+
+    `tangents`: dict name -> tensor over `JACOBIAN_WRT`; a missing name is a zero tangent (ρ is held fixed: a `rho` tangent is a ValueError).  Returns
+    `WarmRainJvp2M(jvp, tendencies)`: `jvp` of shape (4, *rho.shape) in the order of `JACOBIAN_OUTPUTS`; `tendencies` (4, *rho.shape), bit-identical to
+    `bulk_microphysics_tendencies`, with `with_tendencies=True`, else None.  `out=(jvp, tendencies)` lets the caller provide either tensor.
+    Asynchronous on `stream` (default: torch's current stream)."""
+    wr = _warm_rain(mp)
+    return WarmRainJvp2M(*_jvp("cmx_sb2006_warm_rain_jvp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                               (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, JACOBIAN_WRT, _abi.CMX_SB2006_JAC_NOUT, tangents, with_tendencies, out,
+                               stream))
+
+
+def warm_rain_vjp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, wrt=JACOBIAN_WRT, with_tendencies=False, *, out=None,
+                     stream=None) -> WarmRainVjp2M:
+    """Jᵀḡ of the 2-moment warm-rain tendencies behind `cmx_sb2006_warm_rain_vjp_*`: the gradient of Σ_o ḡ_o·out_o with respect to the inputs `wrt`, the
+    Jacobian's columns contracted with the cotangents in registers — what `loss.backward()` needs (cmx.autograd) — without the 24 columns.
+
+    `cotangents`: a sequence of 4 tensors or None in the order of `JACOBIAN_OUTPUTS`; None removes that output from the sum (a tensor of zeros does not:
+    0·Inf is NaN, as contracting the Jacobian would give).  `wrt`: any subset of `JACOBIAN_WRT` in any order.  Returns `WarmRainVjp2M(grad, tendencies,
+    wrt)`: `grad` of shape (len(wrt), *rho.shape); a gradient does not depend on which others are requested.  `tendencies`, `out=(grad, tendencies)` and
+    `stream` as for `warm_rain_jvp_2m`."""
+    wr = _warm_rain(mp)
+    return WarmRainVjp2M(*_vjp("cmx_sb2006_warm_rain_vjp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                               (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, JACOBIAN_WRT, _abi.CMX_SB2006_JAC_NOUT, cotangents, wrt,
+                               with_tendencies, out, stream))
 
 
 AOS_FIELDS = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt")

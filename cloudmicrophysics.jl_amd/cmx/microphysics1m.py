@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _jacobian
+from ._jacobian import _jacobian, _jvp, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -130,6 +130,31 @@ def jacobian_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, wrt=JACOBIAN
         raise TypeError("mp must be Microphysics1MParams")
     return Jacobian1M(*_jacobian("cmx_mp1m_jacobian", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M,
                                  _abi.CMX_MP1M_JAC_NOUT, wrt, with_tendencies, out, stream))
+
+
+Jvp1M = namedtuple("Jvp1M", ["jvp", "tendencies"])
+Vjp1M = namedtuple("Vjp1M", ["grad", "tendencies", "wrt"])
+
+
+def jvp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, tangents, with_tendencies=False, *, out=None, stream=None) -> Jvp1M:
+    """J v of the 1-moment tendencies (Instantaneous mode) behind `cmx_mp1m_jvp_*`: the directional derivative of the four tendencies along `tangents`
+    (dict name -> tensor over `JACOBIAN_WRT_1M`; a missing name is a zero tangent, a `rho` tangent a ValueError), one evaluation of the point function on
+    dual numbers.  Returns `Jvp1M(jvp, tendencies)` with `jvp` of shape (4, *rho.shape) in the order of `JACOBIAN_OUTPUTS_1M`; arguments as for
+    `cmx.warm_rain_jvp_2m`."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    return Jvp1M(*_jvp("cmx_mp1m_jvp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M, _abi.CMX_MP1M_JAC_NOUT,
+                       tangents, with_tendencies, out, stream))
+
+
+def vjp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, wrt=JACOBIAN_WRT_1M, with_tendencies=False, *, out=None, stream=None) -> Vjp1M:
+    """Jᵀḡ of the 1-moment tendencies (Instantaneous mode) behind `cmx_mp1m_vjp_*`: `cotangents` a sequence of 4 tensors or None in the order of
+    `JACOBIAN_OUTPUTS_1M` (None removes that output from the sum), `wrt` any subset of `JACOBIAN_WRT_1M`.  Returns `Vjp1M(grad, tendencies, wrt)` with
+    `grad` of shape (len(wrt), *rho.shape); arguments as for `cmx.warm_rain_vjp_2m`."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    return Vjp1M(*_vjp("cmx_mp1m_vjp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M, _abi.CMX_MP1M_JAC_NOUT,
+                       cotangents, wrt, with_tendencies, out, stream))
 
 
 def bulk_microphysics_tendencies_1m_fields(mode, scheme, mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt=None, nsub=1, *, q_min=None, out=None,

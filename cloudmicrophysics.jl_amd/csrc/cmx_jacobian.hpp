@@ -102,3 +102,6 @@ __global__ __launch_bounds__(BS) void jacobian_kernel(const C c, const JacArgs<F
 #endif
 
 }  // namespace cmx
+
+// J v and Jᵀḡ fused into the same pass: jvp_point / jvp_kernel, vjp_point / vjp_kernel
+#include "cmx_jacobian_products.hpp"

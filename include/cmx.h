@@ -1559,6 +1559,69 @@ int32_t cmx_mp1m_jacobian_f64(const cmx_microphysics_1m_f64 *mp, const cmx_therm
                               double *const jac[CMX_MP1M_JAC_NCOL], double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (16) Products with the Jacobian of the SB2006 warm-rain tendencies (14), fused into the pass that holds the tangents in registers: what a
+ * Jacobian-free Newton–Krylov matvec (J v) and a gradient (Jᵀḡ: calibration, a closure trained through the scheme, torch autograd) consume, without
+ * the 24 columns being written and read back.  State, outputs (cmx_sb2006_jac_out), differentiated inputs (cmx_sb2006_jac_wrt; ρ is held fixed),
+ * derivative rules and instantiation choice are those of (14).
+ *   cmx_sb2006_warm_rain_jvp_*:  jvp[o] = Σ_i ∂out_o/∂in_i · tangents[i]        one evaluation of the point function on duals seeded with the tangent
+ *     tangents[i]   the tangent column of input i (a host array of 6 device column pointers; a NULL member is a zero tangent)
+ *     jvp[o]        NULL, or an array of 4 NULL-able columns
+ *   cmx_sb2006_warm_rain_vjp_*:  grad[i] = Σ_o cotangents[o] · ∂out_o/∂in_i      ⌈n_grad/K⌉ evaluations with unit seeds, contracted before the store
+ *     cotangents[o] the cotangent column ḡ of output o (a host array of 4 device column pointers; a NULL member removes that output from the sum)
+ *     grad[i]       NULL, or an array of 6 NULL-able columns; an input whose gradient is NULL is not differentiated
+ *   tendencies[o]   as in (14): NULL, or 4 NULL-able columns, bit-identical to cmx_sb2006_warm_rain_tendencies_*
+ * The products are plain IEEE arithmetic on the tangents (14) would store: a zero cotangent times an infinite tangent is NaN, as contracting the
+ * columns of (14) would give; only a NULL cotangent removes an output.  The sum runs over the non-NULL cotangents in output order (first product, then
+ * fused multiply-adds).  The value of grad[i] does not depend on which other gradients are requested, bit for bit.  With every member of `tangents`
+ * NULL the products are zeros; with every member of `cotangents` NULL the requested gradients are zeros.
+ * Statuses, their order, the flags and the limiter check as for (14); the `tangents` / `cotangents` table itself NULL, or no output column at all
+ * (`jvp` / `grad` and `tendencies`), is CMX_ERR_BAD_ARG where (14) reports "no output".  A NaN in any of the seven inputs of a point, or in any given
+ * tangent or cotangent value of it, gives NaN in every output of that point (tendencies included) and in that point only.  A pure launch sequence on
+ * `stream`: no allocation, no synchronisation, graph-capturable; any alignment.  f32: J v 7 + 6 columns in, 4 out (68 B/point); Jᵀḡ 7 + 4 in, 6 out.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_warm_rain_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                     const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                     const float *const tangents[CMX_SB2006_JAC_NWRT], float *const jvp[CMX_SB2006_JAC_NOUT],
+                                     float *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_jvp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                     const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
+                                     const double *const tangents[CMX_SB2006_JAC_NWRT], double *const jvp[CMX_SB2006_JAC_NOUT],
+                                     double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_vjp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                     const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                     const float *const cotangents[CMX_SB2006_JAC_NOUT], float *const grad[CMX_SB2006_JAC_NWRT],
+                                     float *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                     const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
+                                     const double *const cotangents[CMX_SB2006_JAC_NOUT], double *const grad[CMX_SB2006_JAC_NWRT],
+                                     double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (17) Products with the Jacobian of the 1-moment tendencies (15): cmx_mp1m_jvp_* and cmx_mp1m_vjp_*, with the arguments and the rules of (16) —
+ * tangents[6] over cmx_mp1m_jac_wrt, cotangents[4] over cmx_mp1m_jac_out, NULL members, the order of the sum, plain IEEE products, subset independence —
+ * and the state, `flags`, instantiation choice, statuses and their order of (15): NULL parameters; the count rule; the flags; n_points = 0 is CMX_OK;
+ * a NULL input column; the `tangents` / `cotangents` table NULL or no output column at all (CMX_ERR_BAD_ARG).  `tendencies` is bit-identical to
+ * cmx_mp1m_tendencies_*.  A NaN in any of the seven inputs of a point (in Float64 also ρ ≤ 0), or in any given tangent or cotangent value of it, gives
+ * NaN in every output of that point and in that point only.  A pure launch sequence on `stream`, graph-capturable; any alignment.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_mp1m_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho, const float *T,
+                         const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                         const float *const tangents[CMX_MP1M_JAC_NWRT], float *const jvp[CMX_MP1M_JAC_NOUT], float *const tendencies[CMX_MP1M_JAC_NOUT],
+                         void *stream);
+int32_t cmx_mp1m_jvp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho, const double *T,
+                         const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                         const double *const tangents[CMX_MP1M_JAC_NWRT], double *const jvp[CMX_MP1M_JAC_NOUT], double *const tendencies[CMX_MP1M_JAC_NOUT],
+                         void *stream);
+int32_t cmx_mp1m_vjp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho, const float *T,
+                         const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                         const float *const cotangents[CMX_MP1M_JAC_NOUT], float *const grad[CMX_MP1M_JAC_NWRT], float *const tendencies[CMX_MP1M_JAC_NOUT],
+                         void *stream);
+int32_t cmx_mp1m_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho, const double *T,
+                         const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                         const double *const cotangents[CMX_MP1M_JAC_NOUT], double *const grad[CMX_MP1M_JAC_NWRT], double *const tendencies[CMX_MP1M_JAC_NOUT],
+                         void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1418,6 +1418,94 @@ function jacobian_1m!(jac, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::Ab
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (16) products with the Jacobian of the SB2006 warm-rain tendencies: J v and Jᵀḡ, fused
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    warm_rain_jvp_2m!(jvp, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, tangents; stream = C_NULL)
+
+J v of the tendencies of `warm_rain_jacobian_2m!`: `tangents` = `CMX_SB2006_JAC_NWRT` (6) device columns or `nothing`s (a zero tangent) in the order
+(T, q_tot, q_lcl, n_lcl, q_rai, n_rai), `jvp` = `nothing` or 4 columns (or `nothing`s) in the order (dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt): one
+evaluation of the point function on dual numbers seeded with the tangent — the matvec of a Jacobian-free Newton–Krylov step.  `tendencies` as there.
+"""
+function warm_rain_jvp_2m!(jvp, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+    tangents; stream = C_NULL) where {WR, FT}
+    length(tangents) == CMX_SB2006_JAC_NWRT || error("tangents: $(CMX_SB2006_JAC_NWRT) columns (or nothing) expected")
+    jvp === nothing || length(jvp) == CMX_SB2006_JAC_NOUT || error("jvp: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = ccall(_fn("cmx_sb2006_warm_rain_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), _ptrs(FT, tangents), _opt_ptrs(FT, jvp), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_jvp")
+    return jvp
+end
+
+"""
+    warm_rain_vjp_2m!(grad, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents; stream = C_NULL)
+
+Jᵀḡ of the tendencies of `warm_rain_jacobian_2m!`: `cotangents` = `CMX_SB2006_JAC_NOUT` (4) device columns or `nothing`s (that output is not part of the
+sum), `grad` = `nothing` or 6 columns (or `nothing`s: that input is not differentiated) in the order (T, q_tot, q_lcl, n_lcl, q_rai, n_rai) — the
+gradient of Σ_o ḡ_o·out_o, contracted on the device before anything is stored.  `tendencies` as there.
+"""
+function warm_rain_vjp_2m!(grad, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+    cotangents; stream = C_NULL) where {WR, FT}
+    length(cotangents) == CMX_SB2006_JAC_NOUT || error("cotangents: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    grad === nothing || length(grad) == CMX_SB2006_JAC_NWRT || error("grad: $(CMX_SB2006_JAC_NWRT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = ccall(_fn("cmx_sb2006_warm_rain_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), _ptrs(FT, cotangents), _opt_ptrs(FT, grad), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
+# (17) products with the Jacobian of the 1-moment tendencies: J v and Jᵀḡ, fused
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    jvp_1m!(jvp, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, tangents; stream = C_NULL)
+
+J v of the tendencies of `jacobian_1m!`: `tangents` = `CMX_MP1M_JAC_NWRT` (6) device columns or `nothing`s (a zero tangent) in the order (T, q_tot, q_lcl,
+q_icl, q_rai, q_sno), `jvp` = `nothing` or 4 columns (or `nothing`s).  Rules as for `warm_rain_jvp_2m!`.
+"""
+function jvp_1m!(jvp, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno, tangents;
+    stream = C_NULL) where {FT}
+    length(tangents) == CMX_MP1M_JAC_NWRT || error("tangents: $(CMX_MP1M_JAC_NWRT) columns (or nothing) expected")
+    jvp === nothing || length(jvp) == CMX_MP1M_JAC_NOUT || error("jvp: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), _ptrs(FT, tangents), _opt_ptrs(FT, jvp), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_jvp")
+    return jvp
+end
+
+"""
+    vjp_1m!(grad, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents; stream = C_NULL)
+
+Jᵀḡ of the tendencies of `jacobian_1m!`: `cotangents` = `CMX_MP1M_JAC_NOUT` (4) device columns or `nothing`s (that output is not part of the sum), `grad` =
+`nothing` or 6 columns (or `nothing`s: that input is not differentiated).  Rules as for `warm_rain_vjp_2m!`.
+"""
+function vjp_1m!(grad, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents;
+    stream = C_NULL) where {FT}
+    length(cotangents) == CMX_MP1M_JAC_NOUT || error("cotangents: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    grad === nothing || length(grad) == CMX_MP1M_JAC_NWRT || error("grad: $(CMX_MP1M_JAC_NWRT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), _ptrs(FT, cotangents), _opt_ptrs(FT, grad), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
