@@ -2,6 +2,7 @@
 Jacobian (warm_rain_jvp_2m / warm_rain_vjp_2m, jvp_1m / vjp_1m): `wrt` validation, `out=` handling, the contiguity checks, the pointer tables of the ABI
 (include/cmx.h §(14) – §(17)) and the call."""
 import ctypes as C
+import itertools
 
 import torch
 
@@ -9,51 +10,10 @@ from . import _lib
 from ._cols import _check_cols, _fam_of, _ptr
 
 
-def _jacobian(entry, params, flags, tps, cols, names, wrt_all, nout, wrt, with_tendencies, out, stream):
-    """(jac, tendencies, wrt) of `entry`_f32 / _f64.  params: the parameter object of the entry (`.c`, `.fam`); cols / names: the state columns, rho first;
-    wrt_all: the entry's differentiable inputs in ABI order; nout: its outputs."""
+def _check_wrt(wrt, wrt_all, what="wrt", rho_is_unknown=False):
     wrt = tuple(wrt)
     for name in wrt:
-        if name not in wrt_all:
-            raise ValueError(f"wrt: unknown input '{name}' (one of {wrt_all}; rho is not differentiated)")
-    if len(set(wrt)) != len(wrt):
-        raise ValueError("wrt: an input is listed twice")
-    if not wrt and not with_tendencies:
-        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
-    ref = _check_cols(cols, names)
-    fam = _fam_of(ref)
-    if fam is not params.fam or not isinstance(tps, fam.thermo):
-        raise TypeError("parameter float type does not match the state columns")
-    jac, tend = out if out is not None else (None, None)
-    if jac is None:
-        jac = torch.empty((nout, len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
-    elif jac.shape != (nout, len(wrt), *ref.shape):
-        raise ValueError(f"out: jac must have shape ({nout}, len(wrt), *rho.shape) = {(nout, len(wrt), *ref.shape)}")
-    if with_tendencies:
-        if tend is None:
-            tend = torch.empty((nout, *ref.shape), dtype=ref.dtype, device=ref.device)
-        elif tend.shape != (nout, *ref.shape):
-            raise ValueError(f"out: tendencies must have shape ({nout}, *rho.shape) = {(nout, *ref.shape)}")
-    elif tend is not None:
-        raise ValueError("out: a tendencies tensor was given but with_tendencies is False")
-    if wrt:
-        _check_cols([ref] + [jac[o, k] for o in range(nout) for k in range(len(wrt))], ["rho"] + ["jac"] * (nout * len(wrt)))
-    if tend is not None:
-        _check_cols([ref] + [tend[o] for o in range(nout)], ["rho"] + ["tendencies"] * nout)
-    ptrs = [None] * (nout * len(wrt_all))
-    for k, name in enumerate(wrt):
-        for o in range(nout):
-            ptrs[o * len(wrt_all) + wrt_all.index(name)] = jac[o, k].data_ptr()
-    jac_p = (C.c_void_p * len(ptrs))(*ptrs)
-    tend_p = (C.c_void_p * nout)(*[tend[o].data_ptr() for o in range(nout)]) if tend is not None else None
-    _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], jac_p, tend_p, stream=stream)
-    return jac, tend, wrt
-
-
-def _check_wrt(wrt, wrt_all, what="wrt"):
-    wrt = tuple(wrt)
-    for name in wrt:
-        if name == "rho":
+        if name == "rho" and not rho_is_unknown:
             raise ValueError(f"{what}: rho is not differentiated")
         if name not in wrt_all:
             raise ValueError(f"{what}: unknown input '{name}' (one of {wrt_all}; rho is not differentiated)")
@@ -62,7 +22,7 @@ def _check_wrt(wrt, wrt_all, what="wrt"):
     return wrt
 
 
-def _prep_product(params, tps, cols, names):
+def _prep(params, tps, cols, names):
     ref = _check_cols(cols, names)
     fam = _fam_of(ref)
     if fam is not params.fam or not isinstance(tps, fam.thermo):
@@ -70,13 +30,13 @@ def _prep_product(params, tps, cols, names):
     return ref, fam
 
 
-def _out_pair(out, ref, shape_a, name_a, nout, with_tendencies):
-    """(first output, tendencies) from `out=`: allocated where None, shapes checked, every leading slice contiguous."""
+def _out_pair(out, ref, shape_a, name_a, nout, with_tendencies, shape_text=""):
+    """(first output, tendencies) from `out=`: allocated where None, shapes checked, every slice a[i…] over the leading shape_a checked like a column."""
     a, tend = out if out is not None else (None, None)
     if a is None:
         a = torch.empty((*shape_a, *ref.shape), dtype=ref.dtype, device=ref.device)
     elif a.shape != (*shape_a, *ref.shape):
-        raise ValueError(f"out: {name_a} must have shape {(*shape_a, *ref.shape)}")
+        raise ValueError(f"out: {name_a} must have shape {shape_text}{(*shape_a, *ref.shape)}")
     if with_tendencies:
         if tend is None:
             tend = torch.empty((nout, *ref.shape), dtype=ref.dtype, device=ref.device)
@@ -84,8 +44,9 @@ def _out_pair(out, ref, shape_a, name_a, nout, with_tendencies):
             raise ValueError(f"out: tendencies must have shape ({nout}, *rho.shape) = {(nout, *ref.shape)}")
     elif tend is not None:
         raise ValueError("out: a tendencies tensor was given but with_tendencies is False")
-    if a.shape[0]:
-        _check_cols([ref] + [a[k] for k in range(a.shape[0])], ["rho"] + [name_a] * a.shape[0])
+    slices = [a[idx] for idx in itertools.product(*map(range, shape_a))]
+    if slices:
+        _check_cols([ref] + slices, ["rho"] + [name_a] * len(slices))
     if tend is not None:
         _check_cols([ref] + [tend[o] for o in range(nout)], ["rho"] + ["tendencies"] * nout)
     return a, tend
@@ -95,12 +56,29 @@ def _table(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
+def _jacobian(entry, params, flags, tps, cols, names, wrt_all, nout, wrt, with_tendencies, out, stream):
+    """(jac, tendencies, wrt) of `entry`_f32 / _f64.  params: the parameter object of the entry (`.c`, `.fam`); cols / names: the state columns, rho first;
+    wrt_all: the entry's differentiable inputs in ABI order; nout: its outputs."""
+    wrt = _check_wrt(wrt, wrt_all, rho_is_unknown=True)
+    if not wrt and not with_tendencies:
+        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
+    ref, fam = _prep(params, tps, cols, names)
+    jac, tend = _out_pair(out, ref, (nout, len(wrt)), "jac", nout, with_tendencies, f"({nout}, len(wrt), *rho.shape) = ")
+    columns = [None] * (nout * len(wrt_all))
+    for k, name in enumerate(wrt):
+        for o in range(nout):
+            columns[o * len(wrt_all) + wrt_all.index(name)] = jac[o, k]
+    _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], _table(columns),
+              _table([tend[o] for o in range(nout)]) if tend is not None else None, stream=stream)
+    return jac, tend, wrt
+
+
 def _jvp(entry, params, flags, tps, cols, names, wrt_all, nout, tangents, with_tendencies, out, stream):
     """(jvp, tendencies) of `entry`_f32 / _f64.  tangents: {name of a differentiable input: tensor}; a missing name is a zero tangent (a NULL column)."""
     if not isinstance(tangents, dict):
         raise TypeError("tangents must be a dict: name of a differentiable input -> tensor")
     _check_wrt(tangents.keys(), wrt_all, "tangents")
-    ref, fam = _prep_product(params, tps, cols, names)
+    ref, fam = _prep(params, tps, cols, names)
     given = [(k, v) for k, v in tangents.items() if v is not None]
     if given:
         _check_cols([ref] + [v for _, v in given], ["rho"] + [f"tangent of {k}" for k, _ in given])
@@ -119,7 +97,7 @@ def _vjp(entry, params, flags, tps, cols, names, wrt_all, nout, cotangents, wrt,
         raise ValueError(f"cotangents: {nout} tensors (or None) expected, one per output")
     if not wrt and not with_tendencies:
         raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
-    ref, fam = _prep_product(params, tps, cols, names)
+    ref, fam = _prep(params, tps, cols, names)
     given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
     if given:
         _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])

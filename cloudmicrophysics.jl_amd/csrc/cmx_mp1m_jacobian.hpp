@@ -1,6 +1,7 @@
-// cmx_mp1m_jacobian.hpp — what the device entry (cmx_mp1m_jacobian.hip) and the host test build (tests/native/jacobian_1m_host.cpp, CMX_HOST_BUILD) share
-// of the 1-moment tendency Jacobian: the tangents per pass and the scheme Mp1mJac that the driver of cmx_jacobian.hpp runs — the point function
-// mp1m_point + mp1m_aggregate (cmx_mp1m.hpp) on the dual value type (cmx_dual.hpp) and the entry's poison rule.  No HIP in here.
+// cmx_mp1m_jacobian.hpp — what the device entries (cmx_mp1m_jacobian.hip) and the host test build (tests/native/derivatives_host.cpp, CMX_HOST_BUILD) share
+// of the 1-moment tendency Jacobian and its products: the tangents per pass, the scheme Mp1mJac that the driver of cmx_jacobian.hpp runs — the point function
+// mp1m_point + mp1m_aggregate (cmx_mp1m.hpp) on the dual value type (cmx_dual.hpp) and the entry's poison rule — and its set-up from the parameter structs
+// (with_mp1m_jac).  No HIP in here.
 #pragma once
 #include <cstdint>
 
@@ -44,14 +45,11 @@ template <uint32_t FLAGS> struct Mp1mJac {
     }
 };
 
-// The entry's names for the driver's pieces: what cmx_mp1m_jacobian.hip launches with and what a host build of this header calls per point
-template <typename FT, int K> using Mp1mJacArgs = JacArgs<FT, K, CMX_MP1M_JAC_NOUT, CMX_MP1M_JAC_NWRT>;
-template <typename FT, int K> inline bool make_jac1m_args(Mp1mJacArgs<FT, K> &a, const FT *const (&in)[7], FT *const *jac, FT *const *tendencies) {
-    return make_jac_args(a, in, jac, tendencies);
-}
-template <typename FT, int K, uint32_t FLAGS, typename C>
-__device__ __forceinline__ void mp1m_jacobian_point(const C &c, const Mp1mJacArgs<FT, K> &a, const FT (&x)[7], int64_t i) {
-    jacobian_point<Mp1mJac<FLAGS>, FT, K>(c, a, x, i);
+// The set-up every 1-moment derivative entry and its host mirror share after the argument checks (check_flags_1m among them: it comes earlier in the
+// entries' status order): the constants and the instantiation flags_1m chooses as in cmx_mp1m_tendencies_*.  Returns f(c, Mp1mJac<FLAGS>{}).
+template <typename FT, typename MP, typename TH, typename F> inline int32_t with_mp1m_jac(const MP &mp, const TH &tps, uint32_t flags, F &&f) {
+    const Mp1mConsts<FT> c = make_mp1m_consts<FT>(mp, tps, flags, (double)Math<FT>::eps_1m());
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto FL) -> int32_t { return f(c, Mp1mJac<decltype(FL)::value>{}); }, flags_1m(flags, c));
 }
 
 }  // namespace cmx

@@ -1,10 +1,12 @@
-// cmx_sb2006_jacobian.hpp — what the device entry (cmx_sb2006_jacobian.hip) and the host test build (tests/native/jacobian_host.cpp, CMX_HOST_BUILD) share
-// of the SB2006 warm-rain Jacobian: the tangents per pass and the scheme SbJac that the driver of cmx_jacobian.hpp runs — the point function sb2006_point on
-// the dual value type (cmx_dual.hpp) and the entry's NaN rule.  No HIP in here.
+// cmx_sb2006_jacobian.hpp — what the device entries (cmx_sb2006_jacobian.hip) and the host test build (tests/native/derivatives_host.cpp, CMX_HOST_BUILD)
+// share of the SB2006 warm-rain Jacobian and its products: the tangents per pass, the scheme SbJac that the driver of cmx_jacobian.hpp runs — the point function
+// sb2006_point on the dual value type (cmx_dual.hpp) and the entry's NaN rule — and its set-up from the parameter structs (with_sb2006_jac).  No HIP in here.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "../../include/cmx.h"
+#include "cmx_dispatch.hpp"
 #include "cmx_jacobian.hpp"
 #include "cmx_sb2006.hpp"
 
@@ -51,11 +53,16 @@ template <bool LIMITED, bool INTPOW> struct SbJac {
     }
 };
 
-// The entry's names for the driver's pieces: what cmx_sb2006_jacobian.hip launches with and what a host build of this header calls per point
-template <typename FT, int K> using SbJacArgs = JacArgs<FT, K, CMX_SB2006_JAC_NOUT, CMX_SB2006_JAC_NWRT>;
-template <typename FT, int K, bool LIMITED, bool INTPOW, typename C>
-__device__ __forceinline__ void sb2006_jacobian_point(const C &c, const SbJacArgs<FT, K> &a, const FT (&x)[7], int64_t i) {
-    jacobian_point<SbJac<LIMITED, INTPOW>, FT, K>(c, a, x, i);
+// The set-up every SB2006 derivative entry and its host mirror share after the argument checks: the statuses of the flags and the limiter pairs, the constants,
+// and the instantiation the tendencies entry selects for the same parameter struct.  Returns f(c, SbJac<LIMITED, INTPOW>{}) or CMX_ERR_BAD_ARG.
+template <typename FT, typename WR, typename TH, typename F> inline int32_t with_sb2006_jac(const WR &wr, const TH &tps, uint32_t flags, F &&f) {
+    if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
+    const bool limited = flags & CMX_SB2006_LIMITED;
+    if (limited && !sb_limiters_ok(wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
+    const SbConsts<FT> c = make_sb_consts<FT>(wr, tps, (const std::conditional_t<std::is_same_v<FT, float>, cmx_rain_vel_f32, cmx_rain_vel_f64> *)nullptr,
+                                              (double)Math<FT>::eps_1m());
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t { return f(c, SbJac<decltype(L)::value, decltype(I)::value>{}); },
+                       flag(limited), flag(sb_integer_exponents(wr)));
 }
 
 }  // namespace cmx

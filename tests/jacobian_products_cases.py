@@ -1,5 +1,5 @@
 """What the tests of the products with the Jacobian share (tests/test_jacobian_products_host.py, tests/test_jacobian_products_gpu.py): the ctypes calls into the
-host build tests/native/jacobian_products_host.cpp, the two schemes' parameter cases as one table, and the MIXED-VECTOR check.
+host build tests/native/derivatives_host.cpp, the two schemes' parameter cases as one table, and the MIXED-VECTOR check.
 
 States, reference Jacobians, bounds and the 1 % set-aside cap are those of tests/jacobian_cases.py and tests/jacobian_1m_cases.py, imported, not restated.
 
@@ -20,13 +20,13 @@ import numpy as np
 
 import jacobian_1m_cases as J1
 import jacobian_cases as JC
-from jacobian_host_build import CT, NPT, _arr, _same_bits, host_fixture  # noqa: F401
+from jacobian_host_build import CT, JAC, JVP, NPT, VJP, _same_bits, host_fixture, host_plain  # noqa: F401
+from jacobian_host_build import host_call as _call
 from cmx import _abi
 from cmx import parameters as P
 
-host = host_fixture("jacobian_products_host")
+host = host_fixture()
 BOUND = JC.BOUND
-JAC, JVP, VJP = 0, 1, 2
 
 
 # ---- the two schemes as one table ---------------------------------------------------------------------------------------------------------------
@@ -86,14 +86,6 @@ def head(scheme, ft, case):
 
 
 # ---- calls into the host build ------------------------------------------------------------------------------------------------------------------
-def _call(host, entry, ft, what, head, k, cols, p, q, tend):
-    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
-    fn = getattr(host, f"host_{entry}_product_{ft}")
-    fn.restype = C.c_int32
-    return fn(C.c_int(what), *head, C.c_int(k), C.c_int64(x[0].size), _arr(ft, x), _arr(ft, p) if p is not None else None, _arr(ft, q) if q is not None else None,
-              _arr(ft, list(tend)) if tend is not None else None)
-
-
 def _given(ft, cols):
     return [np.ascontiguousarray(c, dtype=NPT[ft]) if c is not None else None for c in cols]
 
@@ -126,15 +118,6 @@ def host_vjp(host, entry, ft, head, cols, cotangents, nwrt=6, nout=4, want=None,
     want = [True] * nwrt if want is None else want
     rc = _call(host, entry, ft, VJP, head, k, cols, _given(ft, cotangents) if table else None, [grad[j] if want[j] else None for j in range(nwrt)], tend)
     return grad, tend, rc
-
-
-def host_plain(host, entry, ft, head, cols, nout=4):
-    x = [np.ascontiguousarray(c, dtype=NPT[ft]) for c in cols]
-    y = np.empty((nout, x[0].size), dtype=NPT[ft])
-    fn = getattr(host, f"host_{entry}_plain_{ft}")
-    fn.restype = C.c_int32
-    rc = fn(*head, C.c_int64(x[0].size), _arr(ft, x), _arr(ft, list(y)))
-    return y, rc
 
 
 def assemble(jvp_of, vjp_of, n, ft, nout=4, nwrt=6):

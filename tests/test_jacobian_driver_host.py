@@ -1,5 +1,5 @@
 """The Jacobian driver of csrc/cmx_jacobian.hpp is scheme-independent (no GPU): both real schemes are 4 × 6, so the slot table, the pass loop and the
-stores are run here on the toy scheme of tests/native/jacobian_toy_host.cpp — 3 outputs, 5 differentiated inputs, sums and products only.  On small-integer
+stores are run here on the toy scheme of tests/native/derivatives_host.cpp — 3 outputs, 5 differentiated inputs, sums and products only.  On small-integer
 states every value and derivative is exact in Float32 and Float64, so the analytic Jacobian is asserted with ==.  K = 1 … 5: SLOTS = ⌈5/K⌉·K pads the last
 pass with idle slots for K = 2, 3, 4."""
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 import jacobian_host_build as JH
 from jacobian_host_build import CT, NPT, _same_bits
 
-host = JH.host_fixture("jacobian_toy_host")
+host = JH.host_fixture()
 WRT = ("a", "b", "c", "d", "e")
 W = 2.0
 SENTINEL = -777.0
@@ -30,7 +30,7 @@ def analytic(cols):
 
 def toy(host, ft, cols, wrt=WRT, k=0, with_tendencies=True, null=()):
     """null: (output, input name) members of the Jacobian left NULL."""
-    jac, tend, rc = JH.host_jacobian(host, "toy_jacobian", ft, (CT[ft](W),), cols, WRT, wrt, nout=3, k=k, with_tendencies=with_tendencies, sentinel=SENTINEL,
+    jac, tend, rc = JH.host_jacobian(host, "toy", ft, (CT[ft](W),), cols, WRT, wrt, nout=3, k=k, with_tendencies=with_tendencies, sentinel=SENTINEL,
                                      null=null)
     return jac, tend, rc
 

@@ -1,5 +1,5 @@
-"""The products with the Jacobian without a GPU (include/cmx.h §(16), §(17); csrc/cmx_jacobian_products.hpp): jvp_point / vjp_point and their argument
-tables compiled by g++ for the host (tests/native/jacobian_products_host.cpp) on SbJac, Mp1mJac and the exact toy scheme.
+"""The products with the Jacobian without a GPU (include/cmx.h §(16), §(17); csrc/cmx_jacobian.hpp): jvp_point / vjp_point and their argument
+tables compiled by g++ for the host (tests/native/derivatives_host.cpp) on SbJac, Mp1mJac and the exact toy scheme.
 
   * toy scheme: J v and Jᵀḡ equal the exact products, for every tangent width of the VJP;
   * parity through the existing yardstick: J assembled column by column from six J v with unit tangents and row by row from four Jᵀḡ with unit cotangents,
@@ -243,10 +243,10 @@ def test_statuses_of_the_entry_mirrors(host, oracle, ft, name):
 
 @pytest.mark.parametrize("ft", FTS)
 @pytest.mark.parametrize("stem", ["cmx_sb2006_warm_rain", "cmx_mp1m"])
-@pytest.mark.parametrize("product", ["jvp", "vjp"])
+@pytest.mark.parametrize("product", ["jvp", "vjp", "jacobian"])
 def test_argument_statuses_of_the_library_entries_without_gpu(ft, stem, product):
-    """The eight entries of libcmx.so: the statuses of the scheme's Jacobian entry in its order, the table itself NULL, no output column at all.  Every call
-    below returns before any HIP runtime call."""
+    """The twelve entries of libcmx.so: the statuses of the scheme's Jacobian entry in its order, the table itself NULL (the products; the Jacobian entry takes
+    no table, its result table is jac[24]), no output column at all.  Every call below returns before any HIP runtime call."""
     from cmx import _lib
     from cmx import parameters as P
     fn = getattr(_lib.lib(), f"{stem}_{product}_{ft}")
@@ -254,7 +254,7 @@ def test_argument_statuses_of_the_library_entries_without_gpu(ft, stem, product)
     sb = stem == "cmx_sb2006_warm_rain"
     mp, tps = (P.WarmRainParams2M(ft, True) if sb else P.Microphysics1MParams(ft)), P.ThermodynamicsParameters(ft)
     good = _abi.CMX_SB2006_LIMITED if sb else mp.flags
-    n_in, n_out = (6, 4) if product == "jvp" else (4, 6)
+    n_in, n_out = {"jvp": (6, 4), "vjp": (4, 6), "jacobian": (0, 24)}[product]
     seven = [C.c_void_p(4096 + 64 * k) for k in range(7)]
     table = (C.c_void_p * n_in)(*[8192 + 64 * k for k in range(n_in)])
     res = (C.c_void_p * n_out)(*[16384 + 64 * k for k in range(n_out)])
@@ -263,7 +263,7 @@ def test_argument_statuses_of_the_library_entries_without_gpu(ft, stem, product)
     huge = 16 * 0x7fffffff + 1
 
     def call(flags=good, n=8, cols=seven, p=table, r=res, t=tend, w=mp, th=tps):
-        return fn(C.byref(w.c) if w is not None else None, C.byref(th) if th is not None else None, flags, n, *cols, p, r, t, None)
+        return fn(C.byref(w.c) if w is not None else None, C.byref(th) if th is not None else None, flags, n, *cols, *([p] if n_in else []), r, t, None)
     assert call(w=None) == BAD and call(th=None) == BAD                                   # no parameters
     assert call(n=-1) == BAD and call(n=huge) == UNS and call(n=0) == OK                   # the count rule
     assert call(n=0, cols=[None] * 7, p=None, r=None, t=None) == OK                        # n = 0 returns before the columns matter
@@ -271,6 +271,6 @@ def test_argument_statuses_of_the_library_entries_without_gpu(ft, stem, product)
     assert call(flags=1 << 17, n=0) == (OK if sb else BAD)                                 # SB2006: n = 0 first; 1-moment: the flags first, as its Jacobian entry
     for k in range(7):                                                                     # a NULL input column
         assert call(cols=seven[:k] + [None] + seven[k + 1:]) == BAD, k
-    assert call(p=None) == BAD                                                             # the tangent / cotangent table itself
+    assert not n_in or call(p=None) == BAD                                                 # the tangent / cotangent table itself
     assert call(r=None, t=None) == BAD and call(r=nores, t=None) == BAD and call(r=nores, t=notend) == BAD and call(r=None, t=notend) == BAD    # no output
     del notable

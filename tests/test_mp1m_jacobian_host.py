@@ -1,7 +1,7 @@
 """The 1-moment tendency Jacobian without a GPU (include/cmx.h §(15), cmx.jacobian_1m):
 
   * the dual instantiation of the device point function (csrc/cmx_dual.hpp, csrc/cmx_mp1m_jacobian.hpp) compiled by g++ for the host
-    (tests/native/jacobian_1m_host.cpp) against central differences of the Float64 oracle — tests/jacobian_1m_cases.py has the states, the reference and
+    (tests/native/derivatives_host.cpp) against central differences of the Float64 oracle — tests/jacobian_1m_cases.py has the states, the reference and
     the measure — at the reference's own bound 1e-5 (test/ad_compat_tests.jl:163) in Float64 and the project's Float32 bound 1e-3 in every row in Float32
     (worst Float32 row in this build: 1.5e-4, dq_icl_dt with the alternative options on the cold set);
   * the same parity in the second, input-scaled measure of tests/jacobian_cases.py (every entry weighted by |x_j|: it shows the T column, which the
@@ -32,7 +32,7 @@ from cmx import parameters as P
 
 DT = {"f32": torch.float32, "f64": torch.float64}
 T_FREEZE = 273.15
-host = host_fixture("jacobian_1m_host")
+host = host_fixture()
 
 
 def _head(ft, mp):
@@ -41,11 +41,11 @@ def _head(ft, mp):
 
 def host_jacobian(host, ft, mp, cols, wrt=JC.WRT, k=0, with_tendencies=True):
     """([4, len(wrt), n] Jacobian, [4, n] tendencies, status) of the host build; wrt: names in any order."""
-    return JH.host_jacobian(host, "mp1m_jacobian", ft, _head(ft, mp), cols, JC.WRT, wrt, k=k, with_tendencies=with_tendencies)
+    return JH.host_jacobian(host, "mp1m", ft, _head(ft, mp), cols, JC.WRT, wrt, k=k, with_tendencies=with_tendencies)
 
 
 def host_plain(host, ft, mp, cols):
-    return JH.host_plain(host, "mp1m_plain", ft, _head(ft, mp), cols)
+    return JH.host_plain(host, "mp1m", ft, _head(ft, mp), cols)
 
 
 def _synthetic(ft):

@@ -1,7 +1,7 @@
 """The SB2006 warm-rain Jacobian without a GPU (include/cmx.h §(14), cmx.warm_rain_jacobian_2m):
 
   * the dual instantiation of the device point function (csrc/cmx_dual.hpp, csrc/cmx_sb2006_jacobian.hpp) compiled by g++ for the host
-    (tests/native/jacobian_host.cpp) against central differences of the Float64 oracle — tests/jacobian_cases.py has the states, the reference and the
+    (tests/native/derivatives_host.cpp) against central differences of the Float64 oracle — tests/jacobian_cases.py has the states, the reference and the
     measure — at the reference's own bound 1e-5 (test/ad_compat_tests.jl:163) in Float64 and the project's Float32 bound 1e-3 in every row in Float32 —
     except dn_rai_dt with the perturbed parameter set, which misses it at ONE state (2.2e-3 here, 2.3e-3 on the device) and is held entry by entry to the
     bound its evaporation share earns from the oracle's own Float32-against-Float64 spread of the evaporation rate (jacobian_cases.float32_bound);
@@ -29,7 +29,7 @@ import cmx
 from cmx import _abi, _lib, synthetic
 from cmx import parameters as P
 
-host = host_fixture("jacobian_host")
+host = host_fixture()
 
 
 def _head(ft, wr, limited):
@@ -38,11 +38,11 @@ def _head(ft, wr, limited):
 
 def host_jacobian(host, ft, wr, limited, cols, wrt=JC.WRT, k=0, with_tendencies=True):
     """([4, len(wrt), n] Jacobian, [4, n] tendencies, status) of the host build; wrt: names in any order."""
-    return JH.host_jacobian(host, "sb2006_jacobian", ft, _head(ft, wr, limited), cols, JC.WRT, wrt, k=k, with_tendencies=with_tendencies)
+    return JH.host_jacobian(host, "sb2006", ft, _head(ft, wr, limited), cols, JC.WRT, wrt, k=k, with_tendencies=with_tendencies)
 
 
 def host_plain(host, ft, wr, limited, cols):
-    return JH.host_plain(host, "sb2006_plain", ft, _head(ft, wr, limited), cols)
+    return JH.host_plain(host, "sb2006", ft, _head(ft, wr, limited), cols)
 
 
 # ---- parity against the finite-difference reference ---------------------------------------------------------------------------------------------
