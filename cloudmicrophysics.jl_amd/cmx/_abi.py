@@ -147,6 +147,7 @@ CMX_MP1M_JAC_NCOL = CMX_MP1M_JAC_NOUT * CMX_MP1M_JAC_NWRT
 # the products with the two Jacobians (include/cmx.h §16, §17): <stem>_jvp_* takes tangents[NWRT], jvp[NOUT], tendencies[NOUT]; <stem>_vjp_* takes
 # cotangents[NOUT], grad[NWRT], tendencies[NOUT]
 JACOBIAN_PRODUCT_STEMS = ("cmx_sb2006_warm_rain", "cmx_mp1m")
+# the linearly implicit tendencies of the same two schemes (include/cmx.h §18): <stem>_implicit_tendencies_* takes dt, implicit[NOUT], tendencies[NOUT]
 
 
 def _struct(name, fields):

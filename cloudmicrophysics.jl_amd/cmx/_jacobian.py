@@ -1,8 +1,9 @@
 """The launch path the Jacobian wrappers share (bulk_tendencies.warm_rain_jacobian_2m, microphysics1m.jacobian_1m) and that of the products with the
-Jacobian (warm_rain_jvp_2m / warm_rain_vjp_2m, jvp_1m / vjp_1m): `wrt` validation, `out=` handling, the contiguity checks, the pointer tables of the ABI
-(include/cmx.h §(14) – §(17)) and the call."""
+Jacobian (warm_rain_jvp_2m / warm_rain_vjp_2m, jvp_1m / vjp_1m) and of the linearly implicit tendencies (warm_rain_implicit_tendencies_2m,
+implicit_tendencies_1m): `wrt` validation, `out=` handling, the contiguity checks, the pointer tables of the ABI (include/cmx.h §(14) – §(18)) and the call."""
 import ctypes as C
 import itertools
+import math
 
 import torch
 
@@ -108,3 +109,15 @@ def _vjp(entry, params, flags, tps, cols, names, wrt_all, nout, cotangents, wrt,
     _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], _table(cotangents), _table(grads),
               _table([tend[o] for o in range(nout)]) if tend is not None else None, stream=stream)
     return grad, tend, wrt
+
+
+def _implicit(entry, params, flags, tps, cols, names, nout, dt, with_tendencies, out, stream):
+    """(implicit, tendencies) of `entry`_f32 / _f64: r = (I − dt·J)⁻¹ f over the `nout` species of the scheme.  dt: a finite number ≥ 0."""
+    dt = float(dt)
+    if not (math.isfinite(dt) and dt >= 0.0):
+        raise ValueError("dt must be finite and >= 0")
+    ref, fam = _prep(params, tps, cols, names)
+    impl, tend = _out_pair(out, ref, (nout,), "implicit", nout, with_tendencies)
+    _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], dt,
+              _table([impl[o] for o in range(nout)]), _table([tend[o] for o in range(nout)]) if tend is not None else None, stream=stream)
+    return impl, tend

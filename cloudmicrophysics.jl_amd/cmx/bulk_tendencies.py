@@ -24,7 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _jacobian, _jvp, _vjp
+from ._jacobian import _implicit, _jacobian, _jvp, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -197,6 +197,25 @@ def warm_rain_vjp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotange
     return WarmRainVjp2M(*_vjp("cmx_sb2006_warm_rain_vjp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
                                (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, JACOBIAN_WRT, _abi.CMX_SB2006_JAC_NOUT, cotangents, wrt,
                                with_tendencies, out, stream))
+
+
+WarmRainImplicit2M = namedtuple("WarmRainImplicit2M", ["implicit", "tendencies"])
+
+
+def warm_rain_implicit_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, with_tendencies=False, *, out=None,
+                                     stream=None) -> WarmRainImplicit2M:
+    """The tendency of a linearly implicit (Rosenbrock–Euler) step of the 2-moment warm-rain tendencies behind `cmx_sb2006_warm_rain_implicit_tendencies_*`:
+    r = (I − dt·J)⁻¹ f per point, with f the four tendencies and J their Jacobian with respect to the species (q_lcl, n_lcl, q_rai, n_rai) at fixed ρ, T,
+    q_tot — the 4 × 4 block of `warm_rain_jacobian_2m`, equilibrated and solved in registers in the pass that computes it (partial pivoting), instead of 20
+    columns written, read back and handed to `torch.linalg.solve`.  The step is s ← s + dt·r; r = f in every bit at dt = 0.
+
+    `dt`: seconds, finite and ≥ 0.  Returns `WarmRainImplicit2M(implicit, tendencies)`: `implicit` of shape (4, *rho.shape) in the order of
+    `JACOBIAN_OUTPUTS`; `tendencies` (4, *rho.shape), bit-identical to `bulk_microphysics_tendencies`, with `with_tendencies=True`, else None.
+    `out=(implicit, tendencies)` lets the caller provide either tensor; `implicit` may be a view of the four species columns themselves (in place).  A singular I − dt·J gives a non-finite r at that point only.  No sub-stepping, no
+    positivity limiting of s + dt·r, no autograd through the solve.  Asynchronous on `stream` (default: torch's current stream)."""
+    wr = _warm_rain(mp)
+    return WarmRainImplicit2M(*_implicit("cmx_sb2006_warm_rain_implicit_tendencies", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                                         (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, _abi.CMX_SB2006_JAC_NOUT, dt, with_tendencies, out, stream))
 
 
 AOS_FIELDS = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt")

@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _jacobian, _jvp, _vjp
+from ._jacobian import _implicit, _jacobian, _jvp, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -155,6 +155,20 @@ def vjp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, wrt=J
         raise TypeError("mp must be Microphysics1MParams")
     return Vjp1M(*_vjp("cmx_mp1m_vjp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M, _abi.CMX_MP1M_JAC_NOUT,
                        cotangents, wrt, with_tendencies, out, stream))
+
+
+Implicit1M = namedtuple("Implicit1M", ["implicit", "tendencies"])
+
+
+def implicit_tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, with_tendencies=False, *, out=None, stream=None) -> Implicit1M:
+    """The tendency of a linearly implicit (Rosenbrock–Euler) step of the 1-moment tendencies (Instantaneous mode) behind `cmx_mp1m_implicit_tendencies_*`:
+    r = (I − dt·J)⁻¹ f per point with J the true Jacobian with respect to (q_lcl, q_icl, q_rai, q_sno) — the 4 × 4 block of `jacobian_1m`, not the donor-based
+    linearization of LinearizedAverage — solved in registers in the pass that computes it.  Returns `Implicit1M(implicit, tendencies)` with `implicit` of
+    shape (4, *rho.shape) in the order of `JACOBIAN_OUTPUTS_1M`; arguments as for `cmx.warm_rain_implicit_tendencies_2m`."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    return Implicit1M(*_implicit("cmx_mp1m_implicit_tendencies", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES,
+                                 _abi.CMX_MP1M_JAC_NOUT, dt, with_tendencies, out, stream))
 
 
 def bulk_microphysics_tendencies_1m_fields(mode, scheme, mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt=None, nsub=1, *, q_min=None, out=None,

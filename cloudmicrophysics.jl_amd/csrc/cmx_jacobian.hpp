@@ -1,6 +1,6 @@
 // cmx_jacobian.hpp — the forward-mode derivative driver every scheme's entries share (cmx_sb2006_jacobian.hpp, cmx_mp1m_jacobian.hpp), on the device and in the
 // host test build (tests/native/derivatives_host.cpp, CMX_HOST_BUILD): the table that maps tangent slots to inputs and, per operation — the Jacobian, J v,
-// Jᵀḡ — the argument struct, every pass of one point with its stores, and the kernel.  No HIP outside the CMX_HOST_BUILD guards.
+// Jᵀḡ, the linearly implicit tendency (I − Δt J)⁻¹ f — the argument struct, every pass of one point with its stores, and the kernel.  No HIP outside the CMX_HOST_BUILD guards.
 //
 // A SCHEME is a struct of static members that supplies what differs between two entries:
 //   NOUT, NWRT               outputs and differentiated inputs; a point is x[0] = ρ (held fixed) and x[1 … NWRT], the inputs in the order of the entry's wrt enum
@@ -251,6 +251,240 @@ __device__ __forceinline__ void vjp_point(const C &c, const VjpArgs<FT, K, S::NO
     }
 }
 
+// ---- (I − Δt J)⁻¹ f: the tendency of a linearly implicit (Rosenbrock–Euler) step, solved in the pass that holds the tangents in registers -----------------------
+// The scheme's outputs are the tendencies f of NOUT of its inputs, the species s = in[S::SPECIES0 … S::SPECIES0 + NOUT − 1] (x[1 + S::SPECIES0 + j]); with
+// J = ∂f/∂s at fixed ρ and the other inputs, r = (I − Δt J)⁻¹ f is the tendency of the step s ← s + Δt r.  r and not δ = Δt r: no division, and r = f at Δt = 0.
+//   * The tangents are the Jacobian entry's: run-time unit seeds on the species, ⌈NOUT/K⌉ passes, every input made opaque per pass (keep(), see jacobian_point).
+//     So J does not depend on K, bit for bit, and is what jacobian_point would store; the primal `tend` is the plain instantiation's bit for bit.
+//     The matrix is indexed by constants only and stays in registers.
+//   * A = I − Δt J is formed as fma(−Δt, J_ij, δ_ij) and EQUILIBRATED with exact powers of two, taken from the exponent field (pow2_floor), never a rounding
+//     multiply: column j by c_j = 2^⌊log2 s_j⌋ of the clamped state (1 for an absent species, s_j ≤ 0) — the unknown becomes the relative change r_j/c_j, and a
+//     change of units of a species (kg⁻¹ against kg kg⁻¹: ten orders of magnitude in SB2006) scales row and column of A·diag(c) by the same exact factor —
+//     then row i by the inverse of 2^⌊log2 max_j |A_ij c_j|⌋.  Scaling by a power of two commutes with rounding (short of over- and underflow), so it adds no
+//     error of its own, and the equilibrated system of a state in other units is the same system.
+//   * Gaussian elimination with partial pivoting, fully unrolled: the pivot row moves by compare-and-select swaps (no register array is indexed by a
+//     run-time value), ONE reciprocal per pivot (rcp1: the hardware seed with the library's Newton refinement), multipliers and updates as fma.  A multiplier
+//     or coefficient that is exactly zero leaves the row untouched in every bit (a select), the sign of a zero included: at Δt = 0 the system is I r = f
+//     and r = f in every bit.
+//   * ONE step of iterative refinement in the working precision, from the same factors (a residual and a second substitution, no second division).
+//     Partial pivoting bounds the backward error in the norm of the row, not component by component, and the relative changes r_j / c_j of a trace species
+//     and of a dominant one differ by orders of magnitude: without the step the componentwise backward error ω reached 2e-4 in Float32 (5e-13 in Float64)
+//     on the states of tests/implicit_cases.py — a small component wrong in its fourth digit — with it ω ≤ 1 eps (Float32) / 3 eps (Float64) at every
+//     state and Δt there (Skeel 1980: one step in fixed precision makes Gaussian elimination componentwise backward stable).  Equilibrating the columns
+//     by their maxima instead was worse (ω up to 6e-2), by 2^⌊log2 |f_j|⌋ better (70 eps) but still outside what LAPACK in Float64 rounds to.
+// Edge semantics:
+//   * A zero pivot — a singular I − Δt J — follows IEEE: rcp1(0) = ±Inf and the point's r is non-finite; that point only, no status, no branch.
+//   * An absent species (input ≤ 0) has a zero Jacobian column through the scheme's max0 clamp: its column of A is the unit vector, the solve is regular.
+//   * The library's NaN rule through the scheme's poison() / out(): a NaN in any input of the point (the 1-moment Float64 entry: also ρ ≤ 0) gives NaN in
+//     every output of that point and in no other.
+// All NOUT components of r are computed whatever subset is stored, so a column's bits do not depend on which others are requested.
+// Out of scope: sub-stepping inside the kernel, carrying T or q_tot in the solve, positivity limiting of s + Δt r, autograd through the solve, the 2M + P3 scheme.
+// Tangents per evaluation of the point function, per float type, for both schemes: tuning numbers (-DCMX_IMPLICIT_K_F32=…, -DCMX_IMPLICIT_K_F64=…; 1, 2 or 4).
+// Float32: 1 — the only width inside 128 VGPRs (SB2006 124–127, 1-moment 93–104; K = 2: 148 / 126–142, K = 4: 154 / 159–185, which are faster per call,
+// 0.42 / 0.35 against 0.54 ms per 1e7 SB2006 points, and are given up for the four waves per SIMD the other Float32 kernels of the layer keep).  Float64: 4 —
+// one pass, 330–336 / 308–398 VGPRs at one wave per SIMD like the Jacobian's own K = 3, 1.05 against 1.58 (K = 1, 255 VGPRs, two waves) and 1.46 ms (K = 2).
+// No width spills a VGPR or touches scratch.  The table is DESIGN.md §9; tools/time_implicit.py --fused-only times a build with another K (CMX_LIB).
+#ifndef CMX_IMPLICIT_K_F32
+#define CMX_IMPLICIT_K_F32 1
+#endif
+#ifndef CMX_IMPLICIT_K_F64
+#define CMX_IMPLICIT_K_F64 4
+#endif
+template <typename FT> constexpr int kImplicitK = sizeof(FT) == 4 ? CMX_IMPLICIT_K_F32 : CMX_IMPLICIT_K_F64;
+
+namespace implicit_detail {
+template <typename FT> struct Pow2;
+template <> struct Pow2<float> { using U = uint32_t; static constexpr int MANT = 23, BIAS = 127; };
+template <> struct Pow2<double> { using U = uint64_t; static constexpr int MANT = 52, BIAS = 1023; };
+// 2^⌊log2 |x|⌋ from the exponent field, kept to [2^(1−BIAS), 2^(BIAS−1)] so that it and its inverse are normal numbers (0 and subnormals give the smallest,
+// Inf and NaN the largest)
+template <typename FT> __device__ __forceinline__ FT pow2_floor(FT x) {
+    using P = Pow2<FT>;
+    using U = typename P::U;
+    constexpr U lo = (U)1 << P::MANT, hi = (U)(2 * P::BIAS - 1) << P::MANT;
+    U u = __builtin_bit_cast(U, x) & ((U)(2 * P::BIAS + 1) << P::MANT);
+    u = u < lo ? lo : (u > hi ? hi : u);
+    return __builtin_bit_cast(FT, u);
+}
+// 1/p for p = pow2_floor(·): the exponent field mirrored, exact
+template <typename FT> __device__ __forceinline__ FT pow2_inv(FT p) {
+    using P = Pow2<FT>;
+    using U = typename P::U;
+    return __builtin_bit_cast(FT, (U)(((U)(2 * P::BIAS) << P::MANT) - __builtin_bit_cast(U, p)));
+}
+// 1/d with the IEEE results for d = ±0, ±Inf and NaN: Float64 is the library's rcp (seed, two Newton steps, the seed itself where it is 0 or ±Inf); Float32 the
+// hardware seed (1 ulp) with one Newton step and the same fix-up
+__device__ __forceinline__ double rcp1(double d) { return Math<double>::rcp(d); }
+__device__ __forceinline__ float rcp1(float d) {
+    const float r0 = Math<float>::rcp(d);
+    const float r = Math<float>::fma(r0, Math<float>::fma(-d, r0, 1.0f), r0);
+    return (bool)((int)(r0 == 0.0f) | (int)(__builtin_fabsf(r0) == __builtin_inff())) ? r0 : r;
+}
+__device__ __forceinline__ float absv(float x) { return __builtin_fabsf(x); }
+__device__ __forceinline__ double absv(double x) { return __builtin_fabs(x); }
+template <typename FT> __device__ __forceinline__ void cswap(bool c, FT &a, FT &b) {
+    const FT t = c ? b : a;
+    b = c ? a : b;
+    a = t;
+}
+// acc − m·v; acc itself, in every bit, where m is exactly zero
+template <typename FT> __device__ __forceinline__ FT fnma_nz(FT m, FT v, FT acc) { return m == FT(0) ? acc : Math<FT>::fma(-m, v, acc); }
+
+// P B = L U of an N × N matrix in registers, in place: partial pivoting by compare-and-select swaps, every index a compile-time constant after unrolling.
+// Step k exchanges row k with every later row whose entry in column k is larger (sw[k][i]; afterwards row k holds the largest of rows k … N − 1, the first
+// one on a tie), in the columns k … N − 1 only: the multipliers of the earlier steps stay where substitute() applies them, between the same exchanges.
+// piv[k] = 1 / U_kk, the ONE division of the step; the multipliers take the place of the eliminated entries.
+template <typename FT, int N> __device__ __forceinline__ void factor_pivoted(FT (&B)[N][N], bool (&sw)[N][N], FT (&piv)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            sw[k][i] = absv(B[i][k]) > absv(B[k][k]);
+#pragma unroll
+            for (int j = k; j < N; ++j) cswap(sw[k][i], B[k][j], B[i][j]);
+        }
+        piv[k] = rcp1(B[k][k]);
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) {
+            const FT m = B[i][k] * piv[k];
+            B[i][k] = m;
+#pragma unroll
+            for (int j = k + 1; j < N; ++j) B[i][j] = fnma_nz(m, B[k][j], B[i][j]);
+        }
+    }
+}
+// g ← (P⁻¹ L U)⁻¹ g from the factors: the exchanges and multipliers of step k in the order factor_pivoted took them, then the back substitution
+template <typename FT, int N> __device__ __forceinline__ void substitute(const FT (&LU)[N][N], const bool (&sw)[N][N], const FT (&piv)[N], FT (&g)[N]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) cswap(sw[k][i], g[k], g[i]);
+#pragma unroll
+        for (int i = k + 1; i < N; ++i) g[i] = fnma_nz(LU[i][k], g[k], g[i]);
+    }
+#pragma unroll
+    for (int k = N - 1; k >= 0; --k) {
+        FT acc = g[k];
+#pragma unroll
+        for (int j = k + 1; j < N; ++j) acc = fnma_nz(LU[k][j], g[j], acc);
+        g[k] = acc * piv[k];
+    }
+}
+}  // namespace implicit_detail
+
+// `wrt[s]`: the input tangent slot s = pass·K + k is seeded on, S::SPECIES0 + s.  `impl[q]`: the column of r_q, `tend[q]`: the optional primal f_q; both NULL-able.
+template <typename FT, int K, int NOUT, int NWRT> struct ImplicitArgs {
+    static_assert(NOUT % K == 0, "ImplicitArgs: K divides the number of species");
+    const FT *in[NWRT + 1];           // rho, then the differentiated inputs
+    FT *impl[NOUT];
+    FT *tend[NOUT];
+    int32_t wrt[NOUT];
+    FT dt;
+};
+
+// False if the call has no output column at all.  `implicit` is the caller's table of NOUT members (not NULL itself: the entry checks that), `species0` = S::SPECIES0.
+template <typename FT, int K, int NOUT, int NWRT>
+inline bool make_implicit_args(ImplicitArgs<FT, K, NOUT, NWRT> &a, const FT *const (&in)[NWRT + 1], int species0, double dt, FT *const *implicit, FT *const *tendencies) {
+    a = ImplicitArgs<FT, K, NOUT, NWRT>{};
+    for (int j = 0; j < NWRT + 1; ++j) a.in[j] = in[j];
+    bool any = false;
+    for (int q = 0; q < NOUT; ++q) {
+        a.impl[q] = implicit ? implicit[q] : nullptr;
+        a.tend[q] = tendencies ? tendencies[q] : nullptr;
+        a.wrt[q] = species0 + q;
+        any |= a.impl[q] != nullptr || a.tend[q] != nullptr;
+    }
+    a.dt = (FT)dt;
+    return any;
+}
+// Δt of an implicit entry: finite and ≥ 0
+inline bool implicit_dt_ok(double dt) { return dt >= 0.0 && dt < __builtin_inf(); }
+
+// Every pass of one point, the solve and its stores: the body of the kernel's lane and of the host loop.
+template <typename S, typename FT, int K, typename C>
+__device__ __forceinline__ void implicit_point(const C &c, const ImplicitArgs<FT, K, S::NOUT, S::NWRT> &a, const FT (&x)[S::NWRT + 1], int64_t i) {
+    using namespace implicit_detail;
+    constexpr int N = S::NOUT;
+    static_assert(S::SPECIES0 >= 0 && S::SPECIES0 + N <= S::NWRT, "implicit_point: the species block lies inside the differentiated inputs");
+    FT B[N][N] = {}, g[N] = {};
+#pragma unroll 1
+    for (int pass = 0; pass < N / K; ++pass) {
+        Dual<FT, K> in[S::NWRT], o[N];
+#pragma unroll
+        for (int j = 0; j < S::NWRT; ++j) {
+            in[j].v = keep(x[j + 1]);
+#pragma unroll
+            for (int k = 0; k < K; ++k) in[j].d[k] = a.wrt[pass * K + k] == j ? FT(1) : FT(0);
+        }
+        S::template eval<FT, K>(c, keep(x[0]), in, o);
+        // f from the LAST pass (every pass's primal is the same, bit for bit): not alive across the point function
+        if (pass == N / K - 1) {
+#pragma unroll
+            for (int q = 0; q < N; ++q) g[q] = o[q].v;
+        }
+        // column pass·K + k of A = I − Δt J.  The loop over the passes stays a loop (unrolled, the passes interleave and every intermediate of two point
+        // functions is alive at once), so the column is placed by selects over constant indices, not by an index
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int s = 0; s < N; ++s) {
+                const bool here = s == pass * K + k;
+#pragma unroll
+                for (int q = 0; q < N; ++q) {
+                    const FT v = Math<FT>::fma(-a.dt, o[q].d[k], q == s ? FT(1) : FT(0));
+                    B[q][s] = here ? v : B[q][s];
+                }
+            }
+        }
+    }
+    const auto poison = S::poison(x);
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        if (a.tend[q]) a.tend[q][i] = S::out(g[q], poison);
+    FT cs[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const FT s = x[1 + S::SPECIES0 + j];
+        cs[j] = pow2_floor(s > FT(0) ? s : FT(1));
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        FT m = FT(0);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            B[q][j] *= cs[j];
+            m = Math<FT>::max(m, absv(B[q][j]));
+        }
+        const FT rs = pow2_inv(pow2_floor(m));
+#pragma unroll
+        for (int j = 0; j < N; ++j) B[q][j] *= rs;
+        g[q] *= rs;
+    }
+    // z from the factors, then ONE step of iterative refinement in working precision: ρ = g − B z against the unfactored B, the correction from the same factors
+    FT LU[N][N], piv[N], res[N], z[N];
+    bool sw[N][N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        z[q] = g[q];
+#pragma unroll
+        for (int j = 0; j < N; ++j) LU[q][j] = B[q][j];
+    }
+    factor_pivoted<FT, N>(LU, sw, piv);
+    substitute<FT, N>(LU, sw, piv, z);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        res[q] = g[q];
+#pragma unroll
+        for (int j = 0; j < N; ++j) res[q] = fnma_nz(B[q][j], z[j], res[q]);
+    }
+    substitute<FT, N>(LU, sw, piv, res);
+#pragma unroll
+    for (int q = 0; q < N; ++q) g[q] = res[q] == FT(0) ? z[q] : z[q] + res[q];      // a zero correction leaves z as it is, the sign of a zero included
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        if (a.impl[q]) a.impl[q][i] = S::out(g[q] * cs[q], poison);
+}
+
 #if !defined(CMX_HOST_BUILD)
 // The kernels: one point per lane.  `c`, the scheme's constants struct, stays the FIRST kernel argument: front_consts reads it at offset 0 of the kernel-argument segment.
 template <typename S, typename FT, int K, int BS, typename C>
@@ -292,6 +526,19 @@ __global__ __launch_bounds__(BS) void vjp_kernel(const C c, const VjpArgs<FT, K,
     Math<FT>::prepare();
     if (i >= n) return;
     vjp_point<S, FT, K>(c, a, x, i);
+}
+
+template <typename S, typename FT, int K, int BS, typename C>
+__global__ __launch_bounds__(BS) void implicit_kernel(const C c, const ImplicitArgs<FT, K, S::NOUT, S::NWRT> a, const int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x;
+    FT x[S::NWRT + 1];
+    if (i < n) {
+#pragma unroll
+        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
+    }
+    Math<FT>::prepare();
+    if (i >= n) return;
+    implicit_point<S, FT, K>(c, a, x, i);
 }
 #endif
 

@@ -28,6 +28,7 @@ template <typename FT> constexpr int kJac1mK = sizeof(FT) == 4 ? CMX_JAC1M_K_F32
 // results bit for bit (before its NaN rule, which is `out`).
 template <uint32_t FLAGS> struct Mp1mJac {
     static constexpr int NOUT = CMX_MP1M_JAC_NOUT, NWRT = CMX_MP1M_JAC_NWRT;
+    static constexpr int SPECIES0 = CMX_MP1M_JAC_WRT_Q_LCL;      // the first of the NOUT inputs whose tendencies the outputs are (implicit_point)
     // the poison rule of the 1-moment entries (mp1m_tendencies_point): a NaN in any input column — in Float64 also ρ ≤ 0 (cmx_math.hpp bad_density) — gives NaN
     // in every output of the point.  A select, not SB2006's sum: −0 stays −0
     template <typename FT> static __device__ __forceinline__ bool poison(const FT (&x)[NWRT + 1]) {

@@ -1,5 +1,5 @@
 // cmx_sb2006_jacobian.hip — the Jacobian of the SB2006 warm-rain tendencies (BMT:707-782, 820-854) with respect to the prognostic state, over columns, for
-// gfx950, and its products J v and Jᵀḡ; C-ABI entry points cmx_sb2006_warm_rain_jacobian_* / _jvp_* / _vjp_* (include/cmx.h §(14), §(16)).  The reference
+// gfx950, and its products J v and Jᵀḡ; C-ABI entry points cmx_sb2006_warm_rain_jacobian_* / _jvp_* / _vjp_* / _implicit_tendencies_* (include/cmx.h §(14), §(16), §(18)).  The reference
 // differentiates bulk_microphysics_tendencies with ForwardDiff (test/ad_compat_tests.jl:106-175); here the SAME point function sb2006_point (cmx_sb2006.hpp) is instantiated on the forward-mode dual value
 // type of cmx_dual.hpp — there is no second implementation of the physics and no finite difference.
 //
@@ -81,6 +81,16 @@ static int32_t vjp_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t n,
                     [](auto S) { return vjp_kernel<decltype(S), FT, kVjpK<FT>, kJacBS, SbConsts<FT>>; });
 }
 
+// (I − Δt J)⁻¹ f (cmx_jacobian.hpp implicit_point; include/cmx.h §(18)).  `implicit` is the table: it must not be NULL itself; Δt is checked after the columns.
+template <typename FT, typename WR, typename TH>
+static int32_t implicit_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *const (&in)[7], double dt, FT *const *implicit,
+                              FT *const *tendencies, void *stream) {
+    using A = ImplicitArgs<FT, kImplicitK<FT>, kNOut, kNWrt>;
+    return entry<A>(wr, tps, flags, n, in, implicit != nullptr, stream,
+                    [&](A &a) { return implicit_dt_ok(dt) && make_implicit_args(a, in, SbJac<false, false>::SPECIES0, dt, implicit, tendencies); },
+                    [](auto S) { return implicit_kernel<decltype(S), FT, kImplicitK<FT>, kJacBS, SbConsts<FT>>; });
+}
+
 }  // namespace cmx
 
 extern "C" {
@@ -119,5 +129,17 @@ int32_t cmx_sb2006_warm_rain_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, cons
                                      const double *const cotangents[CMX_SB2006_JAC_NOUT], double *const grad[CMX_SB2006_JAC_NWRT],
                                      double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream) {
     return cmx::vjp_entry<double>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, cotangents, grad, tendencies, stream);
+}
+int32_t cmx_sb2006_warm_rain_implicit_tendencies_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points,
+                                                     const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl,
+                                                     const float *q_rai, const float *n_rai, double dt, float *const implicit[CMX_SB2006_JAC_NOUT],
+                                                     float *const tendencies[CMX_SB2006_JAC_NOUT], void *stream) {
+    return cmx::implicit_entry<float>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, dt, implicit, tendencies, stream);
+}
+int32_t cmx_sb2006_warm_rain_implicit_tendencies_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points,
+                                                     const double *rho, const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl,
+                                                     const double *q_rai, const double *n_rai, double dt, double *const implicit[CMX_SB2006_JAC_NOUT],
+                                                     double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream) {
+    return cmx::implicit_entry<double>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, dt, implicit, tendencies, stream);
 }
 }

@@ -28,6 +28,7 @@ template <typename FT> constexpr int kJacK = sizeof(FT) == 4 ? CMX_JAC_K_F32 : C
 // are sb2006_tendencies_kernel's (cmx_sb2006_kernels.hpp), so the value parts are that kernel's results bit for bit.
 template <bool LIMITED, bool INTPOW> struct SbJac {
     static constexpr int NOUT = CMX_SB2006_JAC_NOUT, NWRT = CMX_SB2006_JAC_NWRT;
+    static constexpr int SPECIES0 = CMX_SB2006_JAC_WRT_Q_LCL;      // the first of the NOUT inputs whose tendencies the outputs are (implicit_point)
     // a NaN in any input column poisons every output of the point (cmx_math.hpp any_nan): x + NaN = NaN, x + 0 = x
     template <typename FT> static __device__ __forceinline__ FT poison(const FT (&x)[NWRT + 1]) {
         return any_nan(x[0], x[2], x[3], x[4], x[5], x[6], x[1]) ? Math<FT>::nan() : FT(0);

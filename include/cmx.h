@@ -1622,6 +1622,42 @@ int32_t cmx_mp1m_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64
                          void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (18) The tendency of a linearly implicit (Rosenbrock–Euler) step of the SB2006 warm-rain tendencies (14) and of the 1-moment tendencies (15), solved in
+ * the pass that holds the Jacobian in registers.  With s the four species whose tendencies the scheme returns — SB2006: q_lcl, n_lcl, q_rai, n_rai;
+ * 1-moment: q_lcl, q_icl, q_rai, q_sno (wrt indices 2 … 5; output q is the tendency of s_q) — f the four tendencies at the point and J = ∂f/∂s the
+ * 4 × 4 species block of (14) / (15), with ρ, T and q_tot held fixed:
+ *     implicit = r = (I − Δt J)⁻¹ f            the step is  s ← s + Δt r;  r = f at Δt = 0
+ *   dt             Δt in seconds, finite and ≥ 0 (rounded to the float type of the entry)
+ *   implicit[q]    a host array of 4 NULL-able device columns, not NULL itself
+ *   tendencies[q]  NULL, or 4 NULL-able columns: f itself, bit-identical to cmx_sb2006_warm_rain_tendencies_* / cmx_mp1m_tendencies_*
+ * J is what (14) / (15) would store, bit for bit.  I − Δt J is equilibrated with exact powers of two (columns from the clamped state, rows from the row
+ * maxima) and solved by Gaussian elimination with partial pivoting in registers; the result is that of torch.linalg.solve on the columns of (14) / (15) to
+ * the backward error of an LU in the entry's float type.  All four components are computed whatever subset is stored: a column's bits do not depend on
+ * which others are requested.  At Δt = 0, implicit is f in every bit.  A singular I − Δt J follows IEEE: non-finite r at that point only, no status.  An
+ * absent species (input ≤ 0) has a zero Jacobian column, the system stays regular.  A NaN in any of the seven inputs of a point (1-moment Float64: also
+ * ρ ≤ 0) gives NaN in every output of that point and in that point only.
+ * State, `flags`, option sets, instantiation choice, statuses and their order are those of (14) resp. (15); `dt` is checked after the columns and the
+ * `implicit` table: negative, NaN or infinite is CMX_ERR_BAD_ARG, as is a NULL `implicit` or no output column at all.  A pure launch sequence on `stream`:
+ * no allocation, no synchronisation, graph-capturable; any alignment; 7 columns in, 4 out (8 with the tendencies).  An output column may be the species
+ * column it steps (in place): a lane reads its point before it writes it.
+ * Not done here: sub-stepping, T or q_tot as unknowns of the solve, positivity limiting of s + Δt r, autograd through the solve, the 2M + P3 scheme.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_warm_rain_implicit_tendencies_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points,
+                                                     const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl,
+                                                     const float *q_rai, const float *n_rai, double dt, float *const implicit[CMX_SB2006_JAC_NOUT],
+                                                     float *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_implicit_tendencies_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points,
+                                                     const double *rho, const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl,
+                                                     const double *q_rai, const double *n_rai, double dt, double *const implicit[CMX_SB2006_JAC_NOUT],
+                                                     double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_implicit_tendencies_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                         const float *T, const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                                         double dt, float *const implicit[CMX_MP1M_JAC_NOUT], float *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_implicit_tendencies_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                         const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                                         double dt, double *const implicit[CMX_MP1M_JAC_NOUT], double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

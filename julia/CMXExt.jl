@@ -1506,6 +1506,49 @@ function vjp_1m!(grad, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::Abstra
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (18) the tendency of a linearly implicit step: (I − Δt J)⁻¹ f of the SB2006 warm-rain and the 1-moment tendencies, solved in registers
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    warm_rain_implicit_tendencies_2m!(implicit, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt; stream = C_NULL)
+
+r = (I − Δt J)⁻¹ f per point, with f the tendencies of `warm_rain_jacobian_2m!` and J their 4 × 4 Jacobian with respect to (q_lcl, n_lcl, q_rai, n_rai) at
+fixed ρ, T, q_tot: the tendency of a linearly implicit (Rosenbrock–Euler) step s ← s + Δt r, solved in the pass that computes J.  `implicit` = 4 columns (or
+`nothing`s) in the order (dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt), `tendencies` = `nothing` or 4 columns (or `nothing`s): f itself.  `dt` finite and ≥ 0;
+r = f in every bit at `dt = 0`.
+"""
+function warm_rain_implicit_tendencies_2m!(implicit, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl,
+    q_rai, n_rai, dt::Real; stream = C_NULL) where {WR, FT}
+    length(implicit) == CMX_SB2006_JAC_NOUT || error("implicit: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = ccall(_fn("cmx_sb2006_warm_rain_implicit_tendencies", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Float64, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), Float64(dt), _ptrs(FT, implicit), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_implicit_tendencies")
+    return implicit
+end
+
+"""
+    implicit_tendencies_1m!(implicit, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt; stream = C_NULL)
+
+r = (I − Δt J)⁻¹ f of the tendencies of `jacobian_1m!` with J their Jacobian with respect to (q_lcl, q_icl, q_rai, q_sno) — the true derivative, not the
+donor-based linearization of LinearizedAverage.  Rules as for `warm_rain_implicit_tendencies_2m!`.
+"""
+function implicit_tendencies_1m!(implicit, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno,
+    dt::Real; stream = C_NULL) where {FT}
+    length(implicit) == CMX_MP1M_JAC_NOUT || error("implicit: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_implicit_tendencies", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Float64, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), Float64(dt), _ptrs(FT, implicit), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_implicit_tendencies")
+    return implicit
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
