@@ -93,7 +93,7 @@ template <> struct Math<double> {
     static constexpr bool IS_F64 = true;
     static constexpr int VEC = 2;
     static constexpr double eps() { return 2.220446049250313e-16; }            // eps(Float64)
-    static constexpr double eps_1m() { return 2.8126442852362996e-103; }      // cbrt(floatmin(Float64))
+    static constexpr double eps_1m() { return 2.812644285236262e-103; }       // cbrt(floatmin(Float64)), correctly rounded (the oracle's cbrt(DBL_MIN))
     // Once per kernel that evaluates Float64 functions, before the first of them and executed by EVERY thread of the workgroup (the
     // streaming kernels issue their column loads first): copies the exp2 / log2 tables of cmx_lean_f64.hpp into LDS (3 KiB) and
     // synchronises

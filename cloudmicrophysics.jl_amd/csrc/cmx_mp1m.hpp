@@ -352,9 +352,12 @@ __device__ __forceinline__ Mp1mSrc<FT> mp1m_point(const C &c0, FT rho, FT T, FT 
     if (fl & CMX_1M_ACCR_ICL_RAI) {
         const B both = m_and(has_icl, has_rai);
         o.accr_icl_rai = both ? FT((q_icl * c->acc_k_icl_rai) * A_rai) : FT(0);
-        // λ_rai⁻^6½ = λ_rai⁻^3½ · λ_rai⁻³
-        const FT p = DEFEXP ? A_rai * pr_r12 : sq * M::exp2_fin(c->sink_e * l2_li_rai);
-        o.freeze_icl_rai = both ? FT((c->sink_k * inv_rho) * (li_icl * p)) : FT(0);
+        // λ_rai⁻^6½ = λ_rai⁻^3½ · λ_rai⁻³ (general exponents: the square of its root).  Just above q_rai = ϵ it is 4e-40 in Float32, below the smallest
+        // normal number, which the hardware flushes to 0 while the term itself is 2e-20: the large constant goes between the two factors
+        const FT k_sink = (c->sink_k * inv_rho) * li_icl;
+        const FT h = DEFEXP ? pr_r12 : FT(M::exp2_fin(c->sink_e * (FT(0.5) * l2_li_rai)));
+        const FT g = DEFEXP ? A_rai : FT(sq * h);
+        o.freeze_icl_rai = both ? FT((k_sink * g) * h) : FT(0);
     }
     if (fl & CMX_1M_ACCR_ICL_SNO) o.accr_icl_sno = m_and(has_icl, has_sno) ? FT((q_icl * c->acc_k_icl_sno) * A_sno) : FT(0);
     c = &consts_after(*c, A_sno);
