@@ -148,6 +148,9 @@ CMX_MP1M_JAC_NCOL = CMX_MP1M_JAC_NOUT * CMX_MP1M_JAC_NWRT
 # cotangents[NOUT], grad[NWRT], tendencies[NOUT]
 JACOBIAN_PRODUCT_STEMS = ("cmx_sb2006_warm_rain", "cmx_mp1m")
 # the linearly implicit tendencies of the same two schemes (include/cmx.h §18): <stem>_implicit_tendencies_* takes dt, implicit[NOUT], tendencies[NOUT]
+# … and their average over nsub substeps (include/cmx.h §19): <stem>_implicit_average_* takes dt, nsub, step_flags, average[NOUT]
+CMX_STEP_NONNEGATIVE = 1
+CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 
 
 def _struct(name, fields):

@@ -223,6 +223,9 @@ def _declare(lib):
             f = getattr(lib, f"{stem}_implicit_tendencies_{s}")       # (dt, implicit[4], tendencies[4])
             f.restype = i32
             f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.c_double, C.POINTER(vp), C.POINTER(vp), vp]
+            f = getattr(lib, f"{stem}_implicit_average_{s}")          # (dt, nsub, step_flags, average[4])
+            f.restype = i32
+            f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.c_double, i32, u32, C.POINTER(vp), vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

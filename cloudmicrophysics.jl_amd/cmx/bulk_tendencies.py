@@ -24,7 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _implicit, _jacobian, _jvp, _vjp
+from ._jacobian import _implicit, _implicit_average, _jacobian, _jvp, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -216,6 +216,20 @@ def warm_rain_implicit_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai
     wr = _warm_rain(mp)
     return WarmRainImplicit2M(*_implicit("cmx_sb2006_warm_rain_implicit_tendencies", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
                                          (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, _abi.CMX_SB2006_JAC_NOUT, dt, with_tendencies, out, stream))
+
+
+def warm_rain_implicit_average_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, out=None, stream=None):
+    """The average tendency of (q_lcl, n_lcl, q_rai, n_rai) over a time step `dt`, taken in `nsub` linearly implicit substeps inside one kernel
+    (`cmx_sb2006_warm_rain_implicit_average_*`): each substep is s ← s + h·r with h = dt/nsub and r = `warm_rain_implicit_tendencies_2m(…, h).implicit` at the
+    current state, T follows the latent heating of the substep (T += L_v/c_p·(Δq_lcl + Δq_rai)), ρ and q_tot stay fixed; the result is (s_end − s_start)/dt.
+    `nonnegative=True` clips every substep: a species never ends one below 0, and one that was negative already never below where it started — without it the
+    plain step leaves a species negative at a large share of states.  include/cmx.h §(19) has the definition, which is normative bit for bit.
+
+    `dt`: seconds, finite and > 0; `nsub`: 1 … 64.  Returns a tensor of shape (4, *rho.shape) in the order of `JACOBIAN_OUTPUTS`; `out=` provides it and may be
+    a view of the four species columns themselves (in place).  No autograd through the average.  Asynchronous on `stream` (default: torch's current stream)."""
+    wr = _warm_rain(mp)
+    return _implicit_average("cmx_sb2006_warm_rain_implicit_average", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                             (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, _abi.CMX_SB2006_JAC_NOUT, dt, nsub, nonnegative, out, stream)
 
 
 AOS_FIELDS = ("dq_lcl_dt", "dn_lcl_dt", "dq_rai_dt", "dn_rai_dt", "dq_ice_dt", "dq_rim_dt", "db_rim_dt", "dn_lcl_activation_dt")

@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _implicit, _jacobian, _jvp, _vjp
+from ._jacobian import _implicit, _implicit_average, _jacobian, _jvp, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -169,6 +169,17 @@ def implicit_tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, d
         raise TypeError("mp must be Microphysics1MParams")
     return Implicit1M(*_implicit("cmx_mp1m_implicit_tendencies", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES,
                                  _abi.CMX_MP1M_JAC_NOUT, dt, with_tendencies, out, stream))
+
+
+def implicit_average_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1, nonnegative=True, *, out=None, stream=None):
+    """The average tendency of (q_lcl, q_icl, q_rai, q_sno) over a time step `dt`, taken in `nsub` linearly implicit substeps inside one kernel
+    (`cmx_mp1m_implicit_average_*`): the sub-stepping of LinearizedAverage — T follows the latent heating, T += (L_v/c_p·(Δq_lcl + Δq_rai) + L_s/c_p·(Δq_icl +
+    Δq_sno)) per substep — on the true Jacobian of `jacobian_1m` instead of the donor-based linearization, every option set.  Returns a tensor of shape
+    (4, *rho.shape) in the order of `JACOBIAN_OUTPUTS_1M`; arguments and rules as for `cmx.warm_rain_implicit_average_2m`."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("mp must be Microphysics1MParams")
+    return _implicit_average("cmx_mp1m_implicit_average", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, _abi.CMX_MP1M_JAC_NOUT, dt,
+                             nsub, nonnegative, out, stream)
 
 
 def bulk_microphysics_tendencies_1m_fields(mode, scheme, mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt=None, nsub=1, *, q_min=None, out=None,

@@ -1,6 +1,6 @@
 // cmx_jacobian.hpp — the forward-mode derivative driver every scheme's entries share (cmx_sb2006_jacobian.hpp, cmx_mp1m_jacobian.hpp), on the device and in the
 // host test build (tests/native/derivatives_host.cpp, CMX_HOST_BUILD): the table that maps tangent slots to inputs and, per operation — the Jacobian, J v,
-// Jᵀḡ, the linearly implicit tendency (I − Δt J)⁻¹ f — the argument struct, every pass of one point with its stores, and the kernel.  No HIP outside the CMX_HOST_BUILD guards.
+// Jᵀḡ, the linearly implicit tendency (I − Δt J)⁻¹ f, the average tendency over sub-stepped implicit steps — the argument struct, every pass of one point with its stores, and the kernel.  No HIP outside the CMX_HOST_BUILD guards.
 //
 // A SCHEME is a struct of static members that supplies what differs between two entries:
 //   NOUT, NWRT               outputs and differentiated inputs; a point is x[0] = ρ (held fixed) and x[1 … NWRT], the inputs in the order of the entry's wrt enum
@@ -10,7 +10,9 @@
 // (ToyJac of tests/native/derivatives_host.cpp is the smallest one.)
 #pragma once
 #include <cstdint>
+#include <limits>
 
+#include "../../include/cmx.h"
 #include "cmx_dual.hpp"
 
 namespace cmx {
@@ -278,7 +280,8 @@ __device__ __forceinline__ void vjp_point(const C &c, const VjpArgs<FT, K, S::NO
 //   * The library's NaN rule through the scheme's poison() / out(): a NaN in any input of the point (the 1-moment Float64 entry: also ρ ≤ 0) gives NaN in
 //     every output of that point and in no other.
 // All NOUT components of r are computed whatever subset is stored, so a column's bits do not depend on which others are requested.
-// Out of scope: sub-stepping inside the kernel, carrying T or q_tot in the solve, positivity limiting of s + Δt r, autograd through the solve, the 2M + P3 scheme.
+// Out of scope: carrying T or q_tot in the solve, autograd through the solve, the 2M + P3 scheme.  Sub-stepping inside the kernel and positivity limiting of
+// s + Δt r are not this entry's either: they are implicit_average_point's, below.
 // Tangents per evaluation of the point function, per float type, for both schemes: tuning numbers (-DCMX_IMPLICIT_K_F32=…, -DCMX_IMPLICIT_K_F64=…; 1, 2 or 4).
 // Float32: 1 — the only width inside 128 VGPRs (SB2006 124–127, 1-moment 93–104; K = 2: 148 / 126–142, K = 4: 154 / 159–185, which are faster per call,
 // 0.42 / 0.35 against 0.54 ms per 1e7 SB2006 points, and are given up for the four waves per SIMD the other Float32 kernels of the layer keep).  Float64: 4 —
@@ -485,6 +488,197 @@ __device__ __forceinline__ void implicit_point(const C &c, const ImplicitArgs<FT
         if (a.impl[q]) a.impl[q][i] = S::out(g[q] * cs[q], poison);
 }
 
+// implicit_point without its stores: r = (I − Δt J)⁻¹ f of the point x, before the scheme's out() — the passes, the equilibration, the factorisation and the
+// refinement step of implicit_point, operation for operation, so that r is implicit_point's in every bit (tests/test_implicit_average_host.py and
+// tests/test_implicit_average_gpu.py compare them through the recipe).  `wrt`: the slot table of ImplicitArgs.  The body of a substep of
+// implicit_average_point.  implicit_point does NOT call it: as its caller it compiled to other Float64 code (SB2006 334 → 338–340 VGPRs, the 1-moment default
+// instantiation 10 → 12 spilled SGPRs; two forms tried, with the primal's stores as a callback), and the existing entries keep the parent's code.
+template <typename S, typename FT, int K, typename C>
+__device__ __forceinline__ void implicit_solve(const C &c, const int32_t (&wrt)[S::NOUT], FT dt, const FT (&x)[S::NWRT + 1], FT (&r)[S::NOUT]) {
+    using namespace implicit_detail;
+    constexpr int N = S::NOUT;
+    static_assert(S::SPECIES0 >= 0 && S::SPECIES0 + N <= S::NWRT, "implicit_solve: the species block lies inside the differentiated inputs");
+    FT B[N][N] = {}, g[N] = {};
+#pragma unroll 1
+    for (int pass = 0; pass < N / K; ++pass) {
+        Dual<FT, K> in[S::NWRT], o[N];
+#pragma unroll
+        for (int j = 0; j < S::NWRT; ++j) {
+            in[j].v = keep(x[j + 1]);
+#pragma unroll
+            for (int k = 0; k < K; ++k) in[j].d[k] = wrt[pass * K + k] == j ? FT(1) : FT(0);
+        }
+        S::template eval<FT, K>(c, keep(x[0]), in, o);
+        // f from EVERY pass (every pass's primal is the same, bit for bit), so from the last: overwritten per pass, f is not alive across the point function
+        // — nor are four registers that wait for the last pass, as with implicit_point's `if (pass == N / K − 1)`
+#pragma unroll
+        for (int q = 0; q < N; ++q) g[q] = o[q].v;
+        // column pass·K + k of A = I − Δt J.  The loop over the passes stays a loop (unrolled, the passes interleave and every intermediate of two point
+        // functions is alive at once), so the column is placed by selects over constant indices, not by an index
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+#pragma unroll
+            for (int s = 0; s < N; ++s) {
+                const bool here = s == pass * K + k;
+#pragma unroll
+                for (int q = 0; q < N; ++q) {
+                    const FT v = Math<FT>::fma(-dt, o[q].d[k], q == s ? FT(1) : FT(0));
+                    B[q][s] = here ? v : B[q][s];
+                }
+            }
+        }
+    }
+    FT cs[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        const FT s = x[1 + S::SPECIES0 + j];
+        cs[j] = pow2_floor(s > FT(0) ? s : FT(1));
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        FT m = FT(0);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            B[q][j] *= cs[j];
+            m = Math<FT>::max(m, absv(B[q][j]));
+        }
+        const FT rs = pow2_inv(pow2_floor(m));
+#pragma unroll
+        for (int j = 0; j < N; ++j) B[q][j] *= rs;
+        g[q] *= rs;
+    }
+    // z from the factors, then ONE step of iterative refinement in working precision: ρ = g − B z against the unfactored B, the correction from the same factors
+    FT LU[N][N], piv[N], res[N], z[N];
+    bool sw[N][N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        z[q] = g[q];
+#pragma unroll
+        for (int j = 0; j < N; ++j) LU[q][j] = B[q][j];
+    }
+    factor_pivoted<FT, N>(LU, sw, piv);
+    substitute<FT, N>(LU, sw, piv, z);
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        res[q] = g[q];
+#pragma unroll
+        for (int j = 0; j < N; ++j) res[q] = fnma_nz(B[q][j], z[j], res[q]);
+    }
+    substitute<FT, N>(LU, sw, piv, res);
+#pragma unroll
+    for (int q = 0; q < N; ++q) g[q] = res[q] == FT(0) ? z[q] : z[q] + res[q];      // a zero correction leaves z as it is, the sign of a zero included
+#pragma unroll
+    for (int q = 0; q < N; ++q) r[q] = g[q] * cs[q];
+}
+
+// ---- The average tendency over Δt from nsub linearly implicit substeps, the substep loop inside the kernel (include/cmx.h §(19)) ----------------------------------
+// What a host model calls per time step: nsub steps s ← s + h r of the solve above with h = Δt/nsub, the temperature following the latent heating of every
+// substep (ρ and q_tot fixed), and (s_end − s_start)/Δt as the result.  The definition is normative, bit for bit: every product and sum below is one IEEE
+// operation of the float type (no fma), the selects are selects (a NaN stays a NaN):
+//     repeat nsub times:
+//         r    = out(implicit_solve(ρ, T, q_tot, s; Δt = h), poison(ρ, T, q_tot, s))      — the implicit entry's result at the current state
+//         sn_j = s_j + r_j·h
+//         CMX_STEP_NONNEGATIVE:  lo_j = s_j < 0 ? s_j : 0;  sn_j = sn_j < lo_j ? lo_j : sn_j
+//         d_j  = (sn_j − s_j)·inv_h
+//         T    = T + S::heating(Lv, Ls, d)·h
+//         s    = sn
+//     average_j = (s_j − s0_j)·inv_dt
+// The limiter: a species never ends a substep below 0, one that was negative already never below where it started.  Without it the Rosenbrock–Euler step
+// leaves a species negative at 17 % (SB2006) and 58 % (1-moment) of the states of tests/implicit_cases.py at Δt = 30 s, nsub = 1; it does not touch the
+// first order of the scheme.  A NaN in an input makes the first r NaN in all components (poison), and so all four averages of that point and of no other;
+// a singular substep solve makes that point non-finite.
+// Registers: alive across the point function are the point x (as in implicit_point), s0 and the uniform loop counter; nothing is read again from memory.
+// Reading ρ, q_tot per substep and s0 after the loop instead (non-temporal, behind an opaque index) saved 4–6 VGPRs that no instantiation needed and cost a
+// memory latency that the one Float64 wave per SIMD cannot hide: 1.32 against 1.06 ms of ONE implicit call at nsub = 1 and 1e7 SB2006 Float64 points.  What
+// made room is implicit_solve taking f from every pass: SB2006 Float32 129–132 → 101–104 VGPRs.  All of a lane's reads come before its writes: `average`
+// may alias the species columns.
+// K per float type: -DCMX_IMPLICIT_AVG_K_F32=…, -DCMX_IMPLICIT_AVG_K_F64=… (1, 2 or 4), by default the implicit entry's; the register table is DESIGN.md §9.
+#ifndef CMX_IMPLICIT_AVG_K_F32
+#define CMX_IMPLICIT_AVG_K_F32 CMX_IMPLICIT_K_F32
+#endif
+#ifndef CMX_IMPLICIT_AVG_K_F64
+#define CMX_IMPLICIT_AVG_K_F64 CMX_IMPLICIT_K_F64
+#endif
+template <typename FT> constexpr int kImplicitAvgK = sizeof(FT) == 4 ? CMX_IMPLICIT_AVG_K_F32 : CMX_IMPLICIT_AVG_K_F64;
+
+// `avg[q]`: the column of average_q (NULL-able).  h = Δt/nsub and the reciprocals as make_mp1m_lin_args (cmx_mp1m.hpp) forms them; Lv = LH_v0/cp_d, Ls = LH_s0/cp_d.
+template <typename FT, int K, int NOUT, int NWRT> struct ImplicitAverageArgs {
+    static_assert(NOUT % K == 0, "ImplicitAverageArgs: K divides the number of species");
+    const FT *in[NWRT + 1];           // rho, then the differentiated inputs
+    FT *avg[NOUT];
+    int32_t wrt[NOUT];
+    int32_t nsub;
+    uint32_t step_flags;
+    FT h, inv_h, inv_dt, Lv, Ls;
+};
+
+// Δt, nsub and the step flags of an average entry: Δt finite and > 0, 1 ≤ nsub ≤ CMX_IMPLICIT_AVERAGE_MAX_NSUB, no unknown flag bit, and h and 1/Δt finite
+// positive normal numbers of the float type (then 1/h is one too)
+template <typename FT> inline bool implicit_average_step_ok(double dt, int32_t nsub, uint32_t step_flags) {
+    if (!(dt > 0.0 && dt < __builtin_inf())) return false;
+    if (nsub < 1 || nsub > CMX_IMPLICIT_AVERAGE_MAX_NSUB) return false;
+    if (step_flags & ~(uint32_t)CMX_STEP_NONNEGATIVE) return false;
+    const FT dt_f = (FT)dt, h = dt_f / (FT)nsub, inv_dt = FT(1) / dt_f;
+    const auto normal = [](FT v) { return v >= std::numeric_limits<FT>::min() && v <= std::numeric_limits<FT>::max(); };
+    return normal(h) && normal(inv_dt);
+}
+
+// False if the call has no output column at all.  `average` is the caller's table of NOUT members (not NULL itself: the entry checks that, and
+// implicit_average_step_ok before this).  LH_v0, LH_s0, cp_d: the thermodynamics struct's fields.
+template <typename FT, int K, int NOUT, int NWRT>
+inline bool make_implicit_average_args(ImplicitAverageArgs<FT, K, NOUT, NWRT> &a, const FT *const (&in)[NWRT + 1], int species0, double dt, int32_t nsub,
+                                       uint32_t step_flags, FT LH_v0, FT LH_s0, FT cp_d, FT *const *average) {
+    a = ImplicitAverageArgs<FT, K, NOUT, NWRT>{};
+    for (int j = 0; j < NWRT + 1; ++j) a.in[j] = in[j];
+    bool any = false;
+    for (int q = 0; q < NOUT; ++q) {
+        a.avg[q] = average ? average[q] : nullptr;
+        a.wrt[q] = species0 + q;
+        any |= a.avg[q] != nullptr;
+    }
+    const FT dt_f = (FT)dt;
+    a.nsub = nsub;
+    a.step_flags = step_flags;
+    a.h = dt_f / (FT)nsub;
+    a.inv_h = FT(1) / a.h;
+    a.inv_dt = FT(1) / dt_f;
+    a.Lv = LH_v0 / cp_d;
+    a.Ls = LH_s0 / cp_d;
+    return any;
+}
+
+// The substeps of one point and its stores: the body of the kernel's lane and of the host loop.  x: the point as the kernel read it; the species and T
+// (x[1 + S::TEMP], if the scheme has one) advance in it.
+template <typename S, typename FT, int K, typename C>
+__device__ __forceinline__ void implicit_average_point(const C &c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> &a, FT (&x)[S::NWRT + 1], int64_t i) {
+    constexpr int N = S::NOUT, S0 = 1 + S::SPECIES0;
+    const bool limit = a.step_flags & CMX_STEP_NONNEGATIVE;
+    FT s0[N];
+#pragma unroll
+    for (int q = 0; q < N; ++q) s0[q] = x[S0 + q];
+#pragma unroll 1
+    for (int32_t sub = 0; sub < a.nsub; ++sub) {
+        FT r[N], d[N];
+        implicit_solve<S, FT, K>(c, a.wrt, a.h, x, r);
+        const auto poison = S::poison(x);
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+            const FT s = x[S0 + q];
+            FT sn = s + S::out(r[q], poison) * a.h;
+            if (limit) {
+                const FT lo = s < FT(0) ? s : FT(0);
+                sn = sn < lo ? lo : sn;
+            }
+            d[q] = (sn - s) * a.inv_h;
+            x[S0 + q] = sn;
+        }
+        if constexpr (S::TEMP >= 0) x[1 + S::TEMP] = x[1 + S::TEMP] + S::heating(a.Lv, a.Ls, d) * a.h;
+    }
+#pragma unroll
+    for (int q = 0; q < N; ++q)
+        if (a.avg[q]) a.avg[q][i] = (x[S0 + q] - s0[q]) * a.inv_dt;
+}
+
 #if !defined(CMX_HOST_BUILD)
 // The kernels: one point per lane.  `c`, the scheme's constants struct, stays the FIRST kernel argument: front_consts reads it at offset 0 of the kernel-argument segment.
 template <typename S, typename FT, int K, int BS, typename C>
@@ -539,6 +733,19 @@ __global__ __launch_bounds__(BS) void implicit_kernel(const C c, const ImplicitA
     Math<FT>::prepare();
     if (i >= n) return;
     implicit_point<S, FT, K>(c, a, x, i);
+}
+
+template <typename S, typename FT, int K, int BS, typename C>
+__global__ __launch_bounds__(BS) void implicit_average_kernel(const C c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> a, const int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x;
+    FT x[S::NWRT + 1];
+    if (i < n) {
+#pragma unroll
+        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
+    }
+    Math<FT>::prepare();
+    if (i >= n) return;
+    implicit_average_point<S, FT, K>(c, a, x, i);
 }
 #endif
 

@@ -1,5 +1,5 @@
 // cmx_mp1m_jacobian.hip — the Jacobian of the 1-moment tendencies (BMT:141-252, 505-514) with respect to the state, over columns, for gfx950, and its
-// products J v and Jᵀḡ; C-ABI entry points cmx_mp1m_jacobian_* / cmx_mp1m_jvp_* / cmx_mp1m_vjp_* / cmx_mp1m_implicit_tendencies_* (include/cmx.h §(15), §(17), §(18)).  The SAME point function
+// products J v and Jᵀḡ; C-ABI entry points cmx_mp1m_jacobian_* / cmx_mp1m_jvp_* / cmx_mp1m_vjp_* / cmx_mp1m_implicit_tendencies_* / cmx_mp1m_implicit_average_* (include/cmx.h §(15), §(17), §(18), §(19)).  The SAME point function
 // mp1m_point + mp1m_aggregate (cmx_mp1m.hpp) that the tendencies entry runs is instantiated on the forward-mode dual value type of cmx_dual.hpp — there is no
 // second implementation of the physics and no finite difference; the donor-based linearization of LinearizedAverage (BMT:269-379) is an approximation and not
 // this.
@@ -93,6 +93,20 @@ static int32_t implicit_entry(const MP *mp, const TH *tps, uint32_t flags, int64
                     [](auto S) { return implicit_kernel<decltype(S), FT, kImplicitK<FT>, kJac1mBS, Mp1mConsts<FT>>; });
 }
 
+// The average tendency over Δt from nsub implicit substeps (cmx_jacobian.hpp implicit_average_point; include/cmx.h §(19)).  `average` is the table: it must
+// not be NULL itself; Δt, nsub and the step flags are checked after the columns.
+template <typename FT, typename MP, typename TH>
+static int32_t implicit_average_entry(const MP *mp, const TH *tps, uint32_t flags, int64_t n, const FT *const (&in)[7], double dt, int32_t nsub,
+                                      uint32_t step_flags, FT *const *average, void *stream) {
+    using A = ImplicitAverageArgs<FT, kImplicitAvgK<FT>, kNOut, kNWrt>;
+    return entry<A>(mp, tps, flags, n, in, average != nullptr, stream,
+                    [&](A &a) {
+                        return implicit_average_step_ok<FT>(dt, nsub, step_flags) &&
+                               make_implicit_average_args(a, in, Mp1mJac<kDefaultFlags>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, average);
+                    },
+                    [](auto S) { return implicit_average_kernel<decltype(S), FT, kImplicitAvgK<FT>, kJac1mBS, Mp1mConsts<FT>>; });
+}
+
 }  // namespace cmx
 
 extern "C" {
@@ -139,5 +153,15 @@ int32_t cmx_mp1m_implicit_tendencies_f64(const cmx_microphysics_1m_f64 *mp, cons
                                          const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
                                          double dt, double *const implicit[CMX_MP1M_JAC_NOUT], double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream) {
     return cmx::implicit_entry<double>(mp, tps, flags, n_points, {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno}, dt, implicit, tendencies, stream);
+}
+int32_t cmx_mp1m_implicit_average_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                      const float *T, const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                                      double dt, int32_t nsub, uint32_t step_flags, float *const average[CMX_MP1M_JAC_NOUT], void *stream) {
+    return cmx::implicit_average_entry<float>(mp, tps, flags, n_points, {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno}, dt, nsub, step_flags, average, stream);
+}
+int32_t cmx_mp1m_implicit_average_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                      const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                                      double dt, int32_t nsub, uint32_t step_flags, double *const average[CMX_MP1M_JAC_NOUT], void *stream) {
+    return cmx::implicit_average_entry<double>(mp, tps, flags, n_points, {rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno}, dt, nsub, step_flags, average, stream);
 }
 }

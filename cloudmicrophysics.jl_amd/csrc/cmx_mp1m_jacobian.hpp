@@ -29,6 +29,11 @@ template <typename FT> constexpr int kJac1mK = sizeof(FT) == 4 ? CMX_JAC1M_K_F32
 template <uint32_t FLAGS> struct Mp1mJac {
     static constexpr int NOUT = CMX_MP1M_JAC_NOUT, NWRT = CMX_MP1M_JAC_NWRT;
     static constexpr int SPECIES0 = CMX_MP1M_JAC_WRT_Q_LCL;      // the first of the NOUT inputs whose tendencies the outputs are (implicit_point)
+    static constexpr int TEMP = CMX_MP1M_JAC_WRT_T;               // the input that follows the latent heating of a substep (implicit_average_point)
+    // the heating rate of the substep's rates d over c_p, the reference's expression (BMT:619-623; plain operations, no fma)
+    template <typename FT> static __device__ __forceinline__ FT heating(FT Lv, FT Ls, const FT (&d)[NOUT]) {
+        return Lv * (d[CMX_MP1M_JAC_DQ_LCL_DT] + d[CMX_MP1M_JAC_DQ_RAI_DT]) + Ls * (d[CMX_MP1M_JAC_DQ_ICL_DT] + d[CMX_MP1M_JAC_DQ_SNO_DT]);
+    }
     // the poison rule of the 1-moment entries (mp1m_tendencies_point): a NaN in any input column — in Float64 also ρ ≤ 0 (cmx_math.hpp bad_density) — gives NaN
     // in every output of the point.  A select, not SB2006's sum: −0 stays −0
     template <typename FT> static __device__ __forceinline__ bool poison(const FT (&x)[NWRT + 1]) {

@@ -1,5 +1,5 @@
 // cmx_sb2006_jacobian.hip — the Jacobian of the SB2006 warm-rain tendencies (BMT:707-782, 820-854) with respect to the prognostic state, over columns, for
-// gfx950, and its products J v and Jᵀḡ; C-ABI entry points cmx_sb2006_warm_rain_jacobian_* / _jvp_* / _vjp_* / _implicit_tendencies_* (include/cmx.h §(14), §(16), §(18)).  The reference
+// gfx950, and its products J v and Jᵀḡ; C-ABI entry points cmx_sb2006_warm_rain_jacobian_* / _jvp_* / _vjp_* / _implicit_tendencies_* / _implicit_average_* (include/cmx.h §(14), §(16), §(18), §(19)).  The reference
 // differentiates bulk_microphysics_tendencies with ForwardDiff (test/ad_compat_tests.jl:106-175); here the SAME point function sb2006_point (cmx_sb2006.hpp) is instantiated on the forward-mode dual value
 // type of cmx_dual.hpp — there is no second implementation of the physics and no finite difference.
 //
@@ -91,6 +91,20 @@ static int32_t implicit_entry(const WR *wr, const TH *tps, uint32_t flags, int64
                     [](auto S) { return implicit_kernel<decltype(S), FT, kImplicitK<FT>, kJacBS, SbConsts<FT>>; });
 }
 
+// The average tendency over Δt from nsub implicit substeps (cmx_jacobian.hpp implicit_average_point; include/cmx.h §(19)).  `average` is the table: it must
+// not be NULL itself; Δt, nsub and the step flags are checked after the columns.
+template <typename FT, typename WR, typename TH>
+static int32_t implicit_average_entry(const WR *wr, const TH *tps, uint32_t flags, int64_t n, const FT *const (&in)[7], double dt, int32_t nsub,
+                                      uint32_t step_flags, FT *const *average, void *stream) {
+    using A = ImplicitAverageArgs<FT, kImplicitAvgK<FT>, kNOut, kNWrt>;
+    return entry<A>(wr, tps, flags, n, in, average != nullptr, stream,
+                    [&](A &a) {
+                        return implicit_average_step_ok<FT>(dt, nsub, step_flags) &&
+                               make_implicit_average_args(a, in, SbJac<false, false>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, average);
+                    },
+                    [](auto S) { return implicit_average_kernel<decltype(S), FT, kImplicitAvgK<FT>, kJacBS, SbConsts<FT>>; });
+}
+
 }  // namespace cmx
 
 extern "C" {
@@ -141,5 +155,17 @@ int32_t cmx_sb2006_warm_rain_implicit_tendencies_f64(const cmx_warm_rain_2m_f64 
                                                      const double *q_rai, const double *n_rai, double dt, double *const implicit[CMX_SB2006_JAC_NOUT],
                                                      double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream) {
     return cmx::implicit_entry<double>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, dt, implicit, tendencies, stream);
+}
+int32_t cmx_sb2006_warm_rain_implicit_average_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points,
+                                                  const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl,
+                                                  const float *q_rai, const float *n_rai, double dt, int32_t nsub, uint32_t step_flags,
+                                                  float *const average[CMX_SB2006_JAC_NOUT], void *stream) {
+    return cmx::implicit_average_entry<float>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, dt, nsub, step_flags, average, stream);
+}
+int32_t cmx_sb2006_warm_rain_implicit_average_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points,
+                                                  const double *rho, const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl,
+                                                  const double *q_rai, const double *n_rai, double dt, int32_t nsub, uint32_t step_flags,
+                                                  double *const average[CMX_SB2006_JAC_NOUT], void *stream) {
+    return cmx::implicit_average_entry<double>(warm_rain, tps, flags, n_points, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, dt, nsub, step_flags, average, stream);
 }
 }

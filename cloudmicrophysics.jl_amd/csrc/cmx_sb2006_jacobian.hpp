@@ -29,6 +29,11 @@ template <typename FT> constexpr int kJacK = sizeof(FT) == 4 ? CMX_JAC_K_F32 : C
 template <bool LIMITED, bool INTPOW> struct SbJac {
     static constexpr int NOUT = CMX_SB2006_JAC_NOUT, NWRT = CMX_SB2006_JAC_NWRT;
     static constexpr int SPECIES0 = CMX_SB2006_JAC_WRT_Q_LCL;      // the first of the NOUT inputs whose tendencies the outputs are (implicit_point)
+    static constexpr int TEMP = CMX_SB2006_JAC_WRT_T;               // the input that follows the latent heating of a substep (implicit_average_point)
+    // the heating rate of the substep's rates d over c_p: condensate formed from vapour, liquid only (plain operations, no fma)
+    template <typename FT> static __device__ __forceinline__ FT heating(FT Lv, FT, const FT (&d)[NOUT]) {
+        return Lv * (d[CMX_SB2006_JAC_DQ_LCL_DT] + d[CMX_SB2006_JAC_DQ_RAI_DT]);
+    }
     // a NaN in any input column poisons every output of the point (cmx_math.hpp any_nan): x + NaN = NaN, x + 0 = x
     template <typename FT> static __device__ __forceinline__ FT poison(const FT (&x)[NWRT + 1]) {
         return any_nan(x[0], x[2], x[3], x[4], x[5], x[6], x[1]) ? Math<FT>::nan() : FT(0);

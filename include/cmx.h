@@ -1640,7 +1640,7 @@ int32_t cmx_mp1m_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64
  * `implicit` table: negative, NaN or infinite is CMX_ERR_BAD_ARG, as is a NULL `implicit` or no output column at all.  A pure launch sequence on `stream`:
  * no allocation, no synchronisation, graph-capturable; any alignment; 7 columns in, 4 out (8 with the tendencies).  An output column may be the species
  * column it steps (in place): a lane reads its point before it writes it.
- * Not done here: sub-stepping, T or q_tot as unknowns of the solve, positivity limiting of s + Δt r, autograd through the solve, the 2M + P3 scheme.
+ * Not done here: T or q_tot as unknowns of the solve, autograd through the solve, the 2M + P3 scheme; sub-stepping and positivity limiting of s + Δt r: (19).
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_warm_rain_implicit_tendencies_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points,
                                                      const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl,
@@ -1656,6 +1656,53 @@ int32_t cmx_mp1m_implicit_tendencies_f32(const cmx_microphysics_1m_f32 *mp, cons
 int32_t cmx_mp1m_implicit_tendencies_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
                                          const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
                                          double dt, double *const implicit[CMX_MP1M_JAC_NOUT], double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (19) The average tendency of the four species of (18) over a time step Δt, taken in `nsub` linearly implicit substeps inside ONE kernel, with the
+ * temperature following the latent heating of every substep — what a host model calls per time step.  The mode the reference has for the 1-moment scheme as
+ * LinearizedAverage (BMT:572-632; entry (5) here) with a donor-based linearization, built on the true Jacobian of (14) / (15) and for the 2-moment warm-rain
+ * scheme as well.  The definition, normative bit for bit — all arithmetic in the entry's float type FT, every product and sum a separate IEEE operation
+ * (no fma), the selects written as selects so that a NaN stays a NaN:
+ *     dt_f = FT(dt);  h = dt_f / FT(nsub);  inv_h = FT(1)/h;  inv_dt = FT(1)/dt_f;  Lv = LH_v0/cp_d;  Ls = LH_s0/cp_d     (fields of `tps`, FT divisions)
+ *     repeat nsub times, with s the four species, T the temperature, ρ and q_tot fixed:
+ *         r    = the `implicit` result of (18) for (ρ, T, q_tot, s) with Δt = h, bit for bit
+ *         sn_j = s_j + r_j*h
+ *         if step_flags has CMX_STEP_NONNEGATIVE:   lo_j = (s_j < 0 ? s_j : 0);   sn_j = (sn_j < lo_j ? lo_j : sn_j)
+ *         d_j  = (sn_j − s_j) * inv_h
+ *         T    = T + (Lv*(d_q_lcl + d_q_rai)) * h                                   SB2006
+ *         T    = T + (Lv*(d_q_lcl + d_q_rai) + Ls*(d_q_icl + d_q_sno)) * h          1-moment (BMT:619-623)
+ *         s    = sn
+ *     average_j = (s_j − s0_j) * inv_dt
+ * With CMX_STEP_NONNEGATIVE a species never ends a substep below 0, and one that was negative already never below where it started; the plain
+ * Rosenbrock–Euler step leaves a species negative at a large share of realistic states.  The limiter does not change the first
+ * order of the scheme in Δt/nsub.
+ *   dt             Δt in seconds: finite and > 0, and h and 1/dt_f finite positive normal numbers of FT
+ *   nsub           1 … CMX_IMPLICIT_AVERAGE_MAX_NSUB
+ *   step_flags     0 or CMX_STEP_NONNEGATIVE
+ *   average[q]     a host array of 4 NULL-able device columns, not NULL itself; a column's bits do not depend on which others are requested
+ * State, `flags`, option sets, instantiation choice, statuses and their order are those of (18); then `dt`, `nsub` and `step_flags` as above — anything else is
+ * CMX_ERR_BAD_ARG, as is a NULL `average` or no output column at all.  The NaN rule is that of (18) in every substep: a NaN in any of the seven inputs of a
+ * point (1-moment Float64: also ρ ≤ 0) gives NaN in all four outputs of that point and in that point only; a singular substep solve makes that point
+ * non-finite and no other.  A pure launch sequence on `stream`: no allocation, no synchronisation, graph-capturable; any alignment; 7 columns in, 4 out.  An
+ * output column may be a species column (in place): a lane reads everything it needs before it writes.
+ * Not done here: adaptive step sizes, T or q_tot as unknowns of the solve, autograd through the average, the `*_fields_*` layouts, the 2M + P3 scheme.
+ * ------------------------------------------------------------------------- */
+#define CMX_STEP_NONNEGATIVE 1u
+#define CMX_IMPLICIT_AVERAGE_MAX_NSUB 64
+int32_t cmx_sb2006_warm_rain_implicit_average_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points,
+                                                  const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl,
+                                                  const float *q_rai, const float *n_rai, double dt, int32_t nsub, uint32_t step_flags,
+                                                  float *const average[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_implicit_average_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points,
+                                                  const double *rho, const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl,
+                                                  const double *q_rai, const double *n_rai, double dt, int32_t nsub, uint32_t step_flags,
+                                                  double *const average[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_implicit_average_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                      const float *T, const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                                      double dt, int32_t nsub, uint32_t step_flags, float *const average[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_implicit_average_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                      const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                                      double dt, int32_t nsub, uint32_t step_flags, double *const average[CMX_MP1M_JAC_NOUT], void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

@@ -1549,6 +1549,50 @@ function implicit_tendencies_1m!(implicit, tendencies, mp::CMP.Microphysics1MPar
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (19) the average tendency over Δt from nsub linearly implicit substeps, the substep loop inside the kernel
+# ----------------------------------------------------------------------------------------------------------------
+const CMX_STEP_NONNEGATIVE = UInt32(1)
+const CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
+
+"""
+    warm_rain_implicit_average_2m!(average, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt; nsub = 1, nonnegative = true, stream = C_NULL)
+
+(s_end − s_start)/Δt of (q_lcl, n_lcl, q_rai, n_rai) after `nsub` substeps s ← s + h r, h = Δt/nsub, with r the result of
+`warm_rain_implicit_tendencies_2m!` at the current state and T following the latent heating of every substep; ρ and q_tot fixed.  `nonnegative`: no species
+ends a substep below 0 (one that was negative already: not below where it started).  `average` = 4 columns (or `nothing`s), which may be the species columns
+themselves.  `dt` finite and > 0, `nsub` from 1 to $(CMX_IMPLICIT_AVERAGE_MAX_NSUB).  include/cmx.h §(19) has the definition, bit for bit.
+"""
+function warm_rain_implicit_average_2m!(average, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+    dt::Real; nsub::Integer = 1, nonnegative::Bool = true, stream = C_NULL) where {WR, FT}
+    length(average) == CMX_SB2006_JAC_NOUT || error("average: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = ccall(_fn("cmx_sb2006_warm_rain_implicit_average", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Float64, Int32, UInt32, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), Float64(dt), Int32(nsub), nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), _ptrs(FT, average), stream)
+    _check(st, "cmx_sb2006_warm_rain_implicit_average")
+    return average
+end
+
+"""
+    implicit_average_1m!(average, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt; nsub = 1, nonnegative = true, stream = C_NULL)
+
+The same for (q_lcl, q_icl, q_rai, q_sno) of the 1-moment scheme: the sub-stepping of LinearizedAverage on the true Jacobian of `jacobian_1m!`.  Rules as for
+`warm_rain_implicit_average_2m!`.
+"""
+function implicit_average_1m!(average, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt::Real;
+    nsub::Integer = 1, nonnegative::Bool = true, stream = C_NULL) where {FT}
+    length(average) == CMX_MP1M_JAC_NOUT || error("average: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_implicit_average", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Float64, Int32, UInt32, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), Float64(dt), Int32(nsub), nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), _ptrs(FT, average), stream)
+    _check(st, "cmx_mp1m_implicit_average")
+    return average
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
