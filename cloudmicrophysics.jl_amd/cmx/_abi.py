@@ -151,6 +151,7 @@ JACOBIAN_PRODUCT_STEMS = ("cmx_sb2006_warm_rain", "cmx_mp1m")
 # … and their average over nsub substeps (include/cmx.h §19): <stem>_implicit_average_* takes dt, nsub, step_flags, average[NOUT]
 CMX_STEP_NONNEGATIVE = 1
 CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
+# … and as tendency operator of the column steps (include/cmx.h §20): cmx_<scheme>_column_implicit_average_sedimentation_* take the same dt, nsub, step_flags
 
 
 def _struct(name, fields):

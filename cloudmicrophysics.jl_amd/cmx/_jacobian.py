@@ -123,21 +123,32 @@ def _implicit(entry, params, flags, tps, cols, names, nout, dt, with_tendencies,
     return impl, tend
 
 
-def _implicit_average(entry, params, flags, tps, cols, names, nout, dt, nsub, nonnegative, out, stream):
-    """average of `entry`_f32 / _f64: (s_end − s_start)/dt over `nsub` linearly implicit substeps of the `nout` species.  dt: finite and > 0 (and dt/nsub and
-    1/dt normal numbers of the float type); nsub: 1 … CMX_IMPLICIT_AVERAGE_MAX_NSUB."""
+def _check_step(dt, nsub):
+    """(dt, nsub) of an average entry as it takes them: dt finite and > 0, nsub 1 … CMX_IMPLICIT_AVERAGE_MAX_NSUB."""
     dt = float(dt)
     if not (math.isfinite(dt) and dt > 0.0):
         raise ValueError("dt must be finite and > 0")
     if isinstance(nsub, bool) or int(nsub) != nsub or not 1 <= int(nsub) <= _abi.CMX_IMPLICIT_AVERAGE_MAX_NSUB:
         raise ValueError(f"nsub must be an integer from 1 to {_abi.CMX_IMPLICIT_AVERAGE_MAX_NSUB}")
-    ref, fam = _prep(params, tps, cols, names)
+    return dt, int(nsub)
+
+
+def _check_step_normal(dt, nsub, dtype):
+    """dt / nsub and 1 / dt must be normal numbers of the state's float type."""
     # h = dt / nsub and 1 / dt as the entry forms them in the float type (a quotient of two Float32 values formed in double and rounded once more is the Float32 quotient)
-    rnd, tiny, huge = ((lambda v: C.c_float(v).value), 2.0 ** -126, 2.0 ** 128 * (1 - 2.0 ** -24)) if ref.dtype == torch.float32 else ((lambda v: v), 2.0 ** -1022, 1.7976931348623157e308)
+    rnd, tiny, huge = ((lambda v: C.c_float(v).value), 2.0 ** -126, 2.0 ** 128 * (1 - 2.0 ** -24)) if dtype == torch.float32 else ((lambda v: v), 2.0 ** -1022, 1.7976931348623157e308)
     dt_f = rnd(dt)
-    if not (tiny <= dt_f <= huge and tiny <= rnd(dt_f / int(nsub)) <= huge and tiny <= rnd(1.0 / dt_f) <= huge):
-        raise ValueError(f"dt / nsub and 1 / dt must be normal numbers of {ref.dtype}")
+    if not (tiny <= dt_f <= huge and tiny <= rnd(dt_f / nsub) <= huge and tiny <= rnd(1.0 / dt_f) <= huge):
+        raise ValueError(f"dt / nsub and 1 / dt must be normal numbers of {dtype}")
+
+
+def _implicit_average(entry, params, flags, tps, cols, names, nout, dt, nsub, nonnegative, out, stream):
+    """average of `entry`_f32 / _f64: (s_end − s_start)/dt over `nsub` linearly implicit substeps of the `nout` species.  dt: finite and > 0 (and dt/nsub and
+    1/dt normal numbers of the float type); nsub: 1 … CMX_IMPLICIT_AVERAGE_MAX_NSUB."""
+    dt, nsub = _check_step(dt, nsub)
+    ref, fam = _prep(params, tps, cols, names)
+    _check_step_normal(dt, nsub, ref.dtype)
     avg, _ = _out_pair((out, None), ref, (nout,), "average", nout, False)
-    _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], dt, int(nsub),
+    _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], dt, nsub,
               _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, _table([avg[o] for o in range(nout)]), stream=stream)
     return avg

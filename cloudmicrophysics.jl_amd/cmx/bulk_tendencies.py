@@ -24,7 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _implicit, _implicit_average, _jacobian, _jvp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -417,6 +417,51 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
     _lib.call("cmx_sb2006_column_tendencies_sedimentation", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
               C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev, _ptr(inv_dz), *[_ptr(t) for t in cols],
               *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)
+    return out
+
+
+def column_implicit_average_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, vel=SB2006VelType,
+                                             vel_params=None, cloud_vel=None, want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None,
+                                             stream=None) -> ColumnTendencies2M:
+    """The 2-moment column step with the sub-stepped implicit average as tendency operator (`cmx_sb2006_column_implicit_average_sedimentation_*`): per point
+    the average tendency of `warm_rain_implicit_average_2m(…, dt, nsub, nonnegative)` — bit for bit — plus, in the same kernel, the first-order upwind
+    sedimentation flux divergence of `column_tendencies_sedimentation` with the fluxes of the INITIAL state (sedimentation stays explicit).  A stable
+    large-`dt` column step in one launch; include/cmx.h §(20) has the definition.
+
+    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused); `inv_dz`, `vel`, `vel_params`, `cloud_vel`,
+    `want_precip_flux` as for `column_tendencies_sedimentation`; `dt`, `nsub`, `nonnegative` as for `warm_rain_implicit_average_2m`.  `out=` provides the
+    outputs; an output must NOT be a state tensor (another workgroup reads the point above).  No autograd.  Asynchronous on `stream`."""
+    wr = _warm_rain(mp)
+    dt, nsub = _check_step(dt, nsub)
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    ref = _check_cols(cols, _NAMES_2M)
+    if ref.dim() != 2:
+        raise ValueError("state columns must have shape (n_col, n_lev)")
+    n_col, n_lev = ref.shape
+    fam = _fam_of(ref)
+    if fam is not wr.fam or not isinstance(tps, fam.thermo) or (cloud_vel is not None and not isinstance(cloud_vel, fam.stokes_vel)):
+        raise TypeError("parameter float type does not match the state columns")
+    _check_step_normal(dt, nsub, ref.dtype)
+    if inv_dz.dtype != ref.dtype or inv_dz.device != ref.device or inv_dz.numel() != n_lev or not inv_dz.is_contiguous():
+        raise ValueError("inv_dz must be a contiguous device vector of n_lev values of the state dtype")
+    flag = _vel_flag(vel)
+    if not flag:
+        raise ValueError("the column step needs a rain fall-speed scheme (SB2006VelType or Chen2022VelTypeRain)")
+    if out is None:
+        out = ColumnTendencies2M(*[torch.empty_like(ref) for _ in range(4)],
+                                 torch.empty(n_col, dtype=ref.dtype, device=ref.device) if want_precip_flux else None)
+    else:
+        _check_cols([ref, *out[:4]], ["rho", *ColumnTendencies2M._fields[:4]])
+        state = {c.data_ptr() for c in cols}
+        if any(o.data_ptr() in state for o in out[:4]):
+            raise ValueError("an output column must not be a state column: this step is not in place")
+    flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | flag
+    velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
+    if not isinstance(velp, fam.rain_vel):
+        raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
+    _lib.call("cmx_sb2006_column_implicit_average_sedimentation", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
+              C.byref(cloud_vel) if cloud_vel is not None else None, flags, dt, nsub, _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev,
+              _ptr(inv_dz), *[_ptr(t) for t in cols], *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)
     return out
 
 

@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _implicit, _implicit_average, _jacobian, _jvp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -336,4 +336,43 @@ def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain,
     _lib.call("cmx_mp1m_column_tendencies_sedimentation", fam, ref.device, C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain),
               C.byref(chen_ice), mp.flags | (shape._column_bit if shape else 0), q_min if lin else 0.0, dt if lin else 0.0, int(nsub) if lin else 0,
               n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]), stream=stream)
+    return ColumnStep1M(*out, *pr)
+
+
+def column_implicit_average_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1,
+                                             nonnegative=True, *, precip=True, stream=None) -> ColumnStep1M:
+    """The 1-moment column step with the sub-stepped implicit average as tendency operator (`cmx_mp1m_column_implicit_average_sedimentation_*`): per point
+    the average tendency of `implicit_average_1m(…, dt, nsub, nonnegative)` — bit for bit, built on the true Jacobian where LinearizedAverage carries a
+    donor-based approximation — plus, in the same kernel, the four sedimentation fluxes and the first-order upwind flux divergence of
+    `column_tendencies_sedimentation_1m`, with the fluxes of the INITIAL state (sedimentation stays explicit).  include/cmx.h §(20) has the definition.
+
+    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused, not copied); `inv_dz` = n_lev values 1/Δz; `dt`, `nsub`,
+    `nonnegative` as for `implicit_average_1m`.  Returns the four total tendencies and (precip=True) the surface rain / snow fluxes.  No snow shape, no
+    autograd.  Asynchronous on `stream` (default: torch's current stream)."""
+    dt, nsub = _check_step(dt, nsub)
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    if rho.dim() != 2:
+        raise ValueError("state tensors must have shape (n_col, n_lev)")
+    # the 2-D tensors THEMSELVES, as in column_tendencies_sedimentation_1m: the kernel reads flat row-major (n_col, n_lev) storage
+    for c, nm in zip(cols, _NAMES):
+        if c.shape != rho.shape:
+            raise ValueError(f"column {nm}: shape {tuple(c.shape)} differs from rho's {tuple(rho.shape)}")
+        if not c.is_contiguous():
+            raise ValueError(f"column {nm} must be a contiguous (n_col, n_lev) tensor (levels contiguous within a column)")
+    flat = [c.view(-1) for c in cols]
+    ref, fam = _prep(mp, tps, flat)
+    _check_step_normal(dt, nsub, ref.dtype)
+    for obj, cls, nm in ((stokes, fam.stokes_vel, "stokes"), (chen_rain, fam.chen2022_rain_vel, "chen_rain"), (chen_ice, fam.chen2022_ice_vel, "chen_ice")):
+        if not isinstance(obj, cls):
+            raise TypeError(f"{nm}: expected the {cls.__name__} struct of the state's float type, got {type(obj).__name__}")
+    n_col, n_lev = rho.shape
+    if inv_dz.numel() != n_lev or inv_dz.dtype != ref.dtype or inv_dz.device != ref.device or not inv_dz.is_contiguous():
+        raise ValueError("inv_dz: n_lev contiguous values of the state's dtype on the state's device")
+    out = [torch.empty(rho.shape, dtype=ref.dtype, device=ref.device) for _ in range(4)]
+    pr = [torch.empty(n_col, dtype=ref.dtype, device=ref.device) if precip else None for _ in range(2)]
+    in_p = (C.c_void_p * 7)(*[c.data_ptr() for c in flat])
+    out_p = (C.c_void_p * 4)(*[o.data_ptr() for o in out])
+    _lib.call("cmx_mp1m_column_implicit_average_sedimentation", fam, ref.device, C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain),
+              C.byref(chen_ice), mp.flags, dt, nsub, _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p,
+              _ptr(pr[0]), _ptr(pr[1]), stream=stream)
     return ColumnStep1M(*out, *pr)

@@ -1705,6 +1705,51 @@ int32_t cmx_mp1m_implicit_average_f64(const cmx_microphysics_1m_f64 *mp, const c
                                       double dt, int32_t nsub, uint32_t step_flags, double *const average[CMX_MP1M_JAC_NOUT], void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (20) The column steps with the average tendency of (19) as tendency operator: what a host model calls per time step — tendencies, fall speeds and first-order
+ * upwind sedimentation in one pass, as cmx_sb2006_column_tendencies_sedimentation_* and cmx_mp1m_column_tendencies_sedimentation_* — with the sub-stepped
+ * implicit average in the place of the instantaneous (or LinearizedAverage) tendencies.  For the 2-moment scheme this is the one column step that is stable at a
+ * large Δt.  ONE kernel; layout, `inv_dz`, the parameter structs, `flags` and the surface-flux outputs are those of the scheme's column entry, `dt`, `nsub`
+ * and `step_flags` those of (19).  The definition, normative — per point k of a column, in the entry's float type FT:
+ *     a_j   = average_j of (19) for (ρ, T, q_tot, s) of the point with (dt, nsub, step_flags), bit for bit
+ *     F, g  = the fluxes F_j = ρ⁺ χ_j⁺ w_j of the four falling species and g = inv_dz[k]/ρ_k⁺ of the scheme's column entry for the same options, bit for bit,
+ *             evaluated at the INITIAL state of the step: sedimentation stays explicit
+ *     out_j = fma(top ? 0 : F_j[k+1], g, fma(−F_j[k], g, a_j)),      top: k = n_lev − 1 (nothing enters through the model top)
+ * — the combining expression of the existing column entries with a_j in the place of the tendency.  The surface outputs (`precip_flux`; `precip_rai`,
+ * `precip_sno`; optional, n_col values) are F at level 0, as in the existing entries.  SB2006 without `cloud_vel`: q_lcl and n_lcl do not fall, their outputs
+ * are a_j themselves (as today, no fma is applied to them).
+ * NaN rule: that of (19) for a point's four a_j — a NaN in any of the seven inputs of a point (1-moment Float64: also ρ ≤ 0) gives NaN in all four outputs of
+ * the point; that of the existing column entries for the fluxes — a NaN in ρ or in a species poisons that species' flux (SB2006: the fluxes of the point) and,
+ * through it, the tendency of the cell below, and nothing else.  Results do not depend on where the kernel's tile boundaries fall, nor on alignment.
+ * Statuses, in this order: those of the scheme's column entry up to and including the column and table checks (NULL structs, n_col < 0, n_lev < 1; the flags —
+ * cmx_mp1m_*: both snow-shape bits CMX_ERR_BAD_ARG, a single one CMX_ERR_UNSUPPORTED; n_col·n_lev above what one launch expresses CMX_ERR_UNSUPPORTED;
+ * n_col·n_lev = 0 is CMX_OK; NULL columns; cmx_sb2006_*: the limiter pairs and the fall-speed table); then `dt`, `nsub` and `step_flags` as in (19)
+ * (CMX_ERR_BAD_ARG).  All four outputs are required.  A pure launch sequence on `stream`: no allocation, no synchronisation, graph-capturable; any alignment.
+ * NOT in place: an output column must not alias an input column — another workgroup reads the point above.  This deliberately differs from (19).
+ * Not done here: the 1-moment snow shapes (CMX_1M_SED_SNOW_OBLATE / _PROLATE: CMX_ERR_UNSUPPORTED), implicit sedimentation, the 2M + P3 column step, the
+ * `*_fields_*` layouts, autograd.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_column_implicit_average_sedimentation_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                                             const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags,
+                                                             int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho, const float *T,
+                                                             const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                                             float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt, float *dn_rai_dt, float *precip_flux,
+                                                             void *stream);
+int32_t cmx_sb2006_column_implicit_average_sedimentation_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                                             const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags,
+                                                             int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho, const double *T,
+                                                             const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                                             const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt, double *dq_rai_dt, double *dn_rai_dt,
+                                                             double *precip_flux, void *stream);
+int32_t cmx_mp1m_column_implicit_average_sedimentation_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                                           const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags,
+                                                           double dt, int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz,
+                                                           const float *const *in, float *const *out, float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_implicit_average_sedimentation_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                                           const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags,
+                                                           double dt, int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz,
+                                                           const double *const *in, double *const *out, double *precip_rai, double *precip_sno, void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),
