@@ -152,6 +152,7 @@ JACOBIAN_PRODUCT_STEMS = ("cmx_sb2006_warm_rain", "cmx_mp1m")
 CMX_STEP_NONNEGATIVE = 1
 CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 # … and as tendency operator of the column steps (include/cmx.h §20): cmx_<scheme>_column_implicit_average_sedimentation_* take the same dt, nsub, step_flags
+# … and with backward-Euler sedimentation (include/cmx.h §21): cmx_<scheme>_column_implicit_step_*, the argument lists of §20
 
 
 def _struct(name, fields):

@@ -227,14 +227,16 @@ def _declare(lib):
             f.restype = i32
             f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.c_double, i32, u32, C.POINTER(vp), vp]
         # the column steps with the implicit average as tendency (include/cmx.h §20): (flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, …)
-        f = getattr(lib, f"cmx_sb2006_column_implicit_average_sedimentation_{s}")
-        f.restype = i32
-        f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel), C.POINTER(fam.stokes_vel), u32, C.c_double, i32, u32,
-                      i64, i32] + [vp] * 13 + [vp]
-        f = getattr(lib, f"cmx_mp1m_column_implicit_average_sedimentation_{s}")
-        f.restype = i32
-        f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), C.POINTER(fam.stokes_vel), C.POINTER(fam.chen2022_rain_vel),
-                      C.POINTER(fam.chen2022_ice_vel), u32, C.c_double, i32, u32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
+        # … and with backward-Euler sedimentation (§21): the same argument lists
+        for step in ("implicit_average_sedimentation", "implicit_step"):
+            f = getattr(lib, f"cmx_sb2006_column_{step}_{s}")
+            f.restype = i32
+            f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel), C.POINTER(fam.stokes_vel), u32, C.c_double, i32, u32,
+                          i64, i32] + [vp] * 13 + [vp]
+            f = getattr(lib, f"cmx_mp1m_column_{step}_{s}")
+            f.restype = i32
+            f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), C.POINTER(fam.stokes_vel), C.POINTER(fam.chen2022_rain_vel),
+                          C.POINTER(fam.chen2022_ice_vel), u32, C.c_double, i32, u32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

@@ -420,20 +420,10 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
     return out
 
 
-def column_implicit_average_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, vel=SB2006VelType,
-                                             vel_params=None, cloud_vel=None, want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None,
-                                             stream=None) -> ColumnTendencies2M:
-    """The 2-moment column step with the sub-stepped implicit average as tendency operator (`cmx_sb2006_column_implicit_average_sedimentation_*`): per point
-    the average tendency of `warm_rain_implicit_average_2m(…, dt, nsub, nonnegative)` — bit for bit — plus, in the same kernel, the first-order upwind
-    sedimentation flux divergence of `column_tendencies_sedimentation` with the fluxes of the INITIAL state (sedimentation stays explicit).  A stable
-    large-`dt` column step in one launch; include/cmx.h §(20) has the definition.
-
-    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused); `inv_dz`, `vel`, `vel_params`, `cloud_vel`,
-    `want_precip_flux` as for `column_tendencies_sedimentation`; `dt`, `nsub`, `nonnegative` as for `warm_rain_implicit_average_2m`.  `out=` provides the
-    outputs; an output must NOT be a state tensor (another workgroup reads the point above).  No autograd.  Asynchronous on `stream`."""
+def _column_implicit_2m(entry, mp, tps, inv_dz, cols, dt, nsub, nonnegative, vel, vel_params, cloud_vel, want_precip_flux, out, stream):
+    """The checks and the call of the two 2-moment column steps that take the implicit average as tendency (include/cmx.h §(20), §(21)): same arguments."""
     wr = _warm_rain(mp)
     dt, nsub = _check_step(dt, nsub)
-    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
     ref = _check_cols(cols, _NAMES_2M)
     if ref.dim() != 2:
         raise ValueError("state columns must have shape (n_col, n_lev)")
@@ -459,10 +449,40 @@ def column_implicit_average_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_l
     velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
     if not isinstance(velp, fam.rain_vel):
         raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
-    _lib.call("cmx_sb2006_column_implicit_average_sedimentation", fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
+    _lib.call(entry, fam, ref.device, C.byref(wr.c), C.byref(tps), C.byref(velp),
               C.byref(cloud_vel) if cloud_vel is not None else None, flags, dt, nsub, _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev,
               _ptr(inv_dz), *[_ptr(t) for t in cols], *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)
     return out
+
+
+def column_implicit_average_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, vel=SB2006VelType,
+                                             vel_params=None, cloud_vel=None, want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None,
+                                             stream=None) -> ColumnTendencies2M:
+    """The 2-moment column step with the sub-stepped implicit average as tendency operator (`cmx_sb2006_column_implicit_average_sedimentation_*`): per point
+    the average tendency of `warm_rain_implicit_average_2m(…, dt, nsub, nonnegative)` — bit for bit — plus, in the same kernel, the first-order upwind
+    sedimentation flux divergence of `column_tendencies_sedimentation` with the fluxes of the INITIAL state (sedimentation stays explicit).  A stable
+    large-`dt` column step in one launch; include/cmx.h §(20) has the definition.
+
+    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused); `inv_dz`, `vel`, `vel_params`, `cloud_vel`,
+    `want_precip_flux` as for `column_tendencies_sedimentation`; `dt`, `nsub`, `nonnegative` as for `warm_rain_implicit_average_2m`.  `out=` provides the
+    outputs; an output must NOT be a state tensor (another workgroup reads the point above).  No autograd.  Asynchronous on `stream`."""
+    return _column_implicit_2m("cmx_sb2006_column_implicit_average_sedimentation", mp, tps, inv_dz, (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), dt, nsub,
+                               nonnegative, vel, vel_params, cloud_vel, want_precip_flux, out, stream)
+
+
+def column_implicit_step_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, vel=SB2006VelType,
+                            vel_params=None, cloud_vel=None, want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None,
+                            stream=None) -> ColumnTendencies2M:
+    """The 2-moment column step that is stable and positive at any Courant number Δt·w/Δz (`cmx_sb2006_column_implicit_step_*`): the average tendency of
+    `warm_rain_implicit_average_2m(…, dt, nsub, nonnegative)` per point — bit for bit — and, in the same kernel, BACKWARD-EULER first-order upwind
+    sedimentation, a top-down recurrence along each column with the fall speeds of the initial state.  Where `column_implicit_average_sedimentation_2m`
+    (explicit fluxes) needs Δt·w/Δz ≤ 1, this step needs no sub-cycling.  `precip_flux` is the flux that leaves the column DURING the step (G_0, not the
+    initial F_0): the column budget closes.  include/cmx.h §(21) has the definition.
+
+    Arguments, result, `out=` and the checks are those of `column_implicit_average_sedimentation_2m`; an output must NOT be a state tensor.  No autograd.
+    Asynchronous on `stream`."""
+    return _column_implicit_2m("cmx_sb2006_column_implicit_step", mp, tps, inv_dz, (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), dt, nsub, nonnegative, vel,
+                               vel_params, cloud_vel, want_precip_flux, out, stream)
 
 
 ColumnTendencies2MP3 = namedtuple(

@@ -339,18 +339,10 @@ def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain,
     return ColumnStep1M(*out, *pr)
 
 
-def column_implicit_average_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1,
-                                             nonnegative=True, *, precip=True, stream=None) -> ColumnStep1M:
-    """The 1-moment column step with the sub-stepped implicit average as tendency operator (`cmx_mp1m_column_implicit_average_sedimentation_*`): per point
-    the average tendency of `implicit_average_1m(…, dt, nsub, nonnegative)` — bit for bit, built on the true Jacobian where LinearizedAverage carries a
-    donor-based approximation — plus, in the same kernel, the four sedimentation fluxes and the first-order upwind flux divergence of
-    `column_tendencies_sedimentation_1m`, with the fluxes of the INITIAL state (sedimentation stays explicit).  include/cmx.h §(20) has the definition.
-
-    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused, not copied); `inv_dz` = n_lev values 1/Δz; `dt`, `nsub`,
-    `nonnegative` as for `implicit_average_1m`.  Returns the four total tendencies and (precip=True) the surface rain / snow fluxes.  No snow shape, no
-    autograd.  Asynchronous on `stream` (default: torch's current stream)."""
+def _column_implicit_1m(entry, mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols, dt, nsub, nonnegative, precip, stream):
+    """The checks and the call of the two 1-moment column steps that take the implicit average as tendency (include/cmx.h §(20), §(21)): same arguments."""
     dt, nsub = _check_step(dt, nsub)
-    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    rho = cols[0]
     if rho.dim() != 2:
         raise ValueError("state tensors must have shape (n_col, n_lev)")
     # the 2-D tensors THEMSELVES, as in column_tendencies_sedimentation_1m: the kernel reads flat row-major (n_col, n_lev) storage
@@ -372,7 +364,34 @@ def column_implicit_average_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ic
     pr = [torch.empty(n_col, dtype=ref.dtype, device=ref.device) if precip else None for _ in range(2)]
     in_p = (C.c_void_p * 7)(*[c.data_ptr() for c in flat])
     out_p = (C.c_void_p * 4)(*[o.data_ptr() for o in out])
-    _lib.call("cmx_mp1m_column_implicit_average_sedimentation", fam, ref.device, C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain),
+    _lib.call(entry, fam, ref.device, C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain),
               C.byref(chen_ice), mp.flags, dt, nsub, _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p,
               _ptr(pr[0]), _ptr(pr[1]), stream=stream)
     return ColumnStep1M(*out, *pr)
+
+
+def column_implicit_average_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1,
+                                             nonnegative=True, *, precip=True, stream=None) -> ColumnStep1M:
+    """The 1-moment column step with the sub-stepped implicit average as tendency operator (`cmx_mp1m_column_implicit_average_sedimentation_*`): per point
+    the average tendency of `implicit_average_1m(…, dt, nsub, nonnegative)` — bit for bit, built on the true Jacobian where LinearizedAverage carries a
+    donor-based approximation — plus, in the same kernel, the four sedimentation fluxes and the first-order upwind flux divergence of
+    `column_tendencies_sedimentation_1m`, with the fluxes of the INITIAL state (sedimentation stays explicit).  include/cmx.h §(20) has the definition.
+
+    State tensors of shape (n_col, n_lev), level 0 lowest, contiguous (a transposed view is refused, not copied); `inv_dz` = n_lev values 1/Δz; `dt`, `nsub`,
+    `nonnegative` as for `implicit_average_1m`.  Returns the four total tendencies and (precip=True) the surface rain / snow fluxes.  No snow shape, no
+    autograd.  Asynchronous on `stream` (default: torch's current stream)."""
+    return _column_implicit_1m("cmx_mp1m_column_implicit_average_sedimentation", mp, tps, stokes, chen_rain, chen_ice, inv_dz,
+                               (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), dt, nsub, nonnegative, precip, stream)
+
+
+def column_implicit_step_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1, nonnegative=True, *,
+                            precip=True, stream=None) -> ColumnStep1M:
+    """The 1-moment column step that is stable and positive at any Courant number Δt·w/Δz (`cmx_mp1m_column_implicit_step_*`): the average tendency of
+    `implicit_average_1m(…, dt, nsub, nonnegative)` per point — bit for bit — and, in the same kernel, BACKWARD-EULER first-order upwind sedimentation of
+    the four species, a top-down recurrence along each column with the fall speeds of the initial state.  Where
+    `column_implicit_average_sedimentation_1m` (explicit fluxes) needs Δt·w/Δz ≤ 1, this step needs no sub-cycling.  The surface fluxes are those that leave
+    the column DURING the step (G_0, not the initial F_0): the column budget closes.  include/cmx.h §(21) has the definition.
+
+    Arguments, result and checks are those of `column_implicit_average_sedimentation_1m`.  No snow shape, no autograd.  Asynchronous on `stream`."""
+    return _column_implicit_1m("cmx_mp1m_column_implicit_step", mp, tps, stokes, chen_rain, chen_ice, inv_dz, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), dt,
+                               nsub, nonnegative, precip, stream)

@@ -158,6 +158,37 @@ __device__ __forceinline__ SedFlux4<FT> mp1m_sed_fluxes(const VC &vc, FT rho, FT
     return F;
 }
 
+// … and the same fluxes TOGETHER WITH the fall speed each one multiplies in (cmx_column_implicit_step.hip: backward-Euler sedimentation needs w itself).
+// F is formed by the operations of mp1m_sed_fluxes above on the same operands, so it has its bits (tests/test_column_implicit_step_gpu.py compares them with
+// inv_dz = 0); w is the value in registers and is not poisoned: a NaN input reaches the step through F.
+template <typename FT> struct SedFluxW4 { FT f[4], w[4]; };   // lcl, icl, rai, sno
+
+template <typename FT, bool GENERAL_GAMMA, typename VC>
+__device__ __forceinline__ SedFluxW4<FT> mp1m_sed_fluxes_w(const VC &vc, FT rho, FT q_lcl, FT q_icl, FT q_rai, FT q_sno) {
+    using M = Math<FT>;
+    const FT r_ = max0(rho), ql = max0(q_lcl), qi = max0(q_icl), qr = max0(q_rai), qs = max0(q_sno);
+    SedFluxW4<FT> F;
+    F.w[0] = vel_lcl_stokes<FT>(vc, r_, ql);
+    F.f[0] = (r_ * ql) * F.w[0];
+    const VC &v1 = consts_after(vc, F.f[0]);
+    const FT l2_rho = log2_floored(r_);
+    F.w[1] = vel_icl_chen<FT>(v1, r_, r_, qi, l2_rho);
+    F.f[1] = (r_ * qi) * F.w[1];
+    const VC &v2 = consts_after(v1, F.f[1]);
+    F.w[2] = vel_rain_chen<FT, GENERAL_GAMMA>(v2, r_, vel_l2_li_rain<FT>(v2, r_, qr), qr, GENERAL_GAMMA ? log2_floored(keep(r_)) : l2_rho);
+    F.f[2] = (r_ * qr) * F.w[2];
+    const VC &v3 = consts_after(v2, F.f[2]);
+    F.w[3] = vel_snow_chen<FT, false>(v3, r_, vel_l2_li_snow<FT>(v3, r_, qs), qs, l2_rho);
+    F.f[3] = (r_ * qs) * F.w[3];
+    auto poison = [&](FT q_s, FT f) -> FT {
+        typename M::Mask bad = nan_mask(rho, q_s);
+        if constexpr (M::IS_F64) bad = (bool)((int)bad | (int)bad_density(rho));
+        return bad ? M::nan() : f;
+    };
+    F.f[0] = poison(q_lcl, F.f[0]); F.f[1] = poison(q_icl, F.f[1]); F.f[2] = poison(q_rai, F.f[2]); F.f[3] = poison(q_sno, F.f[3]);
+    return F;
+}
+
 // *chen_general (optional): true when the Chen-2022 rain table needs the GENERAL instantiation (the Γ fit is not accurate for it)
 template <typename FT, typename MP, typename CH>
 static Vel1mConsts<FT> make_vel1m_consts(const MP &mp, const CH *chen, bool *chen_general = nullptr) {

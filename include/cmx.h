@@ -1725,7 +1725,7 @@ int32_t cmx_mp1m_implicit_average_f64(const cmx_microphysics_1m_f64 *mp, const c
  * n_col·n_lev = 0 is CMX_OK; NULL columns; cmx_sb2006_*: the limiter pairs and the fall-speed table); then `dt`, `nsub` and `step_flags` as in (19)
  * (CMX_ERR_BAD_ARG).  All four outputs are required.  A pure launch sequence on `stream`: no allocation, no synchronisation, graph-capturable; any alignment.
  * NOT in place: an output column must not alias an input column — another workgroup reads the point above.  This deliberately differs from (19).
- * Not done here: the 1-moment snow shapes (CMX_1M_SED_SNOW_OBLATE / _PROLATE: CMX_ERR_UNSUPPORTED), implicit sedimentation, the 2M + P3 column step, the
+ * Not done here: the 1-moment snow shapes (CMX_1M_SED_SNOW_OBLATE / _PROLATE: CMX_ERR_UNSUPPORTED), implicit sedimentation — (21) —, the 2M + P3 column step, the
  * `*_fields_*` layouts, autograd.
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_implicit_average_sedimentation_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
@@ -1748,6 +1748,52 @@ int32_t cmx_mp1m_column_implicit_average_sedimentation_f64(const cmx_microphysic
                                                            const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags,
                                                            double dt, int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz,
                                                            const double *const *in, double *const *out, double *precip_rai, double *precip_sno, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (21) The column steps of (20) with IMPLICIT sedimentation: the average tendency of (19) per point and, in the same kernel, backward-Euler first-order upwind
+ * sedimentation — stable and positive at any Courant number c = Δt·w/Δz, where the explicit fluxes of (20) need c ≤ 1 (rain at 5–9 m/s through 30–100 m
+ * layers at Δt = 30–300 s: c = 2 … 80).  A host model that takes (20) at the Δt the average is built for must sub-cycle sedimentation itself; with these
+ * entries it need not.  The argument lists are exactly those of the (20) entries, the checks and statuses the same in the same order.  The definition,
+ * normative — per column, for each falling species j, in the entry's float type FT, level 0 the lowest:
+ *     a      = average_j of (19) for the point, bit for bit                                                       (as in (20))
+ *     F, g   = F_j = (ρ⁺χ_j⁺)·w_j and g = inv_dz[k]/ρ_k⁺ of the scheme's column entry, bit for bit                (as in (20))
+ *     w      = the fall speed that the scheme's flux function multiplies into F_j (that value itself, not F/(ρχ))
+ *     τ      = FT(dt)·w          c = τ·inv_dz[k]       β = τ·ρ⁺        D = 1 + c       r = 1/D
+ *     A      = c·r               B = fma(β, a, F)·r
+ *     G_k    = top ? B_k : fma(A_k, G_{k+1}, B_k)          top: k = n_lev − 1;  evaluated from the top level downward, in this order
+ *     out_k  = fma(top ? 0 : G_{k+1}, g, fma(−F_k, g, a_k)) · r_k
+ * r is a TRUE (correctly rounded IEEE) division in both float types: exactly 1 at c = 0.  Every other product and sum is a separate IEEE operation except
+ * the fma's written above.  "top" is a select, never a multiplication by zero.
+ * This is backward Euler on ∂χ/∂t = a + (G_{k+1} − G_k)·g with G_k = w_k ρ_k (χ_k + Δt·out_k), the fall speeds frozen at the initial state; substituting gives
+ * G_k = (F_k + β_k a_k + c_k G_{k+1})/(1 + c_k), an affine recurrence with 0 ≤ A < 1.  With inv_dz ≡ 0 the outputs are the averages of (19).
+ * The surface outputs (`precip_flux`; `precip_rai`, `precip_sno`; optional, n_col values) are G at level 0 — the flux that leaves the column DURING the step,
+ * so that the column budget Σ_k ρ_k out_k Δz_k + G_0 = Σ_k ρ_k a_k Δz_k closes — not the initial F_0 of (20).  SB2006 without `cloud_vel`: q_lcl and n_lcl do
+ * not fall, their outputs are a_j themselves, as in (20).
+ * NaN rule: that of (19) for a_j and that of (20) for F_j; on top of those the recurrence carries a NaN in G_j DOWNWARD: it reaches every lower level of the
+ * same species in the same column (of every species, if a_j is NaN at that point: then all four B are), never a higher level and never another column.
+ * Results do not depend on how the kernel divides the columns among workgroups, on alignment, or on the number of columns in the call.  A pure launch
+ * sequence on `stream` (ONE kernel): no allocation, no synchronisation, graph-capturable; any alignment.  NOT in place, as (20).
+ * Not done here: the 1-moment snow shapes (a single CMX_1M_SED_SNOW_* bit: CMX_ERR_UNSUPPORTED, as in (20)), the 2M + P3 column step, the `*_fields_*`
+ * layouts, autograd, fall speeds re-evaluated inside the step.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_column_implicit_step_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                            const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags, int64_t n_col,
+                                            int32_t n_lev, const float *inv_dz, const float *rho, const float *T, const float *q_tot, const float *q_lcl,
+                                            const float *n_lcl, const float *q_rai, const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt,
+                                            float *dn_rai_dt, float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_implicit_step_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                            const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags, int64_t n_col,
+                                            int32_t n_lev, const double *inv_dz, const double *rho, const double *T, const double *q_tot, const double *q_lcl,
+                                            const double *n_lcl, const double *q_rai, const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt,
+                                            double *dq_rai_dt, double *dn_rai_dt, double *precip_flux, void *stream);
+int32_t cmx_mp1m_column_implicit_step_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                          const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, double dt,
+                                          int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *const *in,
+                                          float *const *out, float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_implicit_step_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                          const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, double dt,
+                                          int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *const *in,
+                                          double *const *out, double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

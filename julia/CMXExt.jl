@@ -1638,6 +1638,52 @@ function column_implicit_average_sedimentation!(out, ::BMT.Microphysics1Moment, 
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (21) the column steps of (20) with backward-Euler sedimentation: stable and positive at any Courant number Δt·w/Δz
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    column_implicit_step!(out, BMT.Microphysics2Moment(), mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, …, dt; nsub, nonnegative, precip_flux, stream)
+
+`column_implicit_average_sedimentation!` with backward-Euler upwind sedimentation (a top-down recurrence along each column, the fall speeds those of the initial
+state): no sub-cycling at Δt·w/Δz > 1.  `precip_flux` is the flux that leaves the column during the step.  `out` must not alias the state columns.
+include/cmx.h §(21) has the definition.
+"""
+function column_implicit_step!(out, ::BMT.Microphysics2Moment, mp::CMP.Microphysics2MParams, tps, vel, cloud_vel, n_col::Integer,
+    n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt::Real; nsub::Integer = 1, nonnegative::Bool = true,
+    precip_flux = nothing, stream = C_NULL) where {FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    wr = _warm_rain(mp)
+    flags = (is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vel)
+    st = ccall(_fn("cmx_sb2006_column_implicit_step", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Float64, Int32, UInt32, Int64, Int32, Ptr{FT},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, Float64(dt), Int32(nsub),
+        nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _dp(FT, out.dq_lcl_dt), _dp(FT, out.dn_lcl_dt), _dp(FT, out.dq_rai_dt), _dp(FT, out.dn_rai_dt), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_implicit_step")
+    return out
+end
+
+"""
+    column_implicit_step!(out, BMT.Microphysics1Moment(), mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols, dt; nsub, nonnegative, …)
+
+The 1-moment `column_implicit_average_sedimentation!` with backward-Euler upwind sedimentation of the four species; arguments as there, `precip_rai` and
+`precip_sno` are the fluxes that leave the column during the step.  No snow shape; `out` must not alias `cols`.  include/cmx.h §(21) has the definition.
+"""
+function column_implicit_step!(out, ::BMT.Microphysics1Moment, mp::CMP.Microphysics1MParams, tps, stokes::CMP.StokesRegimeVelType{FT},
+    chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, dt::Real; nsub::Integer = 1, nonnegative::Bool = true, precip_rai = nothing,
+    precip_sno = nothing, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_mp1m_column_implicit_step", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Float64, Int32, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT},
+            Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), Float64(dt), Int32(nsub),
+        nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols), _ptrs(FT, out), _dp(FT, precip_rai), _dp(FT, precip_sno),
+        stream)
+    _check(st, "cmx_mp1m_column_implicit_step")
+    return out
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
