@@ -22,6 +22,7 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
                               ColumnTendencies2M, column_tendencies_sedimentation, ColumnTendencies2MP3,
                               column_tendencies_sedimentation_2m_p3, WarmRainJacobian2M, warm_rain_jacobian_2m, JACOBIAN_WRT, JACOBIAN_OUTPUTS,
                               WarmRainJvp2M, WarmRainVjp2M, warm_rain_jvp_2m, warm_rain_vjp_2m, WarmRainImplicit2M,
+                              WarmRainParamJvp2M, WarmRainParamVjp2M, warm_rain_param_jvp_2m, warm_rain_param_vjp_2m,
                               warm_rain_implicit_tendencies_2m, warm_rain_implicit_average_2m, column_implicit_average_sedimentation_2m, column_implicit_step_2m)
 
 from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_count,  # noqa: F401
@@ -44,7 +45,7 @@ from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Mome
                              TerminalVelocities1M, bulk_microphysics_tendencies_1m, bulk_microphysics_tendencies_1m_fields,
                              microphysics_source_terms_1m, sedimentation_velocities, terminal_velocity_1m, ColumnStep1M,
                              column_tendencies_sedimentation_1m, AbstractSnowShape, Oblate, Prolate, snow_terminal_velocity, Jacobian1M,
-                             JACOBIAN_WRT_1M, JACOBIAN_OUTPUTS_1M, jacobian_1m, Jvp1M, Vjp1M, jvp_1m, vjp_1m, Implicit1M, implicit_tendencies_1m,
+                             JACOBIAN_WRT_1M, JACOBIAN_OUTPUTS_1M, jacobian_1m, Jvp1M, Vjp1M, jvp_1m, vjp_1m, ParamJvp1M, ParamVjp1M, param_jvp_1m, param_vjp_1m, Implicit1M, implicit_tendencies_1m,
                              implicit_average_1m, column_implicit_average_sedimentation_1m, column_implicit_step_1m)
 
 from .microphysics0m import (Microphysics0Moment, bulk_microphysics_tendencies_0m, d_remove_precipitation_d_q_tot,  # noqa: F401

@@ -9,6 +9,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _ptr
+from .parameters import parameter_direction
 
 
 def _check_wrt(wrt, wrt_all, what="wrt", rho_is_unknown=False):
@@ -152,3 +153,55 @@ def _implicit_average(entry, params, flags, tps, cols, names, nout, dt, nsub, no
     _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], dt, nsub,
               _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, _table([avg[o] for o in range(nout)]), stream=stream)
     return avg
+
+
+def _param_directions(params, directions):
+    """The direction tables of the ABI (include/cmx.h §22, §23) from a sequence whose members are {ClimaParams name: weight} mappings or (d_params, d_thermo)
+    pairs of `parameters.parameter_direction`.  params: the parameter object of the entry (`.c`, `.fam`)."""
+    pairs = [parameter_direction(params, d) if isinstance(d, dict) else tuple(d) for d in directions]
+    if not pairs:
+        raise ValueError("directions: at least one direction expected")
+    for a, b in pairs:
+        if not isinstance(a, type(params.c)) or not isinstance(b, params.fam.thermo):
+            raise TypeError("directions: (d_params, d_thermo) structs of the parameters' float type, or {name: weight} mappings")
+    return (type(params.c) * len(pairs))(*[a for a, _ in pairs]), (params.fam.thermo * len(pairs))(*[b for _, b in pairs])
+
+
+def _param_jvp(entry, params, flags, tps, cols, names, nout, directions, with_tendencies, out, stream):
+    """(jvp, tendencies) of `entry`_f32 / _f64: jvp of shape (len(directions), nout, *rho.shape).  More than CMX_PARAM_MAX_DIRS directions are several calls
+    of the entry (the tendencies are the first call's)."""
+    ref, fam = _prep(params, tps, cols, names)
+    d_p, d_tps = _param_directions(params, directions)
+    ndir = len(d_p)
+    jvp, tend = _out_pair(out, ref, (ndir, nout), "jvp", nout, with_tendencies, f"(len(directions), {nout}, *rho.shape) = ")
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], nd, C.byref(d_p[d0]), C.byref(d_tps[d0]),
+                  _table([jvp[d, o] for d in range(d0, d0 + nd) for o in range(nout)]),
+                  _table([tend[o] for o in range(nout)]) if tend is not None and d0 == 0 else None, stream=stream)
+    return jvp, tend
+
+
+def _param_vjp(entry, params, flags, tps, cols, names, nout, cotangents, wrt, with_tendencies, out, stream):
+    """(grad, tendencies, wrt) of `entry`_f32 / _f64: grad a float64 tensor of shape (len(wrt),) on the state's device.  wrt: ClimaParams names (one-hot
+    directions) or directions as for _param_jvp.  The workspace is allocated here per call (the package keeps no cached device scratch) and reused by the
+    calls of one invocation, which are ordered on the stream."""
+    ref, fam = _prep(params, tps, cols, names)
+    wrt = tuple(wrt)
+    d_p, d_tps = _param_directions(params, [{w: 1.0} if isinstance(w, str) else w for w in wrt])
+    cotangents = list(cotangents)
+    if len(cotangents) != nout:
+        raise ValueError(f"cotangents: {nout} tensors (or None) expected, one per output")
+    given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
+    if given:
+        _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])
+    _, tend = _out_pair((None, out), ref, (0,), "grad", nout, with_tendencies)
+    ndir = len(d_p)
+    grad = torch.empty(ndir, dtype=torch.float64, device=ref.device)
+    workspace = torch.empty(min(ndir, _abi.CMX_PARAM_MAX_DIRS) * _abi.CMX_PARAM_VJP_PARTIALS, dtype=torch.float64, device=ref.device)
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        _lib.call(entry, fam, ref.device, C.byref(params.c), C.byref(tps), flags, ref.numel(), *[_ptr(t) for t in cols], _table(cotangents), nd,
+                  C.byref(d_p[d0]), C.byref(d_tps[d0]), _ptr(grad[d0:]), _ptr(workspace),
+                  _table([tend[o] for o in range(nout)]) if tend is not None and d0 == 0 else None, stream=stream)
+    return grad, tend, wrt

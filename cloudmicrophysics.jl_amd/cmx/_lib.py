@@ -226,6 +226,17 @@ def _declare(lib):
             f = getattr(lib, f"{stem}_implicit_average_{s}")          # (dt, nsub, step_flags, average[4])
             f.restype = i32
             f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.c_double, i32, u32, C.POINTER(vp), vp]
+        # the derivatives with respect to the parameters (include/cmx.h §22): (…state…, ndir, d_warm_rain, d_tps, jvp[ndir·4], tendencies[4]) /
+        # (…state…, cotangents[4], ndir, d_warm_rain, d_tps, grad, workspace, tendencies[4])
+        for stem, params in (("cmx_sb2006_warm_rain", fam.warm_rain_2m), ("cmx_mp1m", fam.microphysics_1m)):      # §22, §23
+            f = getattr(lib, f"{stem}_param_jvp_{s}")
+            f.restype = i32
+            f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [i32, C.POINTER(params), C.POINTER(fam.thermo), C.POINTER(vp),
+                                                                                           C.POINTER(vp), vp]
+            f = getattr(lib, f"{stem}_param_vjp_{s}")
+            f.restype = i32
+            f.argtypes = [C.POINTER(params), C.POINTER(fam.thermo), u32, i64] + [vp] * 7 + [C.POINTER(vp), i32, C.POINTER(params), C.POINTER(fam.thermo), vp, vp,
+                                                                                           C.POINTER(vp), vp]
         # the column steps with the implicit average as tendency (include/cmx.h §20): (flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, …)
         # … and with backward-Euler sedimentation (§21): the same argument lists
         for step in ("implicit_average_sedimentation", "implicit_step"):

@@ -7,13 +7,17 @@ can be differentiated by `loss.backward()`, `torch.autograd.grad` and `torch.aut
   * forward mode calls the fused J v entry (`warm_rain_jvp_2m` / `jvp_1m`); an input without a tangent is a NULL tangent column.
 
 ρ is held fixed by the Jacobian entries, so `rho.requires_grad`, or a forward-mode tangent on `rho`, raises NotImplementedError at the call: a silently missing
-gradient is worse than an error.  Not built: double backward (backward is once-differentiable), vmap, the derivative with respect to the parameters, the
+gradient is worse than an error.  `warm_rain_tendencies_2m(…, theta=, names=)` and `tendencies_1m(…, theta=, names=)` also differentiate with respect to the scheme's PARAMETERS: `theta` is a 1-D CPU float64 tensor holding the
+values of the ClimaParams `names`; the forward pass rebuilds the parameter structs with those values (host work, no device sync) and is otherwise the same
+entry; backward calls the parameter-gradient entry (`warm_rain_param_vjp_2m` / `param_vjp_1m`) once for `theta.grad` (and the state Jᵀḡ entry if a state column needs a gradient), forward mode with a tangent on
+`theta` calls `warm_rain_param_jvp_2m` / `param_jvp_1m`.  Not built: double backward (backward is once-differentiable), vmap, the
 fall-speed outputs, LinearizedAverage and the 2M + P3 scheme."""
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import bulk_tendencies as _bt
 from . import microphysics1m as _m1
+from . import parameters as _P
 
 __all__ = ["warm_rain_tendencies_2m", "tendencies_1m"]
 
@@ -76,15 +80,120 @@ _Tendencies1M = _function(
     lambda mp, tps, cols, tangents: _m1.jvp_1m(mp, tps, *cols, tangents))
 
 
-def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai):
+def _theta_function(name, WRT, primal, vjp, jvp, param_vjp, param_jvp):
+    """The torch.autograd.Function of one scheme as a function of the parameter values `theta` (CPU) and the state: inputs (mp, tps, names, theta, rho, six
+    columns), where mp / tps are the parameter objects already rebuilt with `theta`."""
+    class F(torch.autograd.Function):
+        @staticmethod
+        def forward(mp, tps, names, theta, *cols):
+            return tuple(primal(mp, tps, cols))
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            ctx.mp, ctx.tps, ctx.names, _, *cols = inputs
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(*cols)
+            ctx.save_for_forward(*cols)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            out = [None] * (5 + len(WRT))                # mp, tps, names, theta, rho, then the differentiable inputs
+            if all(g is None for g in grads):
+                return tuple(out)
+            cot = [g.contiguous() if g is not None else None for g in grads]
+            if ctx.needs_input_grad[3]:
+                out[3] = param_vjp(ctx.mp, ctx.tps, ctx.saved_tensors, cot, ctx.names).grad.cpu()
+            wrt = tuple(n for k, n in enumerate(WRT) if ctx.needs_input_grad[5 + k])
+            if wrt:
+                r = vjp(ctx.mp, ctx.tps, ctx.saved_tensors, cot, wrt)
+                for k, n in enumerate(wrt):
+                    out[5 + WRT.index(n)] = r.grad[k]
+            return tuple(out)
+
+        @staticmethod
+        def jvp(ctx, t_mp, t_tps, t_names, t_theta, t_rho, *tangents):
+            if t_rho is not None:
+                raise NotImplementedError("forward-mode tangent on rho: the air density is held fixed")
+            parts = []
+            if t_theta is not None:
+                direction = {n: float(t) for n, t in zip(ctx.names, t_theta.tolist())}
+                parts.append(param_jvp(ctx.mp, ctx.tps, ctx.saved_tensors, [direction]).jvp[0])
+            state = {n: t.contiguous() for n, t in zip(WRT, tangents) if t is not None}
+            if state or not parts:
+                parts.append(jvp(ctx.mp, ctx.tps, ctx.saved_tensors, state).jvp)
+            total = parts[0] if len(parts) == 1 else parts[0] + parts[1]
+            return tuple(total[o] for o in range(4))
+    F.__name__ = F.__qualname__ = name
+    return F
+
+
+_WarmRain2MTheta = _theta_function(
+    "WarmRainTendencies2MTheta", _bt.JACOBIAN_WRT,
+    lambda mp, tps, cols: _bt.bulk_microphysics_tendencies(_bt.Microphysics2Moment(), mp, tps, *cols)[:4],
+    lambda mp, tps, cols, cotangents, wrt: _bt.warm_rain_vjp_2m(mp, tps, *cols, cotangents, wrt=wrt),
+    lambda mp, tps, cols, tangents: _bt.warm_rain_jvp_2m(mp, tps, *cols, tangents),
+    lambda mp, tps, cols, cotangents, names: _bt.warm_rain_param_vjp_2m(mp, tps, *cols, cotangents, names),
+    lambda mp, tps, cols, directions: _bt.warm_rain_param_jvp_2m(mp, tps, *cols, directions))
+
+_Tendencies1MTheta = _theta_function(
+    "Tendencies1MTheta", _m1.JACOBIAN_WRT_1M,
+    lambda mp, tps, cols: _m1.bulk_microphysics_tendencies_1m(_m1.Instantaneous(), _m1.Microphysics1Moment(), mp, tps, *cols),
+    lambda mp, tps, cols, cotangents, wrt: _m1.vjp_1m(mp, tps, *cols, cotangents, wrt=wrt),
+    lambda mp, tps, cols, tangents: _m1.jvp_1m(mp, tps, *cols, tangents),
+    lambda mp, tps, cols, cotangents, names: _m1.param_vjp_1m(mp, tps, *cols, cotangents, names),
+    lambda mp, tps, cols, directions: _m1.param_jvp_1m(mp, tps, *cols, directions))
+
+
+def _with_theta(mp, tps, theta, names):
+    """(parameter object, thermodynamics struct, names) rebuilt from mp's own dictionary with names[k] = theta[k]; `tps` itself unless a name feeds it."""
+    if not (isinstance(theta, torch.Tensor) and theta.device.type == "cpu" and theta.dtype == torch.float64 and theta.dim() == 1):
+        raise TypeError("theta: a 1-D CPU float64 tensor expected (the parameter structs are host data)")
+    names = tuple(names) if names is not None else ()
+    if len(names) != theta.numel() or len(set(names)) != len(names) or not names:
+        raise ValueError("names: one distinct ClimaParams name per element of theta expected")
+    one_moment = isinstance(mp, _P.Microphysics1MParams)
+    p = mp if one_moment else _bt._warm_rain(mp)
+    known = _P.MICROPHYSICS_1M_DIRECTION_NAMES if one_moment else _P.WARM_RAIN_2M_DIRECTION_FIELDS
+    for n in names:
+        if n not in known:
+            raise ValueError(f"names: '{n}' feeds no floating field of the scheme's or the thermodynamics parameters")
+    rebuild = (lambda td: _P.Microphysics1MParams(td, **{k: getattr(p.processes, k) for k in p.processes._defaults})) if one_moment else (lambda td: _P.WarmRainParams2M(td, p.is_limited))
+    base = {k: p.td[k] for k in p.td.overridden}
+    feeds_tps = any(f[0][0] == "tps" for n in names for f in [_P.WARM_RAIN_2M_DIRECTION_FIELDS.get(n, (("", "", 0),))])
+    # the rebuild starts from the dictionary, so a struct that no longer is what its dictionary builds would silently lose the caller's edits: refuse it
+    td0 = _P.create_toml_dict(p.td.FT, base)
+    if bytes(rebuild(td0).c) != bytes(p.c):
+        raise ValueError("theta: the fields of mp were changed after construction; put the values into the dictionary mp is built from (create_toml_dict)")
+    if feeds_tps and bytes(_P.ThermodynamicsParameters(td0)) != bytes(tps):
+        raise ValueError("theta: a thermodynamics name rebuilds tps from mp's dictionary, and tps is not what that dictionary builds")
+    td = _P.create_toml_dict(p.td.FT, {**base, **dict(zip(names, theta.detach().tolist()))})
+    return rebuild(td), (_P.ThermodynamicsParameters(td) if feeds_tps else tps), names
+
+
+def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, theta=None, names=None):
     """(dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt) of `cmx.bulk_microphysics_tendencies(Microphysics2Moment(), mp, tps, …)`, bit for bit, differentiable by
-    torch with respect to T, q_tot, q_lcl, n_lcl, q_rai, n_rai (reverse and forward mode; module docstring)."""
+    torch with respect to T, q_tot, q_lcl, n_lcl, q_rai, n_rai (reverse and forward mode; module docstring) and, with `theta` (1-D CPU float64) and `names`
+    (ClimaParams names, `cmx.parameters.WARM_RAIN_2M_DIRECTION_FIELDS`), with respect to those parameters: the structs are rebuilt from `mp`'s dictionary with
+    names[k] = theta[k] (a thermodynamics name rebuilds `tps` from the same dictionary).  Because of that rebuild, an `mp` whose fields were edited after
+    construction — or, with a thermodynamics name, a `tps` that is not what `mp`'s dictionary builds — is a ValueError, not a silently dropped edit."""
     _check_rho(rho)
-    return _WarmRain2M.apply(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    if theta is None:
+        if names is not None:
+            raise ValueError("names without theta")
+        return _WarmRain2M.apply(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    wr, tps_t, names = _with_theta(mp, tps, theta, names)
+    return _WarmRain2MTheta.apply(wr, tps_t, names, theta, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
 
 
-def tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno):
+def tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, theta=None, names=None):
     """(dq_lcl_dt, dq_icl_dt, dq_rai_dt, dq_sno_dt) of `cmx.bulk_microphysics_tendencies_1m(Instantaneous(), Microphysics1Moment(), mp, tps, …)`, bit for bit,
-    differentiable by torch with respect to T, q_tot, q_lcl, q_icl, q_rai, q_sno (reverse and forward mode; module docstring).  Instantaneous mode only."""
+    differentiable by torch with respect to T, q_tot, q_lcl, q_icl, q_rai, q_sno (reverse and forward mode; module docstring) and, with `theta` (1-D CPU float64)
+    and `names` (`cmx.parameters.MICROPHYSICS_1M_DIRECTION_NAMES`), with respect to those parameters; the rules of `warm_rain_tendencies_2m`.  Instantaneous mode only."""
     _check_rho(rho)
-    return _Tendencies1M.apply(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    if theta is None:
+        if names is not None:
+            raise ValueError("names without theta")
+        return _Tendencies1M.apply(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    mp_t, tps_t, names = _with_theta(mp, tps, theta, names)
+    return _Tendencies1MTheta.apply(mp_t, tps_t, names, theta, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)

@@ -24,7 +24,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -197,6 +197,43 @@ def warm_rain_vjp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotange
     return WarmRainVjp2M(*_vjp("cmx_sb2006_warm_rain_vjp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
                                (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, JACOBIAN_WRT, _abi.CMX_SB2006_JAC_NOUT, cotangents, wrt,
                                with_tendencies, out, stream))
+
+
+WarmRainParamJvp2M = namedtuple("WarmRainParamJvp2M", ["jvp", "tendencies"])
+WarmRainParamVjp2M = namedtuple("WarmRainParamVjp2M", ["grad", "tendencies", "wrt"])
+
+
+def warm_rain_param_jvp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, directions, with_tendencies=False, *, out=None, stream=None) -> WarmRainParamJvp2M:
+    """The derivative of the 2-moment warm-rain tendencies with respect to the scheme's PARAMETERS along `directions`, behind
+    `cmx_sb2006_warm_rain_param_jvp_*`: jvp[d, o] = Σ_p ∂`JACOBIAN_OUTPUTS[o]`/∂θ_p·δθ_p⁽ᵈ⁾ per point, the same point function as
+    `bulk_microphysics_tendencies` on forward-mode duals whose tangents are those of the host-folded constants (exact forward mode, no difference quotient).
+
+    `directions`: a sequence of {ClimaParams name: weight} mappings or of (d_warm_rain, d_thermo) pairs from `parameters.parameter_direction`; a one-hot
+    mapping {name: 1.0} gives ∂out/∂name.  Returns `WarmRainParamJvp2M(jvp, tendencies)`: `jvp` of shape (len(directions), 4, *rho.shape); a column does not
+    depend on which other directions are requested.  `tendencies` (4, *rho.shape) with `with_tendencies=True`, else None: bit-identical to
+    `bulk_microphysics_tendencies` unless a direction moves one of the three exponents acnv.b, accr.c, self.d (then the general-exponent instantiation runs:
+    agreement to the parity bound).  `out=(jvp, tendencies)` lets the caller provide either tensor.  More than `CMX_PARAM_MAX_DIRS` = 16 directions are
+    several calls of the entry.  Asynchronous on `stream` (default: torch's current stream)."""
+    wr = _warm_rain(mp)
+    return WarmRainParamJvp2M(*_param_jvp("cmx_sb2006_warm_rain_param_jvp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                                          (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, _abi.CMX_SB2006_JAC_NOUT, directions, with_tendencies, out, stream))
+
+
+def warm_rain_param_vjp_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, wrt, with_tendencies=False, *, out=None,
+                           stream=None) -> WarmRainParamVjp2M:
+    """The gradient of L = Σ_points Σ_o ḡ_o·out_o with respect to the scheme's PARAMETERS, behind `cmx_sb2006_warm_rain_param_vjp_*` — what a calibration
+    needs: grad[k] = dL/d`wrt[k]`, a deterministic reduction over the points in float64 (no atomics: bit-identical from run to run).
+
+    `cotangents`: a sequence of 4 tensors or None in the order of `JACOBIAN_OUTPUTS`; None removes that output from the sum.  `wrt`: ClimaParams names
+    (`parameters.WARM_RAIN_2M_DIRECTION_FIELDS`), or general directions as for `warm_rain_param_jvp_2m` (then grad[k] is the derivative along direction k).
+    Returns `WarmRainParamVjp2M(grad, tendencies, wrt)`: `grad` a float64 tensor of shape (len(wrt),) on the state's device; a NaN in the state or a cotangent
+    of any point makes it NaN.  `tendencies` as for `warm_rain_param_jvp_2m`; `out=tendencies` provides it.  The reduction's workspace (min(len(wrt), 16) × 1024
+    float64) is allocated here per call: the package keeps no cached device scratch (cmx/_cols.py has none), and under graph capture the allocation comes from
+    the capture's pool.  Asynchronous on `stream` (default: torch's current stream)."""
+    wr = _warm_rain(mp)
+    return WarmRainParamVjp2M(*_param_vjp("cmx_sb2006_warm_rain_param_vjp", wr, _abi.CMX_SB2006_LIMITED if wr.is_limited else 0, tps,
+                                          (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai), _NAMES_2M, _abi.CMX_SB2006_JAC_NOUT, cotangents, wrt, with_tendencies, out,
+                                          stream))
 
 
 WarmRainImplicit2M = namedtuple("WarmRainImplicit2M", ["implicit", "tendencies"])

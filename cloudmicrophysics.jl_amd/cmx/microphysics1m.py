@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -155,6 +155,28 @@ def vjp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, wrt=J
         raise TypeError("mp must be Microphysics1MParams")
     return Vjp1M(*_vjp("cmx_mp1m_vjp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, JACOBIAN_WRT_1M, _abi.CMX_MP1M_JAC_NOUT,
                        cotangents, wrt, with_tendencies, out, stream))
+
+
+ParamJvp1M = namedtuple("ParamJvp1M", ["jvp", "tendencies"])
+ParamVjp1M = namedtuple("ParamVjp1M", ["grad", "tendencies", "wrt"])
+
+
+def param_jvp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, directions, with_tendencies=False, *, out=None, stream=None) -> ParamJvp1M:
+    """The derivative of the 1-moment tendencies (Instantaneous mode) with respect to the scheme's PARAMETERS along `directions`, behind
+    `cmx_mp1m_param_jvp_*`: jvp[d, o] = Σ_p ∂`JACOBIAN_OUTPUTS_1M[o]`/∂θ_p·δθ_p⁽ᵈ⁾ per point.  `directions`: {ClimaParams name: weight} mappings
+    (`parameters.MICROPHYSICS_1M_DIRECTION_NAMES`) or (d_mp, d_thermo) pairs of `parameters.parameter_direction`.  Returns `ParamJvp1M(jvp, tendencies)`, `jvp` of
+    shape (len(directions), 4, *rho.shape); `tendencies` are bit-identical to `bulk_microphysics_tendencies_1m` unless a direction moves a size-relation
+    exponent of rain or snow (then the run-time-flags instantiation runs: agreement to the parity bound).  Arguments as for `cmx.warm_rain_param_jvp_2m`."""
+    return ParamJvp1M(*_param_jvp("cmx_mp1m_param_jvp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, _abi.CMX_MP1M_JAC_NOUT,
+                                  directions, with_tendencies, out, stream))
+
+
+def param_vjp_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, wrt, with_tendencies=False, *, out=None, stream=None) -> ParamVjp1M:
+    """The gradient of L = Σ_points Σ_o ḡ_o·out_o of the 1-moment tendencies with respect to the scheme's PARAMETERS, behind `cmx_mp1m_param_vjp_*`:
+    grad[k] = dL/d`wrt[k]`, a deterministic reduction over the points in float64.  `wrt`: ClimaParams names or directions.  Returns
+    `ParamVjp1M(grad, tendencies, wrt)`; arguments and rules as for `cmx.warm_rain_param_vjp_2m`."""
+    return ParamVjp1M(*_param_vjp("cmx_mp1m_param_vjp", mp, mp.flags, tps, (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno), _NAMES, _abi.CMX_MP1M_JAC_NOUT,
+                                  cotangents, wrt, with_tendencies, out, stream))
 
 
 Implicit1M = namedtuple("Implicit1M", ["implicit", "tendencies"])

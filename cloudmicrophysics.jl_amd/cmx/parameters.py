@@ -500,6 +500,7 @@ class WarmRainParams2M:
     def __init__(self, FT, is_limited: bool = True):
         td = _td(FT)
         self.fam = td.fam
+        self.td = td                       # the dictionary it was built from (cmx.autograd rebuilds the struct with `theta` overridden)
         self.is_limited = bool(is_limited)
         self.c = td.fam.warm_rain_2m()
         self.c.seifert_beheng = SB2006(td, is_limited)
@@ -663,6 +664,81 @@ def _particle_mass(fam, r0, m0, me, dm, chim):
     return fam.particle_mass(r0=r0, m0=m0, me=me, delta_m=dm, chi_m=chim, gamma_coeff=math.gamma(me + dm + 1))
 
 
+def _values_1m(g, gamma, log):
+    """{field path of cmx_microphysics_1m: value} from the parameter getter `g(name)`: the ONE statement of how the ClimaParams names become the fields
+    (Microphysics1M.jl params :127-139, 180-206, 263-289; TerminalVelocity.jl:39, 57-63, 121-126; Microphysics1MOptions.jl:296-395).  `Microphysics1MParams`
+    runs it on floats with math.gamma / math.log; `parameter_direction` runs the same expressions on values that carry a tangent."""
+    pi = math.pi
+    v = {}
+
+    def mass(prefix, r0, m0, me, dm, chim):
+        v.update({prefix + "r0": r0, prefix + "m0": m0, prefix + "me": me, prefix + "delta_m": dm, prefix + "chi_m": chim, prefix + "gamma_coeff": gamma(me + dm + 1)})
+    # Rain
+    r0, me, dm, chim = g("rain_drop_length_scale"), g("rain_mass_size_relation_coefficient_me"), g(
+        "rain_mass_size_relation_coefficient_delm"), g("rain_mass_size_relation_coefficient_chim")
+    ae, da, chia = g("rain_cross_section_size_relation_coefficient_ae"), g(
+        "rain_cross_section_size_relation_coefficient_dela"), g("rain_cross_section_size_relation_coefficient_chia")
+    ve, dv, chiv = g("rain_terminal_velocity_size_relation_coefficient_ve"), g(
+        "rain_terminal_velocity_size_relation_coefficient_delv"), g("rain_terminal_velocity_size_relation_coefficient_chiv")
+    v["rain.n0"] = g("rain_drop_size_distribution_coefficient_n0")
+    mass("rain.mass.", r0, g("density_liquid_water") * r0 ** me * pi * 4 / 3, me, dm, chim)
+    v.update({"rain.area.a0": pi * r0 ** ae, "rain.area.ae": ae, "rain.area.delta_a": da, "rain.area.chi_a": chia})
+    v.update({"rain.vent.a": g("rain_ventilation_coefficient_a"), "rain.vent.b": g("rain_ventilation_coefficient_b")})
+    # NB the reference reads r0 of Blk1MVelTypeRain from `snow_flake_length_scale` (TerminalVelocity.jl:39)
+    v.update({"vel_rain.r0": g("snow_flake_length_scale"), "vel_rain.ve": ve, "vel_rain.delta_v": dv, "vel_rain.chi_v": chiv,
+              "vel_rain.rho_w": g("density_liquid_water"), "vel_rain.C_drag": g("rain_drop_drag_coefficient"), "vel_rain.grav": g("gravitational_acceleration"),
+              "vel_rain.gamma_vent": gamma((ve + dv + 5) / 2), "vel_rain.gamma_term": gamma(me + ve + dm + dv + 1),
+              "vel_rain.gamma_accr": gamma(ae + ve + da + dv + 1), "vel_rain.gamma_accr_rain_sink": gamma(me + ae + ve + dm + da + dv + 1)})
+    # Snow
+    r0, me, dm, chim = g("snow_flake_length_scale"), g("snow_mass_size_relation_coefficient_me"), g(
+        "snow_mass_size_relation_coefficient_delm"), g("snow_mass_size_relation_coefficient_chim")
+    ae, da, chia = g("snow_cross_section_size_relation_coefficient"), g(
+        "snow_cross_section_size_relation_coefficient_dela"), g("snow_cross_section_size_relation_coefficient_chia")
+    ve, dv, chiv = g("snow_terminal_velocity_size_relation_coefficient"), g(
+        "snow_terminal_velocity_size_relation_coefficient_delv"), g("snow_terminal_velocity_size_relation_coefficient_chiv")
+    v["snow.mu"], v["snow.nu"] = g("snow_flake_size_distribution_coefficient_mu"), g("snow_flake_size_distribution_coefficient_nu")
+    mass("snow.mass.", r0, r0 ** me / 10, me, dm, chim)
+    v.update({"snow.area.a0": 0.3 * pi * r0 ** ae, "snow.area.ae": ae, "snow.area.delta_a": da, "snow.area.chi_a": chia})
+    v.update({"snow.vent.a": g("snow_ventilation_coefficient_a"), "snow.vent.b": g("snow_ventilation_coefficient_b")})
+    v["snow.phi"], v["snow.kappa"], v["snow.rho_i"] = g("snow_aspect_ratio"), g("snow_aspect_ratio_coefficient"), g("snow_apparent_density")
+    a_obl, a_pro = me + dm - 1.5 * (ae + da), 3 * (ae + da) - 2 * (me + dm)
+    v["snow.gamma_aspect_oblate"] = gamma(a_obl + 4) / math.gamma(4.0)
+    v["snow.gamma_aspect_prolate"] = gamma(a_pro + 4) / math.gamma(4.0)
+    v.update({"vel_snow.r0": r0, "vel_snow.ve": ve, "vel_snow.delta_v": dv, "vel_snow.chi_v": chiv, "vel_snow.v0": 2 ** (9 / 4) * r0 ** ve,
+              "vel_snow.gamma_vent": gamma((ve + dv + 5) / 2), "vel_snow.gamma_term": gamma(me + ve + dm + dv + 1), "vel_snow.gamma_accr": gamma(ae + ve + da + dv + 1)})
+    # Cloud liquid / ice
+    v.update({"cloud_liquid.rho_w": g("density_liquid_water"), "cloud_liquid.r_eff": g("liquid_cloud_effective_radius"),
+              "cloud_liquid.N_0": g("cloud_liquid_sedimentation_number_concentration")})
+    r0, me, dm, chim = g("cloud_ice_crystals_length_scale"), g("cloud_ice_mass_size_relation_coefficient_me"), g(
+        "cloud_ice_mass_size_relation_coefficient_delm"), g("cloud_ice_mass_size_relation_coefficient_chim")
+    v["cloud_ice.n0"] = g("cloud_ice_size_distribution_coefficient_n0")
+    mass("cloud_ice.mass.", r0, g("cloud_ice_apparent_density") * r0 ** me * pi * 4 / 3, me, dm, chim)
+    v["cloud_ice.rho_i"], v["cloud_ice.r_eff"] = g("cloud_ice_apparent_density"), g("ice_cloud_effective_radius")
+    v["cloud_ice.N_0"] = g("cloud_ice_sedimentation_number_concentration")
+    v.update({"air_properties.K_therm": g("thermal_conductivity_of_air"), "air_properties.D_vapor": g("diffusivity_of_water_vapor"),
+              "air_properties.nu_air": g("kinematic_viscosity_of_air")})
+    # process parameters (Microphysics1MOptions.jl:296-395); Frostenberg2023: TemperatureDependent cloud-ice formation (:314-318), log_a = log(a)
+    pp = "process_params."
+    v[pp + "cloud_liquid_formation_tau_relax"] = g("condensation_evaporation_timescale")
+    v[pp + "cloud_ice_formation_tau_relax"] = g("sublimation_deposition_timescale")
+    fa = g("Frostenberg2023_a_coefficient")
+    v.update({pp + "cloud_ice_formation_frostenberg.sigma": g("Frostenberg2023_standard_deviation"), pp + "cloud_ice_formation_frostenberg.a": fa,
+              pp + "cloud_ice_formation_frostenberg.b": g("Frostenberg2023_b_coefficient"),
+              pp + "cloud_ice_formation_frostenberg.T_freeze": g("temperature_water_freeze"), pp + "cloud_ice_formation_frostenberg.log_a": log(fa)})
+    k = g("threshold_smooth_transition_steepness")
+    v.update({pp + "rain_autoconversion.tau": g("rain_autoconversion_timescale"), pp + "rain_autoconversion.k": k,
+              pp + "rain_autoconversion.q_threshold": g("cloud_liquid_water_specific_humidity_autoconversion_threshold")})
+    v.update({pp + "rain_autoconversion_nd.tau": g("rain_autoconversion_timescale"), pp + "rain_autoconversion_nd.alpha": g("Variable_time_scale_autoconversion_coeff_alpha"),
+              pp + "rain_autoconversion_nd.Nc": g("prescribed_cloud_droplet_number_concentration")})
+    v.update({pp + "snow_autoconversion.tau": g("snow_autoconversion_timescale"), pp + "snow_autoconversion.k": k,
+              pp + "snow_autoconversion.q_threshold": g("cloud_ice_specific_humidity_autoconversion_threshold")})
+    v[pp + "r_ice_snow"] = g("ice_snow_threshold_radius")
+    v[pp + "e_lcl_rai"], v[pp + "e_lcl_sno"] = g("cloud_liquid_rain_collision_efficiency"), g("cloud_liquid_snow_collision_efficiency")
+    v[pp + "e_icl_rai"], v[pp + "e_icl_sno"] = g("cloud_ice_rain_collision_efficiency"), g("cloud_ice_snow_collision_efficiency")
+    v[pp + "e_rai_sno"], v[pp + "coeff_disp"] = g("rain_snow_collision_efficiency"), g("rain_snow_velocity_dispersion_coefficient")
+    return v
+
+
 class Microphysics1MParams:
     """CMP.Microphysics1MParams(FT; options…) — src/parameters/Microphysics1MParams.jl:63-103.
 
@@ -673,72 +749,11 @@ class Microphysics1MParams:
     def __init__(self, FT, **options):
         td = _td(FT)
         fam = self.fam = td.fam
+        self.td = td                       # the dictionary it was built from (parameter_direction and cmx.autograd rebuild from it)
         self.processes = Microphysics1MOptions(**options)
-        g = td.__getitem__
-        c = self.c = fam.microphysics_1m()
-        pi = math.pi
-        # Rain
-        r0, me, dm, chim = g("rain_drop_length_scale"), g("rain_mass_size_relation_coefficient_me"), g(
-            "rain_mass_size_relation_coefficient_delm"), g("rain_mass_size_relation_coefficient_chim")
-        ae, da, chia = g("rain_cross_section_size_relation_coefficient_ae"), g(
-            "rain_cross_section_size_relation_coefficient_dela"), g("rain_cross_section_size_relation_coefficient_chia")
-        ve, dv, chiv = g("rain_terminal_velocity_size_relation_coefficient_ve"), g(
-            "rain_terminal_velocity_size_relation_coefficient_delv"), g("rain_terminal_velocity_size_relation_coefficient_chiv")
-        c.rain.n0 = g("rain_drop_size_distribution_coefficient_n0")
-        c.rain.mass = _particle_mass(fam, r0, g("density_liquid_water") * r0 ** me * pi * 4 / 3, me, dm, chim)
-        c.rain.area = fam.particle_area(a0=pi * r0 ** ae, ae=ae, delta_a=da, chi_a=chia)
-        c.rain.vent = fam.ventilation(a=g("rain_ventilation_coefficient_a"), b=g("rain_ventilation_coefficient_b"))
-        # NB the reference reads r0 of Blk1MVelTypeRain from `snow_flake_length_scale` (TerminalVelocity.jl:39)
-        c.vel_rain = fam.blk1m_vel_rain(
-            r0=g("snow_flake_length_scale"), ve=ve, delta_v=dv, chi_v=chiv, rho_w=g("density_liquid_water"),
-            C_drag=g("rain_drop_drag_coefficient"), grav=g("gravitational_acceleration"),
-            gamma_vent=math.gamma((ve + dv + 5) / 2), gamma_term=math.gamma(me + ve + dm + dv + 1),
-            gamma_accr=math.gamma(ae + ve + da + dv + 1), gamma_accr_rain_sink=math.gamma(me + ae + ve + dm + da + dv + 1))
-        # Snow
-        r0, me, dm, chim = g("snow_flake_length_scale"), g("snow_mass_size_relation_coefficient_me"), g(
-            "snow_mass_size_relation_coefficient_delm"), g("snow_mass_size_relation_coefficient_chim")
-        ae, da, chia = g("snow_cross_section_size_relation_coefficient"), g(
-            "snow_cross_section_size_relation_coefficient_dela"), g("snow_cross_section_size_relation_coefficient_chia")
-        ve, dv, chiv = g("snow_terminal_velocity_size_relation_coefficient"), g(
-            "snow_terminal_velocity_size_relation_coefficient_delv"), g("snow_terminal_velocity_size_relation_coefficient_chiv")
-        c.snow.mu, c.snow.nu = g("snow_flake_size_distribution_coefficient_mu"), g("snow_flake_size_distribution_coefficient_nu")
-        c.snow.mass = _particle_mass(fam, r0, r0 ** me / 10, me, dm, chim)
-        c.snow.area = fam.particle_area(a0=0.3 * pi * r0 ** ae, ae=ae, delta_a=da, chi_a=chia)
-        c.snow.vent = fam.ventilation(a=g("snow_ventilation_coefficient_a"), b=g("snow_ventilation_coefficient_b"))
-        c.snow.phi, c.snow.kappa, c.snow.rho_i = g("snow_aspect_ratio"), g("snow_aspect_ratio_coefficient"), g("snow_apparent_density")
-        a_obl, a_pro = me + dm - 1.5 * (ae + da), 3 * (ae + da) - 2 * (me + dm)
-        c.snow.gamma_aspect_oblate = math.gamma(a_obl + 4) / math.gamma(4.0)
-        c.snow.gamma_aspect_prolate = math.gamma(a_pro + 4) / math.gamma(4.0)
-        c.vel_snow = fam.blk1m_vel_snow(
-            r0=r0, ve=ve, delta_v=dv, chi_v=chiv, v0=2 ** (9 / 4) * r0 ** ve, gamma_vent=math.gamma((ve + dv + 5) / 2),
-            gamma_term=math.gamma(me + ve + dm + dv + 1), gamma_accr=math.gamma(ae + ve + da + dv + 1))
-        # Cloud liquid / ice
-        c.cloud_liquid = fam.cloud_liquid(rho_w=g("density_liquid_water"), r_eff=g("liquid_cloud_effective_radius"),
-                                          N_0=g("cloud_liquid_sedimentation_number_concentration"))
-        r0, me, dm, chim = g("cloud_ice_crystals_length_scale"), g("cloud_ice_mass_size_relation_coefficient_me"), g(
-            "cloud_ice_mass_size_relation_coefficient_delm"), g("cloud_ice_mass_size_relation_coefficient_chim")
-        c.cloud_ice.n0 = g("cloud_ice_size_distribution_coefficient_n0")
-        c.cloud_ice.mass = _particle_mass(fam, r0, g("cloud_ice_apparent_density") * r0 ** me * pi * 4 / 3, me, dm, chim)
-        c.cloud_ice.rho_i, c.cloud_ice.r_eff = g("cloud_ice_apparent_density"), g("ice_cloud_effective_radius")
-        c.cloud_ice.N_0 = g("cloud_ice_sedimentation_number_concentration")
-        c.air_properties = AirProperties(td)
-        # process parameters (Microphysics1MOptions.jl:296-395)
-        pp = c.process_params
-        pp.cloud_liquid_formation_tau_relax = g("condensation_evaporation_timescale")
-        pp.cloud_ice_formation_tau_relax = g("sublimation_deposition_timescale")
-        pp.cloud_ice_formation_frostenberg = Frostenberg2023(td)     # TemperatureDependent (Microphysics1MOptions.jl:314-318)
-        k = g("threshold_smooth_transition_steepness")
-        pp.rain_autoconversion = fam.acnv_1m(tau=g("rain_autoconversion_timescale"), k=k, q_threshold=g(
-            "cloud_liquid_water_specific_humidity_autoconversion_threshold"))
-        pp.rain_autoconversion_nd = fam.var_timescale_acnv(
-            tau=g("rain_autoconversion_timescale"), alpha=g("Variable_time_scale_autoconversion_coeff_alpha"),
-            Nc=g("prescribed_cloud_droplet_number_concentration"))
-        pp.snow_autoconversion = fam.acnv_1m(tau=g("snow_autoconversion_timescale"), k=k, q_threshold=g(
-            "cloud_ice_specific_humidity_autoconversion_threshold"))
-        pp.r_ice_snow = g("ice_snow_threshold_radius")
-        pp.e_lcl_rai, pp.e_lcl_sno = g("cloud_liquid_rain_collision_efficiency"), g("cloud_liquid_snow_collision_efficiency")
-        pp.e_icl_rai, pp.e_icl_sno = g("cloud_ice_rain_collision_efficiency"), g("cloud_ice_snow_collision_efficiency")
-        pp.e_rai_sno, pp.coeff_disp = g("rain_snow_collision_efficiency"), g("rain_snow_velocity_dispersion_coefficient")
+        self.c = fam.microphysics_1m()
+        for path, value in _values_1m(td.__getitem__, math.gamma, math.log).items():
+            _add_field(self.c, path, value)
 
     @property
     def flags(self):
@@ -971,3 +986,214 @@ def rain_vel_params(FT):
     v.sb2006 = SB2006VelType(td)
     v.chen2022 = Chen2022VelTypeRain(td)
     return v
+
+
+# ---------------------------------------------------------------------------
+# directions in parameter space (include/cmx.h §22): δθ by ClimaParams NAME
+# ---------------------------------------------------------------------------
+def _digamma(x):
+    """ψ(x) for x > 0: the recurrence up to x ≥ 8, then the asymptotic series (error < 1e-15 there)."""
+    if not x > 0:
+        raise ValueError("digamma: positive argument expected")
+    s = 0.0
+    while x < 8.0:
+        s -= 1.0 / x
+        x += 1.0
+    f = 1.0 / (x * x)
+    return s + math.log(x) - 0.5 / x - f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))))
+
+
+def _pdf_c_dz(c, k, wrt_nu):
+    """∂ loggamma_z{k} / ∂ν (wrt_nu) or ∂μ of the cloud PDF: z_k = (ν + k)/μ."""
+    p = c.seifert_beheng.pdf_c
+    z = (p.nu_c + k) / p.mu_c
+    return _digamma(z) * (1.0 / p.mu_c if wrt_nu else -z / p.mu_c)
+
+
+def _evap_beta(c, field):
+    """∂(field)/∂β of the derived evaporation fields (EvaporationSB2006)."""
+    e = c.seifert_beheng.evap
+    half_ln6 = 0.5 * math.log(6.0)
+    if field == "b_vent_1":
+        return e.b_vent_1 * (1.5 * _digamma(2.5 + 1.5 * e.beta) - half_ln6)
+    return -half_ln6 * e.b_vent_0_coeff
+
+
+_SB = "seifert_beheng."
+# name → ((struct, field path, ∂field/∂name as a number or a function of the warm-rain struct), …); struct: "wr" = cmx_warm_rain_2m, "tps" = cmx_thermo.
+# One name may feed several fields; the derived fields follow the constructors above (CloudParticlePDF_SB2006, EvaporationSB2006).
+WARM_RAIN_2M_DIRECTION_FIELDS = {
+    "SB2006_cloud_gamma_distribution_coeff_nu": (("wr", _SB + "pdf_c.nu_c", 1.0), ("wr", _SB + "pdf_c.loggamma_z1", lambda c: _pdf_c_dz(c, 1, True)),
+                                                 ("wr", _SB + "pdf_c.loggamma_z2", lambda c: _pdf_c_dz(c, 2, True))),
+    "SB2006_cloud_gamma_distribution_coeff_mu": (("wr", _SB + "pdf_c.mu_c", 1.0), ("wr", _SB + "pdf_c.loggamma_z1", lambda c: _pdf_c_dz(c, 1, False)),
+                                                 ("wr", _SB + "pdf_c.loggamma_z2", lambda c: _pdf_c_dz(c, 2, False))),
+    "SB2006_cloud_droplets_min_mass": (("wr", _SB + "pdf_c.xc_min", 1.0),),
+    "SB2006_raindrops_min_mass": (("wr", _SB + "pdf_r.xr_min", 1.0), ("wr", _SB + "pdf_c.xc_max", 1.0), ("wr", _SB + "acnv.x_star", 1.0)),
+    "SB2006_raindrops_max_mass": (("wr", _SB + "pdf_r.xr_max", 1.0),),
+    "SB2006_rain_distribution_coeff_nu": (("wr", _SB + "pdf_r.nu_r", 1.0),),
+    "SB2006_rain_distribution_coeff_mu": (("wr", _SB + "pdf_r.mu_r", 1.0),),
+    "SB2006_raindrops_size_distribution_coeff_N0_min": (("wr", _SB + "pdf_r.N0_min", 1.0),),
+    "SB2006_raindrops_size_distribution_coeff_N0_max": (("wr", _SB + "pdf_r.N0_max", 1.0),),
+    "SB2006_raindrops_size_distribution_coeff_lambda_min": (("wr", _SB + "pdf_r.lambda_min", 1.0),),
+    "SB2006_raindrops_size_distribution_coeff_lambda_max": (("wr", _SB + "pdf_r.lambda_max", 1.0),),
+    "SB2006_reference_air_density": (("wr", _SB + "pdf_r.rho_0", 1.0), ("wr", _SB + "acnv.rho_0", 1.0), ("wr", _SB + "accr.rho_0", 1.0),
+                                     ("wr", _SB + "evap.rho_0", 1.0)),
+    "density_liquid_water": (("wr", _SB + "pdf_c.rho_w", 1.0), ("wr", _SB + "pdf_r.rho_w", 1.0)),
+    "SB2006_collection_kernel_coeff_kcc": (("wr", _SB + "acnv.kcc", 1.0),),
+    "SB2006_autoconversion_correcting_function_coeff_A": (("wr", _SB + "acnv.A", 1.0),),
+    "SB2006_autoconversion_correcting_function_coeff_a": (("wr", _SB + "acnv.a", 1.0),),
+    "SB2006_autoconversion_correcting_function_coeff_b": (("wr", _SB + "acnv.b", 1.0),),
+    "SB2006_collection_kernel_coeff_kcr": (("wr", _SB + "accr.kcr", 1.0),),
+    "SB2006_accretion_correcting_function_coeff_tau0": (("wr", _SB + "accr.tau_0", 1.0),),
+    "SB2006_accretion_correcting_function_coeff_c": (("wr", _SB + "accr.c", 1.0),),
+    "SB2006_collection_kernel_coeff_krr": (("wr", _SB + "self.krr", 1.0),),
+    "SB2006_collection_kernel_coeff_kapparr": (("wr", _SB + "self.kappa_rr", 1.0),),
+    "SB2006_raindrops_self-collection_coeff_d": (("wr", _SB + "self.d", 1.0),),
+    "SB2006_raindrops_equilibrium_mean_diameter": (("wr", _SB + "brek.Deq", 1.0),),
+    "SB2006_raindrops_breakup_mean_diameter_threshold": (("wr", _SB + "brek.Dr_th", 1.0),),
+    "SB2006_raindrops_breakup_coeff_kbr": (("wr", _SB + "brek.kbr", 1.0),),
+    "SB2006_raindrops_breakup_coeff_kappabr": (("wr", _SB + "brek.kappa_br", 1.0),),
+    "SB2006_ventilation_factor_coeff_av": (("wr", _SB + "evap.av", 1.0), ("wr", _SB + "evap.a_vent_1", 6.0 ** (-1.0 / 3.0)),
+                                           ("wr", _SB + "evap.a_vent_0_coeff", 36.0 ** (1.0 / 3.0))),
+    "SB2006_ventilation_factor_coeff_bv": (("wr", _SB + "evap.bv", 1.0), ("wr", _SB + "evap.b_vent_1", lambda c: c.seifert_beheng.evap.b_vent_1 / c.seifert_beheng.evap.bv),
+                                           ("wr", _SB + "evap.b_vent_0_coeff", lambda c: c.seifert_beheng.evap.b_vent_0_coeff / c.seifert_beheng.evap.bv)),
+    "SB2006_rain_evaporation_coeff_alpha": (("wr", _SB + "evap.alpha", 1.0),),
+    "SB2006_rain_evaporation_coeff_beta": (("wr", _SB + "evap.beta", 1.0), ("wr", _SB + "evap.b_vent_1", lambda c: _evap_beta(c, "b_vent_1")),
+                                           ("wr", _SB + "evap.b_vent_0_coeff", lambda c: _evap_beta(c, "b_vent_0_coeff")), ("wr", _SB + "evap.beta_vent_0", 1.5)),
+    "Horn2012_number_concentration_adjustment_timescale": (("wr", _SB + "numadj.tau", 1.0),),
+    "thermal_conductivity_of_air": (("wr", "air_properties.K_therm", 1.0),),
+    "diffusivity_of_water_vapor": (("wr", "air_properties.D_vapor", 1.0),),
+    "kinematic_viscosity_of_air": (("wr", "air_properties.nu_air", 1.0),),
+    "condensation_evaporation_timescale": (("wr", "condevap_tau_relax", 1.0),),
+    "sublimation_deposition_timescale": (("wr", "subdep_tau_relax", 1.0),),
+    "gas_constant_vapor": (("tps", "R_v", 1.0),), "gas_constant_dry_air": (("tps", "R_d", 1.0),),
+    "isobaric_specific_heat_dry_air": (("tps", "cp_d", 1.0),), "isobaric_specific_heat_vapor": (("tps", "cp_v", 1.0),),
+    "isobaric_specific_heat_liquid": (("tps", "cp_l", 1.0),), "isobaric_specific_heat_ice": (("tps", "cp_i", 1.0),),
+    "latent_heat_vaporization_at_reference": (("tps", "LH_v0", 1.0),), "latent_heat_sublimation_at_reference": (("tps", "LH_s0", 1.0),),
+    "thermodynamics_temperature_reference": (("tps", "T_0", 1.0),), "temperature_triple_point": (("tps", "T_triple", 1.0),),
+    "pressure_triple_point": (("tps", "press_triple", 1.0),), "temperature_water_freeze": (("tps", "T_freeze", 1.0),),
+    "isochoric_specific_heat_liquid": (("tps", "cv_l", 1.0),),
+}
+
+
+def _add_field(struct, path, value):
+    *head, leaf = path.split(".")
+    for name in head:
+        struct = getattr(struct, name)
+    setattr(struct, leaf, getattr(struct, leaf) + value)
+
+
+class _Tangent:
+    """A value and one tangent: the number type `_values_1m` runs on for `parameter_direction` (exact forward mode through +, −, ·, /, ** with positive
+    bases, Γ and log)."""
+    __slots__ = ("v", "d")
+
+    def __init__(self, v, d=0.0):
+        self.v, self.d = float(v), float(d)
+
+    @staticmethod
+    def lift(x):
+        return x if isinstance(x, _Tangent) else _Tangent(x)
+
+    def __neg__(self):
+        return _Tangent(-self.v, -self.d)
+
+    def __add__(self, o):
+        o = _Tangent.lift(o)
+        return _Tangent(self.v + o.v, self.d + o.d)
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = _Tangent.lift(o)
+        return _Tangent(self.v - o.v, self.d - o.d)
+
+    def __rsub__(self, o):
+        return _Tangent.lift(o) - self
+
+    def __mul__(self, o):
+        o = _Tangent.lift(o)
+        return _Tangent(self.v * o.v, self.d * o.v + self.v * o.d)
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = _Tangent.lift(o)
+        q = self.v / o.v
+        return _Tangent(q, (self.d - q * o.d) / o.v)
+
+    def __rtruediv__(self, o):
+        return _Tangent.lift(o) / self
+
+    def __pow__(self, o):
+        o = _Tangent.lift(o)
+        p = self.v ** o.v
+        return _Tangent(p, p * ((o.d * math.log(self.v) if o.d else 0.0) + o.v * self.d / self.v))
+
+    def __rpow__(self, o):
+        return _Tangent.lift(o) ** self
+
+
+def _tangent_gamma(x):
+    g = math.gamma(x.v)
+    return _Tangent(g, g * _digamma(x.v) * x.d)
+
+
+def _tangent_log(x):
+    return _Tangent(math.log(x.v), x.d / x.v)
+
+
+def _names_1m():
+    names = []
+    _values_1m(lambda n: names.append(n) or DEFAULT_PARAMETERS[n], math.gamma, math.log)
+    return tuple(dict.fromkeys(names))
+
+
+# the ClimaParams names that reach cmx_microphysics_1m (through `_values_1m`) or the thermodynamics struct: what `parameter_direction` accepts for the 1-moment scheme
+MICROPHYSICS_1M_DIRECTION_NAMES = _names_1m() + tuple(k for k, f in WARM_RAIN_2M_DIRECTION_FIELDS.items() if f[0][0] == "tps" and k not in _names_1m())
+
+
+def microphysics_1m_direction_fields(params, name):
+    """{field path of cmx_microphysics_1m: ∂field/∂name at `params`}, the non-zero ones: the name → fields table of the 1-moment scheme, row `name`."""
+    v = _values_1m(lambda n: _Tangent(params.td[n], 1.0 if n == name else 0.0), _tangent_gamma, _tangent_log)
+    return {path: x.d for path, x in v.items() if isinstance(x, _Tangent) and x.d != 0.0}
+
+
+def _direction_1m(params, weights):
+    for name in weights:
+        if name not in MICROPHYSICS_1M_DIRECTION_NAMES:
+            raise ValueError(f"parameter_direction: '{name}' feeds no floating field of the 1-moment or thermodynamics parameters")
+    d_mp, d_tps = params.fam.microphysics_1m(), params.fam.thermo()
+    v = _values_1m(lambda n: _Tangent(params.td[n], float(weights.get(n, 0.0))), _tangent_gamma, _tangent_log)
+    for path, x in v.items():
+        if isinstance(x, _Tangent) and x.d != 0.0:
+            _add_field(d_mp, path, x.d)
+    for name, weight in weights.items():
+        for which, path, dfield in WARM_RAIN_2M_DIRECTION_FIELDS.get(name, ()):
+            if which == "tps":
+                _add_field(d_tps, path, float(weight) * dfield)
+    return d_mp, d_tps
+
+
+def parameter_direction(params, weights: Mapping):
+    """A direction δθ in parameter space for the parameter-derivative entries (`cmx.bulk_tendencies.warm_rain_param_jvp_2m` / `warm_rain_param_vjp_2m`,
+    `cmx.microphysics1m.param_jvp_1m` / `param_vjp_1m`; include/cmx.h §22, §23): `weights` maps ClimaParams NAMES to δ(name), and the result is the pair
+    (d_params, d_thermo) of structs of the entry's own parameter types whose fields hold Σ_name ∂field/∂name · δ(name) — the exact derivative of the struct
+    constructors at `params`.  One name may feed several fields (`SB2006_raindrops_min_mass`: pdf_r.xr_min, pdf_c.xc_max, acnv.x_star) and derived ones (the
+    cloud-PDF shape coefficients → loggamma_z1/2, the ventilation coefficients and β → the folded ventilation pair; a 1-moment size-relation exponent → m0,
+    a0 and the Γ fields).
+
+    `params`: `WarmRainParams2M` or `Microphysics2MParams` (its warm-rain part; the explicit table `WARM_RAIN_2M_DIRECTION_FIELDS`), or
+    `Microphysics1MParams` (the constructor's own expressions `_values_1m` run in forward mode; `microphysics_1m_direction_fields` gives a row of that table,
+    `MICROPHYSICS_1M_DIRECTION_NAMES` the names).  A name that reaches no floating field of these structs, or an unknown name, raises ValueError."""
+    if isinstance(params, Microphysics1MParams):
+        return _direction_1m(params, weights)
+    wr = getattr(params, "warm_rain", params)
+    if not isinstance(wr, WarmRainParams2M):
+        raise TypeError("parameter_direction: WarmRainParams2M, Microphysics2MParams or Microphysics1MParams expected")
+    d = {"wr": wr.fam.warm_rain_2m(), "tps": wr.fam.thermo()}
+    for name, weight in weights.items():
+        fields = WARM_RAIN_2M_DIRECTION_FIELDS.get(name)
+        if fields is None:
+            raise ValueError(f"parameter_direction: '{name}' feeds no floating field of the warm-rain or thermodynamics parameters")
+        for which, path, dfield in fields:
+            _add_field(d[which], path, float(weight) * (dfield(wr.c) if callable(dfield) else dfield))
+    return d["wr"], d["tps"]

@@ -234,7 +234,21 @@ template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> flat_where(
     return r;
 }
 // the phase boundary of the constants (cmx_math.hpp consts_after) waits for the VALUE
+template <typename CT> struct holds_duals : std::false_type {};
+template <template <typename> class CT, typename FT, int K> struct holds_duals<CT<Dual<FT, K>>> : std::true_type {};
 template <typename C, typename FT, int K> __device__ __forceinline__ const C &consts_after(const C &c, const Dual<FT, K> &dep) { return consts_after(c, dep.v); }
 #undef CMX_DUAL_FOR
+
+// The constants a scheme's eval hands to its point function: front_consts (cmx_math.hpp) — unless the constants struct holds duals itself, as for the
+// parameter derivatives (cmx_jacobian.hpp param_jvp_point).  Those stay the plain reference to the kernel argument in both float types: a class in the
+// constant address space binds to no reference parameter of the operators above (tried: 30 errors in sb2006_point).  Tried as well, and measured (one MI355X,
+// 1e7 points, ms per direction of the SB2006 parameter gradient at one direction per launch): the kernel-argument pointer cast to a plain one behind the empty
+// asm of consts_after, per phase — the loads stay scalar and the Float64 kernel parks 190–196 instead of 292–340 SGPRs: Float64 0.58 → 0.50, Float32 0.18 → 0.22.
+// Not kept: slower in Float32, and in Float64 two directions per launch gain more (0.35) without casting a plain pointer back into the constant address space.
+template <typename FT, bool ALSO = false, typename CT> __device__ __forceinline__ decltype(auto) scheme_consts(const CT &c) {
+    if constexpr (holds_duals<CT>::value) return (c);
+    else return front_consts<FT, ALSO>(c);
+}
+
 
 }  // namespace cmx

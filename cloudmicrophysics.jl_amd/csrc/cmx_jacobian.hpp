@@ -11,6 +11,7 @@
 #pragma once
 #include <cstdint>
 #include <limits>
+#include <type_traits>
 
 #include "../../include/cmx.h"
 #include "cmx_dual.hpp"
@@ -679,6 +680,117 @@ __device__ __forceinline__ void implicit_average_point(const C &c, const Implici
         if (a.avg[q]) a.avg[q][i] = (x[S0 + q] - s0[q]) * a.inv_dt;
 }
 
+// ---- ∂/∂θ: the derivatives with respect to the scheme's PARAMETERS (include/cmx.h §(22)) ------------------------------------------------------------------------
+// The roles are exchanged: the state enters as constants — Dual(x), every tangent a structural zero that costs nothing — and the CONSTANTS are the duals: the
+// scheme's constants struct on Dual<FT, KP>, whose tangent slot k holds ċ = Dc(θ)[δθ⁽ᵏ⁾] of direction k, formed on the host in exact forward mode
+// (cmx_param_tangent.hpp).  The point function is the one every other entry runs; all constant tangents are run-time values, so nothing about them folds.
+//   * KP directions per evaluation, a tuning number per float type (-DCMX_PARAM_K_F32=…, -DCMX_PARAM_K_F64=…): 4 / 2.  A launch costs about the same whatever
+//     share of its slots is in use (measured, one MI355X, 1e7 points, ms per launch of the SB2006 gradient kernel — Float32 KP = 1, 2, 4: 0.18, 0.36, 0.36;
+//     Float64 KP = 1, 2: 0.58, 0.73), so a call takes wide launches while at least kParamWideMin directions remain (3 / 2: where the wide launch is cheaper than
+//     single ones) and single-direction launches for the rest.  (Timed on the SB2006 gradient kernel only; the jvp kernels and the 1-moment scheme take the same numbers.)  Each tangent slot is computed by the same operations whatever KP is and whatever the other slots
+//     hold, so a column's bits do not depend on KP, on the other directions of the call or on how the call was split.  Registers: HISTORY.md.
+//   * The value parts are the plain instantiation's bit for bit, like every dual evaluation (cmx_dual.hpp).
+//   * The NaN rule is the scheme's: every stored value goes through out(·, poison(x)).
+#ifndef CMX_PARAM_K_F32
+#define CMX_PARAM_K_F32 4
+#endif
+#ifndef CMX_PARAM_K_F64
+#define CMX_PARAM_K_F64 2
+#endif
+template <typename FT> constexpr int kParamK = sizeof(FT) == 4 ? CMX_PARAM_K_F32 : CMX_PARAM_K_F64;
+template <typename FT> constexpr int kParamWideMin = sizeof(FT) == 4 ? 3 : 2;
+// The launches of a call: f(std::integral_constant<int, KP>{}, d0) for the directions d0 … d0 + KP − 1, wide (kParamK) while at least kParamWideMin remain,
+// then one direction at a time.
+template <typename FT, typename F> inline void for_each_param_launch(int ndir, F &&f) {
+    for (int d0 = 0; d0 < ndir;) {
+        if (kParamK<FT> > 1 && ndir - d0 >= kParamWideMin<FT>) {
+            f(std::integral_constant<int, kParamK<FT>>{}, d0);
+            d0 += kParamK<FT>;
+        } else {
+            f(std::integral_constant<int, 1>{}, d0);
+            d0 += 1;
+        }
+    }
+}
+
+// `jvp[k][q]`: the column of Σ_p ∂out_q/∂θ_p·δθ_p of the direction in tangent slot k (NULL: not wanted, or an idle slot).  `tend`: the optional primal columns.
+template <typename FT, int KP, int NOUT, int NWRT> struct ParamJvpArgs {
+    const FT *in[NWRT + 1];           // rho, then the other inputs
+    FT *tend[NOUT];
+    FT *jvp[KP][NOUT];
+};
+
+// the scheme on the dual constants `cd` at the point x
+template <typename S, typename FT, int KP, typename CD>
+__device__ __forceinline__ void param_eval(const CD &cd, const FT (&x)[S::NWRT + 1], Dual<FT, KP> (&o)[S::NOUT]) {
+    Dual<FT, KP> in[S::NWRT];
+#pragma unroll
+    for (int j = 0; j < S::NWRT; ++j) in[j] = Dual<FT, KP>(x[j + 1]);
+    S::template eval<FT, KP>(cd, x[0], in, o);
+}
+
+template <typename S, typename FT, int KP, typename CD>
+__device__ __forceinline__ void param_jvp_point(const CD &cd, const ParamJvpArgs<FT, KP, S::NOUT, S::NWRT> &a, const FT (&x)[S::NWRT + 1], int64_t i) {
+    const auto poison = S::poison(x);
+    Dual<FT, KP> o[S::NOUT];
+    param_eval<S, FT, KP>(cd, x, o);
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q)
+        if (a.tend[q]) a.tend[q][i] = S::out(o[q].v, poison);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+#pragma unroll
+        for (int q = 0; q < S::NOUT; ++q) {
+            FT *const col = a.jvp[k][q];
+            if (col) col[i] = S::out(o[q].d[k], poison);
+        }
+    }
+}
+
+// The gradient is a REDUCTION over the points: grad[d] = Σ_i Σ_q ḡ_q,i·(∂out_q/∂θ·δθ⁽ᵈ⁾)_i.  Per point the Σ_q is vjp_point's chain of fma over the non-NULL
+// cotangents (seeded with −0; no cotangent at all: +0), read after eval; it goes through out(·, poison), is widened to double and added to the lane's
+// accumulator of the slot.  A NaN in the state or in a cotangent of a point makes the sum NaN (IEEE) and that point's tendencies NaN.
+template <typename FT, int NOUT, int NWRT> struct ParamVjpArgs {
+    const FT *in[NWRT + 1];
+    const FT *cot[NOUT];
+    FT *tend[NOUT];
+    int32_t ncot;                     // the non-NULL members of cot
+};
+
+template <typename S, typename FT, int KP, typename CD>
+__device__ __forceinline__ void param_vjp_point(const CD &cd, const ParamVjpArgs<FT, S::NOUT, S::NWRT> &a, const FT (&x)[S::NWRT + 1], int64_t i, double (&acc)[KP]) {
+    const auto poison = S::poison(x);
+    Dual<FT, KP> o[S::NOUT];
+    param_eval<S, FT, KP>(cd, x, o);
+    FT g[S::NOUT];
+    int gnan = 0;
+    const int64_t ic = products_detail::after(i, o[S::NOUT - 1].v);
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q) {
+        g[q] = a.cot[q] ? products_detail::ld(a.cot[q], ic) : FT(0);
+        gnan |= (int)(g[q] != g[q]);      // bitwise on purpose: no branch
+    }
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q)
+        if (a.tend[q]) a.tend[q][i] = gnan ? Math<FT>::nan() : S::out(o[q].v, poison);
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        FT s = a.ncot ? -FT(0) : FT(0);
+#pragma unroll
+        for (int q = 0; q < S::NOUT; ++q)
+            if (a.cot[q]) s = Math<FT>::fma(g[q], o[q].d[k], s);
+        acc[k] += (double)S::out(s, poison);
+    }
+}
+
+// The decomposition of the reduction, a function of n alone (not of the device): CMX_PARAM_VJP_PARTIALS workgroups of `bs` lanes, workgroup b owns the
+// contiguous chunk [b·chunk, (b + 1)·chunk), chunk = n split that many ways and rounded up to a multiple of bs; lane t of it takes the points
+// b·chunk + t, + bs, … in index order.
+inline int64_t param_vjp_chunk(int64_t n, int64_t bs) {
+    const int64_t c = (n + CMX_PARAM_VJP_PARTIALS - 1) / CMX_PARAM_VJP_PARTIALS;
+    return (c + bs - 1) / bs * bs;
+}
+
 #if !defined(CMX_HOST_BUILD)
 // The kernels: one point per lane.  `c`, the scheme's constants struct, stays the FIRST kernel argument: front_consts reads it at offset 0 of the kernel-argument segment.
 template <typename S, typename FT, int K, int BS, typename C>
@@ -746,6 +858,74 @@ __global__ __launch_bounds__(BS) void implicit_average_kernel(const C c, const I
     Math<FT>::prepare();
     if (i >= n) return;
     implicit_average_point<S, FT, K>(c, a, x, i);
+}
+
+// ∂/∂θ·δθ: the constants struct `c` holds duals — still the first kernel argument, no copy and no allocation on the device
+template <typename S, typename FT, int KP, int BS, typename CD>
+__global__ __launch_bounds__(BS) void param_jvp_kernel(const CD c, const ParamJvpArgs<FT, KP, S::NOUT, S::NWRT> a, const int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x;
+    FT x[S::NWRT + 1];
+    if (i < n) {
+#pragma unroll
+        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
+    }
+    Math<FT>::prepare();
+    if (i >= n) return;
+    param_jvp_point<S, FT, KP>(c, a, x, i);
+}
+
+// Stage 1 of the gradient (param_vjp_chunk has the decomposition): the lane's accumulators, then the 64 lanes of a wave in a fixed shuffle tree, then the waves
+// left to right → ws[k·CMX_PARAM_VJP_PARTIALS + b].  No floating-point atomics: the result is a pure function of the inputs and n, bit-identical from run to run.
+template <typename S, typename FT, int KP, int BS, typename CD>
+__global__ __launch_bounds__(BS) void param_vjp_kernel(const CD c, const ParamVjpArgs<FT, S::NOUT, S::NWRT> a, const int64_t n, const int64_t chunk,
+                                                       const int32_t nlive, double *__restrict__ ws) {
+    static_assert(BS % 64 == 0 && KP <= BS, "whole waves");
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    Math<FT>::prepare();
+    double acc[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (int64_t i = lo + threadIdx.x; i < hi; i += BS) {
+        FT x[S::NWRT + 1];
+#pragma unroll
+        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
+        param_vjp_point<S, FT, KP>(c, a, x, i, acc);
+    }
+    __shared__ double part[KP][BS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        double t = acc[k];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+        if (lane == 0) part[k][wave] = t;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nlive) {      // nlive ≤ KP: the slots of the launch that hold a direction; the workspace has no room for the idle ones
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < BS / 64; ++w) t += part[threadIdx.x][w];
+        ws[(int64_t)threadIdx.x * CMX_PARAM_VJP_PARTIALS + blockIdx.x] = t;
+    }
+}
+
+// Stage 2: one workgroup per direction; lane t adds the partials 4t … 4t + 3 left to right, then the same tree → grad[d].
+template <int BS> __global__ __launch_bounds__(BS) void param_vjp_finish_kernel(const double *__restrict__ ws, double *__restrict__ grad) {
+    static_assert(CMX_PARAM_VJP_PARTIALS == 4 * BS && BS % 64 == 0, "stage 2 gives each lane four partials");
+    const double *p = ws + (int64_t)blockIdx.x * CMX_PARAM_VJP_PARTIALS + 4 * threadIdx.x;
+    double t = ((p[0] + p[1]) + p[2]) + p[3];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    __shared__ double part[BS / 64];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < BS / 64; ++w) s += part[w];
+        grad[blockIdx.x] = s;
+    }
 }
 #endif
 

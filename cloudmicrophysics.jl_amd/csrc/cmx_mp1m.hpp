@@ -79,117 +79,126 @@ template <typename CT> inline auto flags_1m(uint32_t flags, const CT &c) {
     return one_of<kDefaultFlags, kRuntimeFlags>(flags == CMX_1M_DEFAULT_OPTIONS && mp1m_default_exponents(c) ? kDefaultFlags : kRuntimeFlags);
 }
 
-template <typename FT, typename MP, typename TH>
-static Mp1mConsts<FT> make_mp1m_consts(const MP &mp, const TH &tp, uint32_t flags, double eps) {
-    Mp1mConsts<FT> c{};
+// The fold, generic in how a parameter is read and in the scalar the result holds (as make_sb_consts_from, cmx_sb2006.hpp): P(field) / Q(field) read a field of
+// `mp` / `tp` as the working scalar W — double for the plain fold (make_mp1m_consts below: R = FT, the double arithmetic it always was), a value with a tangent for
+// the parameter derivatives (cmx_param_tangent.hpp: R = W = ParamTan; the value parts are the plain fold's in every bit).
+template <typename FT, typename R, typename MP, typename TH, typename PW, typename PT>
+static Mp1mConsts<R> make_mp1m_consts_from(const MP &mp, const TH &tp, uint32_t flags, double eps, const PW &P, const PT &Q) {
+    using std::cbrt; using std::exp; using std::expm1; using std::fmax; using std::log2; using std::pow; using std::sqrt;
+    using W = decltype(P(mp.rain.n0));
+    Mp1mConsts<R> c{};
     const double l2e = 1.4426950408889634074, ln2 = 0.69314718055994530942, pi = 3.14159265358979323846;
     c.flags = flags;
-    const double Rv = tp.R_v, T0 = tp.T_0;
-    const double dcp_l = (double)tp.cp_v - (double)tp.cp_l, dcp_i = (double)tp.cp_v - (double)tp.cp_i;
-    c.T_0 = (FT)T0; c.T_freeze = (FT)tp.T_freeze; c.LH_v0 = (FT)tp.LH_v0; c.LH_s0 = (FT)tp.LH_s0;
-    c.LH_f0 = (FT)((double)tp.LH_s0 - (double)tp.LH_v0);
-    c.dcp_l = (FT)dcp_l; c.dcp_i = (FT)dcp_i; c.dcp_f = (FT)((double)tp.cp_l - (double)tp.cp_i);
-    c.R_v = (FT)Rv; c.inv_R_v = (FT)(1.0 / Rv); c.cv_l = (FT)tp.cv_l;
-    c.ps_c0 = (FT)std::log2((double)tp.press_triple);
-    c.psl_a = (FT)(dcp_l / Rv); c.psl_b = (FT)(((double)tp.LH_v0 - dcp_l * T0) / Rv * l2e);
-    c.psi_a = (FT)(dcp_i / Rv); c.psi_b = (FT)(((double)tp.LH_s0 - dcp_i * T0) / Rv * l2e);
-    c.inv_T_tr = (FT)(1.0 / (double)tp.T_triple);
-    c.cp_d = (FT)tp.cp_d; c.cpm_qt = (FT)((double)tp.cp_v - (double)tp.cp_d);
-    c.cpm_ql = (FT)((double)tp.cp_l - (double)tp.cp_v); c.cpm_qi = (FT)((double)tp.cp_i - (double)tp.cp_v);
+    const W Rv = Q(tp.R_v), T0 = Q(tp.T_0);
+    const W dcp_l = Q(tp.cp_v) - Q(tp.cp_l), dcp_i = Q(tp.cp_v) - Q(tp.cp_i);
+    c.T_0 = (R)T0; c.T_freeze = (R)Q(tp.T_freeze); c.LH_v0 = (R)Q(tp.LH_v0); c.LH_s0 = (R)Q(tp.LH_s0);
+    c.LH_f0 = (R)(Q(tp.LH_s0) - Q(tp.LH_v0));
+    c.dcp_l = (R)dcp_l; c.dcp_i = (R)dcp_i; c.dcp_f = (R)(Q(tp.cp_l) - Q(tp.cp_i));
+    c.R_v = (R)Rv; c.inv_R_v = (R)(1.0 / Rv); c.cv_l = (R)Q(tp.cv_l);
+    c.ps_c0 = (R)log2(Q(tp.press_triple));
+    c.psl_a = (R)(dcp_l / Rv); c.psl_b = (R)((Q(tp.LH_v0) - dcp_l * T0) / Rv * l2e);
+    c.psi_a = (R)(dcp_i / Rv); c.psi_b = (R)((Q(tp.LH_s0) - dcp_i * T0) / Rv * l2e);
+    c.inv_T_tr = (R)(1.0 / Q(tp.T_triple));
+    c.cp_d = (R)Q(tp.cp_d); c.cpm_qt = (R)(Q(tp.cp_v) - Q(tp.cp_d));
+    c.cpm_ql = (R)(Q(tp.cp_l) - Q(tp.cp_v)); c.cpm_qi = (R)(Q(tp.cp_i) - Q(tp.cp_v));
     const auto &pp = mp.process_params;
-    c.tau_l = (FT)pp.cloud_liquid_formation_tau_relax; c.tau_i = (FT)pp.cloud_ice_formation_tau_relax;
-    c.inv_tau_i = (FT)(1.0 / (double)pp.cloud_ice_formation_tau_relax);
-    const double K_safe = std::fmax((double)mp.air_properties.K_therm, eps), D_safe = std::fmax((double)mp.air_properties.D_vapor, eps);
-    const double nu_air = mp.air_properties.nu_air;
-    c.inv_K = (FT)(1.0 / K_safe); c.Rv_over_D = (FT)(Rv / D_safe); c.eps_1m = (FT)eps; c.l2_eps = (FT)std::log2(eps);
-    c.inv_eps = (FT)(1.0 / eps);
-    c.K_therm = (FT)mp.air_properties.K_therm;
+    c.tau_l = (R)P(pp.cloud_liquid_formation_tau_relax); c.tau_i = (R)P(pp.cloud_ice_formation_tau_relax);
+    c.inv_tau_i = (R)(1.0 / P(pp.cloud_ice_formation_tau_relax));
+    const W K_safe = fmax(P(mp.air_properties.K_therm), eps), D_safe = fmax(P(mp.air_properties.D_vapor), eps);
+    const W nu_air = P(mp.air_properties.nu_air);
+    c.inv_K = (R)(1.0 / K_safe); c.Rv_over_D = (R)(Rv / D_safe); c.eps_1m = (R)eps; c.l2_eps = (R)std::log2(eps);
+    c.inv_eps = (R)(1.0 / eps);
+    c.K_therm = (R)P(mp.air_properties.K_therm);
     {   // τ_relax (NonEq:32-50): N = (−b T_c/10)⁹/a, r = ∛(3 q/(4π N ρᵢ)) ∨ 1e-6, τ_dep⁻¹ = 4π D_vapor N r
         const auto &fr = pp.cloud_ice_formation_frostenberg;
-        c.td_b10 = (FT)((double)fr.b / 10.0); c.td_l2a = (FT)((double)fr.log_a * l2e);
-        c.td_c3 = (FT)(3.0 / (4.0 * pi * (double)mp.cloud_ice.rho_i)); c.td_fourpiD = (FT)(4.0 * pi * (double)mp.air_properties.D_vapor);
+        c.td_b10 = (R)(P(fr.b) / 10.0); c.td_l2a = (R)(P(fr.log_a) * l2e);
+        c.td_c3 = (R)(3.0 / (4.0 * pi * P(mp.cloud_ice.rho_i))); c.td_fourpiD = (R)(4.0 * pi * P(mp.air_properties.D_vapor));
     }
     // CM1.lambda_inverse :126-152 — λ⁻¹ = (ρ q r0^d / (χm m0 n0 Γ(d+1)))^(1/(d+1)) floored at r0·1e-5, d = me + Δm
-    auto slope = [&](const auto &m, double n0, double root, FT &aa, FT &bb, FT &fl, FT *pa, FT *pb, FT *pf) {
-        const double d = (double)m.me + (double)m.delta_m;
-        const double denom_wo_n0 = (double)m.chi_m * (double)m.m0 * (double)m.gamma_coeff;
-        const double cc = std::log2(std::pow((double)m.r0, d) / denom_wo_n0) - (n0 > 0 ? std::log2(std::fmax(n0, eps)) : 0.0);
-        const double ee = 1.0 / (d + 1.0), floor_ = std::log2((double)m.r0 * 1e-5);
-        aa = (FT)ee; bb = (FT)(cc * ee); fl = (FT)floor_;
-        if (pa) { *pa = (FT)(ee * root); *pb = (FT)(cc * ee * root); *pf = (FT)(floor_ * root); }
+    auto slope = [&](const auto &m, W n0, W root, R &aa, R &bb, R &fl, R *pa, R *pb, R *pf) {
+        const W d = P(m.me) + P(m.delta_m);
+        const W denom_wo_n0 = P(m.chi_m) * P(m.m0) * P(m.gamma_coeff);
+        const W cc = log2(pow(P(m.r0), d) / denom_wo_n0) - ((double)n0 > 0 ? log2(fmax(n0, eps)) : W(0.0));
+        const W ee = 1.0 / (d + 1.0), floor_ = log2(P(m.r0) * 1e-5);
+        aa = (R)ee; bb = (R)(cc * ee); fl = (R)floor_;
+        if (pa) { *pa = (R)(ee * root); *pb = (R)(cc * ee * root); *pf = (R)(floor_ * root); }
     };
-    slope(mp.rain.mass, (double)mp.rain.n0, 0.25, c.lam_a_rai, c.lam_b_rai, c.lam_floor_rai, &c.lamp_a_rai, &c.lamp_b_rai, &c.lamp_floor_rai);
-    slope(mp.snow.mass, 0.0, 0.125, c.lam_a_sno, c.lam_b_sno, c.lam_floor_sno, &c.lamp_a_sno, &c.lamp_b_sno, &c.lamp_floor_sno);
-    slope(mp.cloud_ice.mass, (double)mp.cloud_ice.n0, 1.0, c.lam_a_icl, c.lam_b_icl, c.lam_floor_icl, nullptr, nullptr, nullptr);
-    c.sno_l2_mu = (FT)std::log2((double)mp.snow.mu); c.sno_nu = (FT)mp.snow.nu;
-    const double n0_rai = mp.rain.n0, n0_icl = mp.cloud_ice.n0;
+    slope(mp.rain.mass, P(mp.rain.n0), 0.25, c.lam_a_rai, c.lam_b_rai, c.lam_floor_rai, &c.lamp_a_rai, &c.lamp_b_rai, &c.lamp_floor_rai);
+    slope(mp.snow.mass, W(0.0), 0.125, c.lam_a_sno, c.lam_b_sno, c.lam_floor_sno, &c.lamp_a_sno, &c.lamp_b_sno, &c.lamp_floor_sno);
+    slope(mp.cloud_ice.mass, P(mp.cloud_ice.n0), 1.0, c.lam_a_icl, c.lam_b_icl, c.lam_floor_icl, nullptr, nullptr, nullptr);
+    c.sno_l2_mu = (R)log2(P(mp.snow.mu)); c.sno_nu = (R)P(mp.snow.nu);
+    const W n0_rai = P(mp.rain.n0), n0_icl = P(mp.cloud_ice.n0);
     const auto &vr = mp.vel_rain;
     const auto &vs = mp.vel_snow;
     // get_v0 :101-104: v0 = √(8/3/C_drag · g r0 (ρw/ρ − 1)) = v0c · √(ρw/ρ − 1);  snow: a parameter
-    const double v0c = std::sqrt(8.0 / 3.0 / (double)vr.C_drag * (double)vr.grav * (double)vr.r0), v0s = vs.v0;
-    c.rho_w = (FT)vr.rho_w;
+    const W v0c = sqrt(8.0 / 3.0 / P(vr.C_drag) * P(vr.grav) * P(vr.r0)), v0s = P(vs.v0);
+    c.rho_w = (R)P(vr.rho_w);
     // terminal_velocity :223-238: χv v0 (λ⁻¹/r0)^(ve+Δv) Γ_term/Γ_coeff
-    auto vt = [&](const auto &v, const auto &m, double v0, FT &kk, FT &ee) {
-        const double p = (double)v.ve + (double)v.delta_v;
-        kk = (FT)((double)v.chi_v * (double)v.gamma_term / (double)m.gamma_coeff * std::pow((double)m.r0, -p) * v0);
-        ee = (FT)p;
+    auto vt = [&](const auto &v, const auto &m, W v0, R &kk, R &ee) {
+        const W p = P(v.ve) + P(v.delta_v);
+        kk = (R)(P(v.chi_v) * P(v.gamma_term) / P(m.gamma_coeff) * pow(P(m.r0), -p) * v0);
+        ee = (R)p;
     };
     vt(vr, mp.rain.mass, v0c, c.vt_k_rai, c.vt_e_rai);
     vt(vs, mp.snow.mass, v0s, c.vt_k_sno, c.vt_e_sno);
     // autoconversion
-    auto logistic = [&](const auto &a, FT &qthr, FT &y2, FT &emk, FT &omemk, FT &kl2e, FT &out, FT &inv_tau) {
-        const double x0 = std::fmax((double)a.q_threshold, (double)Math<FT>::eps_1m()), k = a.k;
-        qthr = (FT)a.q_threshold; y2 = (FT)(k / x0 * l2e); emk = (FT)std::exp(-k); omemk = (FT)(-std::expm1(-k)); kl2e = (FT)(k * l2e);
-        out = (FT)(ln2 * x0 / k / (double)a.tau); inv_tau = (FT)(1.0 / (double)a.tau);
+    auto logistic = [&](const auto &a, R &qthr, R &y2, R &emk, R &omemk, R &kl2e, R &out, R &inv_tau) {
+        const W x0 = fmax(P(a.q_threshold), (double)Math<FT>::eps_1m()), k = P(a.k);
+        qthr = (R)P(a.q_threshold); y2 = (R)(k / x0 * l2e); emk = (R)exp(-k); omemk = (R)(-expm1(-k)); kl2e = (R)(k * l2e);
+        out = (R)(ln2 * x0 / k / P(a.tau)); inv_tau = (R)(1.0 / P(a.tau));
     };
     logistic(pp.rain_autoconversion, c.ka_qthr, c.ka_y2, c.ka_emk, c.ka_omemk, c.ka_kl2e, c.ka_out, c.ka_inv_tau);
     logistic(pp.snow_autoconversion, c.ks_qthr, c.ks_y2, c.ks_emk, c.ks_omemk, c.ks_kl2e, c.ks_out, c.ks_inv_tau);
-    c.nd_coeff = (FT)(1.0 / ((double)pp.rain_autoconversion_nd.tau *
-                             std::pow((double)pp.rain_autoconversion_nd.Nc / 1e8, (double)pp.rain_autoconversion_nd.alpha)));
-    c.r_is = (FT)pp.r_ice_snow;
-    c.r_is2_over_me = (FT)((double)pp.r_ice_snow * (double)pp.r_ice_snow / ((double)mp.cloud_ice.mass.me + (double)mp.cloud_ice.mass.delta_m));
-    c.four_pi_n0_icl = (FT)(4.0 * pi * n0_icl);
+    c.nd_coeff = (R)(1.0 / (P(pp.rain_autoconversion_nd.tau) *
+                             pow(P(pp.rain_autoconversion_nd.Nc) / 1e8, P(pp.rain_autoconversion_nd.alpha))));
+    c.r_is = (R)P(pp.r_ice_snow);
+    c.r_is2_over_me = (R)(P(pp.r_ice_snow) * P(pp.r_ice_snow) / (P(mp.cloud_ice.mass.me) + P(mp.cloud_ice.mass.delta_m)));
+    c.four_pi_n0_icl = (R)(4.0 * pi * n0_icl);
     // accretion :491-514: q_clo E n0 a0 v0 χa χv λ⁻¹ Γ_accr / (r0/λ⁻¹)^p,  p = ae+ve+Δa+Δv
-    auto acc = [&](const auto &m, const auto &a, const auto &v, double E, double n0v0, FT &kk, FT &ee) {
-        const double p = (double)a.ae + (double)v.ve + (double)a.delta_a + (double)v.delta_v;
-        kk = (FT)(E * (double)a.a0 * (double)a.chi_a * (double)v.chi_v * (double)v.gamma_accr * std::pow((double)m.r0, -p) * n0v0);
-        ee = (FT)(1.0 + p);
+    auto acc = [&](const auto &m, const auto &a, const auto &v, W E, W n0v0, R &kk, R &ee) {
+        const W p = P(a.ae) + P(v.ve) + P(a.delta_a) + P(v.delta_v);
+        kk = (R)(E * P(a.a0) * P(a.chi_a) * P(v.chi_v) * P(v.gamma_accr) * pow(P(m.r0), -p) * n0v0);
+        ee = (R)(1.0 + p);
     };
-    FT tmp;
-    acc(mp.rain.mass, mp.rain.area, vr, pp.e_lcl_rai, n0_rai * v0c, c.acc_k_lcl_rai, c.acc_e_rai);
-    acc(mp.rain.mass, mp.rain.area, vr, pp.e_icl_rai, n0_rai * v0c, c.acc_k_icl_rai, tmp);
-    acc(mp.snow.mass, mp.snow.area, vs, pp.e_lcl_sno, v0s, c.acc_k_lcl_sno, c.acc_e_sno);
-    acc(mp.snow.mass, mp.snow.area, vs, pp.e_icl_sno, v0s, c.acc_k_icl_sno, tmp);
+    R tmp;
+    acc(mp.rain.mass, mp.rain.area, vr, P(pp.e_lcl_rai), n0_rai * v0c, c.acc_k_lcl_rai, c.acc_e_rai);
+    acc(mp.rain.mass, mp.rain.area, vr, P(pp.e_icl_rai), n0_rai * v0c, c.acc_k_icl_rai, tmp);
+    acc(mp.snow.mass, mp.snow.area, vs, P(pp.e_lcl_sno), v0s, c.acc_k_lcl_sno, c.acc_e_sno);
+    acc(mp.snow.mass, mp.snow.area, vs, P(pp.e_icl_sno), v0s, c.acc_k_icl_sno, tmp);
     {   // accretion_rain_sink :535-561
         const auto &m = mp.rain.mass;
         const auto &a = mp.rain.area;
-        const double P = (double)m.me + (double)a.ae + (double)vr.ve + (double)m.delta_m + (double)a.delta_a + (double)vr.delta_v;
-        c.sink_k = (FT)((double)pp.e_icl_rai * n0_rai * n0_icl * (double)m.m0 * (double)a.a0 * (double)m.chi_m * (double)a.chi_a *
-                        (double)vr.chi_v * (double)vr.gamma_accr_rain_sink * std::pow((double)m.r0, -P) * v0c);
-        c.sink_e = (FT)(1.0 + P);
+        const W psum = P(m.me) + P(a.ae) + P(vr.ve) + P(m.delta_m) + P(a.delta_a) + P(vr.delta_v);
+        c.sink_k = (R)(P(pp.e_icl_rai) * n0_rai * n0_icl * P(m.m0) * P(a.a0) * P(m.chi_m) * P(a.chi_a) *
+                        P(vr.chi_v) * P(vr.gamma_accr_rain_sink) * pow(P(m.r0), -psum) * v0c);
+        c.sink_e = (R)(1.0 + psum);
     }
     // accretion_snow_rain :604-644 with type_j: π m0 χm E Γ_coeff / r0^δ · n0_rai n0_sno |Δv| / ρ ·
     //   (2 λi⁻³ λj⁻^(δ+1) + 2(δ+1) λi⁻² λj⁻^(δ+2) + (δ+2)(δ+1) λi⁻¹ λj⁻^(δ+3)) = … · λi⁻¹ λj⁻^(δ+1) · 2 (λi⁻² + (δ+1) λi⁻¹λj⁻¹ + ½(δ+2)(δ+1) λj⁻²)
-    auto rs = [&](const auto &mj, FT &kk, FT &dp1, FT &q1, FT &q2) {
-        const double d = (double)mj.me + (double)mj.delta_m;
-        kk = (FT)(2.0 * pi * (double)mj.m0 * (double)mj.chi_m * (double)pp.e_rai_sno * (double)mj.gamma_coeff * std::pow((double)mj.r0, -d) * n0_rai);
-        dp1 = (FT)(d + 1.0); q1 = (FT)(d + 1.0); q2 = (FT)(0.5 * (d + 2.0) * (d + 1.0));
+    auto rs = [&](const auto &mj, R &kk, R &dp1, R &q1, R &q2) {
+        const W d = P(mj.me) + P(mj.delta_m);
+        kk = (R)(2.0 * pi * P(mj.m0) * P(mj.chi_m) * P(pp.e_rai_sno) * P(mj.gamma_coeff) * pow(P(mj.r0), -d) * n0_rai);
+        dp1 = (R)(d + 1.0); q1 = (R)(d + 1.0); q2 = (R)(0.5 * (d + 2.0) * (d + 1.0));
     };
     rs(mp.rain.mass, c.rs_k_rai, c.rs_dp1_rai, c.rs_q1_rai, c.rs_q2_rai);
     rs(mp.snow.mass, c.rs_k_sno, c.rs_dp1_sno, c.rs_q1_sno, c.rs_q2_sno);
-    c.coeff_disp = (FT)pp.coeff_disp;
+    c.coeff_disp = (R)P(pp.coeff_disp);
     // ventilation factor (CM1:948-956): a + b ∛Sc Γ_vent √(2 χv/ν) · √v0 · λ⁻¹^(1/2 + (ve+Δv)/2) / r0^((ve+Δv)/2), times 4π n0 [rain]
-    const double cbrt_Sc = std::cbrt(nu_air / D_safe);
-    auto vent = [&](const auto &ve_, const auto &v, const auto &m, double pre, double sqrt_v0, FT &aa, FT &bb, FT &ee) {
-        const double h = ((double)v.ve + (double)v.delta_v) / 2.0;
-        aa = (FT)(pre * (double)ve_.a);
-        bb = (FT)(pre * (double)ve_.b * cbrt_Sc * (double)v.gamma_vent * std::sqrt(2.0 * (double)v.chi_v / nu_air) * std::pow((double)m.r0, -h) * sqrt_v0);
-        ee = (FT)(0.5 + h);
+    const W cbrt_Sc = cbrt(nu_air / D_safe);
+    auto vent = [&](const auto &ve_, const auto &v, const auto &m, W pre, W sqrt_v0, R &aa, R &bb, R &ee) {
+        const W h = (P(v.ve) + P(v.delta_v)) / 2.0;
+        aa = (R)(pre * P(ve_.a));
+        bb = (R)(pre * P(ve_.b) * cbrt_Sc * P(v.gamma_vent) * sqrt(2.0 * P(v.chi_v) / nu_air) * pow(P(m.r0), -h) * sqrt_v0);
+        ee = (R)(0.5 + h);
     };
-    vent(mp.rain.vent, vr, mp.rain.mass, 4.0 * pi * n0_rai, std::sqrt(v0c), c.ven_a_rai, c.ven_b_rai, c.ven_e_rai);
-    vent(mp.snow.vent, vs, mp.snow.mass, 4.0 * pi, std::sqrt(v0s), c.ven_a_sno, c.ven_b_sno, c.ven_e_sno);
-    c.mi_k = (FT)(4.0 * pi * n0_icl * (double)mp.air_properties.K_therm);
+    vent(mp.rain.vent, vr, mp.rain.mass, 4.0 * pi * n0_rai, sqrt(v0c), c.ven_a_rai, c.ven_b_rai, c.ven_e_rai);
+    vent(mp.snow.vent, vs, mp.snow.mass, 4.0 * pi, sqrt(v0s), c.ven_a_sno, c.ven_b_sno, c.ven_e_sno);
+    c.mi_k = (R)(4.0 * pi * n0_icl * P(mp.air_properties.K_therm));
     return c;
+}
+template <typename FT, typename MP, typename TH>
+static Mp1mConsts<FT> make_mp1m_consts(const MP &mp, const TH &tp, uint32_t flags, double eps) {
+    return make_mp1m_consts_from<FT, FT>(mp, tp, flags, eps, [](const auto &f) { return (double)f; }, [](const auto &f) { return (double)f; });
 }
 
 // The source terms of one point, before the warm / cold routing of the three temperature-routed accretion terms (BMT:171-198): of each
@@ -211,8 +220,8 @@ template <typename FT> struct Mp1mSrc {
 // eps(FT)·t·x0 (the oracle reports 2 t x0 as the operand scale of this term); the right side has absolute error eps(FT)·x0/k from the
 // rounding of its argument near 1, the same class.  x arrives clamped to ≥ 0; x0 < ϵ (a parameter-only case: the reference returns x)
 // takes a wave-uniform branch of the run-time-flags instantiations.
-template <typename FT, bool REGULAR, typename S> __device__ __forceinline__ FT logistic_rate(FT x, S qthr, S y2c, S emk, S omemk, S kl2e, S out, S inv_tau, S eps) {
-    using M = Math<FT>;      // FT: the value type, S: its scalar type (the constants)
+template <typename FT, bool REGULAR, typename S, typename E> __device__ __forceinline__ FT logistic_rate(FT x, S qthr, S y2c, S emk, S omemk, S kl2e, S out, S inv_tau, E eps) {
+    using M = Math<FT>;      // FT: the value type, S: the type of the constants (its scalar type, or duals for the parameter derivatives), E: of ϵ
     // REGULAR: the host has checked x0 ≥ ϵ (mp1m_default_exponents) — no branch in the default Float32 instantiation, whose four points
     // per lane then stay one basic block.  (The Float64 default instantiation keeps the never-taken scalar branch: without it the
     // scheduler hoists the autoconversion constants across the phase boundary and spills 38 SGPR pairs to VGPR lanes, 933 → 1000
@@ -232,7 +241,7 @@ __device__ __forceinline__ Mp1mSrc<FT> mp1m_point(const C &c0, FT rho, FT T, FT 
     const uint32_t fl = FLAGS == kRuntimeFlags ? c->flags : FLAGS;
     constexpr bool DEFEXP = FLAGS != kRuntimeFlags && (FLAGS & kDefExpBit) != 0;
     using B = typename M::Mask;
-    const typename M::Scalar eps = c->eps_1m;   // ϵ_numerics(FT) = cbrt(floatmin(FT))  Utilities.jl:318
+    const auto eps = c->eps_1m;   // (the constants' type: the scalar type, or a dual for the parameter derivatives)  ϵ_numerics(FT) = cbrt(floatmin(FT))  Utilities.jl:318
     // clamp_to_nonneg — BMT:147-152 (T is not clamped)
     rho = max0(rho); q_tot = max0(q_tot); q_lcl = max0(q_lcl);
     q_icl = max0(q_icl); q_rai = max0(q_rai); q_sno = max0(q_sno);

@@ -80,109 +80,115 @@ template <typename K, typename PR> inline void fill_rain_pdf_limiters(K &k, cons
     k.xr_min = p.xr_min; k.xr_max = p.xr_max; k.N0_min = p.N0_min; k.N0_max = p.N0_max; k.lam_min = p.lambda_min; k.lam_max = p.lambda_max;
 }
 
-template <typename FT, typename WR, typename TH, typename VL>
-inline SbConsts<FT> make_sb_consts(const WR &wr, const TH &tp, const VL *vel, double eps_1m) {
-    SbConsts<FT> c{};
+// The fold, generic in how a parameter is read and in the scalar the result holds: P(field) / Q(field) read a field of `wr` / `tp` as the working scalar W —
+// double for the plain fold (make_sb_consts below: R = FT, every line the double arithmetic it always was), a value with a tangent for the parameter
+// derivatives (cmx_param_tangent.hpp: R = W = ParamTan; the value parts are the plain fold's in every bit).  The mathematical functions are found by
+// argument-dependent lookup for such a W.  The velocity constants are folded by the plain fold only.
+template <typename FT, typename R, typename WR, typename TH, typename VL, typename PW, typename PT>
+inline SbConsts<R> make_sb_consts_from(const WR &wr, const TH &tp, const VL *vel, double eps_1m, const PW &P, const PT &Q) {
+    using std::cbrt; using std::fmax; using std::log2; using std::sqrt;
+    using W = decltype(P(wr.condevap_tau_relax));
+    SbConsts<R> c{};
     const auto &sb = wr.seifert_beheng;
-    const double pi = 3.14159265358979323846;
-    const double l2e = 1.4426950408889634074;
+    const W pi = 3.14159265358979323846;
+    const W l2e = 1.4426950408889634074;
     // thermo
-    const double dcp = (double)tp.cp_v - (double)tp.cp_l;
-    c.T_0 = (FT)tp.T_0;
-    c.LH_v0 = (FT)tp.LH_v0;
-    c.dcp = (FT)dcp;
-    c.R_v = (FT)tp.R_v;
-    c.inv_R_v = (FT)(1.0 / (double)tp.R_v);
-    c.ps_c0 = (FT)std::log2((double)tp.press_triple);
-    c.ps_a = (FT)(dcp / (double)tp.R_v);
-    c.ps_b = (FT)(((double)tp.LH_v0 - dcp * (double)tp.T_0) / (double)tp.R_v * l2e);
-    c.inv_T_tr = (FT)(1.0 / (double)tp.T_triple);
-    c.cp_d = (FT)tp.cp_d;
-    c.cpm_qt = (FT)((double)tp.cp_v - (double)tp.cp_d);
-    c.cpm_ql = (FT)((double)tp.cp_l - (double)tp.cp_v);
-    c.tau_ce = (FT)wr.condevap_tau_relax;
-    const double K_safe = std::fmax((double)wr.air_properties.K_therm, eps_1m);
-    const double D_safe = std::fmax((double)wr.air_properties.D_vapor, eps_1m);
-    c.inv_K = (FT)(1.0 / K_safe);
-    c.Rv_over_D = (FT)((double)tp.R_v / D_safe);
-    c.eps_1m = (FT)eps_1m;
+    const W dcp = Q(tp.cp_v) - Q(tp.cp_l);
+    c.T_0 = (R)Q(tp.T_0);
+    c.LH_v0 = (R)Q(tp.LH_v0);
+    c.dcp = (R)dcp;
+    c.R_v = (R)Q(tp.R_v);
+    c.inv_R_v = (R)(1.0 / Q(tp.R_v));
+    c.ps_c0 = (R)log2(Q(tp.press_triple));
+    c.ps_a = (R)(dcp / Q(tp.R_v));
+    c.ps_b = (R)((Q(tp.LH_v0) - dcp * Q(tp.T_0)) / Q(tp.R_v) * l2e);
+    c.inv_T_tr = (R)(1.0 / Q(tp.T_triple));
+    c.cp_d = (R)Q(tp.cp_d);
+    c.cpm_qt = (R)(Q(tp.cp_v) - Q(tp.cp_d));
+    c.cpm_ql = (R)(Q(tp.cp_l) - Q(tp.cp_v));
+    c.tau_ce = (R)P(wr.condevap_tau_relax);
+    const W K_safe = fmax(P(wr.air_properties.K_therm), eps_1m);
+    const W D_safe = fmax(P(wr.air_properties.D_vapor), eps_1m);
+    c.inv_K = (R)(1.0 / K_safe);
+    c.Rv_over_D = (R)(Q(tp.R_v) / D_safe);
+    c.eps_1m = (R)eps_1m;
     // rain PSD
     const auto &pr = sb.pdf_r;
-    c.xr_min = (FT)pr.xr_min;
-    c.xr_max = (FT)pr.xr_max;
-    c.N0_min = (FT)pr.N0_min;
-    c.N0_max = (FT)pr.N0_max;
-    c.lam_min = (FT)pr.lambda_min;
-    c.lam_max = (FT)pr.lambda_max;
-    c.pi_rho_w = (FT)(pi * (double)pr.rho_w);
+    c.xr_min = (R)P(pr.xr_min);
+    c.xr_max = (R)P(pr.xr_max);
+    c.N0_min = (R)P(pr.N0_min);
+    c.N0_max = (R)P(pr.N0_max);
+    c.lam_min = (R)P(pr.lambda_min);
+    c.lam_max = (R)P(pr.lambda_max);
+    c.pi_rho_w = (R)(pi * P(pr.rho_w));
     // evaporation
     const auto &ev = sb.evap;
-    const double x_star_ev = (double)pr.xr_min;  // CM2:795
-    c.l2_6xstar = (FT)std::log2(6.0 * x_star_ev);
-    c.l2_Drc = (FT)std::log2(6.0 / (pi * (double)pr.rho_w));
-    c.l2_pi_rho_w = (FT)std::log2(pi * (double)pr.rho_w);
-    c.l2_xr_min = (FT)std::log2((double)pr.xr_min); c.l2_xr_max = (FT)std::log2((double)pr.xr_max);
-    c.l2_N0_min = (FT)std::log2(std::fmax((double)pr.N0_min, 1e-300)); c.l2_N0_max = (FT)std::log2(std::fmax((double)pr.N0_max, 1e-300));
-    c.l2_lam_min = (FT)std::log2(std::fmax((double)pr.lambda_min, 1e-300)); c.l2_lam_max = (FT)std::log2(std::fmax((double)pr.lambda_max, 1e-300));
-    c.inv_eps_1m = (FT)(1.0 / eps_1m);
-    auto gincl = [](double a, FT &c1, FT &e1, FT &c2, FT &e2) {
-        c1 = (FT)(0.33 - 0.7 * a);
-        e1 = (FT)(0.08 - 0.93 * a);
-        c2 = (FT)(1.34 - 0.1 * a);
-        e2 = (FT)(0.8 - a);
+    const W x_star_ev = P(pr.xr_min);  // CM2:795
+    c.l2_6xstar = (R)log2(6.0 * x_star_ev);
+    c.l2_Drc = (R)log2(6.0 / (pi * P(pr.rho_w)));
+    c.l2_pi_rho_w = (R)log2(pi * P(pr.rho_w));
+    c.l2_xr_min = (R)log2(P(pr.xr_min)); c.l2_xr_max = (R)log2(P(pr.xr_max));
+    c.l2_N0_min = (R)log2(fmax(P(pr.N0_min), 1e-300)); c.l2_N0_max = (R)log2(fmax(P(pr.N0_max), 1e-300));
+    c.l2_lam_min = (R)log2(fmax(P(pr.lambda_min), 1e-300)); c.l2_lam_max = (R)log2(fmax(P(pr.lambda_max), 1e-300));
+    c.inv_eps_1m = (R)(1.0 / eps_1m);
+    auto gincl = [](W a, R &c1, R &e1, R &c2, R &e2) {
+        c1 = (R)(0.33 - 0.7 * a);
+        e1 = (R)(0.08 - 0.93 * a);
+        c2 = (R)(1.34 - 0.1 * a);
+        e2 = (R)(0.8 - a);
     };
-    gincl(-1.0, c.ga_c1, c.ga_e1, c.ga_c2, c.ga_e2);
-    gincl((double)ev.beta_vent_0, c.gb_c1, c.gb_e1, c.gb_c2, c.gb_e2);
-    const double cbrt_Sc = std::cbrt((double)wr.air_properties.nu_air / D_safe);
+    gincl(W(-1.0), c.ga_c1, c.ga_e1, c.ga_c2, c.ga_e2);
+    gincl(P(ev.beta_vent_0), c.gb_c1, c.gb_e1, c.gb_c2, c.gb_e2);
+    const W cbrt_Sc = cbrt(P(wr.air_properties.nu_air) / D_safe);
     // 1/(c1 t^e1 + c2 t^e2) scaled by a_vent_0 resp. b_vent_0·∛Sc: fold the scale into c1, c2
     {
-        const double sa = (double)ev.a_vent_0_coeff, sb = (double)ev.b_vent_0_coeff * cbrt_Sc;
-        c.ga_c1 = (FT)((0.33 + 0.7) / sa); c.ga_c2 = (FT)((1.34 + 0.1) / sa);
-        const double ab = (double)ev.beta_vent_0;
-        c.gb_c1 = (FT)((0.33 - 0.7 * ab) / sb); c.gb_c2 = (FT)((1.34 - 0.1 * ab) / sb);
+        const W sa = P(ev.a_vent_0_coeff), sb = P(ev.b_vent_0_coeff) * cbrt_Sc;
+        c.ga_c1 = (R)((0.33 + 0.7) / sa); c.ga_c2 = (R)((1.34 + 0.1) / sa);
+        const W ab = P(ev.beta_vent_0);
+        c.gb_c1 = (R)((0.33 - 0.7 * ab) / sb); c.gb_c2 = (R)((1.34 - 0.1 * ab) / sb);
     }
-    c.a_vent_1 = (FT)ev.a_vent_1;
-    c.bSc_vent_1 = (FT)((double)ev.b_vent_1 * cbrt_Sc);
-    c.sqrt_alpha_nu = (FT)std::sqrt((double)ev.alpha / (double)wr.air_properties.nu_air);
-    c.beta = (FT)ev.beta;
-    c.ev_rho0_q = (FT)std::sqrt(std::sqrt((double)ev.rho_0));
-    c.sqrt_alpha_nu_rho0q = (FT)(std::sqrt((double)ev.alpha / (double)wr.air_properties.nu_air) * std::sqrt(std::sqrt((double)ev.rho_0)));
-    c.two_pi = (FT)(2.0 * pi);
-    c.l2_gate_N = (FT)std::log2((double)Math<FT>::eps() * x_star_ev);
-    c.tstar_Dr = (FT)(std::cbrt(6.0 * x_star_ev) * std::cbrt(6.0 / (pi * (double)pr.rho_w)));
+    c.a_vent_1 = (R)P(ev.a_vent_1);
+    c.bSc_vent_1 = (R)(P(ev.b_vent_1) * cbrt_Sc);
+    c.sqrt_alpha_nu = (R)sqrt(P(ev.alpha) / P(wr.air_properties.nu_air));
+    c.beta = (R)P(ev.beta);
+    c.ev_rho0_q = (R)sqrt(sqrt(P(ev.rho_0)));
+    c.sqrt_alpha_nu_rho0q = (R)(sqrt(P(ev.alpha) / P(wr.air_properties.nu_air)) * sqrt(sqrt(P(ev.rho_0))));
+    c.two_pi = (R)(2.0 * pi);
+    c.l2_gate_N = (R)log2((double)Math<FT>::eps() * x_star_ev);
+    c.tstar_Dr = (R)(cbrt(6.0 * x_star_ev) * cbrt(6.0 / (pi * P(pr.rho_w))));
     // autoconversion
     const auto &ac = sb.acnv;
-    const double nu_c = (double)sb.pdf_c.nu_c;
-    const double kfac = (double)ac.kcc / 20.0 / (double)ac.x_star * (nu_c + 2) * (nu_c + 4) /
+    const W nu_c = P(sb.pdf_c.nu_c);
+    const W kfac = P(ac.kcc) / 20.0 / P(ac.x_star) * (nu_c + 2) * (nu_c + 4) /
                         ((nu_c + 1) * (nu_c + 1));
-    c.sqrt_kfac = (FT)std::sqrt(kfac);
-    c.x_star = (FT)ac.x_star;
-    c.inv_x_star = (FT)(1.0 / (double)ac.x_star);
-    c.acnv_A = (FT)ac.A;
-    c.acnv_a = (FT)ac.a;
-    c.acnv_b = (FT)ac.b;
-    c.acnv_rho0 = (FT)ac.rho_0;
-    c.ksc = (FT)((double)ac.kcc * (nu_c + 2) / (nu_c + 1) * (double)ac.rho_0);
+    c.sqrt_kfac = (R)sqrt(kfac);
+    c.x_star = (R)P(ac.x_star);
+    c.inv_x_star = (R)(1.0 / P(ac.x_star));
+    c.acnv_A = (R)P(ac.A);
+    c.acnv_a = (R)P(ac.a);
+    c.acnv_b = (R)P(ac.b);
+    c.acnv_rho0 = (R)P(ac.rho_0);
+    c.ksc = (R)(P(ac.kcc) * (nu_c + 2) / (nu_c + 1) * P(ac.rho_0));
     // accretion
-    c.kcr_s = (FT)((double)sb.accr.kcr * std::sqrt((double)sb.accr.rho_0));
-    c.tau_0 = (FT)sb.accr.tau_0;
-    c.accr_c = (FT)sb.accr.c;
+    c.kcr_s = (R)(P(sb.accr.kcr) * sqrt(P(sb.accr.rho_0)));
+    c.tau_0 = (R)P(sb.accr.tau_0);
+    c.accr_c = (R)P(sb.accr.c);
     // rain self-collection / breakup
-    c.krr_s = (FT)((double)sb.self.krr * std::sqrt((double)pr.rho_0));
-    c.kappa_rr_K = (FT)((double)sb.self.kappa_rr * std::cbrt(pi * (double)pr.rho_w / 36.0));
-    c.self_d = (FT)sb.self.d;
-    c.Deq = (FT)sb.brek.Deq;
-    c.Dr_th = (FT)sb.brek.Dr_th;
-    c.kbr = (FT)sb.brek.kbr;
-    c.kappa_br_l2e = (FT)((double)sb.brek.kappa_br * l2e);
+    c.krr_s = (R)(P(sb.self.krr) * sqrt(P(pr.rho_0)));
+    c.kappa_rr_K = (R)(P(sb.self.kappa_rr) * cbrt(pi * P(pr.rho_w) / 36.0));
+    c.self_d = (R)P(sb.self.d);
+    c.Deq = (R)P(sb.brek.Deq);
+    c.Dr_th = (R)P(sb.brek.Dr_th);
+    c.kbr = (R)P(sb.brek.kbr);
+    c.kappa_br_l2e = (R)(P(sb.brek.kappa_br) * l2e);
     // number adjustment
-    c.inv_tau_na = (FT)(1.0 / (double)sb.numadj.tau);
-    c.inv_xc_min = (FT)(1.0 / (double)sb.pdf_c.xc_min);
-    c.inv_xc_max = (FT)(1.0 / (double)sb.pdf_c.xc_max);
-    c.inv_xr_min = (FT)(1.0 / (double)pr.xr_min);
-    c.inv_xr_max = (FT)(1.0 / (double)pr.xr_max);
+    c.inv_tau_na = (R)(1.0 / P(sb.numadj.tau));
+    c.inv_xc_min = (R)(1.0 / P(sb.pdf_c.xc_min));
+    c.inv_xc_max = (R)(1.0 / P(sb.pdf_c.xc_max));
+    c.inv_xr_min = (R)(1.0 / P(pr.xr_min));
+    c.inv_xr_max = (R)(1.0 / P(pr.xr_max));
     // velocities
-    if (vel) {
+    if constexpr (std::is_same<R, FT>::value) if (vel) {
         const auto &v = vel->sb2006;
         c.vel_s = (FT)std::sqrt((double)v.rho_0);
         c.aR = (FT)v.aR;
@@ -204,6 +210,10 @@ inline SbConsts<FT> make_sb_consts(const WR &wr, const TH &tp, const VL *vel, do
         (void)make_chen_log<FT>(ch, c.chl);        // the entry points test the fit themselves (chen_vel_kind)
     }
     return c;
+}
+template <typename FT, typename WR, typename TH, typename VL>
+inline SbConsts<FT> make_sb_consts(const WR &wr, const TH &tp, const VL *vel, double eps_1m) {
+    return make_sb_consts_from<FT, FT>(wr, tp, vel, eps_1m, [](const auto &f) { return (double)f; }, [](const auto &f) { return (double)f; });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@
 #include "../../include/cmx.h"
 #include "cmx_dispatch.hpp"
 #include "cmx_jacobian.hpp"
+#include "cmx_param_tangent.hpp"
 #include "cmx_sb2006.hpp"
 
 namespace cmx {
@@ -50,8 +51,8 @@ template <bool LIMITED, bool INTPOW> struct SbJac {
         const D qt = max0(in[CMX_SB2006_JAC_WRT_Q_TOT]), ql = max0(in[CMX_SB2006_JAC_WRT_Q_LCL]), nl = max0(in[CMX_SB2006_JAC_WRT_N_LCL]);
         const D qr = max0(in[CMX_SB2006_JAC_WRT_Q_RAI]), nr = max0(in[CMX_SB2006_JAC_WRT_N_RAI]);
         // N = ρ n — BMT:718-719.  `c` is the kernel's constants argument: Float64 reads it through the kernel-argument segment, phase by phase
-        // (cmx_math.hpp front_consts)
-        const SbRates<D> p = sb2006_point<D, LIMITED, VEL_NONE, false, INTPOW>(front_consts<FT>(c), r_, T, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
+        // (cmx_math.hpp front_consts; constants that are duals themselves: the plain reference, cmx_dual.hpp scheme_consts)
+        const SbRates<D> p = sb2006_point<D, LIMITED, VEL_NONE, false, INTPOW>(scheme_consts<FT>(c), r_, T, qt, ql, qr, r_ * nl, r_ * nr, nl, nr);
         o[CMX_SB2006_JAC_DQ_LCL_DT] = (p.cond + p.au_dq_lcl) + p.ac_dq_lcl;
         o[CMX_SB2006_JAC_DN_LCL_DT] = MD::fma(p.lsc_plus_au + p.ac_dN_lcl, p.inv_rho, p.na_lcl);
         o[CMX_SB2006_JAC_DQ_RAI_DT] = (p.evq + p.au_dq_rai) + p.ac_dq_rai;
@@ -69,6 +70,45 @@ template <typename FT, typename WR, typename TH, typename F> inline int32_t with
                                               (double)Math<FT>::eps_1m());
     return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t { return f(c, SbJac<decltype(L)::value, decltype(I)::value>{}); },
                        flag(limited), flag(sb_integer_exponents(wr)));
+}
+
+// ---- ∂/∂θ (cmx_jacobian.hpp param_jvp_point / param_vjp_point; include/cmx.h §(22)) ------------------------------------------------------------------------------
+// The constants of ONE launch: tangent slot k holds ċ of direction d0 + k (an idle slot past ndir: zeros), from the fold of make_sb_consts_from on ParamTan.
+// Every slot's value parts are the same, and the plain fold's, bit for bit.
+template <typename FT, int KP, typename WR, typename TH>
+inline SbConsts<Dual<FT, KP>> make_sb_param_consts(const WR &wr, const TH &tps, const WR *d_wr, const TH *d_tps, int d0, int ndir) {
+    using VL = std::conditional_t<std::is_same_v<FT, float>, cmx_rain_vel_f32, cmx_rain_vel_f64>;
+    SbConsts<Dual<FT, KP>> cd{};
+    for (int k = 0; k < KP; ++k) {
+        const bool live = d0 + k < ndir;
+        const SbConsts<ParamTan> ct = make_sb_consts_from<FT, ParamTan>(wr, tps, (const VL *)nullptr, (double)Math<FT>::eps_1m(),
+                                                                        ParamReader<WR>{wr, live ? d_wr + d0 + k : nullptr},
+                                                                        ParamReader<TH>{tps, live && d_tps ? d_tps + d0 + k : nullptr});
+        pack_param_consts<KP>(ct, k, cd);
+    }
+    return cd;
+}
+// the kernel-argument segment holds the dual constants next to the column tables
+static_assert(sizeof(SbConsts<Dual<float, kParamK<float>>>) + 512 <= 4096 && sizeof(SbConsts<Dual<double, kParamK<double>>>) + 512 <= 4096,
+              "CMX_PARAM_K_F32 / CMX_PARAM_K_F64: the constants with their tangents must fit the 4 KiB kernel-argument segment");
+
+// The checks of the directions and the instantiation choice, after the entry's own argument checks: 1 ≤ ndir ≤ CMX_PARAM_MAX_DIRS, the table, finite
+// components, then the flags and limiters of with_sb2006_jac.  The integer-exponent instantiation has no derivative with respect to acnv.b, accr.c, self.d:
+// it runs only if the tendencies entry would select it AND no direction moves one of the three.  Returns f(SbJac<LIMITED, INTPOW>{}) or CMX_ERR_BAD_ARG.
+template <typename FT, typename WR, typename TH, typename F>
+inline int32_t with_sb2006_param(const WR &wr, const TH &tps, uint32_t flags, int32_t ndir, const WR *d_wr, const TH *d_tps, F &&f) {
+    if (ndir < 1 || ndir > CMX_PARAM_MAX_DIRS || !d_wr) return CMX_ERR_BAD_ARG;
+    bool exponents = false;
+    for (int d = 0; d < ndir; ++d) {
+        if (!all_finite<FT>(d_wr[d]) || (d_tps && !all_finite<FT>(d_tps[d]))) return CMX_ERR_BAD_ARG;
+        const auto &sb = d_wr[d].seifert_beheng;
+        exponents |= sb.acnv.b != 0 || sb.accr.c != 0 || sb.self.d != 0;
+    }
+    if (flags & ~(uint32_t)CMX_SB2006_LIMITED) return CMX_ERR_BAD_ARG;
+    const bool limited = flags & CMX_SB2006_LIMITED;
+    if (limited && !sb_limiters_ok(wr)) return CMX_ERR_BAD_ARG;
+    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t { return f(SbJac<decltype(L)::value, decltype(I)::value>{}); },
+                       flag(limited), flag(sb_integer_exponents(wr) && !exponents));
 }
 
 }  // namespace cmx

@@ -1796,6 +1796,85 @@ int32_t cmx_mp1m_column_implicit_step_f64(const cmx_microphysics_1m_f64 *mp, con
                                           double *const *out, double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (22) The derivatives of the SB2006 warm-rain tendencies (14) with respect to the PARAMETERS θ — what a calibration, or a closure trained through the
+ * scheme, needs: dL/dθ, not dL/dx.  State, `flags`, outputs (cmx_sb2006_jac_out) and derivative rules are those of (14); the state is held fixed.
+ * A DIRECTION is a pair of structs of the entry's own parameter types whose floating fields hold δθ: d_warm_rain[d] (a host array of `ndir` structs) and
+ * d_tps[d] (NULL: zero).  For each direction the host forms the tangent ċ = Dc(θ)[δθ] of every folded constant in exact forward mode in double (no
+ * difference quotient); the tangents travel as kernel arguments (no allocation, no copy to the device), and the device runs the SAME point function as
+ * the tendencies entry on forward-mode duals whose tangents are those of the constants.
+ *   cmx_sb2006_warm_rain_param_jvp_*:  jvp[d·4 + o] = Σ_p ∂out_o/∂θ_p · δθ_p⁽ᵈ⁾ per point
+ *     jvp           a host array of ndir·4 NULL-able device columns
+ *   cmx_sb2006_warm_rain_param_vjp_*:  grad[d] = Σ_points Σ_o cotangents[o] · (∂out_o/∂θ · δθ⁽ᵈ⁾), accumulated in DOUBLE; a one-hot direction gives dL/dθ_p
+ *     cotangents[o] the cotangent column ḡ of output o (a host array of 4 device column pointers; a NULL member removes that output from the sum)
+ *     grad          `ndir` doubles of DEVICE memory
+ *     workspace     ndir · CMX_PARAM_VJP_PARTIALS doubles of device memory owned by the caller (the library allocates nothing)
+ *   tendencies[o]   NULL, or 4 NULL-able columns
+ * The reduction is that of (3): a fixed number of workgroups each own a contiguous chunk, a lane adds its points in index order (per point the sum over the
+ * outputs is the fused multiply-add chain of (16), widened to double), a fixed shuffle tree, a finish launch.  No floating-point atomics: grad is a pure
+ * function of the inputs and n_points, bit-identical from run to run and from device to device.  n_points = 0 sets grad to zeros.
+ * A call with more directions than one launch carries is a sequence of launches on `stream`; a jvp column's bits and a grad value's bits do not depend on
+ * which other directions are in the call, on ndir or on how the call was split.
+ * INSTANTIATION.  If no direction has a non-zero component on acnv.b, accr.c or self.d, the instantiation the tendencies entry selects runs and `tendencies`
+ * is bit-identical to cmx_sb2006_warm_rain_tendencies_*.  Otherwise the general (exp2(e·log2 x)) instantiation runs for the whole call — a power by
+ * multiplication has no derivative with respect to its exponent — and `tendencies` agrees with the tendencies entry to the parity bound, not bit for bit.
+ * Constants that only feed compares (thresholds, gates) contribute no derivative: the derivative is that of the branch taken.
+ * Statuses, in this order: NULL parameters; the count rule (param_jvp: n_points = 0 is CMX_OK; param_vjp writes grad for n_points = 0 too and goes on with every
+ * check below but the columns, so a bad call is refused whatever n_points is); NULL columns; ndir outside
+ * 1 … CMX_PARAM_MAX_DIRS; a NULL direction table (param_vjp: or a NULL cotangent table); no output at all (param_vjp: a NULL grad or workspace); a
+ * non-finite component in a direction; the flags and limiters of (14) — all CMX_ERR_BAD_ARG, all before the first enqueue.  NaN rule: a NaN in any of the
+ * seven inputs of a point gives NaN in every jvp and tendency of that point; in param_vjp a NaN in a point's state or cotangents makes every grad[d] NaN.
+ * Graph-capturable; any alignment.  The 1-moment scheme: (23).  Not done here: the fall-speed outputs, the implicit and column entries, second derivatives.
+ * ------------------------------------------------------------------------- */
+#define CMX_PARAM_MAX_DIRS 16
+#define CMX_PARAM_VJP_PARTIALS 1024
+int32_t cmx_sb2006_warm_rain_param_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                           const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                           int32_t ndir, const cmx_warm_rain_2m_f32 *d_warm_rain, const cmx_thermo_f32 *d_tps, float *const *jvp,
+                                           float *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_param_jvp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                           const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                           const double *n_rai, int32_t ndir, const cmx_warm_rain_2m_f64 *d_warm_rain, const cmx_thermo_f64 *d_tps,
+                                           double *const *jvp, double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+int32_t cmx_sb2006_warm_rain_param_vjp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho,
+                                           const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                           const float *const cotangents[CMX_SB2006_JAC_NOUT], int32_t ndir, const cmx_warm_rain_2m_f32 *d_warm_rain,
+                                           const cmx_thermo_f32 *d_tps, double *grad, double *workspace, float *const tendencies[CMX_SB2006_JAC_NOUT],
+                                           void *stream);
+int32_t cmx_sb2006_warm_rain_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                                           const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                           const double *n_rai, const double *const cotangents[CMX_SB2006_JAC_NOUT], int32_t ndir,
+                                           const cmx_warm_rain_2m_f64 *d_warm_rain, const cmx_thermo_f64 *d_tps, double *grad, double *workspace,
+                                           double *const tendencies[CMX_SB2006_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (23) The derivatives of the 1-moment tendencies (15) with respect to the PARAMETERS: cmx_mp1m_param_jvp_* and cmx_mp1m_param_vjp_*, with the arguments and
+ * the rules of (22) — directions d_mp[d] (cmx_microphysics_1m_*) + d_tps[d] | NULL, jvp[d·4 + o] over cmx_mp1m_jac_out, grad / workspace, NULL members, the
+ * reduction, the launches, bit independence from the other directions and from the split — and the state, `flags`, NaN rule (Float64: also ρ ≤ 0) and statuses
+ * of (15): NULL parameters; the count rule; the flags; param_jvp: n_points = 0 is CMX_OK; NULL columns; then ndir, the tables, the outputs and non-finite
+ * directions as in (22).
+ * INSTANTIATION.  The default-options instantiation of (5) holds nine slope-parameter exponents as compile-time numbers (rain: fall speed, accretion, ice–rain
+ * sink, snow–rain kernel, ventilation; snow: the same without the sink).  It runs — and `tendencies` is bit-identical to cmx_mp1m_tendencies_* — only if the
+ * tendencies entry would select it AND no direction gives one of the nine a non-zero tangent (the size-relation exponents me, Δm, ae, Δa, ve, Δv of rain and
+ * snow do).  Otherwise the run-time-flags instantiation runs for the whole call and `tendencies` agrees to the parity bound, not bit for bit.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_mp1m_param_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho, const float *T,
+                               const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno, int32_t ndir,
+                               const cmx_microphysics_1m_f32 *d_mp, const cmx_thermo_f32 *d_tps, float *const *jvp,
+                               float *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_param_jvp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                               const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                               int32_t ndir, const cmx_microphysics_1m_f64 *d_mp, const cmx_thermo_f64 *d_tps, double *const *jvp,
+                               double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_param_vjp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho, const float *T,
+                               const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno,
+                               const float *const cotangents[CMX_MP1M_JAC_NOUT], int32_t ndir, const cmx_microphysics_1m_f32 *d_mp,
+                               const cmx_thermo_f32 *d_tps, double *grad, double *workspace, float *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+int32_t cmx_mp1m_param_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n_points, const double *rho,
+                               const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
+                               const double *const cotangents[CMX_MP1M_JAC_NOUT], int32_t ndir, const cmx_microphysics_1m_f64 *d_mp,
+                               const cmx_thermo_f64 *d_tps, double *grad, double *workspace, double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1465,6 +1465,122 @@ function warm_rain_vjp_2m!(grad, tendencies, mp::CMP.Microphysics2MParams{WR, No
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (22) the derivatives of the SB2006 warm-rain tendencies with respect to the parameters
+# ----------------------------------------------------------------------------------------------------------------
+const CMX_PARAM_MAX_DIRS = 16
+const CMX_PARAM_VJP_PARTIALS = 1024
+
+# the direction tables of (22): `d_warm_rain` = 1 … 16 warm-rain parameter objects whose fields hold δθ, `d_tps` = nothing (zero) or as many thermodynamics ones
+function _param_directions(d_warm_rain, d_tps)
+    1 <= length(d_warm_rain) <= CMX_PARAM_MAX_DIRS || error("directions: 1 … $(CMX_PARAM_MAX_DIRS) expected")
+    d_tps === nothing || length(d_tps) == length(d_warm_rain) || error("d_tps: nothing or one per direction expected")
+    dw = [pack(_warm_rain(d)) for d in d_warm_rain]
+    dt = d_tps === nothing ? nothing : [CmxThermo(d) for d in d_tps]
+    return dw, dt
+end
+
+"""
+    warm_rain_param_jvp_2m!(jvp, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, d_warm_rain, d_tps = nothing; stream = C_NULL)
+
+The derivative of the tendencies of `warm_rain_jacobian_2m!` with respect to the PARAMETERS along the directions `d_warm_rain[d]` (+ `d_tps[d]`): parameter
+objects of the types of `mp` / `tps` whose fields hold δθ.  `jvp` = `length(d_warm_rain)·4` device columns (or `nothing`s), direction-major in the order
+(dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt).  `tendencies` as there (bit-identical to the tendencies entry unless a direction moves an exponent).
+"""
+function warm_rain_param_jvp_2m!(jvp, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+    d_warm_rain, d_tps = nothing; stream = C_NULL) where {WR, FT}
+    dw, dt = _param_directions(d_warm_rain, d_tps)
+    jvp === nothing || length(jvp) == length(dw) * CMX_SB2006_JAC_NOUT || error("jvp: $(CMX_SB2006_JAC_NOUT) columns (or nothing) per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = GC.@preserve dw dt ccall(_fn("cmx_sb2006_warm_rain_param_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{FT}},
+            Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt), _opt_ptrs(FT, jvp), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_param_jvp")
+    return jvp
+end
+
+"""
+    warm_rain_param_vjp_2m!(grad, workspace, tendencies, mp, tps, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, d_warm_rain, d_tps = nothing; stream = C_NULL)
+
+The gradient of Σ_points Σ_o ḡ_o·out_o along the parameter directions of `warm_rain_param_jvp_2m!`: `grad` = a device array of `length(d_warm_rain)` Float64,
+`workspace` = a device array of `length(d_warm_rain)·CMX_PARAM_VJP_PARTIALS` Float64 owned by the caller, `cotangents` = 4 device columns or `nothing`s (that
+output is not part of the sum).  A deterministic reduction in double: no atomics, the same bits from run to run.
+"""
+function warm_rain_param_vjp_2m!(grad, workspace, tendencies, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, n_lcl,
+    q_rai, n_rai, cotangents, d_warm_rain, d_tps = nothing; stream = C_NULL) where {WR, FT}
+    dw, dt = _param_directions(d_warm_rain, d_tps)
+    length(cotangents) == CMX_SB2006_JAC_NOUT || error("cotangents: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    length(grad) >= length(dw) || error("grad: one Float64 per direction expected")
+    length(workspace) >= length(dw) * CMX_PARAM_VJP_PARTIALS || error("workspace: $(CMX_PARAM_VJP_PARTIALS) Float64 per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)
+    st = GC.@preserve dw dt ccall(_fn("cmx_sb2006_warm_rain_param_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Int32, Ptr{Cvoid}, Ptr{Cvoid},
+            Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), flags, length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai),
+        _dp(FT, n_rai), _ptrs(FT, cotangents), Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt), _dp(Float64, grad),
+        _dp(Float64, workspace), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_sb2006_warm_rain_param_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
+# (23) the derivatives of the 1-moment tendencies with respect to the parameters
+# ----------------------------------------------------------------------------------------------------------------
+# the direction tables of (23): `d_mp` = 1 … 16 Microphysics1MParams whose fields hold δθ, `d_tps` = nothing (zero) or as many thermodynamics ones
+function _param_directions_1m(d_mp, d_tps)
+    1 <= length(d_mp) <= CMX_PARAM_MAX_DIRS || error("directions: 1 … $(CMX_PARAM_MAX_DIRS) expected")
+    d_tps === nothing || length(d_tps) == length(d_mp) || error("d_tps: nothing or one per direction expected")
+    return [pack(d) for d in d_mp], (d_tps === nothing ? nothing : [CmxThermo(d) for d in d_tps])
+end
+
+"""
+    param_jvp_1m!(jvp, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, d_mp, d_tps = nothing; stream = C_NULL)
+
+The derivative of the tendencies of `jacobian_1m!` with respect to the PARAMETERS along the directions `d_mp[d]` (+ `d_tps[d]`).  Rules as for
+`warm_rain_param_jvp_2m!`.
+"""
+function param_jvp_1m!(jvp, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno, d_mp, d_tps = nothing;
+    stream = C_NULL) where {FT}
+    dw, dt = _param_directions_1m(d_mp, d_tps)
+    jvp === nothing || length(jvp) == length(dw) * CMX_MP1M_JAC_NOUT || error("jvp: $(CMX_MP1M_JAC_NOUT) columns (or nothing) per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = GC.@preserve dw dt ccall(_fn("cmx_mp1m_param_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{FT}},
+            Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt), _opt_ptrs(FT, jvp), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_param_jvp")
+    return jvp
+end
+
+"""
+    param_vjp_1m!(grad, workspace, tendencies, mp, tps, ρ, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, d_mp, d_tps = nothing; stream = C_NULL)
+
+The gradient of Σ_points Σ_o ḡ_o·out_o of the 1-moment tendencies along the parameter directions of `param_jvp_1m!`.  Rules as for `warm_rain_param_vjp_2m!`.
+"""
+function param_vjp_1m!(grad, workspace, tendencies, mp::CMP.Microphysics1MParams, tps, ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents,
+    d_mp, d_tps = nothing; stream = C_NULL) where {FT}
+    dw, dt = _param_directions_1m(d_mp, d_tps)
+    length(cotangents) == CMX_MP1M_JAC_NOUT || error("cotangents: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    length(grad) >= length(dw) || error("grad: one Float64 per direction expected")
+    length(workspace) >= length(dw) * CMX_PARAM_VJP_PARTIALS || error("workspace: $(CMX_PARAM_VJP_PARTIALS) Float64 per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = GC.@preserve dw dt ccall(_fn("cmx_mp1m_param_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}}, Int32, Ptr{Cvoid}, Ptr{Cvoid},
+            Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{FT}}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), option_bits(mp), length(ρ), _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai),
+        _dp(FT, q_sno), _ptrs(FT, cotangents), Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt), _dp(Float64, grad),
+        _dp(Float64, workspace), _opt_ptrs(FT, tendencies), stream)
+    _check(st, "cmx_mp1m_param_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (17) products with the Jacobian of the 1-moment tendencies: J v and Jᵀḡ, fused
 # ----------------------------------------------------------------------------------------------------------------
 """
