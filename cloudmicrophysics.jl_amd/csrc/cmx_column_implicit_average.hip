@@ -1,5 +1,5 @@
 // cmx_column_implicit_average.hip — the column steps with the sub-stepped implicit average as tendency operator: per point the average tendency of
-// include/cmx.h §(19) (cmx_jacobian.hpp implicit_average_point) and, in the same pass, the first-order upwind sedimentation of the existing column steps
+// include/cmx.h §(19) (cmx_jacobian.hpp implicit_average_substeps) and, in the same pass, the first-order upwind sedimentation of the existing column steps
 // (cmx_sb2006_column.hip, cmx_mp1m_column.hip) evaluated at the INITIAL state; C-ABI entry points cmx_sb2006_column_implicit_average_sedimentation_* and
 // cmx_mp1m_column_implicit_average_sedimentation_* (include/cmx.h §(20)).  One kernel family for both schemes and both float types:
 //     out_j[k] = fma(top ? 0 : F_j[k+1], g, fma(−F_j[k], g, a_j)),   g = inv_dz[k] / ρ_k
@@ -8,8 +8,8 @@
 // Kernel shape: ONE point per lane in both float types.  The average is bound by VALU issue (hundreds of instructions per pass, nsub·4/K passes),
 // so the 16-byte accesses, the alignment split and the f32x2 pairing of the streaming column kernels buy nothing here; any alignment and any n go through one
 // launch.  A lane
-//   1. reads its seven values and runs the substeps — the loop of implicit_average_point, written a second time below because the averages are needed in
-//      registers and not in memory (implicit_average_point and the kernels that call it are untouched and keep their code);
+//   1. reads its seven values and runs the substeps, the averages left in registers: the loop of implicit_average_substeps (cmx_jacobian.hpp), of which this
+//      kernel keeps a copy because the call was measured slower here (the comment at the loop has the numbers);
 //   2. AFTER the loop evaluates the flux-only function of the scheme (sed_fluxes_of_point, cmx_sb2006_sed.hpp; mp1m_sed_fluxes, cmx_mp1m_vel.hpp) from ρ and
 //      the initial species, which the loop keeps in registers anyway: nothing of the fluxes is live across the point function.  The flux constants are read
 //      through the kernel-argument segment at this point (front_consts, consts_after), in both float types;
@@ -20,16 +20,9 @@
 // The flux options — rain velocity scheme, cloud sedimentation, run-time Γ — are wave-uniform run-time branches around the existing flux functions'
 // instantiations (the same inline code on the same operands: the same bits); the tendency options are template arguments through the average entries' own
 // dispatch (the flags of with_sb2006_jac, with_mp1m_jac).  8 + 4 kernels.  The outputs must not alias the inputs: lane BS − 1 reads the next tile's first point.
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
-#include "../../include/cmx.h"
-#include "cmx_launch.hpp"
-#include "cmx_mp1m_jacobian.hpp"
-#include "cmx_mp1m_vel.hpp"
-#include "cmx_sb2006_jacobian.hpp"
-#include "cmx_sb2006_sed.hpp"
+// The flux side of each scheme, the kernel-argument struct and the entry layer (checks, constants) are cmx_column_implicit.hpp's, shared with
+// cmx_column_implicit_step.hip; here are the kernel, its IO struct, its launch and the extern "C" functions.
+#include "cmx_column_implicit.hpp"
 
 namespace cmx {
 
@@ -48,71 +41,9 @@ template <typename FT> struct ImplicitColIO {
     FastDivU32 lev_div;    // division by n_lev for flat indices below 2³² (cmx_launch.hpp fastdiv)
 };
 
-// ---- the flux side of a scheme: its constants (kernel argument KA: the tendency constants FIRST, where the scheme's eval reads them through front_consts),
-// 1/ρ as the scheme's column entry forms it, and the fluxes of the four species of one raw point in the order of the outputs -------------------------------
-template <typename FT, bool LIMITED> struct SbFlux {
-    struct KA { SbConsts<FT> c; CloudVelConsts<FT> cv; };
-    static constexpr int precip(int p) { return p == 0 ? CMX_SB2006_JAC_DQ_RAI_DT : -1; }      // the species of io.precip[p], −1: none
-    // sb2006_point: ρ^(-1/2) of the clamped ρ, squared
-    static __device__ __forceinline__ FT inv_rho(FT rho) {
-        const FT rs_rho = Math<FT>::rsqrt(max0(rho));
-        return rs_rho * rs_rho;
-    }
-    // without cloud sedimentation q_lcl and n_lcl do not fall: their outputs are the averages themselves
-    static __device__ __forceinline__ bool falls(int q, const int32_t (&opt)[2]) { return q >= CMX_SB2006_JAC_DQ_RAI_DT || opt[1] != 0; }
-    template <int VEL, bool CLOUD, typename C>
-    static __device__ __forceinline__ void one(const C &c, const CloudVelConsts<FT> &cv, FT rho, const FT (&s)[4], FT (&F)[4]) {
-        const SedFlux<FT> f = sed_fluxes_of_point<FT, LIMITED, VEL, CLOUD>(c, cv, rho, s[0], s[1], s[2], s[3]);
-        F[CMX_SB2006_JAC_DQ_LCL_DT] = f.q_lcl;
-        F[CMX_SB2006_JAC_DN_LCL_DT] = f.n_lcl;
-        F[CMX_SB2006_JAC_DQ_RAI_DT] = f.q_rai;
-        F[CMX_SB2006_JAC_DN_RAI_DT] = f.n_rai;
-    }
-    // s: q_lcl, n_lcl, q_rai, n_rai.  `dep`: the value the constants wait for (consts_after)
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
-        const auto &c = consts_after(front_consts<FT, true>(ka), dep).c;
-        if (opt[0] == VEL_SB) {
-            if (opt[1]) one<VEL_SB, true>(c, ka.cv, rho, s, F);
-            else one<VEL_SB, false>(c, ka.cv, rho, s, F);
-        } else if (opt[0] == VEL_CHEN) {
-            if (opt[1]) one<VEL_CHEN, true>(c, ka.cv, rho, s, F);
-            else one<VEL_CHEN, false>(c, ka.cv, rho, s, F);
-        } else {
-            if (opt[1]) one<VEL_CHEN_GEN, true>(c, ka.cv, rho, s, F);
-            else one<VEL_CHEN_GEN, false>(c, ka.cv, rho, s, F);
-        }
-    }
-};
-
-template <typename FT> struct Mp1mFlux {
-    struct KA { Mp1mConsts<FT> c; Vel1mConsts<FT> vc; };
-    static constexpr int precip(int p) { return p == 0 ? CMX_MP1M_JAC_DQ_RAI_DT : CMX_MP1M_JAC_DQ_SNO_DT; }
-    static __device__ __forceinline__ FT inv_rho(FT rho) { return Math<FT>::rcp(max0(rho)); }
-    static __device__ __forceinline__ bool falls(int, const int32_t (&)[2]) { return true; }
-    // s: q_lcl, q_icl, q_rai, q_sno
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
-        const auto &vc = consts_after(front_consts<FT, true>(ka), dep).vc;
-        SedFlux4<FT> f;
-        if (opt[0]) f = mp1m_sed_fluxes<FT, true>(vc, rho, s[0], s[1], s[2], s[3]);
-        else f = mp1m_sed_fluxes<FT, false>(vc, rho, s[0], s[1], s[2], s[3]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) F[q] = f.f[q];
-    }
-};
-
-// The ONE kernel argument: the constants first (the scheme's eval and the flux functions read them at offset 0 of the kernel-argument segment), then the
-// average entry's arguments and the column geometry.  One struct, so that everything the lane needs only AFTER the substeps — the output pointers, the
-// geometry, the flux options — can be read through the kernel-argument pointer at that point (consts_after) instead
-// of waiting in SGPRs, and from there in VGPR lanes, across the point function: the Float64 instantiations have no register to spare.
-template <typename S, typename FX, typename FT, int K> struct ImplicitColArgs {
-    typename FX::KA ka;
-    ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> a;
-    ImplicitColIO<FT> io;
-};
-
 // S: the scheme of the average entries (SbJac<…>, Mp1mJac<…>); FX: its flux side.
 template <typename S, typename FX, typename FT, int K, int BS>
-__global__ __launch_bounds__(BS) void implicit_average_column_kernel(const ImplicitColArgs<S, FX, FT, K> k0) {
+__global__ __launch_bounds__(BS) void implicit_average_column_kernel(const ImplicitColumnArgs<S, FX, FT, K, ImplicitColIO<FT>> k0) {
     using M = Math<FT>;
     constexpr int N = S::NOUT, S0 = 1 + S::SPECIES0;
     static_assert(N == 4 && S0 + N == S::NWRT + 1, "implicit_average_column_kernel: four species, the last four inputs of the point");
@@ -137,8 +68,11 @@ __global__ __launch_bounds__(BS) void implicit_average_column_kernel(const Impli
 #pragma unroll
         for (int q = 0; q < N; ++q) s0[q] = x[S0 + q];
         if (threadIdx.x < OWN) {
-            // ---- the substeps: implicit_average_point (cmx_jacobian.hpp) operation for operation, the averages kept in registers instead of stored.  A
-            // second copy on purpose: as a value-returning core called from both, the existing kernel would have to be shown to keep its code in every instantiation
+            // ---- the substeps: implicit_average_substeps (cmx_jacobian.hpp) operation for operation.  The one copy of that loop, kept because it was
+            // measured: with the call in its place this kernel compiles to the same instructions on permuted registers (same VGPR / SGPR / spill counts)
+            // and runs slower at 1e7 points — Float64 SB2006 3.890 → 3.947 ms, 1-moment 4.784 → 4.849 ms at nsub = 4 against a spread of 0.010 / 0.012 ms;
+            // with s0 handed to the core the same.  The same code at another address runs as before, so it is not placement (HISTORY.md has the table).
+            // tests/test_column_implicit_average_gpu.py holds this copy to the average entry in every bit.
             const bool limit = a.step_flags & CMX_STEP_NONNEGATIVE;
 #pragma unroll 1
             for (int32_t sub = 0; sub < a.nsub; ++sub) {
@@ -222,79 +156,16 @@ template <typename FT> static ImplicitColIO<FT> make_io(const FT *inv_dz, FT *pr
     return io;
 }
 
-// Statuses: those of cmx_sb2006_column_tendencies_sedimentation_* in its order, up to and including the columns and the limiter / fall-speed tables; then
-// Δt, nsub and the step flags as the average entries check them.
-template <typename FT, typename WR, typename TH, typename VL, typename ST>
-static int32_t sb2006_entry(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags, int64_t n_col,
-                            int32_t n_lev, const FT *inv_dz, const FT *const (&in)[7], FT *const (&out)[4], FT *precip, void *stream) {
-    if (!wr || !tps || !vel || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (flags & ~(uint32_t)(CMX_SB2006_LIMITED | CMX_VEL_SB2006 | CMX_VEL_CHEN2022)) return CMX_ERR_BAD_ARG;
-    const bool sbv = flags & CMX_VEL_SB2006, chv = flags & CMX_VEL_CHEN2022;
-    if (sbv == chv) return CMX_ERR_BAD_ARG;                      // exactly one rain fall-speed scheme
-    if (n_col > kMaxPoints / n_lev) return CMX_ERR_UNSUPPORTED;  // n_col·n_lev must fit one launch (cmx_launch.hpp)
-    const int64_t n = n_col * (int64_t)n_lev;
-    if (n == 0) return CMX_OK;
-    if (!inv_dz) return CMX_ERR_BAD_ARG;
-    for (const FT *p : in)
-        if (!p) return CMX_ERR_BAD_ARG;
-    for (FT *p : out)
-        if (!p) return CMX_ERR_BAD_ARG;
-    const bool limited = flags & CMX_SB2006_LIMITED;
-    if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
-    if (sbv && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;      // the not-limited SB2006 fall speed needs aR < bR
-    if (!implicit_average_step_ok<FT>(dt, nsub, step_flags)) return CMX_ERR_BAD_ARG;
-    constexpr int K = kImplicitAvgK<FT>;
-    ImplicitAverageArgs<FT, K, CMX_SB2006_JAC_NOUT, CMX_SB2006_JAC_NWRT> a;
-    make_implicit_average_args(a, in, SbJac<false, false>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, &out[0]);
-    const int velk = sbv ? VEL_SB : chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1) or the general instantiation (cmx_math.hpp ChenGamma)
-    const ImplicitColIO<FT> io = make_io<FT>(inv_dz, precip, nullptr, n, n_lev, velk, cloud_vel != nullptr);
-    // the constants of the column entry: those of the average entries (with_sb2006_jac) plus the fall-speed members, which no tendency reads
-    const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
-    CloudVelConsts<FT> cv{};
-    if (cloud_vel) cv = make_cloud_vel_consts<FT>(wr->seifert_beheng.pdf_c, *cloud_vel);
-    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t {
-        using S = SbJac<decltype(L)::value, decltype(I)::value>;
-        using FX = SbFlux<FT, decltype(L)::value>;
-        const ImplicitColArgs<S, FX, FT, K> k{{c, cv}, a, io};
-        launch_grid(implicit_average_column_kernel<S, FX, FT, K, kImplColBS>, column_grid(n), dim3(kImplColBS), 0, reinterpret_cast<hipStream_t>(stream), k);
+// the callable of the entry layer (cmx_column_implicit.hpp): the IO struct and the launch
+template <typename FT> static auto column_launch(const FT *inv_dz, FT *precip0, FT *precip1, int64_t n_col, int32_t n_lev, void *stream) {
+    return [=](auto scheme, auto fx, const auto &ka, const auto &a, int32_t opt0, int32_t opt1) -> int32_t {
+        constexpr int K = kImplicitAvgK<FT>;
+        const int64_t n = n_col * (int64_t)n_lev;
+        const ImplicitColumnArgs<decltype(scheme), decltype(fx), FT, K, ImplicitColIO<FT>> k{ka, a, make_io<FT>(inv_dz, precip0, precip1, n, n_lev, opt0, opt1)};
+        launch_grid(implicit_average_column_kernel<decltype(scheme), decltype(fx), FT, K, kImplColBS>, column_grid(n), dim3(kImplColBS), 0,
+                    reinterpret_cast<hipStream_t>(stream), k);
         return launched();
-    }, flag(limited), flag(sb_integer_exponents(*wr)));
-}
-
-// Statuses: those of cmx_mp1m_column_tendencies_sedimentation_* in its order, up to and including the columns (a single snow-shape bit, which that entry
-// accepts, is CMX_ERR_UNSUPPORTED where that entry decodes the shape); then Δt, nsub and the step flags as the average entries check them.
-template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
-static int32_t mp1m_entry(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags,
-                          int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, FT *const *out, FT *precip_rai, FT *precip_sno,
-                          void *stream) {
-    if (!mp || !tps || !stokes || !chen_rain || !chen_ice || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    const uint32_t shape_bits = flags & (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE);
-    if (shape_bits == (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE)) return CMX_ERR_BAD_ARG;
-    if (shape_bits) return CMX_ERR_UNSUPPORTED;
-    if (const int32_t st = check_flags_1m(flags)) return st;
-    if (n_col > kMaxPoints / n_lev) return CMX_ERR_UNSUPPORTED;  // n_col·n_lev must fit one launch (cmx_launch.hpp)
-    const int64_t n = n_col * (int64_t)n_lev;
-    if (n == 0) return CMX_OK;
-    if (!inv_dz || !in || !out) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < 7; ++j)
-        if (!in[j]) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < 4; ++j)
-        if (!out[j]) return CMX_ERR_BAD_ARG;
-    if (!implicit_average_step_ok<FT>(dt, nsub, step_flags)) return CMX_ERR_BAD_ARG;
-    constexpr int K = kImplicitAvgK<FT>;
-    const FT *const cols[7] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6]};
-    ImplicitAverageArgs<FT, K, CMX_MP1M_JAC_NOUT, CMX_MP1M_JAC_NWRT> a;
-    make_implicit_average_args(a, cols, Mp1mJac<kDefaultFlags>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, out);
-    bool general = false;
-    Vel1mConsts<FT> vc = make_vel1m_consts<FT>(*mp, chen_rain, &general);
-    add_sedimentation_consts<FT>(vc, *mp, stokes, chen_ice);
-    const ImplicitColIO<FT> io = make_io<FT>(inv_dz, precip_rai, precip_sno, n, n_lev, general, 0);
-    return with_mp1m_jac<FT>(*mp, *tps, flags, [&](const Mp1mConsts<FT> &c, auto scheme) -> int32_t {
-        using S = decltype(scheme);
-        const ImplicitColArgs<S, Mp1mFlux<FT>, FT, K> k{{c, vc}, a, io};
-        launch_grid(implicit_average_column_kernel<S, Mp1mFlux<FT>, FT, K, kImplColBS>, column_grid(n), dim3(kImplColBS), 0, reinterpret_cast<hipStream_t>(stream), k);
-        return launched();
-    });
+    };
 }
 
 }  // namespace cmx
@@ -306,8 +177,9 @@ int32_t cmx_sb2006_column_implicit_average_sedimentation_f32(const cmx_warm_rain
                                                              const float *inv_dz, const float *rho, const float *T, const float *q_tot, const float *q_lcl,
                                                              const float *n_lcl, const float *q_rai, const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt, float *dn_rai_dt,
                                                              float *precip_flux, void *stream) {
-    return cmx::sb2006_entry<float>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai},
-                                    {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt}, precip_flux, stream);
+    return cmx::sb2006_implicit_column_entry<float>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz,
+                                                    {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt},
+                                                    cmx::column_launch<float>(inv_dz, precip_flux, nullptr, n_col, n_lev, stream));
 }
 int32_t cmx_sb2006_column_implicit_average_sedimentation_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
                                                              const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags,
@@ -315,19 +187,22 @@ int32_t cmx_sb2006_column_implicit_average_sedimentation_f64(const cmx_warm_rain
                                                              const double *inv_dz, const double *rho, const double *T, const double *q_tot, const double *q_lcl,
                                                              const double *n_lcl, const double *q_rai, const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt, double *dq_rai_dt, double *dn_rai_dt,
                                                              double *precip_flux, void *stream) {
-    return cmx::sb2006_entry<double>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai},
-                                     {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt}, precip_flux, stream);
+    return cmx::sb2006_implicit_column_entry<double>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz,
+                                                     {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt},
+                                                     cmx::column_launch<double>(inv_dz, precip_flux, nullptr, n_col, n_lev, stream));
 }
 int32_t cmx_mp1m_column_implicit_average_sedimentation_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
                                                            const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags,
                                                            double dt, int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz,
                                                            const float *const *in, float *const *out, float *precip_rai, float *precip_sno, void *stream) {
-    return cmx::mp1m_entry<float>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out, precip_rai, precip_sno, stream);
+    return cmx::mp1m_implicit_column_entry<float>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out,
+                                                cmx::column_launch<float>(inv_dz, precip_rai, precip_sno, n_col, n_lev, stream));
 }
 int32_t cmx_mp1m_column_implicit_average_sedimentation_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
                                                            const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags,
                                                            double dt, int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz,
                                                            const double *const *in, double *const *out, double *precip_rai, double *precip_sno, void *stream) {
-    return cmx::mp1m_entry<double>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out, precip_rai, precip_sno, stream);
+    return cmx::mp1m_implicit_column_entry<double>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out,
+                                                 cmx::column_launch<double>(inv_dz, precip_rai, precip_sno, n_col, n_lev, stream));
 }
 }

@@ -10,9 +10,9 @@
 // Kernel shape: the recurrence runs down a column, so a workgroup OWNS a contiguous range of whole columns (cols_per_wg of them, a host-side tuning number
 // that no result depends on) and no workgroup ever waits for another.  It walks its range in chunks of BS flat points from the highest index to the lowest.
 // Per chunk
-//   1. parallel — one point per lane, as in cmx_column_implicit_average.hip: the substeps (the loop of implicit_average_point a third time, for the reason
-//      given there), then the (F, w) flux function of the scheme (sed_fluxes_w_of_point, mp1m_sed_fluxes_w: the operations of the flux-only functions on the
-//      same operands).  The lane forms A and B, stores them to LDS at once and keeps fma(−F, g, a), g and r: the Float64 instantiations have no register to
+//   1. parallel — one point per lane, as in cmx_column_implicit_average.hip: the substeps (implicit_average_substeps, cmx_jacobian.hpp: the loop
+//      of the average entry itself), then the (F, w) flux function of the scheme (sed_fluxes_w_of_point, mp1m_sed_fluxes_w: the operations of the
+//      flux-only functions on the same operands).  The lane forms A and B, stores them to LDS at once and keeps fma(−F, g, a), g and r: the Float64 instantiations have no register to
 //      spare.  Barrier.
 //   2. serial — one lane per (column segment inside the chunk, species) runs G = fma(A, G_up, B) down its segment: one dependent fma per level, the A and B
 //      reads do not depend on the chain.  A segment that starts below a column top takes G_up from the carry of the chunk before (LDS, two slots used in
@@ -21,16 +21,9 @@
 //   3. parallel — every lane reads G_{k+1} and stores `out`; the lane at level 0 stores G_0.
 // The flux options are wave-uniform run-time branches, the tendency options template arguments through the average entries' own dispatch, as in the sibling:
 // 8 + 4 kernels.  The outputs must not alias the inputs (the entries keep the rule of §(20)).
-#include <hip/hip_runtime.h>
-
-#include <type_traits>
-
-#include "../../include/cmx.h"
-#include "cmx_launch.hpp"
-#include "cmx_mp1m_jacobian.hpp"
-#include "cmx_mp1m_vel.hpp"
-#include "cmx_sb2006_jacobian.hpp"
-#include "cmx_sb2006_sed.hpp"
+// The flux side of each scheme, the kernel-argument struct and the entry layer — so the statuses of the §(20) entries, in their order — are
+// cmx_column_implicit.hpp's, shared with the sibling; here are the kernel, its IO struct, its launch and the extern "C" functions.
+#include "cmx_column_implicit.hpp"
 
 namespace cmx {
 
@@ -53,65 +46,10 @@ template <typename FT> struct ImplicitStepIO {
     FastDivU32 lev_div;    // division by n_lev (cmx_launch.hpp fastdiv)
 };
 
-// ---- the flux side of a scheme, with fall speeds: the constants (tendency constants FIRST), 1/ρ as the scheme's column entry forms it, and (F, w) of the four
-// species of one raw point in the order of the outputs -----------------------------------------------------------------------------------------------------
-template <typename FT, bool LIMITED> struct SbFluxW {
-    struct KA { SbConsts<FT> c; CloudVelConsts<FT> cv; };
-    static constexpr int precip(int p) { return p == 0 ? CMX_SB2006_JAC_DQ_RAI_DT : -1; }
-    static __device__ __forceinline__ FT inv_rho(FT rho) {
-        const FT rs_rho = Math<FT>::rsqrt(max0(rho));
-        return rs_rho * rs_rho;
-    }
-    static __device__ __forceinline__ bool falls(int q, const int32_t (&opt)[2]) { return q >= CMX_SB2006_JAC_DQ_RAI_DT || opt[1] != 0; }
-    template <int VEL, bool CLOUD, typename C>
-    static __device__ __forceinline__ void one(const C &c, const CloudVelConsts<FT> &cv, FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
-        const SedFluxW<FT> f = sed_fluxes_w_of_point<FT, LIMITED, VEL, CLOUD>(c, cv, rho, s[0], s[1], s[2], s[3]);
-        F[CMX_SB2006_JAC_DQ_LCL_DT] = f.F.q_lcl; w[CMX_SB2006_JAC_DQ_LCL_DT] = f.w.q_lcl;
-        F[CMX_SB2006_JAC_DN_LCL_DT] = f.F.n_lcl; w[CMX_SB2006_JAC_DN_LCL_DT] = f.w.n_lcl;
-        F[CMX_SB2006_JAC_DQ_RAI_DT] = f.F.q_rai; w[CMX_SB2006_JAC_DQ_RAI_DT] = f.w.q_rai;
-        F[CMX_SB2006_JAC_DN_RAI_DT] = f.F.n_rai; w[CMX_SB2006_JAC_DN_RAI_DT] = f.w.n_rai;
-    }
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
-        const auto &c = consts_after(front_consts<FT, true>(ka), dep).c;
-        if (opt[0] == VEL_SB) {
-            if (opt[1]) one<VEL_SB, true>(c, ka.cv, rho, s, F, w);
-            else one<VEL_SB, false>(c, ka.cv, rho, s, F, w);
-        } else if (opt[0] == VEL_CHEN) {
-            if (opt[1]) one<VEL_CHEN, true>(c, ka.cv, rho, s, F, w);
-            else one<VEL_CHEN, false>(c, ka.cv, rho, s, F, w);
-        } else {
-            if (opt[1]) one<VEL_CHEN_GEN, true>(c, ka.cv, rho, s, F, w);
-            else one<VEL_CHEN_GEN, false>(c, ka.cv, rho, s, F, w);
-        }
-    }
-};
-
-template <typename FT> struct Mp1mFluxW {
-    struct KA { Mp1mConsts<FT> c; Vel1mConsts<FT> vc; };
-    static constexpr int precip(int p) { return p == 0 ? CMX_MP1M_JAC_DQ_RAI_DT : CMX_MP1M_JAC_DQ_SNO_DT; }
-    static __device__ __forceinline__ FT inv_rho(FT rho) { return Math<FT>::rcp(max0(rho)); }
-    static __device__ __forceinline__ bool falls(int, const int32_t (&)[2]) { return true; }
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
-        const auto &vc = consts_after(front_consts<FT, true>(ka), dep).vc;
-        SedFluxW4<FT> f;
-        if (opt[0]) f = mp1m_sed_fluxes_w<FT, true>(vc, rho, s[0], s[1], s[2], s[3]);
-        else f = mp1m_sed_fluxes_w<FT, false>(vc, rho, s[0], s[1], s[2], s[3]);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { F[q] = f.f[q]; w[q] = f.w[q]; }
-    }
-};
-
-// The ONE kernel argument, the constants first (front_consts), as in cmx_column_implicit_average.hip
-template <typename S, typename FX, typename FT, int K> struct ImplicitStepArgs {
-    typename FX::KA ka;
-    ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> a;
-    ImplicitStepIO<FT> io;
-};
-
 // Float32: compiled for four waves per SIMD, where cmx_column_implicit_average.hip runs (without the request 130–134 registers, three waves: 1-moment 0.82 → 0.76 ms,
 // SB2006 0.69 → 0.66 ms per 1e7 points at nsub = 1; no vector register spills, no scratch instruction).  Float64 sits at one wave per SIMD either way.
 template <typename S, typename FX, typename FT, int K, int BS>
-__global__ __launch_bounds__(BS, sizeof(FT) == 4 ? 4 : 1) void implicit_sedimentation_step_kernel(const ImplicitStepArgs<S, FX, FT, K> k0) {
+__global__ __launch_bounds__(BS, sizeof(FT) == 4 ? 4 : 1) void implicit_sedimentation_step_kernel(const ImplicitColumnArgs<S, FX, FT, K, ImplicitStepIO<FT>> k0) {
     using M = Math<FT>;
     constexpr int N = S::NOUT, S0 = 1 + S::SPECIES0;
     static_assert(N == 4 && S0 + N == S::NWRT + 1, "implicit_sedimentation_step_kernel: four species, the last four inputs of the point");
@@ -139,28 +77,7 @@ __global__ __launch_bounds__(BS, sizeof(FT) == 4 ? 4 : 1) void implicit_sediment
             for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
 #pragma unroll
             for (int q = 0; q < N; ++q) s0[q] = x[S0 + q];
-            // ---- the substeps: implicit_average_point (cmx_jacobian.hpp) operation for operation, the averages kept in registers
-            const bool limit = a.step_flags & CMX_STEP_NONNEGATIVE;
-#pragma unroll 1
-            for (int32_t sub = 0; sub < a.nsub; ++sub) {
-                FT r[N], d[N];
-                implicit_solve<S, FT, K>(k0.ka.c, a.wrt, a.h, x, r);
-                const auto poison = S::poison(x);
-#pragma unroll
-                for (int q = 0; q < N; ++q) {
-                    const FT s = x[S0 + q];
-                    FT sn = s + S::out(r[q], poison) * a.h;
-                    if (limit) {
-                        const FT lo = s < FT(0) ? s : FT(0);
-                        sn = sn < lo ? lo : sn;
-                    }
-                    d[q] = (sn - s) * a.inv_h;
-                    x[S0 + q] = sn;
-                }
-                if constexpr (S::TEMP >= 0) x[1 + S::TEMP] = x[1 + S::TEMP] + S::heating(a.Lv, a.Ls, d) * a.h;
-            }
-#pragma unroll
-            for (int q = 0; q < N; ++q) avg[q] = (x[S0 + q] - s0[q]) * a.inv_dt;
+            implicit_average_substeps<S, FT, K>(k0.ka.c, a, x, avg);
             // ---- fluxes and fall speeds of the INITIAL state
             {
                 const auto &kq = consts_after(front_consts<FT, true>(k0), avg[N - 1]);
@@ -263,76 +180,15 @@ static ImplicitStepIO<FT> make_io(const FT *inv_dz, FT *precip0, FT *precip1, in
 // (n_col ≤ kMaxPoints / n_lev and at least 16 points per workgroup — n_lev ≥ 16, or ≥ 512 columns of fewer levels — keep the grid inside HIP's 2^31 − 1)
 template <typename FT> static dim3 step_grid(const ImplicitStepIO<FT> &io) { return dim3((unsigned)tile_grid(io.n_col, io.cols_per_wg)); }
 
-// Statuses: those of cmx_sb2006_column_implicit_average_sedimentation_* in its order.
-template <typename FT, typename WR, typename TH, typename VL, typename ST>
-static int32_t sb2006_entry(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags, int64_t n_col,
-                            int32_t n_lev, const FT *inv_dz, const FT *const (&in)[7], FT *const (&out)[4], FT *precip, void *stream) {
-    if (!wr || !tps || !vel || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (flags & ~(uint32_t)(CMX_SB2006_LIMITED | CMX_VEL_SB2006 | CMX_VEL_CHEN2022)) return CMX_ERR_BAD_ARG;
-    const bool sbv = flags & CMX_VEL_SB2006, chv = flags & CMX_VEL_CHEN2022;
-    if (sbv == chv) return CMX_ERR_BAD_ARG;                      // exactly one rain fall-speed scheme
-    if (n_col > kMaxPoints / n_lev) return CMX_ERR_UNSUPPORTED;  // n_col·n_lev must fit one launch (cmx_launch.hpp)
-    const int64_t n = n_col * (int64_t)n_lev;
-    if (n == 0) return CMX_OK;
-    if (!inv_dz) return CMX_ERR_BAD_ARG;
-    for (const FT *p : in)
-        if (!p) return CMX_ERR_BAD_ARG;
-    for (FT *p : out)
-        if (!p) return CMX_ERR_BAD_ARG;
-    const bool limited = flags & CMX_SB2006_LIMITED;
-    if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;      // clamp_ordered needs ordered limiter pairs
-    if (sbv && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;      // the not-limited SB2006 fall speed needs aR < bR
-    if (!implicit_average_step_ok<FT>(dt, nsub, step_flags)) return CMX_ERR_BAD_ARG;
-    constexpr int K = kImplicitAvgK<FT>;
-    ImplicitAverageArgs<FT, K, CMX_SB2006_JAC_NOUT, CMX_SB2006_JAC_NWRT> a;
-    make_implicit_average_args(a, in, SbJac<false, false>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, &out[0]);
-    const int velk = sbv ? VEL_SB : chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1) or the general instantiation (cmx_math.hpp ChenGamma)
-    const ImplicitStepIO<FT> io = make_io<FT>(inv_dz, precip, nullptr, n_col, n_lev, velk, cloud_vel != nullptr, dt);
-    const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
-    CloudVelConsts<FT> cv{};
-    if (cloud_vel) cv = make_cloud_vel_consts<FT>(wr->seifert_beheng.pdf_c, *cloud_vel);
-    return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto L, auto I) -> int32_t {
-        using S = SbJac<decltype(L)::value, decltype(I)::value>;
-        using FX = SbFluxW<FT, decltype(L)::value>;
-        const ImplicitStepArgs<S, FX, FT, K> k{{c, cv}, a, io};
-        launch_grid(implicit_sedimentation_step_kernel<S, FX, FT, K, kImplStepBS>, step_grid(io), dim3(kImplStepBS), 0, reinterpret_cast<hipStream_t>(stream), k);
+// the callable of the entry layer (cmx_column_implicit.hpp): the IO struct and the launch
+template <typename FT> static auto step_launch(const FT *inv_dz, FT *precip0, FT *precip1, int64_t n_col, int32_t n_lev, double dt, void *stream) {
+    return [=](auto scheme, auto fx, const auto &ka, const auto &a, int32_t opt0, int32_t opt1) -> int32_t {
+        constexpr int K = kImplicitAvgK<FT>;
+        const ImplicitColumnArgs<decltype(scheme), decltype(fx), FT, K, ImplicitStepIO<FT>> k{ka, a, make_io<FT>(inv_dz, precip0, precip1, n_col, n_lev, opt0, opt1, dt)};
+        launch_grid(implicit_sedimentation_step_kernel<decltype(scheme), decltype(fx), FT, K, kImplStepBS>, step_grid(k.io), dim3(kImplStepBS), 0,
+                    reinterpret_cast<hipStream_t>(stream), k);
         return launched();
-    }, flag(limited), flag(sb_integer_exponents(*wr)));
-}
-
-// Statuses: those of cmx_mp1m_column_implicit_average_sedimentation_* in its order.
-template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
-static int32_t mp1m_entry(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags,
-                          int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, FT *const *out, FT *precip_rai, FT *precip_sno,
-                          void *stream) {
-    if (!mp || !tps || !stokes || !chen_rain || !chen_ice || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    const uint32_t shape_bits = flags & (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE);
-    if (shape_bits == (CMX_1M_SED_SNOW_OBLATE | CMX_1M_SED_SNOW_PROLATE)) return CMX_ERR_BAD_ARG;
-    if (shape_bits) return CMX_ERR_UNSUPPORTED;
-    if (const int32_t st = check_flags_1m(flags)) return st;
-    if (n_col > kMaxPoints / n_lev) return CMX_ERR_UNSUPPORTED;  // n_col·n_lev must fit one launch (cmx_launch.hpp)
-    const int64_t n = n_col * (int64_t)n_lev;
-    if (n == 0) return CMX_OK;
-    if (!inv_dz || !in || !out) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < 7; ++j)
-        if (!in[j]) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < 4; ++j)
-        if (!out[j]) return CMX_ERR_BAD_ARG;
-    if (!implicit_average_step_ok<FT>(dt, nsub, step_flags)) return CMX_ERR_BAD_ARG;
-    constexpr int K = kImplicitAvgK<FT>;
-    const FT *const cols[7] = {in[0], in[1], in[2], in[3], in[4], in[5], in[6]};
-    ImplicitAverageArgs<FT, K, CMX_MP1M_JAC_NOUT, CMX_MP1M_JAC_NWRT> a;
-    make_implicit_average_args(a, cols, Mp1mJac<kDefaultFlags>::SPECIES0, dt, nsub, step_flags, (FT)tps->LH_v0, (FT)tps->LH_s0, (FT)tps->cp_d, out);
-    bool general = false;
-    Vel1mConsts<FT> vc = make_vel1m_consts<FT>(*mp, chen_rain, &general);
-    add_sedimentation_consts<FT>(vc, *mp, stokes, chen_ice);
-    const ImplicitStepIO<FT> io = make_io<FT>(inv_dz, precip_rai, precip_sno, n_col, n_lev, general, 0, dt);
-    return with_mp1m_jac<FT>(*mp, *tps, flags, [&](const Mp1mConsts<FT> &c, auto scheme) -> int32_t {
-        using S = decltype(scheme);
-        const ImplicitStepArgs<S, Mp1mFluxW<FT>, FT, K> k{{c, vc}, a, io};
-        launch_grid(implicit_sedimentation_step_kernel<S, Mp1mFluxW<FT>, FT, K, kImplStepBS>, step_grid(io), dim3(kImplStepBS), 0, reinterpret_cast<hipStream_t>(stream), k);
-        return launched();
-    });
+    };
 }
 
 }  // namespace cmx
@@ -343,27 +199,31 @@ int32_t cmx_sb2006_column_implicit_step_f32(const cmx_warm_rain_2m_f32 *warm_rai
                                             int32_t n_lev, const float *inv_dz, const float *rho, const float *T, const float *q_tot, const float *q_lcl,
                                             const float *n_lcl, const float *q_rai, const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt,
                                             float *dn_rai_dt, float *precip_flux, void *stream) {
-    return cmx::sb2006_entry<float>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai},
-                                    {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt}, precip_flux, stream);
+    return cmx::sb2006_implicit_column_entry<float>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz,
+                                                    {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt},
+                                                    cmx::step_launch<float>(inv_dz, precip_flux, nullptr, n_col, n_lev, dt, stream));
 }
 int32_t cmx_sb2006_column_implicit_step_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
                                             const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, double dt, int32_t nsub, uint32_t step_flags, int64_t n_col,
                                             int32_t n_lev, const double *inv_dz, const double *rho, const double *T, const double *q_tot, const double *q_lcl,
                                             const double *n_lcl, const double *q_rai, const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt,
                                             double *dq_rai_dt, double *dn_rai_dt, double *precip_flux, void *stream) {
-    return cmx::sb2006_entry<double>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai},
-                                     {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt}, precip_flux, stream);
+    return cmx::sb2006_implicit_column_entry<double>(warm_rain, tps, vel, cloud_vel, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz,
+                                                     {rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai}, {dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt},
+                                                     cmx::step_launch<double>(inv_dz, precip_flux, nullptr, n_col, n_lev, dt, stream));
 }
 int32_t cmx_mp1m_column_implicit_step_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
                                           const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, double dt,
                                           int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *const *in,
                                           float *const *out, float *precip_rai, float *precip_sno, void *stream) {
-    return cmx::mp1m_entry<float>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out, precip_rai, precip_sno, stream);
+    return cmx::mp1m_implicit_column_entry<float>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out,
+                                                  cmx::step_launch<float>(inv_dz, precip_rai, precip_sno, n_col, n_lev, dt, stream));
 }
 int32_t cmx_mp1m_column_implicit_step_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
                                           const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, double dt,
                                           int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *const *in,
                                           double *const *out, double *precip_rai, double *precip_sno, void *stream) {
-    return cmx::mp1m_entry<double>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out, precip_rai, precip_sno, stream);
+    return cmx::mp1m_implicit_column_entry<double>(mp, tps, stokes, chen_rain, chen_ice, flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, in, out,
+                                                   cmx::step_launch<double>(inv_dz, precip_rai, precip_sno, n_col, n_lev, dt, stream));
 }
 }

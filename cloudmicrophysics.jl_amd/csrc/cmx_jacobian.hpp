@@ -648,10 +648,11 @@ inline bool make_implicit_average_args(ImplicitAverageArgs<FT, K, NOUT, NWRT> &a
     return any;
 }
 
-// The substeps of one point and its stores: the body of the kernel's lane and of the host loop.  x: the point as the kernel read it; the species and T
-// (x[1 + S::TEMP], if the scheme has one) advance in it.
+// The substeps of one point, the averages returned in registers: the loop of implicit_average_kernel, of implicit_sedimentation_step_kernel
+// (cmx_column_implicit_step.hip) and of the host loop.  (implicit_average_column_kernel, cmx_column_implicit_average.hip, keeps a copy: the call was measured
+// slower there.  A change here is a change there.)  x: the point as the kernel read it; the species and T (x[1 + S::TEMP], if the scheme has one) advance in it.
 template <typename S, typename FT, int K, typename C>
-__device__ __forceinline__ void implicit_average_point(const C &c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> &a, FT (&x)[S::NWRT + 1], int64_t i) {
+__device__ __forceinline__ void implicit_average_substeps(const C &c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> &a, FT (&x)[S::NWRT + 1], FT (&avg)[S::NOUT]) {
     constexpr int N = S::NOUT, S0 = 1 + S::SPECIES0;
     const bool limit = a.step_flags & CMX_STEP_NONNEGATIVE;
     FT s0[N];
@@ -676,8 +677,17 @@ __device__ __forceinline__ void implicit_average_point(const C &c, const Implici
         if constexpr (S::TEMP >= 0) x[1 + S::TEMP] = x[1 + S::TEMP] + S::heating(a.Lv, a.Ls, d) * a.h;
     }
 #pragma unroll
-    for (int q = 0; q < N; ++q)
-        if (a.avg[q]) a.avg[q][i] = (x[S0 + q] - s0[q]) * a.inv_dt;
+    for (int q = 0; q < N; ++q) avg[q] = (x[S0 + q] - s0[q]) * a.inv_dt;
+}
+
+// The substeps and their stores: the body of implicit_average_kernel's lane
+template <typename S, typename FT, int K, typename C>
+__device__ __forceinline__ void implicit_average_point(const C &c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> &a, FT (&x)[S::NWRT + 1], int64_t i) {
+    FT avg[S::NOUT];
+    implicit_average_substeps<S, FT, K>(c, a, x, avg);
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q)
+        if (a.avg[q]) a.avg[q][i] = avg[q];
 }
 
 // ---- ∂/∂θ: the derivatives with respect to the scheme's PARAMETERS (include/cmx.h §(22)) ------------------------------------------------------------------------

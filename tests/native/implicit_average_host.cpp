@@ -1,5 +1,7 @@
 // implicit_average_host.cpp — TEST INFRASTRUCTURE: the host build of the sub-stepped implicit average (csrc/cmx_jacobian.hpp: ImplicitAverageArgs,
-// implicit_average_step_ok, make_implicit_average_args, implicit_average_point) compiled by g++ for the HOST (CMX_HOST_BUILD) on three schemes — SbJac and
+// implicit_average_step_ok, make_implicit_average_args, implicit_average_point and through it implicit_average_substeps: the substep loop that the average
+// kernel and the column kernel of cmx_column_implicit_step.hip both call, so this build covers the loop of both; the column kernel of
+// cmx_column_implicit_average.hip keeps a measured copy, which only its device test holds to this one) compiled by g++ for the HOST (CMX_HOST_BUILD) on three schemes — SbJac and
 // Mp1mJac, each set up by the function the device entries call (with_sb2006_jac / with_mp1m_jac), and a LINEAR toy scheme f = M s without a temperature, whose
 // average has a closed form (tests/test_implicit_average_host.py).  What it is compared with, the recipe over the implicit entry, comes from
 // tests/native/implicit_host.cpp.  Like that file it is NOT part of libcmx.so and no CPU fallback.  The mirrors return the statuses of the device entries for
