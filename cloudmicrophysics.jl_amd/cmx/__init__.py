@@ -20,7 +20,7 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
                               bulk_microphysics_tendencies_fields, bulk_microphysics_tendencies_2m_p3_fields,
                               bulk_2m_cloud_to_rain, cloud_terminal_velocity, column_sums, sb2006_process_rates,
                               ColumnTendencies2M, column_tendencies_sedimentation, ColumnTendencies2MP3,
-                              column_tendencies_sedimentation_2m_p3, WarmRainJacobian2M, warm_rain_jacobian_2m, JACOBIAN_WRT, JACOBIAN_OUTPUTS,
+                              column_tendencies_sedimentation_2m_p3, column_implicit_sedimentation_2m_p3, WarmRainJacobian2M, warm_rain_jacobian_2m, JACOBIAN_WRT, JACOBIAN_OUTPUTS,
                               WarmRainJvp2M, WarmRainVjp2M, warm_rain_jvp_2m, warm_rain_vjp_2m, WarmRainImplicit2M,
                               WarmRainParamJvp2M, WarmRainParamVjp2M, warm_rain_param_jvp_2m, warm_rain_param_vjp_2m,
                               warm_rain_implicit_tendencies_2m, warm_rain_implicit_average_2m, column_implicit_average_sedimentation_2m, column_implicit_step_2m)

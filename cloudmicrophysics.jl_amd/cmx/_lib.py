@@ -176,6 +176,11 @@ def _declare(lib):
         f.restype = i32
         f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.p3_ice_params), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel),
                       C.POINTER(fam.stokes_vel), u32, i32, fam.ft, i64, i32, vp, C.POINTER(vp), C.POINTER(vp)] + [vp] * 5 + [vp]
+        # … with backward-Euler sedimentation (include/cmx.h §24): the same list with `double dt` after p
+        f = getattr(lib, f"cmx_mp2m_p3_column_implicit_sedimentation_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.p3_ice_params), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel),
+                      C.POINTER(fam.stokes_vel), u32, i32, fam.ft, C.c_double, i64, i32, vp, C.POINTER(vp), C.POINTER(vp)] + [vp] * 5 + [vp]
         f = getattr(lib, f"cmx_gamma_inc_{s}")
         f.restype = i32
         f.argtypes = [i64, vp, vp, vp, vp, vp]

@@ -17,6 +17,7 @@ reference's array of NamedTuples, with the same field names.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import namedtuple
 from typing import Optional
 
@@ -547,10 +548,17 @@ def column_tendencies_sedimentation_2m_p3(mp, tps, inv_dz, rho, T, q_tot, q_lcl,
     not the reference's: include/cmx.h).  `inv_dz`: the n_lev values 1/Δz_k.  Returns `ColumnTendencies2MP3`: the eight tendencies,
     `log_lambda` (cache it: it is the next step's `log_lambda_guess`), the ice fall speeds, and — `want_precip_flux` — the surface
     fluxes of q_rai and q_ice per column.  Points without ice: log λ = −Inf, speeds 0."""
+    return _column_2m_p3("cmx_mp2m_p3_column_tendencies_sedimentation", None, mp, tps, inv_dz, (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim),
+                         log_lambda_guess, inpc_log_shift, vel, vel_params, cloud_vel, p, brent_iters, aspect_ratio, want_precip_flux, out, stream)
+
+
+def _column_2m_p3(entry, dt, mp, tps, inv_dz, cols, log_lambda_guess, inpc_log_shift, vel, vel_params, cloud_vel, p, brent_iters, aspect_ratio,
+                  want_precip_flux, out, stream):
+    """The checks and the call of the two 2M + P3 column steps (include/cmx.h (9b), §(24)): the same arguments; `dt`: None for (9b), else
+    the step of §(24), judged last, as the C entry does."""
     if not (isinstance(mp, Microphysics2MParams) and mp.ice is not None):
         raise TypeError("mp must be Microphysics2MParams(FT, with_ice=True)")
     names = ("rho", "T", "q_tot", "q_lcl", "n_lcl", "q_rai", "n_rai", "q_ice", "n_ice", "q_rim", "b_rim")
-    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim)
     ref = _check_cols(cols, names)
     if ref.dim() != 2:
         raise ValueError("state columns must have shape (n_col, n_lev)")
@@ -581,14 +589,38 @@ def column_tendencies_sedimentation_2m_p3(mp, tps, inv_dz, rho, T, q_tot, q_lcl,
     velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
     if not isinstance(velp, fam.rain_vel):
         raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
+    after_p = ()
+    if dt is not None:
+        dt = float(dt)
+        if not (math.isfinite(dt) and dt >= 0.0):
+            raise ValueError("dt must be finite and >= 0")
+        after_p = (dt,)
     flags = mp.ice.flags | (0 if aspect_ratio else _abi.CMX_P3_NO_ASPECT_RATIO) | _P3COL_VEL[flag]
     in_p = (C.c_void_p * 13)(*[t.data_ptr() for t in cols], log_lambda_guess.data_ptr() if log_lambda_guess is not None else None,
                              inpc_log_shift.data_ptr() if inpc_log_shift is not None else None)
     out_p = (C.c_void_p * 8)(*[t.data_ptr() for t in out[:8]])
-    _lib.call("cmx_mp2m_p3_column_tendencies_sedimentation", fam, ref.device, C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), C.byref(velp),
-              C.byref(cloud_vel) if cloud_vel is not None else None, flags, int(brent_iters), p, n_col, n_lev, _ptr(inv_dz), in_p, out_p,
+    _lib.call(entry, fam, ref.device, C.byref(mp.warm_rain.c), C.byref(mp.ice.c), C.byref(tps), C.byref(velp),
+              C.byref(cloud_vel) if cloud_vel is not None else None, flags, int(brent_iters), p, *after_p, n_col, n_lev, _ptr(inv_dz), in_p, out_p,
               _ptr(out.log_lambda), _ptr(out.v_ice_n), _ptr(out.v_ice_m), _ptr(out.precip_rai), _ptr(out.precip_ice), stream=stream)
     return out
+
+
+def column_implicit_sedimentation_2m_p3(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, dt, *,
+                                        log_lambda_guess=None, inpc_log_shift=None, vel=SB2006VelType, vel_params=None, cloud_vel=None,
+                                        p: float = 1e-6, brent_iters: int = 0, aspect_ratio: bool = True, want_precip_flux: bool = False,
+                                        out: Optional[ColumnTendencies2MP3] = None, stream=None) -> ColumnTendencies2MP3:
+    """`column_tendencies_sedimentation_2m_p3` with IMPLICIT sedimentation, behind `cmx_mp2m_p3_column_implicit_sedimentation_*`: the shape solve, the ice fall
+    speeds and the eight tendencies are those of that step (the same launches, the same bits), and backward-Euler first-order upwind sedimentation — a top-down
+    recurrence along each column with the fall speeds of the initial state — stands in the place of the explicit flux divergence.  Stable at any Courant
+    number Δt·w/Δz, where the explicit step needs ≤ 1 (rimed ice at 5–9 m/s, rain at up to 12 m/s): no sub-cycling.  `precip_rai` and `precip_ice` are the
+    fluxes that leave the column DURING the step (G_0, not the initial F_0): the column budget closes.  include/cmx.h §(24) has the definition.
+
+    `dt`: the step [s], finite and ≥ 0 (at 0 the result is that of `column_tendencies_sedimentation_2m_p3`).  Every other argument, the keywords, the checks
+    and the result are those of `column_tendencies_sedimentation_2m_p3`.  No autograd.  Asynchronous on `stream`."""
+    if dt is None:
+        raise TypeError("dt must be a number")
+    return _column_2m_p3("cmx_mp2m_p3_column_implicit_sedimentation", dt, mp, tps, inv_dz, (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim),
+                         log_lambda_guess, inpc_log_shift, vel, vel_params, cloud_vel, p, brent_iters, aspect_ratio, want_precip_flux, out, stream)
 
 
 _SCHEMES_2M = {"KK2000": _abi.CMX_2M_KK2000, "B1994": _abi.CMX_2M_B1994, "TC1980": _abi.CMX_2M_TC1980, "LD2004": _abi.CMX_2M_LD2004}

@@ -14,12 +14,14 @@
 // (3) is new: one kernel, lanes along the flat index i = col·n_lev + k with 16-byte accesses, the flux of the cell above handed across lanes
 // through an LDS halo exactly as in sb2006_column_kernel, the point after a launch's last tile evaluated by the same flux function from the
 // raw columns — results, NaN propagation included, do not depend on where tile or launch boundaries fall.
+// The entry layer — the checks in their order, steps (1) and (2), the constants of (3) — the species enum and the flux function of a raw point are
+// cmx_mp2m_p3_column.hpp's, shared with the implicit step of include/cmx.h §(24) (cmx_mp2m_p3_column_implicit.hip); here are the products kernel and its
+// launch, the kernel of step (3), its IO struct and launches, and the extern "C" functions.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
 
-#include "cmx_launch.hpp"
-#include "cmx_sb2006.hpp"
+#include "cmx_mp2m_p3_column.hpp"
 
 namespace cmx {
 
@@ -45,9 +47,7 @@ __global__ __launch_bounds__(kBlock) void p3col_products_kernel(const FT *__rest
 }
 
 // ---- step (3) -------------------------------------------------------------------------------------------------------------------
-// species in the order of the tendency columns
-enum : int { SP_QLCL = 0, SP_NLCL, SP_QRAI, SP_NRAI, SP_QICE, SP_NICE, SP_QRIM, SP_BRIM, SP_N };
-
+// species: the enum of cmx_mp2m_p3_column.hpp, in the order of the tendency columns
 template <typename FT> struct P3SedIO {
     const FT *rho, *q_lcl, *n_lcl, *q_rai, *n_rai, *q_ice, *n_ice, *q_rim, *b_rim, *v_n, *v_m;
     FT *tend[SP_N];        // read-modify-written
@@ -59,48 +59,8 @@ template <typename FT> struct P3SedIO {
     FastDivU32 lev_div;    // division by n_lev for flat indices below 2³² (cmx_launch.hpp fastdiv)
 };
 
-// The downward fluxes ρ χ w of ONE raw point (clamp_to_nonneg as in the tendencies, BMT:912-921) — the only place they are formed: a lane's
-// own points and the point after a launch's last tile both go through it.  Rain: the PSD and fall speeds of sed_fluxes_of_point
-// (cmx_sb2006_column.hip), the same inline functions on the same operands.  Ice: the fall speeds of step (1).
-// NaN rule: a NaN in ρ or in a column a species' flux depends on gives a NaN flux — rain (q_rai, n_rai: both speeds come from both moments),
-// ice (q_ice, n_ice, q_rim, b_rim, v_n, v_m: the four ice species share the two fall speeds), cloud (q_lcl, n_lcl).
-template <typename FT, bool LIMITED, int VEL, bool CLOUD, typename C>
-__device__ __forceinline__ void p3col_fluxes_of_point(const C &c, const CloudVelConsts<FT> &cv, FT rho, FT q_lcl, FT n_lcl, FT q_rai, FT n_rai, FT q_ice,
-                                                      FT n_ice, FT q_rim, FT b_rim, FT v_n, FT v_m, FT (&f)[SP_N]) {
-    using M = Math<FT>;
-    const FT eps = M::eps();
-    const FT r_ = max0(rho);
-    {
-        const FT qr = max0(q_rai), nr = max0(n_rai);
-        const FT rs_rho = M::rsqrt(r_);
-        const FT N_rai = r_ * nr;
-        const FT L_rai = r_ * M::max(qr, eps);
-        const SbRainPsd<FT> psd = sb2006_rain_psd<FT, LIMITED>(c, L_rai, M::max(N_rai, eps));
-        FT vt_n, vt_m;
-        sb2006_rain_velocity<FT, LIMITED, VEL>(c, r_, rs_rho, psd.l2_lam, N_rai < eps, qr < eps, vt_n, vt_m);
-        const bool bad = any_nan(rho, q_rai, n_rai);
-        f[SP_QRAI] = bad ? M::nan() : (r_ * qr) * vt_m;
-        f[SP_NRAI] = bad ? M::nan() : (r_ * nr) * vt_n;
-    }
-    {
-        const bool bad = any_nan(rho, q_ice, n_ice, q_rim, b_rim, v_n, v_m);
-        f[SP_QICE] = bad ? M::nan() : (r_ * max0(q_ice)) * v_m;
-        f[SP_NICE] = bad ? M::nan() : (r_ * max0(n_ice)) * v_n;
-        f[SP_QRIM] = bad ? M::nan() : (r_ * max0(q_rim)) * v_m;
-        f[SP_BRIM] = bad ? M::nan() : (r_ * max0(b_rim)) * v_m;
-    }
-    f[SP_QLCL] = FT(0);
-    f[SP_NLCL] = FT(0);
-    if constexpr (CLOUD) {
-        const FT ql = max0(q_lcl), nl = max0(n_lcl);
-        FT vc_n, vc_m;
-        sb2006_cloud_velocity(cv, ql, r_, r_ * nl, vc_n, vc_m);
-        const bool bad = any_nan(rho, q_lcl, n_lcl);
-        f[SP_QLCL] = bad ? M::nan() : (r_ * ql) * vc_m;
-        f[SP_NLCL] = bad ? M::nan() : (r_ * nl) * vc_n;
-    }
-}
-
+// The fluxes of a raw point: p3col_fluxes_of_point (cmx_mp2m_p3_column.hpp, shared with the implicit step of §(24)).  The fall speeds it hands out as well
+// are not used here.
 // lanes per workgroup and the tile geometry are those of sb2006_column_kernel (256 lanes, tiles that overlap by one lane: CMX_COLUMN_BS there)
 #ifndef CMX_P3COL_BS
 #define CMX_P3COL_BS 256
@@ -142,14 +102,14 @@ __global__ __launch_bounds__(BS) void mp2m_p3_sedimentation_kernel(const SbConst
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
     if (nvalid < BS && threadIdx.x == BS - 1) {        // last workgroup of the launch only (lane BS−1 has no vector there)
         const int64_t e = first + (tile0 + nvalid) * VEC;
-        FT f[SP_N];
+        FT f[SP_N], w[SP_N];
 #pragma unroll
         for (int q = 0; q < SP_N; ++q) f[q] = FT(0);
         if (e < io.n) {
             FT ql = FT(0), nl = FT(0);
             if constexpr (CLOUD) { ql = io.q_lcl[e]; nl = io.n_lcl[e]; }
             p3col_fluxes_of_point<FT, LIMITED, VEL, CLOUD>(front_consts<FT>(c), cv, io.rho[e], ql, nl, io.q_rai[e], io.n_rai[e], io.q_ice[e], io.n_ice[e],
-                                                           io.q_rim[e], io.b_rim[e], io.v_n[e], io.v_m[e], f);
+                                                           io.q_rim[e], io.b_rim[e], io.v_n[e], io.v_m[e], f, w);
         }
 #pragma unroll
         for (int q = 0; q < SP_N; ++q) halo[BS][q] = f[q];
@@ -173,10 +133,10 @@ __global__ __launch_bounds__(BS) void mp2m_p3_sedimentation_kernel(const SbConst
         int32_t lv = lev;
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
-            FT ql = FT(0), nl = FT(0);
+            FT ql = FT(0), nl = FT(0), w[SP_N];
             if constexpr (CLOUD) { ql = q_lcl[k]; nl = n_lcl[k]; }
             p3col_fluxes_of_point<FT, LIMITED, VEL, CLOUD>(front_consts<FT>(c), cv, rho[k], ql, nl, q_rai[k], n_rai[k], q_ice[k], n_ice[k], q_rim[k],
-                                                           b_rim[k], v_n[k], v_m[k], F[k]);
+                                                           b_rim[k], v_n[k], v_m[k], F[k], w);
             g[k] = io.inv_dz[lv] * M::rcp(max0(rho[k]));
             if (++lv == io.n_lev) lv = 0;
         }
@@ -225,92 +185,48 @@ static bool launch_p3_sedimentation(bool limited, int vel, bool cloud, const SbC
     }, flag(limited), one_of<VEL_SB, VEL_CHEN, VEL_CHEN_GEN>(vel), flag(cloud));
 }
 
-// steps (1) and (2): the library's own entries of the float type
-static int32_t shape_velocities(const cmx_p3_ice_params_f32 *ip, uint32_t flags, int32_t brent_iters, float p, int64_t n, const float *rq, const float *rn,
-                                const float *x3, const float *x4, const float *rho, const float *guess, float *loglam, float *v_n, float *v_m, void *st) {
-    return cmx_p3_shape_terminal_velocities_f32(&ip->scheme, &ip->vel_ice, &ip->quad, flags, brent_iters, p, n, rq, rn, x3, x4, rho, guess, loglam, nullptr, v_n, v_m, st);
-}
-static int32_t shape_velocities(const cmx_p3_ice_params_f64 *ip, uint32_t flags, int32_t brent_iters, double p, int64_t n, const double *rq, const double *rn,
-                                const double *x3, const double *x4, const double *rho, const double *guess, double *loglam, double *v_n, double *v_m, void *st) {
-    return cmx_p3_shape_terminal_velocities_f64(&ip->scheme, &ip->vel_ice, &ip->quad, flags, brent_iters, p, n, rq, rn, x3, x4, rho, guess, loglam, nullptr, v_n, v_m, st);
-}
-static int32_t tendencies(const cmx_warm_rain_2m_f32 *wr, const cmx_p3_ice_params_f32 *ip, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n,
-                          const float *const *in, const float *loglam, float *const *out, void *st) {
-    return cmx_microphysics_2m_p3_tendencies_f32(wr, ip, tps, flags, n, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], in[10], loglam, in[12], out, st);
-}
-static int32_t tendencies(const cmx_warm_rain_2m_f64 *wr, const cmx_p3_ice_params_f64 *ip, const cmx_thermo_f64 *tps, uint32_t flags, int64_t n,
-                          const double *const *in, const double *loglam, double *const *out, void *st) {
-    return cmx_microphysics_2m_p3_tendencies_f64(wr, ip, tps, flags, n, in[0], in[1], in[2], in[3], in[4], in[5], in[6], in[7], in[8], in[9], in[10], loglam, in[12], out, st);
-}
-
-enum : int { IN_RHO = 0, IN_T, IN_QTOT, IN_QLCL, IN_NLCL, IN_QRAI, IN_NRAI, IN_QICE, IN_NICE, IN_QRIM, IN_BRIM, IN_GUESS, IN_SHIFT };
-
-template <typename FT, typename WR, typename IP, typename TH, typename VL, typename ST>
-static int32_t p3_column_entry(const WR *wr, const IP *ip, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int32_t brent_iters, FT p,
-                               int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, FT *const *tend, FT *loglam, FT *v_n, FT *v_m,
-                               FT *precip_rai, FT *precip_ice, void *stream) {
-    constexpr uint32_t kP3 = CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO | CMX_P3_RAIN_PDF_LIMITED;
-    if (!wr || !ip || !tps || !vel || !in || !tend || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (flags & ~(uint32_t)(kP3 | CMX_P3COL_VEL_SB2006 | CMX_P3COL_VEL_CHEN2022)) return CMX_ERR_BAD_ARG;
-    const bool sbv = flags & CMX_P3COL_VEL_SB2006, chv = flags & CMX_P3COL_VEL_CHEN2022;
-    if (sbv == chv) return CMX_ERR_BAD_ARG;                      // exactly one rain fall-speed scheme
-    if (n_col > kMaxPoints / n_lev) return CMX_ERR_UNSUPPORTED;  // n_col·n_lev must fit one launch (cmx_launch.hpp)
-    const int64_t n = n_col * (int64_t)n_lev;
-    // the collision kernel of step (2) gives a workgroup as few as 4 states (collision_geometry, cmx_p3_collisions.hip): refused here, before any launch
-    if (n > 4 * ((int64_t)0x7fffffff - 7)) return CMX_ERR_UNSUPPORTED;
-    if (n == 0) return CMX_OK;
-    if (!inv_dz || !loglam || !v_n || !v_m) return CMX_ERR_BAD_ARG;
-    for (int k = 0; k <= IN_BRIM; ++k) if (!in[k]) return CMX_ERR_BAD_ARG;       // the warm start and the INPC shift are optional
-    for (int q = 0; q < SP_N; ++q) if (!tend[q]) return CMX_ERR_BAD_ARG;
-    const bool limited = (flags & CMX_P3_RAIN_PDF_LIMITED) != 0;
-    if (limited && !sb_limiters_ok(*wr)) return CMX_ERR_BAD_ARG;                 // clamp_ordered needs ordered limiter pairs
-    if (sbv && !sb_rain_vel_ok(*vel, limited)) return CMX_ERR_BAD_ARG;           // the not-limited SB2006 fall speed needs aR < bR
-    // what steps (1) and (2) would refuse after the first launch was enqueued: the quadrature order and the quantile level
-    if (ip->quad.n < 1 || ip->quad.n > CMX_QUAD_MAX || !(p > FT(0) && p < FT(0.5))) return CMX_ERR_BAD_ARG;
-
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// step (1)'s products, for both column entries (declared in cmx_mp2m_p3_column.hpp)
+template <typename FT> int32_t p3col_launch_products(const FT *const *in, FT *const *tend, int64_t n, hipStream_t s) {
     constexpr int VEC = Math<FT>::VEC;
-    // (1) ρ·(q_ice, n_ice, q_rim, b_rim) → the last four tendency columns, then shape + fall speeds on them
-    {
-        const void *ptrs[] = {in[IN_RHO], in[IN_QICE], in[IN_NICE], in[IN_QRIM], in[IN_BRIM], tend[SP_QICE], tend[SP_NICE], tend[SP_QRIM], tend[SP_BRIM]};
-        for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
-            constexpr int V = decltype(vec_tag)::value;
-            launch<kBlock>(p3col_products_kernel<FT, V>, count / V, s, in[IN_RHO] + lo, in[IN_QICE] + lo, in[IN_NICE] + lo, in[IN_QRIM] + lo, in[IN_BRIM] + lo,
-                           tend[SP_QICE] + lo, tend[SP_NICE] + lo, tend[SP_QRIM] + lo, tend[SP_BRIM] + lo, count / V);
-        });
-        if (const int32_t e = launched()) return e;
-    }
-    if (const int32_t e = shape_velocities(ip, flags & (CMX_P3_SLOPE_CONSTANT | CMX_P3_NO_ASPECT_RATIO), brent_iters, p, n, tend[SP_QICE], tend[SP_NICE],
-                                           tend[SP_QRIM], tend[SP_BRIM], in[IN_RHO], in[IN_GUESS], loglam, v_n, v_m, stream))
-        return e;
-    // (2) the eight tendencies.  log λ is read only where ice is present (p3_collision_kernel: q_ice > ϵ, n_ice > ϵ and both products ≥ ϵ), which is
-    // where step (1) solved for it: the −Inf of the other points goes in as it is and is never loaded
-    if (const int32_t e = tendencies(wr, ip, tps, flags & kP3, n, in, loglam, tend, stream)) return e;
-    // (3) fall speeds of rain (and cloud) + the flux divergence of the falling species
-    const SbConsts<FT> c = make_sb_consts<FT>(*wr, *tps, vel, (double)Math<FT>::eps_1m());
-    CloudVelConsts<FT> cv{};
-    if (cloud_vel) cv = make_cloud_vel_consts<FT>(wr->seifert_beheng.pdf_c, *cloud_vel);
-    P3SedIO<FT> io{};
-    io.rho = in[IN_RHO]; io.q_lcl = in[IN_QLCL]; io.n_lcl = in[IN_NLCL]; io.q_rai = in[IN_QRAI]; io.n_rai = in[IN_NRAI];
-    io.q_ice = in[IN_QICE]; io.n_ice = in[IN_NICE]; io.q_rim = in[IN_QRIM]; io.b_rim = in[IN_BRIM]; io.v_n = v_n; io.v_m = v_m;
-    for (int q = 0; q < SP_N; ++q) io.tend[q] = tend[q];
-    io.inv_dz = inv_dz; io.precip_rai = precip_rai; io.precip_ice = precip_ice;
-    io.n = n; io.n_lev = n_lev; io.inv_n_lev = 1.0 / (double)n_lev; io.lev_div = make_fastdiv((uint32_t)n_lev);
-    const int velk = sbv ? VEL_SB : chen_vel_kind<FT>(vel->chen2022);   // fitted Γ(b(ρ)+1) or the general instantiation (cmx_math.hpp ChenGamma)
-    const bool cloud = cloud_vel != nullptr;
-    // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches compose exactly
-    const void *ptrs[] = {io.rho, io.q_lcl, io.n_lcl, io.q_rai, io.n_rai, io.q_ice, io.n_ice, io.q_rim, io.b_rim, io.v_n, io.v_m,
-                          tend[0], tend[1], tend[2], tend[3], tend[4], tend[5], tend[6], tend[7]};
-    // Float64: one point per lane, as in sb2006_column_kernel — two points hold two fall-speed evaluations' table reads and take 198–272 VGPRs
-    // (one wave per SIMD) where one point takes 67–153
-    constexpr int SVEC = sizeof(FT) == 8 ? 1 : VEC;
-    bool known = true;
-    for_each_range<FT, SVEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+    const void *ptrs[] = {in[IN_RHO], in[IN_QICE], in[IN_NICE], in[IN_QRIM], in[IN_BRIM], tend[SP_QICE], tend[SP_NICE], tend[SP_QRIM], tend[SP_BRIM]};
+    for_each_range<FT, VEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
         constexpr int V = decltype(vec_tag)::value;
-        known &= launch_p3_sedimentation<FT, V>(limited, velk, cloud, c, cv, io, lo, count / V, s);
+        launch<kBlock>(p3col_products_kernel<FT, V>, count / V, s, in[IN_RHO] + lo, in[IN_QICE] + lo, in[IN_NICE] + lo, in[IN_QRIM] + lo, in[IN_BRIM] + lo,
+                       tend[SP_QICE] + lo, tend[SP_NICE] + lo, tend[SP_QRIM] + lo, tend[SP_BRIM] + lo, count / V);
     });
-    if (!known) return CMX_ERR_BAD_ARG;      // unreachable: velk is VEL_SB or what chen_vel_kind gives
     return launched();
+}
+template int32_t p3col_launch_products<float>(const float *const *, float *const *, int64_t, hipStream_t);
+template int32_t p3col_launch_products<double>(const double *const *, double *const *, int64_t, hipStream_t);
+
+// the callable of the entry layer (cmx_mp2m_p3_column.hpp): the IO struct and the launches of step (3)
+template <typename FT, typename ST>
+static auto explicit_sedimentation(const ST *cloud_vel, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, FT *const *tend, FT *v_n, FT *v_m,
+                                   FT *precip_rai, FT *precip_ice, void *stream) {
+    return [=](bool limited, int velk, const SbConsts<FT> &c, const CloudVelConsts<FT> &cv) -> int32_t {
+        hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+        const int64_t n = n_col * (int64_t)n_lev;
+        P3SedIO<FT> io{};
+        io.rho = in[IN_RHO]; io.q_lcl = in[IN_QLCL]; io.n_lcl = in[IN_NLCL]; io.q_rai = in[IN_QRAI]; io.n_rai = in[IN_NRAI];
+        io.q_ice = in[IN_QICE]; io.n_ice = in[IN_NICE]; io.q_rim = in[IN_QRIM]; io.b_rim = in[IN_BRIM]; io.v_n = v_n; io.v_m = v_m;
+        for (int q = 0; q < SP_N; ++q) io.tend[q] = tend[q];
+        io.inv_dz = inv_dz; io.precip_rai = precip_rai; io.precip_ice = precip_ice;
+        io.n = n; io.n_lev = n_lev; io.inv_n_lev = 1.0 / (double)n_lev; io.lev_div = make_fastdiv((uint32_t)n_lev);
+        const bool cloud = cloud_vel != nullptr;
+        // scalar head, vector body, scalar tail (cmx_split.hpp); the halo point of each range is read from the full columns, so the launches compose exactly
+        const void *ptrs[] = {io.rho, io.q_lcl, io.n_lcl, io.q_rai, io.n_rai, io.q_ice, io.n_ice, io.q_rim, io.b_rim, io.v_n, io.v_m,
+                              tend[0], tend[1], tend[2], tend[3], tend[4], tend[5], tend[6], tend[7]};
+        // Float64: one point per lane, as in sb2006_column_kernel — two points hold two fall-speed evaluations' table reads and take 198–272 VGPRs
+        // (one wave per SIMD) where one point takes 67–153
+        constexpr int VEC = Math<FT>::VEC, SVEC = sizeof(FT) == 8 ? 1 : VEC;
+        bool known = true;
+        for_each_range<FT, SVEC>(ptrs, n, [&](auto vec_tag, int64_t lo, int64_t count) {
+            constexpr int V = decltype(vec_tag)::value;
+            known &= launch_p3_sedimentation<FT, V>(limited, velk, cloud, c, cv, io, lo, count / V, s);
+        });
+        if (!known) return CMX_ERR_BAD_ARG;      // unreachable: velk is VEL_SB or what chen_vel_kind gives
+        return launched();
+    };
 }
 
 }  // namespace cmx
@@ -323,7 +239,9 @@ int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f32(const cmx_warm_rain_2m_f
                                                         const float *const *in, float *const *tendencies, float *log_lambda, float *v_ice_n,
                                                         float *v_ice_m, float *precip_rai, float *precip_ice, void *stream) {
     return cmx::p3_column_entry<float>(warm_rain, ice, tps, rain_vel, cloud_vel, flags, brent_iters, p, n_col, n_lev, inv_dz, in, tendencies, log_lambda,
-                                       v_ice_n, v_ice_m, precip_rai, precip_ice, stream);
+                                       v_ice_n, v_ice_m, true, stream,
+                                       cmx::explicit_sedimentation<float>(cloud_vel, n_col, n_lev, inv_dz, in, tendencies, v_ice_n, v_ice_m, precip_rai,
+                                                                          precip_ice, stream));
 }
 int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_p3_ice_params_f64 *ice, const cmx_thermo_f64 *tps,
                                                         const cmx_rain_vel_f64 *rain_vel, const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags,
@@ -331,7 +249,9 @@ int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f64(const cmx_warm_rain_2m_f
                                                         const double *const *in, double *const *tendencies, double *log_lambda, double *v_ice_n,
                                                         double *v_ice_m, double *precip_rai, double *precip_ice, void *stream) {
     return cmx::p3_column_entry<double>(warm_rain, ice, tps, rain_vel, cloud_vel, flags, brent_iters, p, n_col, n_lev, inv_dz, in, tendencies, log_lambda,
-                                        v_ice_n, v_ice_m, precip_rai, precip_ice, stream);
+                                        v_ice_n, v_ice_m, true, stream,
+                                        cmx::explicit_sedimentation<double>(cloud_vel, n_col, n_lev, inv_dz, in, tendencies, v_ice_n, v_ice_m, precip_rai,
+                                                                            precip_ice, stream));
 }
 
 }  // extern "C"

@@ -1180,8 +1180,8 @@ int32_t cmx_microphysics_2m_p3_tendencies_fields_f64(const cmx_warm_rain_2m_f64 
  * or above the 4·(2^31 − 8) states of the collision kernel's smallest tile → CMX_ERR_UNSUPPORTED; n_col = 0 → CMX_OK; then a NULL required column,
  * disordered limiters, a quadrature order outside 1…CMX_QUAD_MAX or p outside (0, ½) → CMX_ERR_BAD_ARG.
  * cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup). */
-#define CMX_P3COL_VEL_SB2006    (1u << 8)   /* cmx_mp2m_p3_column_tendencies_sedimentation_* only: rain fall speeds as with CMX_VEL_SB2006   */
-#define CMX_P3COL_VEL_CHEN2022  (1u << 9)   /* cmx_mp2m_p3_column_tendencies_sedimentation_* only: rain fall speeds as with CMX_VEL_CHEN2022 */
+#define CMX_P3COL_VEL_SB2006    (1u << 8)   /* the 2M + P3 column entries (9b), (24) only: rain fall speeds as with CMX_VEL_SB2006 */
+#define CMX_P3COL_VEL_CHEN2022  (1u << 9)   /* the 2M + P3 column entries (9b), (24) only: rain fall speeds as with CMX_VEL_CHEN2022 */
 int32_t cmx_mp2m_p3_column_tendencies_sedimentation_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_p3_ice_params_f32 *ice, const cmx_thermo_f32 *tps,
                                                         const cmx_rain_vel_f32 *rain_vel, const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags,
                                                         int32_t brent_iters, float p, int64_t n_col, int32_t n_lev, const float *inv_dz,
@@ -1773,7 +1773,7 @@ int32_t cmx_mp1m_column_implicit_average_sedimentation_f64(const cmx_microphysic
  * same species in the same column (of every species, if a_j is NaN at that point: then all four B are), never a higher level and never another column.
  * Results do not depend on how the kernel divides the columns among workgroups, on alignment, or on the number of columns in the call.  A pure launch
  * sequence on `stream` (ONE kernel): no allocation, no synchronisation, graph-capturable; any alignment.  NOT in place, as (20).
- * Not done here: the 1-moment snow shapes (a single CMX_1M_SED_SNOW_* bit: CMX_ERR_UNSUPPORTED, as in (20)), the 2M + P3 column step, the `*_fields_*`
+ * Not done here: the 1-moment snow shapes (a single CMX_1M_SED_SNOW_* bit: CMX_ERR_UNSUPPORTED, as in (20)), the 2M + P3 column step — (24) —, the `*_fields_*`
  * layouts, autograd, fall speeds re-evaluated inside the step.
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_implicit_step_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
@@ -1873,6 +1873,55 @@ int32_t cmx_mp1m_param_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_ther
                                const double *T, const double *q_tot, const double *q_lcl, const double *q_icl, const double *q_rai, const double *q_sno,
                                const double *const cotangents[CMX_MP1M_JAC_NOUT], int32_t ndir, const cmx_microphysics_1m_f64 *d_mp,
                                const cmx_thermo_f64 *d_tps, double *grad, double *workspace, double *const tendencies[CMX_MP1M_JAC_NOUT], void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (24) The 2M + P3 column step (9b) with IMPLICIT sedimentation: backward-Euler first-order upwind sedimentation of the eight falling species, stable at any
+ * Courant number c = Δt·w/Δz, where the explicit flux divergence of (9b) needs c ≤ 1 (rimed ice at 5–9 m/s, rain at up to 12 m/s through 30–500 m layers:
+ * the largest c is 7–10 at Δt = 30 s and 74–99 at Δt = 300 s on the test states, with the fall speeds of this library on an MI355X).  A host model that
+ * calls (9b) must sub-cycle sedimentation itself; with these entries it need not.  The
+ * argument list is that of the (9b) entries with one `double dt` inserted after `p`; layout, `in`, `tendencies`, `log_lambda`, `v_ice_n`, `v_ice_m` and `flags`
+ * are those of (9b).  The call runs steps 1 and 2 of (9b) unchanged — products → shape and fall speeds → the eight tendencies: the same launches, hence the
+ * same bits for log_lambda, v_ice_n, v_ice_m and the tendencies a_j — and ONE kernel in the place of step 3.  The definition, normative — per column, for
+ * each falling species j, in the entry's float type FT, level 0 the lowest:
+ *     a      = the tendency of step 2 at the point, bit for bit
+ *     F, w   = the flux F_j = (ρ⁺χ_j⁺)·w_j of step 3 of (9b), bit for bit, and the fall speed w_j that step multiplies into it (that value itself, not F/(ρχ)):
+ *              the rain speeds w_m (q_rai) and w_n (n_rai), v_ice_m (q_ice, q_rim, b_rim), v_ice_n (n_ice), with cloud_vel c_m (q_lcl) and c_n (n_lcl)
+ *     g      = inv_dz[k]·rcp(ρ⁺), exactly as step 3 of (9b) forms it
+ *     τ      = FT(dt)·w          c = τ·inv_dz[k]       β = τ·ρ⁺        r = 1/(1 + c)
+ *     A      = c·r               B = fma(β, a, F)·r
+ *     G_k    = top ? B_k : fma(A_k, G_{k+1}, B_k)          top: k = n_lev − 1;  evaluated from the top level downward, in this order
+ *     out_k  = fma(top ? 0 : G_{k+1}, g, fma(−F_k, g, a_k)) · r_k
+ * r is a TRUE (correctly rounded IEEE) division in both float types: exactly 1 at c = 0.  Every other product and sum is a separate IEEE operation except the
+ * fma's written above.  out_j overwrites tendencies[j].  Without cloud_vel the two cloud columns are not touched: they keep the tendencies of step 2.
+ * This is backward Euler on ∂χ/∂t = a + (G_{k+1} − G_k)·g with G_k = w_k ρ_k (χ_k + Δt·out_k), the fall speeds frozen at the initial state, as in (21); the
+ * tendency a is NOT limited here (the limiter of (19) has no counterpart in (9)), so χ + Δt·out can be negative where χ + Δt·a is — the step adds no
+ * negativity of its own to what the tendencies alone would leave.
+ * precip_rai, precip_ice (optional, n_col values) are G at level 0 of q_rai and q_ice — the flux that leaves the column DURING the step, so that the column
+ * budget Σ_k ρ_k out_k Δz_k + G_0 = Σ_k ρ_k a_k Δz_k closes — not the initial F_0 of (9b).
+ * Two consequences of the definition:
+ *   - dt = 0: c = 0, r = 1, A = 0 and G = F, so the entry is the (9b) entry value for value (wherever a and F are finite).  The only possible difference is a
+ *     −0 that becomes +0 at the top level, where fma(0, g, ·) stands in the place of the select.
+ *   - inv_dz ≡ 0: c = 0, r = 1 and g = 0, so the outputs are the pointwise tendencies of step 2 for every dt.
+ * `dt` must be finite and ≥ 0, and FT(dt) must be finite (0 ≤ dt ≤ the largest finite FT).  Statuses: those of (9b) in their order, then `dt`
+ * (CMX_ERR_BAD_ARG) — all of them before any HIP
+ * call; n_col = 0 is CMX_OK whatever dt is, as it is whatever the columns are.
+ * NaN rule: that of (9b) for a_j and F_j; on top of it the recurrence carries a non-finite G DOWNWARD — a non-finite a_j or F_j at level l makes out_j non-finite
+ * at every level ≤ l of that species in that column; it never reaches a level above l and never another column.
+ * Results do not depend on how the kernel divides the columns among workgroups, on alignment, or on the number of columns in the call.  A pure launch
+ * sequence on `stream` (products → shape + fall speeds → tendencies → implicit sedimentation): no allocation, no synchronisation, graph-capturable.  The
+ * tendency columns must not alias an input column, as in (9b).
+ * Not done here: implicit (Jacobian-based) P3 tendencies, fall speeds re-evaluated inside the step, the `*_fields_*` layouts, autograd.
+ * ------------------------------------------------------------------------- */
+int32_t cmx_mp2m_p3_column_implicit_sedimentation_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_p3_ice_params_f32 *ice, const cmx_thermo_f32 *tps,
+                                                      const cmx_rain_vel_f32 *rain_vel, const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags,
+                                                      int32_t brent_iters, float p, double dt, int64_t n_col, int32_t n_lev, const float *inv_dz,
+                                                      const float *const *in, float *const *tendencies, float *log_lambda, float *v_ice_n, float *v_ice_m,
+                                                      float *precip_rai, float *precip_ice, void *stream);
+int32_t cmx_mp2m_p3_column_implicit_sedimentation_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_p3_ice_params_f64 *ice, const cmx_thermo_f64 *tps,
+                                                      const cmx_rain_vel_f64 *rain_vel, const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags,
+                                                      int32_t brent_iters, double p, double dt, int64_t n_col, int32_t n_lev, const double *inv_dz,
+                                                      const double *const *in, double *const *tendencies, double *log_lambda, double *v_ice_n,
+                                                      double *v_ice_m, double *precip_rai, double *precip_ice, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

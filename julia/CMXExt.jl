@@ -1800,6 +1800,36 @@ function column_implicit_step!(out, ::BMT.Microphysics1Moment, mp::CMP.Microphys
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (24) the 2M + P3 column step of (9b) with backward-Euler sedimentation of the eight falling species
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    column_implicit_sedimentation!(out, BMT.Microphysics2Moment(), mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+                                   q_ice, n_ice, q_rim, b_rim, logλ, v_ice_n, v_ice_m, dt; logλ_guess, inpc_log_shift, p, brent_iters, precip_rai, precip_ice, stream)
+
+The 2M + P3 `column_tendencies_sedimentation!` (shape solve, ice fall speeds and the eight tendencies: the same launches, the same bits) with backward-Euler
+upwind sedimentation in the place of the explicit flux divergence — a top-down recurrence along each column with the fall speeds of the initial state: no
+sub-cycling at Δt·w/Δz > 1.  `precip_rai` and `precip_ice` are the fluxes that leave the column during the step.  `dt ≥ 0`; at `dt = 0` the result is that of
+`column_tendencies_sedimentation!`.  `out` must not alias the state columns.  include/cmx.h §(24) has the definition.
+"""
+function column_implicit_sedimentation!(out, ::BMT.Microphysics2Moment, mp::CMP.Microphysics2MParams{WR, <:CMP.P3IceParams}, tps, vel, cloud_vel,
+    n_col::Integer, n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, logλ, v_ice_n, v_ice_m,
+    dt::Real; logλ_guess = nothing, inpc_log_shift = nothing, p = 1e-6, brent_iters::Integer = 0, precip_rai = nothing, precip_ice = nothing,
+    stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    length(out) == 8 || error("out: the eight tendency columns")
+    flags = p3_flags(_ice(mp)) | (_vel_flag(vel) == CMX_VEL_SB2006 ? CMX_P3COL_VEL_SB2006 : CMX_P3COL_VEL_CHEN2022)
+    in = _ptrs(FT, (ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, q_ice, n_ice, q_rim, b_rim, logλ_guess, inpc_log_shift))
+    st = ccall(_fn("cmx_mp2m_p3_column_implicit_sedimentation", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int32, FT, Float64, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(_warm_rain(mp))), Ref(pack(_ice(mp))), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, brent_iters, FT(p),
+        Float64(dt), n_col, n_lev, _dp(FT, inv_dz), in, _ptrs(FT, out), _dp(FT, logλ), _dp(FT, v_ice_n), _dp(FT, v_ice_m), _dp(FT, precip_rai),
+        _dp(FT, precip_ice), stream)
+    _check(st, "cmx_mp2m_p3_column_implicit_sedimentation")
+    return out
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
