@@ -155,6 +155,9 @@ CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 # … and with backward-Euler sedimentation (include/cmx.h §21): cmx_<scheme>_column_implicit_step_*, the argument lists of §20
 # the 2M + P3 column step with backward-Euler sedimentation (include/cmx.h §24): cmx_mp2m_p3_column_implicit_sedimentation_* takes the argument list of
 # cmx_mp2m_p3_column_tendencies_sedimentation_* (9b) with one `double dt` (≥ 0) after p, and the flag bits CMX_P3COL_VEL_* of that entry
+# J v and Jᵀḡ of the SB2006 column step with sedimentation (include/cmx.h §25): cmx_sb2006_column_jvp_* / _vjp_* take the head of
+# cmx_sb2006_column_tendencies_sedimentation_* through n_rai, then tangents[NWRT], jvp[NOUT], jvp_precip, tendencies[NOUT], precip_flux resp.
+# cotangents[NOUT], cot_precip, grad[NWRT], tendencies[NOUT], precip_flux, in the orders of SB2006_JAC_WRT / SB2006_JAC_OUT
 # the derivatives with respect to the parameters (include/cmx.h §22, §23: cmx_mp1m_param_jvp_* / _param_vjp_* take the same lists over cmx_microphysics_1m): cmx_sb2006_warm_rain_param_jvp_* takes ndir, d_warm_rain[ndir], d_tps[ndir], jvp[ndir·NOUT],
 # tendencies[NOUT]; …_param_vjp_* takes cotangents[NOUT], ndir, d_warm_rain, d_tps, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies
 CMX_PARAM_MAX_DIRS = 16

@@ -253,6 +253,15 @@ def _declare(lib):
             f.restype = i32
             f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), C.POINTER(fam.stokes_vel), C.POINTER(fam.chen2022_rain_vel),
                           C.POINTER(fam.chen2022_ice_vel), u32, C.c_double, i32, u32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
+        # J v and Jᵀḡ of the SB2006 column step (include/cmx.h §25): the head of cmx_sb2006_column_tendencies_sedimentation_* through n_rai, then
+        # (tangents[6], jvp[4], jvp_precip, tendencies[4], precip_flux) / (cotangents[4], cot_precip, grad[6], tendencies[4], precip_flux)
+        head = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel), C.POINTER(fam.stokes_vel), u32, i64, i32] + [vp] * 8
+        f = getattr(lib, f"cmx_sb2006_column_jvp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), C.POINTER(vp), vp, C.POINTER(vp), vp, vp]
+        f = getattr(lib, f"cmx_sb2006_column_vjp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), vp, vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

@@ -10,8 +10,9 @@ can be differentiated by `loss.backward()`, `torch.autograd.grad` and `torch.aut
 gradient is worse than an error.  `warm_rain_tendencies_2m(…, theta=, names=)` and `tendencies_1m(…, theta=, names=)` also differentiate with respect to the scheme's PARAMETERS: `theta` is a 1-D CPU float64 tensor holding the
 values of the ClimaParams `names`; the forward pass rebuilds the parameter structs with those values (host work, no device sync) and is otherwise the same
 entry; backward calls the parameter-gradient entry (`warm_rain_param_vjp_2m` / `param_vjp_1m`) once for `theta.grad` (and the state Jᵀḡ entry if a state column needs a gradient), forward mode with a tangent on
-`theta` calls `warm_rain_param_jvp_2m` / `param_jvp_1m`.  Not built: double backward (backward is once-differentiable), vmap, the
-fall-speed outputs, LinearizedAverage and the 2M + P3 scheme."""
+`theta` calls `warm_rain_param_jvp_2m` / `param_jvp_1m`.  `cmx.autograd.column_tendencies_sedimentation_2m` is the SB2006 column step with sedimentation and its precipitation flux (`cmx.column_tendencies_sedimentation`),
+differentiated through the fall speeds and the flux divergence by `column_vjp_2m` / `column_jvp_2m`; ρ and `inv_dz` are held fixed.  Not built: double backward (backward is once-differentiable), vmap, the
+fall-speed outputs of the pointwise entry, parameter derivatives through the column, LinearizedAverage and the 2M + P3 scheme."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -19,7 +20,7 @@ from . import bulk_tendencies as _bt
 from . import microphysics1m as _m1
 from . import parameters as _P
 
-__all__ = ["warm_rain_tendencies_2m", "tendencies_1m"]
+__all__ = ["warm_rain_tendencies_2m", "tendencies_1m"]      # (tests/test_autograd_host.py pins the pointwise pair; the column step is reached by its name)
 
 
 def _check_rho(rho):
@@ -29,8 +30,9 @@ def _check_rho(rho):
         raise NotImplementedError("forward-mode tangent on rho: the air density is held fixed, the tendencies are not differentiated with respect to rho")
 
 
-def _function(name, WRT, primal, vjp, jvp):
-    """The torch.autograd.Function of one scheme: WRT names the differentiable inputs (state columns 1 … 6), the three callables are its launches."""
+def _function(name, WRT, primal, vjp, jvp, tangents_out=lambda r: tuple(r.jvp[o] for o in range(4))):
+    """The torch.autograd.Function of one scheme: WRT names the differentiable inputs (state columns 1 … 6), the three callables are its launches;
+    tangents_out: the output tangents from what `jvp` returns (an entry with more than the four point outputs gives its own)."""
     class F(torch.autograd.Function):
         @staticmethod
         def forward(mp, tps, *cols):
@@ -62,7 +64,7 @@ def _function(name, WRT, primal, vjp, jvp):
             if t_rho is not None:
                 raise NotImplementedError("forward-mode tangent on rho: the air density is held fixed")
             r = jvp(ctx.mp, ctx.tps, ctx.saved_tensors, {n: t.contiguous() for n, t in zip(WRT, tangents) if t is not None})
-            return tuple(r.jvp[o] for o in range(4))
+            return tangents_out(r)
     F.__name__ = F.__qualname__ = name
     return F
 
@@ -72,6 +74,25 @@ _WarmRain2M = _function(
     lambda mp, tps, cols: _bt.bulk_microphysics_tendencies(_bt.Microphysics2Moment(), mp, tps, *cols)[:4],
     lambda mp, tps, cols, cotangents, wrt: _bt.warm_rain_vjp_2m(mp, tps, *cols, cotangents, wrt=wrt),
     lambda mp, tps, cols, tangents: _bt.warm_rain_jvp_2m(mp, tps, *cols, tangents))
+
+
+class _ColumnStep:
+    """What the column step takes next to the parameters and the state — held fixed, not differentiated: travels in the `mp` slot of `_function`."""
+    def __init__(self, mp, inv_dz, options):
+        self.mp, self.inv_dz, self.options = mp, inv_dz, options
+
+
+def _column_primal(step, tps, cols):
+    r = _bt.column_tendencies_sedimentation(step.mp, tps, step.inv_dz, *cols, want_precip_flux=True, **step.options)
+    return tuple(r)
+
+
+# five outputs: the four tendencies and the precipitation flux (one value per column); its cotangent is the fifth gradient
+_Column2M = _function(
+    "ColumnTendenciesSedimentation2M", _bt.JACOBIAN_WRT, _column_primal,
+    lambda step, tps, cols, cotangents, wrt: _bt.column_vjp_2m(step.mp, tps, step.inv_dz, *cols, cotangents[:4], cotangents[4], wrt=wrt, **step.options),
+    lambda step, tps, cols, tangents: _bt.column_jvp_2m(step.mp, tps, step.inv_dz, *cols, tangents, **step.options),
+    tangents_out=lambda r: (*(r.jvp[o] for o in range(4)), r.jvp_precip))
 
 _Tendencies1M = _function(
     "Tendencies1M", _m1.JACOBIAN_WRT_1M,
@@ -184,6 +205,18 @@ def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, 
         return _WarmRain2M.apply(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
     wr, tps_t, names = _with_theta(mp, tps, theta, names)
     return _WarmRain2MTheta.apply(wr, tps_t, names, theta, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+
+
+def column_tendencies_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, *, vel=_bt.SB2006VelType, vel_params=None, cloud_vel=None):
+    """(dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt, precip_flux) of `cmx.column_tendencies_sedimentation(mp, tps, inv_dz, …, want_precip_flux=True)`, bit for
+    bit — the tendencies with the sedimentation flux divergence, shape (n_col, n_lev), and the surface precipitation flux, shape (n_col,) — differentiable by
+    torch with respect to T, q_tot, q_lcl, n_lcl, q_rai, n_rai: backward is ONE Jᵀḡ launch (`cmx.column_vjp_2m`, the cotangent of the precipitation flux
+    included: `precip_flux.sum().backward()` fills `.grad` of the state), forward mode ONE J v launch (`cmx.column_jvp_2m`).  ρ and `inv_dz` are held fixed:
+    asking for their gradient, or a forward-mode tangent on them, raises NotImplementedError."""
+    _check_rho(rho)
+    if inv_dz.requires_grad or torch.autograd.forward_ad.unpack_dual(inv_dz).tangent is not None:
+        raise NotImplementedError("inv_dz is held fixed: the column step is not differentiated with respect to the layer thickness")
+    return _Column2M.apply(_ColumnStep(mp, inv_dz, dict(vel=vel, vel_params=vel_params, cloud_vel=cloud_vel)), tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
 
 
 def tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, theta=None, names=None):

@@ -25,7 +25,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
-from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _check_wrt, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _table, _vjp
 from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
 
 
@@ -456,6 +456,100 @@ def column_tendencies_sedimentation(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl
               C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev, _ptr(inv_dz), *[_ptr(t) for t in cols],
               *[_ptr(t) for t in out[:4]], _ptr(out.precip_flux), stream=stream)
     return out
+
+
+ColumnJvp2M = namedtuple("ColumnJvp2M", ["jvp", "jvp_precip", "tendencies", "precip_flux"])
+ColumnVjp2M = namedtuple("ColumnVjp2M", ["grad", "tendencies", "precip_flux", "wrt"])
+
+
+def _column_products_head(mp, tps, inv_dz, cols, vel, vel_params, cloud_vel):
+    """The checks of `column_tendencies_sedimentation` for the two products with its Jacobian: (reference column, float family, the ABI arguments from the
+    parameter structs through n_rai)."""
+    wr = _warm_rain(mp)
+    ref = _check_cols(cols, _NAMES_2M)
+    if ref.dim() != 2:
+        raise ValueError("state columns must have shape (n_col, n_lev)")
+    n_col, n_lev = ref.shape
+    fam = _fam_of(ref)
+    if fam is not wr.fam or not isinstance(tps, fam.thermo) or (cloud_vel is not None and not isinstance(cloud_vel, fam.stokes_vel)):
+        raise TypeError("parameter float type does not match the state columns")
+    if inv_dz.dtype != ref.dtype or inv_dz.device != ref.device or inv_dz.numel() != n_lev or not inv_dz.is_contiguous():
+        raise ValueError("inv_dz must be a contiguous device vector of n_lev values of the state dtype")
+    flag = _vel_flag(vel)
+    if not flag:
+        raise ValueError("the column step needs a rain fall-speed scheme (SB2006VelType or Chen2022VelTypeRain)")
+    velp = vel_params if vel_params is not None else rain_vel_params(fam.sfx)
+    if not isinstance(velp, fam.rain_vel):
+        raise TypeError("vel_params must be the cmx_rain_vel struct of the state's float type")
+    flags = (_abi.CMX_SB2006_LIMITED if wr.is_limited else 0) | flag
+    keep = (wr, velp)      # the structs the pointers below refer to
+    return ref, fam, keep, (C.byref(wr.c), C.byref(tps), C.byref(velp), C.byref(cloud_vel) if cloud_vel is not None else None, flags, n_col, n_lev,
+                            _ptr(inv_dz), *[_ptr(t) for t in cols])
+
+
+def _column_primal_out(ref, with_tendencies):
+    if not with_tendencies:
+        return None, None
+    return torch.empty((4, *ref.shape), dtype=ref.dtype, device=ref.device), torch.empty(ref.shape[0], dtype=ref.dtype, device=ref.device)
+
+
+def column_jvp_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, tangents, with_tendencies=False, *, vel=SB2006VelType, vel_params=None,
+                  cloud_vel=None, stream=None) -> ColumnJvp2M:
+    """J v of `column_tendencies_sedimentation` — the four tendencies WITH the upwind flux divergence of the falling species — and of its precipitation flux,
+    behind `cmx_sb2006_column_jvp_*` (include/cmx.h §25): the matvec of a Newton–Krylov solver that treats microphysics and sedimentation implicitly
+    together.  One launch; ρ and `inv_dz` are held fixed.
+
+    State columns of shape (n_col, n_lev), `inv_dz`, `vel`, `vel_params`, `cloud_vel` as for `column_tendencies_sedimentation`.  `tangents`: dict name ->
+    tensor of the state's shape over `JACOBIAN_WRT`; a missing name is a zero tangent.  Returns `ColumnJvp2M(jvp, jvp_precip, tendencies, precip_flux)`:
+    `jvp` of shape (4, n_col, n_lev) in the order of `JACOBIAN_OUTPUTS`, `jvp_precip` (n_col,); with `with_tendencies=True` also `tendencies`
+    (4, n_col, n_lev) and `precip_flux` (n_col,), bit-identical to `column_tendencies_sedimentation`, else None.  Asynchronous on `stream`."""
+    if not isinstance(tangents, dict):
+        raise TypeError("tangents must be a dict: name of a differentiable input -> tensor")
+    _check_wrt(tangents.keys(), JACOBIAN_WRT, "tangents")
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    ref, fam, keep, head = _column_products_head(mp, tps, inv_dz, cols, vel, vel_params, cloud_vel)
+    given = [(k, v) for k, v in tangents.items() if v is not None]
+    if given:
+        _check_cols([ref] + [v for _, v in given], ["rho"] + [f"tangent of {k}" for k, _ in given])
+    jvp = torch.empty((4, *ref.shape), dtype=ref.dtype, device=ref.device)
+    jvp_precip = torch.empty(ref.shape[0], dtype=ref.dtype, device=ref.device)
+    tend, precip = _column_primal_out(ref, with_tendencies)
+    _lib.call("cmx_sb2006_column_jvp", fam, ref.device, *head, _table([tangents.get(name) for name in JACOBIAN_WRT]), _table([jvp[o] for o in range(4)]),
+              _ptr(jvp_precip), _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(precip), stream=stream)
+    return ColumnJvp2M(jvp, jvp_precip, tend, precip)
+
+
+def column_vjp_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, cot_precip=None, wrt=JACOBIAN_WRT, with_tendencies=False, *,
+                  vel=SB2006VelType, vel_params=None, cloud_vel=None, stream=None) -> ColumnVjp2M:
+    """Jᵀḡ of `column_tendencies_sedimentation` and its precipitation flux behind `cmx_sb2006_column_vjp_*` (include/cmx.h §25): the gradient of
+    Σ ḡ·tendencies + Σ p̄·precip_flux with respect to the inputs `wrt` — what `loss(precip_flux).backward()` needs (cmx.autograd).  One launch.
+
+    `cotangents`: a sequence of 4 tensors of the state's shape or None in the order of `JACOBIAN_OUTPUTS` (None: that output is not part of the sum);
+    `cot_precip`: a tensor of n_col values or None.  `wrt`: any subset of `JACOBIAN_WRT` in any order.  Returns `ColumnVjp2M(grad, tendencies, precip_flux,
+    wrt)`: `grad` of shape (len(wrt), n_col, n_lev) — a cotangent at level k reaches the gradients at levels k and k + 1 of its column; a gradient does not
+    depend on which others are requested.  `tendencies`, `precip_flux` and the other arguments as for `column_jvp_2m`."""
+    wrt = _check_wrt(wrt, JACOBIAN_WRT)
+    cotangents = list(cotangents)
+    if len(cotangents) != 4:
+        raise ValueError("cotangents: 4 tensors (or None) expected, one per output")
+    if not wrt and not with_tendencies:
+        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    ref, fam, keep, head = _column_products_head(mp, tps, inv_dz, cols, vel, vel_params, cloud_vel)
+    given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
+    if given:
+        _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])
+    if cot_precip is not None and (cot_precip.dtype != ref.dtype or cot_precip.device != ref.device or cot_precip.shape != (ref.shape[0],)
+                                   or not cot_precip.is_contiguous()):
+        raise ValueError("cot_precip must be a contiguous device vector of n_col values of the state dtype")
+    grad = torch.empty((len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
+    grads = [None] * len(JACOBIAN_WRT)
+    for k, name in enumerate(wrt):
+        grads[JACOBIAN_WRT.index(name)] = grad[k]
+    tend, precip = _column_primal_out(ref, with_tendencies)
+    _lib.call("cmx_sb2006_column_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip), _table(grads),
+              _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(precip), stream=stream)
+    return ColumnVjp2M(grad, tend, precip, wrt)
 
 
 def _column_implicit_2m(entry, mp, tps, inv_dz, cols, dt, nsub, nonnegative, vel, vel_params, cloud_vel, want_precip_flux, out, stream):

@@ -233,6 +233,11 @@ template <typename FT, int K> __device__ __forceinline__ Dual<FT, K> flat_where(
     CMX_DUAL_FOR r.d[k] = gate ? FT(0) : x.d[k];
     return r;
 }
+// Γ of the general Chen-2022 fall speed (cmx_math.hpp tgamma_general): its argument b_i(ρ) + 1 depends on the state through ρ only, which no entry
+// differentiates — the value part, every tangent the literal zero
+template <typename FT, int K> struct TGammaGeneral<Dual<FT, K>> {
+    static __device__ __forceinline__ Dual<FT, K> eval(const Dual<FT, K> &z) { return Dual<FT, K>(tgamma_general<FT>(z.v)); }
+};
 // the phase boundary of the constants (cmx_math.hpp consts_after) waits for the VALUE
 template <typename CT> struct holds_duals : std::false_type {};
 template <template <typename> class CT, typename FT, int K> struct holds_duals<CT<Dual<FT, K>>> : std::true_type {};

@@ -358,14 +358,18 @@ template <typename FT, typename G, typename VT> __device__ __forceinline__ VT ch
 
 // Γ(z) for ANY argument (the reference evaluates SF.gamma at run time, Common.jl:414-422): OCML's tgamma — ≈ 110 (Float32) / 300
 // (Float64) instructions, used only by the GENERAL instantiations that parameter sets outside the polynomial window above select
-template <typename FT> __device__ __forceinline__ FT tgamma_general(FT z) {
+// (a struct, so that the dual value type can specialise it partially: cmx_dual.hpp)
+template <typename FT> struct TGammaGeneral {
+    static __device__ __forceinline__ FT eval(FT z) {
 #if defined(CMX_HOST_BUILD)
-    return (FT)std::tgamma((double)z);
+        return (FT)std::tgamma((double)z);
 #else
-    if constexpr (sizeof(FT) == 8) return ::tgamma(z);
-    else return ::tgammaf(z);
+        if constexpr (sizeof(FT) == 8) return ::tgamma(z);
+        else return ::tgammaf(z);
 #endif
-}
+    }
+};
+template <typename FT> __device__ __forceinline__ FT tgamma_general(FT z) { return TGammaGeneral<FT>::eval(z); }
 #if CMX_HAVE_PACKED
 template <> __device__ __forceinline__ f32x2 tgamma_general<f32x2>(f32x2 z) { return f32x2{tgamma_general<float>(z.x), tgamma_general<float>(z.y)}; }
 #endif

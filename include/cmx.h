@@ -1924,6 +1924,64 @@ int32_t cmx_mp2m_p3_column_implicit_sedimentation_f64(const cmx_warm_rain_2m_f64
                                                       double *v_ice_m, double *precip_rai, double *precip_ice, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (25) The products J v and Jᵀḡ with the Jacobian of the SB2006 COLUMN step (2b) — tendencies, fall speeds and upwind flux divergence in one call, plus the
+ * surface precipitation flux — with respect to the prognostic state: cmx_sb2006_column_jvp_* and cmx_sb2006_column_vjp_*.  (16) differentiates the point
+ * function without its fall speeds; these differentiate what a host model steps.  J v is the matvec of a Newton–Krylov solver that treats microphysics and
+ * sedimentation implicitly together; Jᵀḡ with the cotangent of the precipitation flux is what loss(precip_flux).backward() needs (cmx.autograd).
+ * The function that is differentiated, normative — per column, level 0 the lowest, x_k = (T, q_tot, q_lcl, n_lcl, q_rai, n_rai)_k:
+ *     out_k  = tend(ρ_k, x_k) + g_k·(F_{k+1} − F_k)        g_k = inv_dz[k]·(1/ρ_k⁺)        F_{n_lev} = 0        precip = F_0[q_rai]
+ * F_k = ρ⁺χ⁺w: the fluxes of q_rai and n_rai, and of q_lcl and n_lcl when `cloud_vel` is given; the flux terms apply to those species' tendencies only.  The
+ * fluxes are those of (2b): the fall speeds the point function returns, multiplied as there.  ρ and inv_dz are held FIXED, as ρ is in (14) – (19).
+ * The clamps of the inputs, the ε floors, the gates and the max(0, ·) of the fall speeds are part of the function; the derivative is that of the branch taken,
+ * as in (14).  In the general Chen-2022 instantiation the Γ terms depend on ρ only: they are evaluated on the value and carry no tangent.
+ * With Ḟ_k = (∂F_k/∂x_k)·v_k, and J_pt the Jacobian of tend at the point:
+ *     J v:    ẏ_k = J_pt(x_k)·v_k + g_k·(Ḟ_{k+1} − Ḟ_k)          ṗ = Ḟ_0[q_rai], one value per column
+ *     Jᵀḡ:    x̄_k = J_pt(x_k)ᵀ·ḡ_k + (∂F_k/∂x_k)ᵀ·λ_k            λ_k[s] = −g_k·ḡ_k[s] + [k > 0]·g_{k−1}·ḡ_{k−1}[s] + [k = 0 and s = q_rai]·p̄
+ * for each falling species s; p̄ is the cotangent of the precipitation flux, one value per column.  The block Jacobian is upper bidiagonal in the level
+ * index and never couples two columns.
+ * Arguments: the head of the (2b) entries through n_rai, with its layout (n_col columns of n_lev contiguous levels), flags, limiter and fall-speed checks and
+ * their statuses, in that entry's order; then
+ *   jvp:  tangents[6] in the order of cmx_sb2006_jac_wrt (the table or a member NULL: a zero tangent), jvp[4] in the order of cmx_sb2006_jac_out, jvp_precip
+ *         (n_col values), tendencies[4], precip_flux (n_col values);
+ *   vjp:  cotangents[4] (the table or a member NULL: that output is structurally absent from the sum), cot_precip (n_col values or NULL: absent), grad[6],
+ *         tendencies[4], precip_flux.
+ * Every output table, every member and every output column may be NULL; a call with no output at all is CMX_ERR_BAD_ARG, and so is an output that is one of
+ * the call's input columns (a lane reads its neighbours).  n_col·n_lev is limited as in (2b); n_col = 0 is CMX_OK.
+ * Requested `tendencies` and `precip_flux` are those of the (2b) entry on the same columns, bit for bit.  The products are plain IEEE arithmetic on the
+ * tangents: Jᵀḡ accumulates the point sums with ḡ in output order, then the fluxes with λ in the order q_rai, n_rai, q_lcl, n_lcl, as one chain of fma
+ * seeded with −0 (no term at all: +0); each gradient comes from its own tangent slot, so its bits do not depend on which other gradients are requested.  T
+ * and q_tot do not enter the fluxes.  With inv_dz ≡ 0 the products equal those of (16) under == wherever the flux tangents are finite.
+ * NaN rule: a NaN in any state input, or in any given tangent or cotangent value of a point (p̄ counts for the level-0 point), gives NaN in every output of
+ * that point.  A NaN in an input of the fluxes (ρ, q_lcl, n_lcl, q_rai, n_rai) reaches the cell below through F and Ḟ exactly as in (2b), and the column's
+ * precipitation outputs at level 0; a NaN tangent reaches Ḟ by plain IEEE arithmetic.  In Jᵀḡ a NaN in ḡ_{k−1} or ρ_{k−1} reaches x̄_k by plain IEEE
+ * propagation through λ_k.  There is no other rule.
+ * Results do not depend on how the kernels divide the columns among workgroups, on alignment, or on the number of columns in the call.  Both entries are
+ * pure launches on `stream`: no allocation, no synchronisation, graph-capturable.
+ * Not done here: the 1-moment and the 2M + P3 column steps, derivatives with respect to ρ, inv_dz or the parameters through the column, the implicit
+ * column steps (20), (21).  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_column_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                  const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
+                                  const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                  const float *const tangents[CMX_SB2006_JAC_NWRT], float *const jvp[CMX_SB2006_JAC_NOUT], float *jvp_precip,
+                                  float *const tendencies[CMX_SB2006_JAC_NOUT], float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_jvp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                  const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho,
+                                  const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
+                                  const double *const tangents[CMX_SB2006_JAC_NWRT], double *const jvp[CMX_SB2006_JAC_NOUT], double *jvp_precip,
+                                  double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
+int32_t cmx_sb2006_column_vjp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                  const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
+                                  const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                  const float *const cotangents[CMX_SB2006_JAC_NOUT], const float *cot_precip, float *const grad[CMX_SB2006_JAC_NWRT],
+                                  float *const tendencies[CMX_SB2006_JAC_NOUT], float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                  const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho,
+                                  const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
+                                  const double *const cotangents[CMX_SB2006_JAC_NOUT], const double *cot_precip, double *const grad[CMX_SB2006_JAC_NWRT],
+                                  double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -1830,6 +1830,62 @@ function column_implicit_sedimentation!(out, ::BMT.Microphysics2Moment, mp::CMP.
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (25) products with the Jacobian of the SB2006 column step (2b): tendencies, fall speeds and sedimentation, and the precipitation flux
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    column_jvp_2m!(jvp, jvp_precip, tendencies, precip_flux, mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, tangents; stream = C_NULL)
+
+J v of `column_tendencies_sedimentation!(out, BMT.Microphysics2Moment(), …)` — the four tendencies WITH the upwind flux divergence of the falling species — and
+of its precipitation flux, with respect to (T, q_tot, q_lcl, n_lcl, q_rai, n_rai); ρ and `inv_dz` are held fixed.  The matvec of a Newton–Krylov solver over
+the column.  `tangents` = `nothing` or 6 columns (or `nothing`s: a zero tangent), `jvp`, `tendencies` = `nothing` or 4 columns (or `nothing`s), `jvp_precip`,
+`precip_flux` = `nothing` or `n_col` values.  `tendencies` and `precip_flux` are those of `column_tendencies_sedimentation!`, bit for bit.  No output may be
+one of the input columns.  include/cmx.h §(25) has the definition.
+"""
+function column_jvp_2m!(jvp, jvp_precip, tendencies, precip_flux, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, vel, cloud_vel, n_col::Integer,
+    n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, tangents; stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    tangents === nothing || length(tangents) == CMX_SB2006_JAC_NWRT || error("tangents: $(CMX_SB2006_JAC_NWRT) columns (or nothing) expected")
+    jvp === nothing || length(jvp) == CMX_SB2006_JAC_NOUT || error("jvp: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = (is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vel)
+    st = ccall(_fn("cmx_sb2006_column_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _opt_ptrs(FT, tangents), _opt_ptrs(FT, jvp), _dp(FT, jvp_precip), _opt_ptrs(FT, tendencies), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_jvp")
+    return jvp
+end
+
+"""
+    column_vjp_2m!(grad, tendencies, precip_flux, mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, cot_precip; stream = C_NULL)
+
+Jᵀḡ of the same function: `cotangents` = `nothing` or 4 columns (or `nothing`s: that output is not part of the sum), `cot_precip` = `nothing` or the `n_col`
+cotangents of the precipitation flux, `grad` = `nothing` or 6 columns (or `nothing`s: that input is not differentiated).  The gradient of
+Σ ḡ·out + Σ p̄·precip_flux, contracted on the device; a cotangent at level k reaches the gradients at levels k and k + 1 of its column.  `tendencies`,
+`precip_flux` and the aliasing rule as for `column_jvp_2m!`.
+"""
+function column_vjp_2m!(grad, tendencies, precip_flux, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, vel, cloud_vel, n_col::Integer, n_lev::Integer,
+    inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, cot_precip; stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    cotangents === nothing || length(cotangents) == CMX_SB2006_JAC_NOUT || error("cotangents: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    grad === nothing || length(grad) == CMX_SB2006_JAC_NWRT || error("grad: $(CMX_SB2006_JAC_NWRT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = (is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vel)
+    st = ccall(_fn("cmx_sb2006_column_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _opt_ptrs(FT, cotangents), _dp(FT, cot_precip), _opt_ptrs(FT, grad), _opt_ptrs(FT, tendencies), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
