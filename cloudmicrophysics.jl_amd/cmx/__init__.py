@@ -24,7 +24,8 @@ from .bulk_tendencies import (Chen2022VelTypeRain, Microphysics2Moment, SB2006Pr
                               WarmRainJvp2M, WarmRainVjp2M, warm_rain_jvp_2m, warm_rain_vjp_2m, WarmRainImplicit2M,
                               WarmRainParamJvp2M, WarmRainParamVjp2M, warm_rain_param_jvp_2m, warm_rain_param_vjp_2m,
                               warm_rain_implicit_tendencies_2m, warm_rain_implicit_average_2m, column_implicit_average_sedimentation_2m, column_implicit_step_2m,
-                              ColumnJvp2M, ColumnVjp2M, column_jvp_2m, column_vjp_2m)
+                              ColumnJvp2M, ColumnVjp2M, column_jvp_2m, column_vjp_2m,
+                              ColumnParamJvp2M, ColumnParamVjp2M, column_param_jvp_2m, column_param_vjp_2m)
 
 from .ice_nucleation import (IceNucleationRates, a_w_eT, a_w_ice, domain_error_count,  # noqa: F401
                              ice_nucleation_rates, liquid_freezing_rate, h2so4_solution, mohler2006_deposition, MohlerDeposition, deposition_J,

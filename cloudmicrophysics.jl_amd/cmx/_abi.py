@@ -158,6 +158,9 @@ CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 # J v and Jᵀḡ of the SB2006 column step with sedimentation (include/cmx.h §25): cmx_sb2006_column_jvp_* / _vjp_* take the head of
 # cmx_sb2006_column_tendencies_sedimentation_* through n_rai, then tangents[NWRT], jvp[NOUT], jvp_precip, tendencies[NOUT], precip_flux resp.
 # cotangents[NOUT], cot_precip, grad[NWRT], tendencies[NOUT], precip_flux, in the orders of SB2006_JAC_WRT / SB2006_JAC_OUT
+# … and its derivatives with respect to the parameters (include/cmx.h §26): cmx_sb2006_column_param_jvp_* / _param_vjp_* take the same head, then ndir,
+# d_warm_rain, d_tps, d_vel, d_cloud_vel, jvp[ndir·NOUT], jvp_precip[ndir], tendencies[NOUT], precip_flux resp. cotangents[NOUT], cot_precip, ndir, the four
+# direction tables, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies[NOUT], precip_flux
 # the derivatives with respect to the parameters (include/cmx.h §22, §23: cmx_mp1m_param_jvp_* / _param_vjp_* take the same lists over cmx_microphysics_1m): cmx_sb2006_warm_rain_param_jvp_* takes ndir, d_warm_rain[ndir], d_tps[ndir], jvp[ndir·NOUT],
 # tendencies[NOUT]; …_param_vjp_* takes cotangents[NOUT], ndir, d_warm_rain, d_tps, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies
 CMX_PARAM_MAX_DIRS = 16

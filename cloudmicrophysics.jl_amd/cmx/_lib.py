@@ -262,6 +262,16 @@ def _declare(lib):
         f = getattr(lib, f"cmx_sb2006_column_vjp_{s}")
         f.restype = i32
         f.argtypes = head + [C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), vp, vp]
+        # the derivatives of the same step with respect to the parameters (include/cmx.h §26): the same head, then
+        # (ndir, d_warm_rain, d_tps, d_vel, d_cloud_vel, jvp[ndir·4], jvp_precip[ndir], tendencies[4], precip_flux) /
+        # (cotangents[4], cot_precip, ndir, d_warm_rain, d_tps, d_vel, d_cloud_vel, grad, workspace, tendencies[4], precip_flux)
+        dirs = [i32, C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel), C.POINTER(fam.stokes_vel)]
+        f = getattr(lib, f"cmx_sb2006_column_param_jvp_{s}")
+        f.restype = i32
+        f.argtypes = head + dirs + [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]
+        f = getattr(lib, f"cmx_sb2006_column_param_vjp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), vp] + dirs + [vp, vp, C.POINTER(vp), vp, vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

@@ -12,7 +12,8 @@ values of the ClimaParams `names`; the forward pass rebuilds the parameter struc
 entry; backward calls the parameter-gradient entry (`warm_rain_param_vjp_2m` / `param_vjp_1m`) once for `theta.grad` (and the state Jᵀḡ entry if a state column needs a gradient), forward mode with a tangent on
 `theta` calls `warm_rain_param_jvp_2m` / `param_jvp_1m`.  `cmx.autograd.column_tendencies_sedimentation_2m` is the SB2006 column step with sedimentation and its precipitation flux (`cmx.column_tendencies_sedimentation`),
 differentiated through the fall speeds and the flux divergence by `column_vjp_2m` / `column_jvp_2m`; ρ and `inv_dz` are held fixed.  Not built: double backward (backward is once-differentiable), vmap, the
-fall-speed outputs of the pointwise entry, parameter derivatives through the column, LinearizedAverage and the 2M + P3 scheme."""
+fall-speed outputs of the pointwise entry, LinearizedAverage and the 2M + P3 scheme.  With `theta=, names=` the column step is also differentiated with respect to the
+parameters, the fall-speed parameters included (`column_param_vjp_2m` / `column_param_jvp_2m`, include/cmx.h §26)."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -101,7 +102,8 @@ _Tendencies1M = _function(
     lambda mp, tps, cols, tangents: _m1.jvp_1m(mp, tps, *cols, tangents))
 
 
-def _theta_function(name, WRT, primal, vjp, jvp, param_vjp, param_jvp):
+def _theta_function(name, WRT, primal, vjp, jvp, param_vjp, param_jvp, tangents_out=lambda r: tuple(r.jvp[o] for o in range(4)),
+                    param_tangents_out=lambda r: tuple(r.jvp[0][o] for o in range(4))):
     """The torch.autograd.Function of one scheme as a function of the parameter values `theta` (CPU) and the state: inputs (mp, tps, names, theta, rho, six
     columns), where mp / tps are the parameter objects already rebuilt with `theta`."""
     class F(torch.autograd.Function):
@@ -139,12 +141,11 @@ def _theta_function(name, WRT, primal, vjp, jvp, param_vjp, param_jvp):
             parts = []
             if t_theta is not None:
                 direction = {n: float(t) for n, t in zip(ctx.names, t_theta.tolist())}
-                parts.append(param_jvp(ctx.mp, ctx.tps, ctx.saved_tensors, [direction]).jvp[0])
+                parts.append(param_tangents_out(param_jvp(ctx.mp, ctx.tps, ctx.saved_tensors, [direction])))
             state = {n: t.contiguous() for n, t in zip(WRT, tangents) if t is not None}
             if state or not parts:
-                parts.append(jvp(ctx.mp, ctx.tps, ctx.saved_tensors, state).jvp)
-            total = parts[0] if len(parts) == 1 else parts[0] + parts[1]
-            return tuple(total[o] for o in range(4))
+                parts.append(tangents_out(jvp(ctx.mp, ctx.tps, ctx.saved_tensors, state)))
+            return parts[0] if len(parts) == 1 else tuple(a + b for a, b in zip(*parts))
     F.__name__ = F.__qualname__ = name
     return F
 
@@ -166,7 +167,18 @@ _Tendencies1MTheta = _theta_function(
     lambda mp, tps, cols, directions: _m1.param_jvp_1m(mp, tps, *cols, directions))
 
 
-def _with_theta(mp, tps, theta, names):
+# the column step as a function of theta: the parameter objects in the `mp` slot are a _ColumnStep whose structs were all rebuilt with theta
+_Column2MTheta = _theta_function(
+    "ColumnTendenciesSedimentation2MTheta", _bt.JACOBIAN_WRT, _column_primal,
+    lambda step, tps, cols, cotangents, wrt: _bt.column_vjp_2m(step.mp, tps, step.inv_dz, *cols, cotangents[:4], cotangents[4], wrt=wrt, **step.options),
+    lambda step, tps, cols, tangents: _bt.column_jvp_2m(step.mp, tps, step.inv_dz, *cols, tangents, **step.options),
+    lambda step, tps, cols, cotangents, names: _bt.column_param_vjp_2m(step.mp, tps, step.inv_dz, *cols, cotangents[:4], cotangents[4], names, **step.options),
+    lambda step, tps, cols, directions: _bt.column_param_jvp_2m(step.mp, tps, step.inv_dz, *cols, directions, **step.options),
+    tangents_out=lambda r: (*(r.jvp[o] for o in range(4)), r.jvp_precip),
+    param_tangents_out=lambda r: (*(r.jvp[0][o] for o in range(4)), r.jvp_precip[0]))
+
+
+def _with_theta(mp, tps, theta, names, known=None):
     """(parameter object, thermodynamics struct, names) rebuilt from mp's own dictionary with names[k] = theta[k]; `tps` itself unless a name feeds it."""
     if not (isinstance(theta, torch.Tensor) and theta.device.type == "cpu" and theta.dtype == torch.float64 and theta.dim() == 1):
         raise TypeError("theta: a 1-D CPU float64 tensor expected (the parameter structs are host data)")
@@ -175,7 +187,8 @@ def _with_theta(mp, tps, theta, names):
         raise ValueError("names: one distinct ClimaParams name per element of theta expected")
     one_moment = isinstance(mp, _P.Microphysics1MParams)
     p = mp if one_moment else _bt._warm_rain(mp)
-    known = _P.MICROPHYSICS_1M_DIRECTION_NAMES if one_moment else _P.WARM_RAIN_2M_DIRECTION_FIELDS
+    if known is None:
+        known = _P.MICROPHYSICS_1M_DIRECTION_NAMES if one_moment else _P.WARM_RAIN_2M_DIRECTION_FIELDS
     for n in names:
         if n not in known:
             raise ValueError(f"names: '{n}' feeds no floating field of the scheme's or the thermodynamics parameters")
@@ -190,6 +203,19 @@ def _with_theta(mp, tps, theta, names):
         raise ValueError("theta: a thermodynamics name rebuilds tps from mp's dictionary, and tps is not what that dictionary builds")
     td = _P.create_toml_dict(p.td.FT, {**base, **dict(zip(names, theta.detach().tolist()))})
     return rebuild(td), (_P.ThermodynamicsParameters(td) if feeds_tps else tps), names
+
+
+def _column_with_theta(mp, tps, theta, names, vel_params, cloud_vel):
+    """_with_theta for the column step: the two fall-speed structs are rebuilt from the same dictionary as `mp`, and one that this dictionary does not
+    build is refused like an edited `mp`."""
+    wr, tps_t, names = _with_theta(mp, tps, theta, names, known=_P.COLUMN_2M_DIRECTION_FIELDS)
+    p = _bt._warm_rain(mp)
+    td0 = _P.create_toml_dict(p.td.FT, {k: p.td[k] for k in p.td.overridden})
+    if vel_params is not None and bytes(_P.rain_vel_params(td0)) != bytes(vel_params):
+        raise ValueError("theta: vel_params is not what mp's dictionary builds; put the values into the dictionary mp is built from (create_toml_dict)")
+    if cloud_vel is not None and bytes(_P.StokesRegimeVelType(td0)) != bytes(cloud_vel):
+        raise ValueError("theta: cloud_vel is not what mp's dictionary builds; put the values into the dictionary mp is built from (create_toml_dict)")
+    return wr, tps_t, names, _P.rain_vel_params(wr.td), (_P.StokesRegimeVelType(wr.td) if cloud_vel is not None else None)
 
 
 def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, theta=None, names=None):
@@ -207,15 +233,28 @@ def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, 
     return _WarmRain2MTheta.apply(wr, tps_t, names, theta, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
 
 
-def column_tendencies_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, *, vel=_bt.SB2006VelType, vel_params=None, cloud_vel=None):
+def column_tendencies_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, *, vel=_bt.SB2006VelType, vel_params=None, cloud_vel=None,
+                                       theta=None, names=None):
     """(dq_lcl_dt, dn_lcl_dt, dq_rai_dt, dn_rai_dt, precip_flux) of `cmx.column_tendencies_sedimentation(mp, tps, inv_dz, …, want_precip_flux=True)`, bit for
     bit — the tendencies with the sedimentation flux divergence, shape (n_col, n_lev), and the surface precipitation flux, shape (n_col,) — differentiable by
     torch with respect to T, q_tot, q_lcl, n_lcl, q_rai, n_rai: backward is ONE Jᵀḡ launch (`cmx.column_vjp_2m`, the cotangent of the precipitation flux
     included: `precip_flux.sum().backward()` fills `.grad` of the state), forward mode ONE J v launch (`cmx.column_jvp_2m`).  ρ and `inv_dz` are held fixed:
-    asking for their gradient, or a forward-mode tangent on them, raises NotImplementedError."""
+    asking for their gradient, or a forward-mode tangent on them, raises NotImplementedError.
+
+    With `theta` (1-D CPU float64) and `names` (ClimaParams names, `cmx.parameters.COLUMN_2M_DIRECTION_FIELDS` — the fall-speed parameters included) also with
+    respect to those parameters: ALL the structs — `mp`, `tps` if a name feeds it, the rain fall-speed struct and `cloud_vel` if given — are rebuilt from
+    `mp`'s dictionary with names[k] = theta[k]; backward fills `theta.grad` with ONE `cmx.column_param_vjp_2m` call (plus the Jᵀḡ launch if a state column
+    needs a gradient), forward mode with a tangent on `theta` calls `cmx.column_param_jvp_2m`.  A `vel_params` or `cloud_vel` that the dictionary does not
+    build is a ValueError.  The Chen-2022 table is held fixed (no name reaches it)."""
     _check_rho(rho)
     if inv_dz.requires_grad or torch.autograd.forward_ad.unpack_dual(inv_dz).tangent is not None:
         raise NotImplementedError("inv_dz is held fixed: the column step is not differentiated with respect to the layer thickness")
+    if theta is not None:
+        wr, tps_t, names, velp, cv = _column_with_theta(mp, tps, theta, names, vel_params, cloud_vel)
+        return _Column2MTheta.apply(_ColumnStep(wr, inv_dz, dict(vel=vel, vel_params=velp, cloud_vel=cv)), tps_t, names, theta, rho, T, q_tot, q_lcl, n_lcl,
+                                    q_rai, n_rai)
+    if names is not None:
+        raise ValueError("names without theta")
     return _Column2M.apply(_ColumnStep(mp, inv_dz, dict(vel=vel, vel_params=vel_params, cloud_vel=cloud_vel)), tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
 
 

@@ -26,7 +26,7 @@ import torch
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr, _segments
 from ._jacobian import _check_step, _check_step_normal, _check_wrt, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _table, _vjp
-from .parameters import Microphysics2MParams, WarmRainParams2M, rain_vel_params
+from .parameters import Microphysics2MParams, WarmRainParams2M, column_parameter_direction, rain_vel_params
 
 
 class Microphysics2Moment:
@@ -550,6 +550,83 @@ def column_vjp_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, co
     _lib.call("cmx_sb2006_column_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip), _table(grads),
               _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(precip), stream=stream)
     return ColumnVjp2M(grad, tend, precip, wrt)
+
+
+ColumnParamJvp2M = namedtuple("ColumnParamJvp2M", ["jvp", "jvp_precip", "tendencies", "precip_flux"])
+ColumnParamVjp2M = namedtuple("ColumnParamVjp2M", ["grad", "tendencies", "precip_flux", "wrt"])
+
+
+def _column_param_directions(mp, fam, directions, vel_params, cloud_vel):
+    """The four direction tables of include/cmx.h §26 from a sequence whose members are {ClimaParams name: weight} mappings or the 4-tuples of
+    `parameters.column_parameter_direction`."""
+    wr = _warm_rain(mp)
+    quads = [column_parameter_direction(wr, d, vel_params, cloud_vel) if isinstance(d, dict) else tuple(d) for d in directions]
+    if not quads:
+        raise ValueError("directions: at least one direction expected")
+    types = (fam.warm_rain_2m, fam.thermo, fam.rain_vel, fam.stokes_vel)
+    for q in quads:
+        if len(q) != 4 or not all(isinstance(a, t) for a, t in zip(q, types)):
+            raise TypeError("directions: (d_warm_rain, d_thermo, d_rain_vel, d_stokes_vel) structs of the state's float type, or {name: weight} mappings")
+    return [(t * len(quads))(*[q[k] for q in quads]) for k, t in enumerate(types)]
+
+
+def column_param_jvp_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, directions, with_tendencies=False, *, vel=SB2006VelType, vel_params=None,
+                        cloud_vel=None, stream=None) -> ColumnParamJvp2M:
+    """J_θ·δθ of `column_tendencies_sedimentation` — the four tendencies with the flux divergence of the falling species — and of its precipitation flux with
+    respect to the scheme's PARAMETERS, the fall-speed parameters included, behind `cmx_sb2006_column_param_jvp_*` (include/cmx.h §26).  The state, ρ and
+    `inv_dz` are held fixed.
+
+    Arguments as for `column_jvp_2m`; `directions`: a sequence of {ClimaParams name: weight} mappings (`parameters.COLUMN_2M_DIRECTION_FIELDS` has the names)
+    or of the 4-tuples of `parameters.column_parameter_direction`.  Returns `ColumnParamJvp2M(jvp, jvp_precip, tendencies, precip_flux)`: `jvp` of shape
+    (len(directions), 4, n_col, n_lev), `jvp_precip` (len(directions), n_col); a column does not depend on which other directions are in the call.  The
+    Chen-2022 table is held fixed: a direction on it raises CmxStatusError (CMX_ERR_UNSUPPORTED).  Asynchronous on `stream`."""
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    ref, fam, keep, head = _column_products_head(mp, tps, inv_dz, cols, vel, vel_params, cloud_vel)
+    tables = _column_param_directions(mp, fam, directions, keep[1], cloud_vel)
+    ndir = len(tables[0])
+    jvp = torch.empty((ndir, 4, *ref.shape), dtype=ref.dtype, device=ref.device)
+    jvp_precip = torch.empty((ndir, ref.shape[0]), dtype=ref.dtype, device=ref.device)
+    tend, precip = _column_primal_out(ref, with_tendencies)
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        first = d0 == 0 and tend is not None
+        _lib.call("cmx_sb2006_column_param_jvp", fam, ref.device, *head, nd, *[C.byref(t[d0]) for t in tables],
+                  _table([jvp[d, o] for d in range(d0, d0 + nd) for o in range(4)]), _table([jvp_precip[d] for d in range(d0, d0 + nd)]),
+                  _table([tend[o] for o in range(4)]) if first else None, _ptr(precip) if first else None, stream=stream)
+    return ColumnParamJvp2M(jvp, jvp_precip, tend, precip)
+
+
+def column_param_vjp_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, cot_precip=None, wrt=(), with_tendencies=False, *,
+                        vel=SB2006VelType, vel_params=None, cloud_vel=None, stream=None) -> ColumnParamVjp2M:
+    """The gradient of Σ ḡ·tendencies + Σ p̄·precip_flux of `column_tendencies_sedimentation` with respect to the PARAMETERS behind
+    `cmx_sb2006_column_param_vjp_*` (include/cmx.h §26): what `loss(precip_flux).backward()` needs to reach `theta` (cmx.autograd).
+
+    `cotangents`, `cot_precip` as for `column_vjp_2m`; `wrt`: ClimaParams names (one-hot directions) or directions as for `column_param_jvp_2m`.  Returns
+    `ColumnParamVjp2M(grad, tendencies, precip_flux, wrt)`: `grad` a float64 tensor of len(wrt) values on the state's device — a fixed-order reduction,
+    bit-identical from run to run."""
+    wrt = tuple(wrt)
+    cotangents = list(cotangents)
+    if len(cotangents) != 4:
+        raise ValueError("cotangents: 4 tensors (or None) expected, one per output")
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    ref, fam, keep, head = _column_products_head(mp, tps, inv_dz, cols, vel, vel_params, cloud_vel)
+    tables = _column_param_directions(mp, fam, [{w: 1.0} if isinstance(w, str) else w for w in wrt], keep[1], cloud_vel)
+    given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
+    if given:
+        _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])
+    if cot_precip is not None and (cot_precip.dtype != ref.dtype or cot_precip.device != ref.device or cot_precip.shape != (ref.shape[0],)
+                                   or not cot_precip.is_contiguous()):
+        raise ValueError("cot_precip must be a contiguous device vector of n_col values of the state dtype")
+    ndir = len(tables[0])
+    grad = torch.empty(ndir, dtype=torch.float64, device=ref.device)
+    workspace = torch.empty(min(ndir, _abi.CMX_PARAM_MAX_DIRS) * _abi.CMX_PARAM_VJP_PARTIALS, dtype=torch.float64, device=ref.device)
+    tend, precip = _column_primal_out(ref, with_tendencies)
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        first = d0 == 0 and tend is not None
+        _lib.call("cmx_sb2006_column_param_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip), nd, *[C.byref(t[d0]) for t in tables],
+                  _ptr(grad[d0:]), _ptr(workspace), _table([tend[o] for o in range(4)]) if first else None, _ptr(precip) if first else None, stream=stream)
+    return ColumnParamVjp2M(grad, tend, precip, wrt)
 
 
 def _column_implicit_2m(entry, mp, tps, inv_dz, cols, dt, nsub, nonnegative, vel, vel_params, cloud_vel, want_precip_flux, out, stream):

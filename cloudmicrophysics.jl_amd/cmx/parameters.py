@@ -1197,3 +1197,37 @@ def parameter_direction(params, weights: Mapping):
         for which, path, dfield in fields:
             _add_field(d[which], path, float(weight) * (dfield(wr.c) if callable(dfield) else dfield))
     return d["wr"], d["tps"]
+
+
+# The directions of the SB2006 COLUMN step with its fall speeds (include/cmx.h §26): the §22 table plus the fields of the two fall-speed structs.  struct:
+# "wr", "tps" as above, "vel" = cmx_rain_vel (its sb2006 part; the Chen-2022 table is held fixed and has no row), "cloud_vel" = cmx_stokes_vel.
+COLUMN_2M_DIRECTION_FIELDS = {k: tuple(v) for k, v in WARM_RAIN_2M_DIRECTION_FIELDS.items()}
+COLUMN_2M_DIRECTION_FIELDS.update({
+    "SB2006_raindrops_terminal_velocity_coeff_aR": (("vel", "sb2006.aR", 1.0),),
+    "SB2006_raindrops_terminal_velocity_coeff_bR": (("vel", "sb2006.bR", 1.0),),
+    "SB2006_raindrops_terminal_velocity_coeff_cR": (("vel", "sb2006.cR", 1.0),),
+    "gravitational_acceleration": (("cloud_vel", "grav", 1.0), ("vel", "sb2006.grav", 1.0)),
+})
+COLUMN_2M_DIRECTION_FIELDS["SB2006_reference_air_density"] += (("vel", "sb2006.rho_0", 1.0),)
+COLUMN_2M_DIRECTION_FIELDS["density_liquid_water"] += (("cloud_vel", "rho_w", 1.0), ("vel", "sb2006.rho_w", 1.0))
+COLUMN_2M_DIRECTION_FIELDS["kinematic_viscosity_of_air"] += (("cloud_vel", "nu_air", 1.0), ("vel", "sb2006.nu_air", 1.0))
+
+
+def column_parameter_direction(mp, weights: Mapping, vel_params=None, cloud_vel=None):
+    """A direction δθ for the parameter derivatives of the SB2006 column step (`cmx.column_param_jvp_2m` / `column_param_vjp_2m`; include/cmx.h §26): the four
+    structs (d_warm_rain, d_thermo, d_rain_vel, d_stokes_vel) of the entry's own types whose fields hold Σ_name ∂field/∂name · δ(name), by the table
+    `COLUMN_2M_DIRECTION_FIELDS` — the table of `parameter_direction` plus the rain fall-speed coefficients aR, bR, cR, the gravitational acceleration, and the
+    fall-speed fields that the reference air density, the density of water and the viscosity of air also feed.  `mp`: `WarmRainParams2M` or
+    `Microphysics2MParams`.  `vel_params`, `cloud_vel`: accepted for symmetry with the wrappers (the table holds no function of their values).  The
+    Chen-2022 table has no row: it is held fixed."""
+    wr = getattr(mp, "warm_rain", mp)
+    if not isinstance(wr, WarmRainParams2M):
+        raise TypeError("column_parameter_direction: WarmRainParams2M or Microphysics2MParams expected")
+    d = {"wr": wr.fam.warm_rain_2m(), "tps": wr.fam.thermo(), "vel": wr.fam.rain_vel(), "cloud_vel": wr.fam.stokes_vel()}
+    for name, weight in weights.items():
+        fields = COLUMN_2M_DIRECTION_FIELDS.get(name)
+        if fields is None:
+            raise ValueError(f"column_parameter_direction: '{name}' feeds no floating field of the column step's parameters")
+        for which, path, dfield in fields:
+            _add_field(d[which], path, float(weight) * (dfield(wr.c) if callable(dfield) else dfield))
+    return d["wr"], d["tps"], d["vel"], d["cloud_vel"]

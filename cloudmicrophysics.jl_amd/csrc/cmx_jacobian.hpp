@@ -884,24 +884,11 @@ __global__ __launch_bounds__(BS) void param_jvp_kernel(const CD c, const ParamJv
     param_jvp_point<S, FT, KP>(c, a, x, i);
 }
 
-// Stage 1 of the gradient (param_vjp_chunk has the decomposition): the lane's accumulators, then the 64 lanes of a wave in a fixed shuffle tree, then the waves
-// left to right → ws[k·CMX_PARAM_VJP_PARTIALS + b].  No floating-point atomics: the result is a pure function of the inputs and n, bit-identical from run to run.
-template <typename S, typename FT, int KP, int BS, typename CD>
-__global__ __launch_bounds__(BS) void param_vjp_kernel(const CD c, const ParamVjpArgs<FT, S::NOUT, S::NWRT> a, const int64_t n, const int64_t chunk,
-                                                       const int32_t nlive, double *__restrict__ ws) {
+// The end of stage 1 of the gradient, shared by every kernel that feeds the reduction (param_vjp_kernel below; column_param_vjp_kernel,
+// cmx_sb2006_column_param.hip): the lane's accumulators, then the 64 lanes of a wave in a fixed shuffle tree, then the waves left to right →
+// ws[k·CMX_PARAM_VJP_PARTIALS + b].  Every lane of the workgroup calls it.
+template <int KP, int BS> __device__ __forceinline__ void param_vjp_reduce(const double (&acc)[KP], const int32_t nlive, double *__restrict__ ws) {
     static_assert(BS % 64 == 0 && KP <= BS, "whole waves");
-    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
-    Math<FT>::prepare();
-    double acc[KP];
-#pragma unroll
-    for (int k = 0; k < KP; ++k) acc[k] = 0.0;
-#pragma unroll 1
-    for (int64_t i = lo + threadIdx.x; i < hi; i += BS) {
-        FT x[S::NWRT + 1];
-#pragma unroll
-        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
-        param_vjp_point<S, FT, KP>(c, a, x, i, acc);
-    }
     __shared__ double part[KP][BS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -918,6 +905,26 @@ __global__ __launch_bounds__(BS) void param_vjp_kernel(const CD c, const ParamVj
         for (int w = 0; w < BS / 64; ++w) t += part[threadIdx.x][w];
         ws[(int64_t)threadIdx.x * CMX_PARAM_VJP_PARTIALS + blockIdx.x] = t;
     }
+}
+
+// Stage 1 of the gradient (param_vjp_chunk has the decomposition): the lane's accumulators, then param_vjp_reduce.  No floating-point atomics: the result is
+// a pure function of the inputs and n, bit-identical from run to run.
+template <typename S, typename FT, int KP, int BS, typename CD>
+__global__ __launch_bounds__(BS) void param_vjp_kernel(const CD c, const ParamVjpArgs<FT, S::NOUT, S::NWRT> a, const int64_t n, const int64_t chunk,
+                                                       const int32_t nlive, double *__restrict__ ws) {
+    const int64_t lo = (int64_t)blockIdx.x * chunk, hi = lo + chunk < n ? lo + chunk : n;
+    Math<FT>::prepare();
+    double acc[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) acc[k] = 0.0;
+#pragma unroll 1
+    for (int64_t i = lo + threadIdx.x; i < hi; i += BS) {
+        FT x[S::NWRT + 1];
+#pragma unroll
+        for (int j = 0; j < S::NWRT + 1; ++j) x[j] = __builtin_nontemporal_load(a.in[j] + i);
+        param_vjp_point<S, FT, KP>(c, a, x, i, acc);
+    }
+    param_vjp_reduce<KP, BS>(acc, nlive, ws);
 }
 
 // Stage 2: one workgroup per direction; lane t adds the partials 4t … 4t + 3 left to right, then the same tree → grad[d].

@@ -3,7 +3,8 @@
 //
 //   ParamTan            a value and ONE tangent in double.  The value part of every operation is the plain double operation, so the value parts of a folded
 //                       constants struct are the plain instantiation's in every bit; the tangent follows the analytic rule.  fmax carries the tangent of the
-//                       operand it returns (the first one on a tie), like the branching operations of cmx_dual.hpp.
+//                       operand it returns (the first one on a tie), like the branching operations of cmx_dual.hpp.  lgamma carries ψ(x)·ẋ (digamma
+//                       below: the cloud fall-speed fold make_cloud_vel_consts_from, cmx_sb2006.hpp).
 //   ParamReader         reads a field of a parameter struct as ParamTan: the value from the struct, the tangent from the field at the same offset of the
 //                       DIRECTION struct (the same C type holding δθ; NULL: zero).  The parameter structs are plain aggregates of one float type.
 //   pack_param_consts   a constants struct of ParamTan members → tangent slot k of the same struct of Dual<FT, KP> members (value parts rounded to FT exactly
@@ -51,6 +52,20 @@ inline ParamTan pow(ParamTan x, ParamTan y) {      // x > 0
     const double p = std::pow(x.v, y.v);
     return {p, p * (y.d * std::log(x.v) + y.v * x.d / x.v)};
 }
+// ψ(x) = d log Γ(x)/dx for x > 0 in double: the recurrence ψ(x) = ψ(x + 1) − 1/x up to x ≥ 6, then the asymptotic series through B₁₄ (its first omitted
+// term, B₁₆/(16 x¹⁶), is below 2e-13 there).  NaN for x ≤ 0: no fold takes log Γ there.
+inline double digamma(double x) {
+    if (!(x > 0.0)) return std::nan("");
+    double s = 0.0;
+    while (x < 6.0) {
+        s -= 1.0 / x;
+        x += 1.0;
+    }
+    const double f = 1.0 / (x * x);
+    const double series = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132 - f * (691.0 / 32760 - f * (1.0 / 12)))))));
+    return s + std::log(x) - 0.5 / x - series;
+}
+inline ParamTan lgamma(ParamTan x) { return {std::lgamma(x.v), digamma(x.v) * x.d}; }
 inline ParamTan fmax(ParamTan a, ParamTan b) { return (b.v > a.v || a.v != a.v) ? ParamTan{std::fmax(a.v, b.v), b.d} : ParamTan{std::fmax(a.v, b.v), a.d}; }
 
 // every floating member of a parameter struct or of a direction is finite (the structs hold nothing else)

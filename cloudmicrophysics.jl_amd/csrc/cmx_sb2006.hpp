@@ -83,10 +83,13 @@ template <typename K, typename PR> inline void fill_rain_pdf_limiters(K &k, cons
 // The fold, generic in how a parameter is read and in the scalar the result holds: P(field) / Q(field) read a field of `wr` / `tp` as the working scalar W —
 // double for the plain fold (make_sb_consts below: R = FT, every line the double arithmetic it always was), a value with a tangent for the parameter
 // derivatives (cmx_param_tangent.hpp: R = W = ParamTan; the value parts are the plain fold's in every bit).  The mathematical functions are found by
-// argument-dependent lookup for such a W.  The velocity constants are folded by the plain fold only.
-template <typename FT, typename R, typename WR, typename TH, typename VL, typename PW, typename PT>
-inline SbConsts<R> make_sb_consts_from(const WR &wr, const TH &tp, const VL *vel, double eps_1m, const PW &P, const PT &Q) {
-    using std::cbrt; using std::fmax; using std::log2; using std::sqrt;
+// argument-dependent lookup for such a W.  V(field) reads a field of `vel->sb2006` the same way: the SB2006 rain fall-speed constants carry tangents too
+// (include/cmx.h §(26)).  The Chen-2022 table is held fixed: its constants are the plain fold's values with zero tangents, and the fitted coefficients
+// ChenLog<R> are ChenLog<FT>'s (a table of tangent-carrying scalars has the Float64 degree in both float types, cmx_math.hpp; the monomials past the Float32
+// degree stay zero and are not read).
+template <typename FT, typename R, typename WR, typename TH, typename VL, typename PW, typename PT, typename PV>
+inline SbConsts<R> make_sb_consts_from(const WR &wr, const TH &tp, const VL *vel, double eps_1m, const PW &P, const PT &Q, const PV &V) {
+    using std::cbrt; using std::exp; using std::fmax; using std::log; using std::log2; using std::sqrt;
     using W = decltype(P(wr.condevap_tau_relax));
     SbConsts<R> c{};
     const auto &sb = wr.seifert_beheng;
@@ -188,32 +191,51 @@ inline SbConsts<R> make_sb_consts_from(const WR &wr, const TH &tp, const VL *vel
     c.inv_xr_min = (R)(1.0 / P(pr.xr_min));
     c.inv_xr_max = (R)(1.0 / P(pr.xr_max));
     // velocities
-    if constexpr (std::is_same<R, FT>::value) if (vel) {
+    if (vel) {
         const auto &v = vel->sb2006;
-        c.vel_s = (FT)std::sqrt((double)v.rho_0);
-        c.aR = (FT)v.aR;
-        c.bR = (FT)v.bR;
-        c.cR = (FT)v.cR;
-        const double rc2 = -1.0 / (double)v.cR * std::log((double)v.aR / (double)v.bR);  // 2·r_c
-        c.rc2 = (FT)rc2;
-        c.e_rc2cR = (FT)std::exp(-rc2 * (double)v.cR);
+        c.vel_s = (R)sqrt(V(v.rho_0));
+        c.aR = (R)V(v.aR);
+        c.bR = (R)V(v.bR);
+        c.cR = (R)V(v.cR);
+        const W rc2 = -1.0 / V(v.cR) * log(V(v.aR) / V(v.bR));  // 2·r_c
+        c.rc2 = (R)rc2;
+        c.e_rc2cR = (R)exp(-rc2 * V(v.cR));
         const auto &ch = vel->chen2022;
-        c.ch_rho0_l2e = (FT)((double)ch.rho_0 * l2e);
+        c.ch_rho0_l2e = (R)(FT)((double)ch.rho_0 * 1.4426950408889634074);
         for (int i = 0; i < 3; ++i) {
-            c.ch_a[i] = (FT)ch.a[i];
-            c.ch_b[i] = (FT)ch.b[i];
-            c.ch_c1000[i] = (FT)((double)ch.c[i] * 1000.0);
+            c.ch_a[i] = (R)(FT)ch.a[i];
+            c.ch_b[i] = (R)(FT)ch.b[i];
+            c.ch_c1000[i] = (R)(FT)((double)ch.c[i] * 1000.0);
         }
-        c.ch_a3_pow = (FT)ch.a3_pow;
-        c.ch_b_rho = (FT)ch.b_rho;
-        c.l2_1000 = (FT)std::log2(1000.0);
-        (void)make_chen_log<FT>(ch, c.chl);        // the entry points test the fit themselves (chen_vel_kind)
+        c.ch_a3_pow = (R)(FT)ch.a3_pow;
+        c.ch_b_rho = (R)(FT)ch.b_rho;
+        c.l2_1000 = (R)(FT)std::log2(1000.0);
+        if constexpr (std::is_same<R, FT>::value) {
+            (void)make_chen_log<FT>(ch, c.chl);        // the entry points test the fit themselves (chen_vel_kind)
+        } else {
+            ChenLog<FT> g{};
+            (void)make_chen_log<FT>(ch, g);
+            for (int i = 0; i < 3; ++i) {
+                for (int kk = 0; kk < 2; ++kk)
+                    for (int m = 0; m <= ChenLog<FT>::D; ++m) c.chl.c[kk][i][m] = (R)g.c[kk][i][m];
+                c.chl.sgn[i] = (R)g.sgn[i];
+                c.chl.b1[i] = (R)g.b1[i];
+                c.chl.b4[i] = (R)g.b4[i];
+            }
+        }
     }
     return c;
 }
+// the same with `vel` read plainly: no tangent on a fall-speed constant (the point entries of §(22), which run no fall speed)
+template <typename FT, typename R, typename WR, typename TH, typename VL, typename PW, typename PT>
+inline SbConsts<R> make_sb_consts_from(const WR &wr, const TH &tp, const VL *vel, double eps_1m, const PW &P, const PT &Q) {
+    using W = decltype(P(wr.condevap_tau_relax));
+    return make_sb_consts_from<FT, R>(wr, tp, vel, eps_1m, P, Q, [](const auto &f) { return W((double)f); });
+}
 template <typename FT, typename WR, typename TH, typename VL>
 inline SbConsts<FT> make_sb_consts(const WR &wr, const TH &tp, const VL *vel, double eps_1m) {
-    return make_sb_consts_from<FT, FT>(wr, tp, vel, eps_1m, [](const auto &f) { return (double)f; }, [](const auto &f) { return (double)f; });
+    return make_sb_consts_from<FT, FT>(wr, tp, vel, eps_1m, [](const auto &f) { return (double)f; }, [](const auto &f) { return (double)f; },
+                                       [](const auto &f) { return (double)f; });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -238,16 +260,24 @@ template <typename FT> struct SbRates {
 // droplet mass x̄ = ρq/N:  vt_n = pref·K₂₃·x̄^(2/3),  vt_m = pref·K₅₃·x̄^(5/3)·N/(ρq) = pref·K₅₃·x̄^(2/3),
 // K_n = (Γ(z₁)/Γ(z₂))^n · Γ(z₁ + n/μ)/Γ(z₁) parameter-only (host, double).
 template <typename FT> struct CloudVelConsts { FT pre_c, rho_w, K23, K53; };
+// Generic in how a parameter is read and in the scalar the result holds, like make_sb_consts_from: P(field) reads a field of `pdf` (loggamma_z1 and
+// loggamma_z2 are read as FIELDS, like every other), S(field) one of `vel`; R = FT with plain readers is the fold it always was, operation for operation.
+template <typename FT, typename R, typename PDF, typename VEL, typename PP, typename PS>
+inline CloudVelConsts<R> make_cloud_vel_consts_from(const PDF &pdf, const VEL &vel, const PP &P, const PS &S) {
+    using std::cbrt; using std::exp; using std::lgamma; using std::pow;
+    using W = decltype(P(pdf.nu_c));
+    const W pi = 3.14159265358979323846, nu = P(pdf.nu_c), mu = P(pdf.mu_c), z1 = (nu + 1.0) / mu;
+    const W dlg = P(pdf.loggamma_z1) - P(pdf.loggamma_z2);   // log Γ(z₁)/Γ(z₂)
+    CloudVelConsts<R> c;
+    c.rho_w = (R)S(vel.rho_w);
+    c.pre_c = (R)(1.0 / 18.0 * cbrt(pow(6.0 / S(vel.rho_w) / pi, W(2.0))) * S(vel.grav) / S(vel.nu_air));
+    c.K23 = (R)exp(2.0 / 3.0 * dlg + lgamma(z1 + 2.0 / 3.0 / mu) - lgamma(z1));
+    c.K53 = (R)exp(5.0 / 3.0 * dlg + lgamma(z1 + 5.0 / 3.0 / mu) - lgamma(z1));
+    return c;
+}
 template <typename FT, typename PDF, typename VEL>
 inline CloudVelConsts<FT> make_cloud_vel_consts(const PDF &pdf, const VEL &vel) {
-    const double pi = 3.14159265358979323846, nu = pdf.nu_c, mu = pdf.mu_c, z1 = (nu + 1.0) / mu;
-    const double dlg = (double)pdf.loggamma_z1 - (double)pdf.loggamma_z2;   // log Γ(z₁)/Γ(z₂)
-    CloudVelConsts<FT> c;
-    c.rho_w = (FT)vel.rho_w;
-    c.pre_c = (FT)(1.0 / 18.0 * std::cbrt(std::pow(6.0 / (double)vel.rho_w / pi, 2.0)) * (double)vel.grav / (double)vel.nu_air);
-    c.K23 = (FT)std::exp(2.0 / 3.0 * dlg + std::lgamma(z1 + 2.0 / 3.0 / mu) - std::lgamma(z1));
-    c.K53 = (FT)std::exp(5.0 / 3.0 * dlg + std::lgamma(z1 + 5.0 / 3.0 / mu) - std::lgamma(z1));
-    return c;
+    return make_cloud_vel_consts_from<FT, FT>(pdf, vel, [](const auto &f) { return (double)f; }, [](const auto &f) { return (double)f; });
 }
 template <typename FT, typename CV>      // FT: the value type; CV: CloudVelConsts of its scalar type
 __device__ __forceinline__ void sb2006_cloud_velocity(const CV &c, FT q, FT r, FT N, FT &vt_n, FT &vt_m) {

@@ -62,8 +62,9 @@ template <bool LIMITED, int VEL, bool CLOUD, bool INTPOW> struct SbColJac {
         return rs * rs;
     }
     // in: the six differentiated inputs in the order of cmx_sb2006_jac_wrt; o: the point sums, F: the fluxes, g = inv_dz·(1/ρ⁺)
-    template <typename FT, int K, typename C>
-    static __device__ __forceinline__ void eval(const C &c, const CloudVelConsts<FT> &cv, FT rho, FT inv_dz, const Dual<FT, K> (&in)[NWRT], Dual<FT, K> (&o)[NOUT],
+    // (CV: CloudVelConsts<FT>, or CloudVelConsts<Dual<FT, K>> next to constants that hold duals themselves: cmx_sb2006_column_param.hpp)
+    template <typename FT, int K, typename C, typename CV>
+    static __device__ __forceinline__ void eval(const C &c, const CV &cv, FT rho, FT inv_dz, const Dual<FT, K> (&in)[NWRT], Dual<FT, K> (&o)[NOUT],
                                                 Dual<FT, K> (&F)[4], FT &g) {
         using D = Dual<FT, K>;
         using MD = Math<D>;

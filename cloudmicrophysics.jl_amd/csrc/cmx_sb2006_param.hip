@@ -117,3 +117,11 @@ int32_t cmx_sb2006_warm_rain_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain
                                         workspace, tendencies, stream);
 }
 }
+
+// Stage 2 of the parameter gradients for the other translation units that feed the reduction (cmx_sb2006_column_param.hip): the one instantiation of
+// param_vjp_finish_kernel this file already launches.  (At the end of the file: the kernels are emitted in the order of their first use.)
+namespace cmx {
+void launch_param_vjp_finish(int32_t ndir, const double *workspace, double *grad, hipStream_t stream) {
+    launch_grid(param_vjp_finish_kernel<kParamBS>, dim3((unsigned)ndir), dim3(kParamBS), 0, stream, workspace, grad);
+}
+}  // namespace cmx

@@ -1823,7 +1823,7 @@ int32_t cmx_mp1m_column_implicit_step_f64(const cmx_microphysics_1m_f64 *mp, con
  * 1 … CMX_PARAM_MAX_DIRS; a NULL direction table (param_vjp: or a NULL cotangent table); no output at all (param_vjp: a NULL grad or workspace); a
  * non-finite component in a direction; the flags and limiters of (14) — all CMX_ERR_BAD_ARG, all before the first enqueue.  NaN rule: a NaN in any of the
  * seven inputs of a point gives NaN in every jvp and tendency of that point; in param_vjp a NaN in a point's state or cotangents makes every grad[d] NaN.
- * Graph-capturable; any alignment.  The 1-moment scheme: (23).  Not done here: the fall-speed outputs, the implicit and column entries, second derivatives.
+ * Graph-capturable; any alignment.  The 1-moment scheme: (23).  Not done here: the fall-speed outputs, the implicit entries, second derivatives.  The SB2006 column step with its fall speeds: (26).
  * ------------------------------------------------------------------------- */
 #define CMX_PARAM_MAX_DIRS 16
 #define CMX_PARAM_VJP_PARTIALS 1024
@@ -1957,8 +1957,8 @@ int32_t cmx_mp2m_p3_column_implicit_sedimentation_f64(const cmx_warm_rain_2m_f64
  * propagation through λ_k.  There is no other rule.
  * Results do not depend on how the kernels divide the columns among workgroups, on alignment, or on the number of columns in the call.  Both entries are
  * pure launches on `stream`: no allocation, no synchronisation, graph-capturable.
- * Not done here: the 1-moment and the 2M + P3 column steps, derivatives with respect to ρ, inv_dz or the parameters through the column, the implicit
- * column steps (20), (21).  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * Not done here: the 1-moment and the 2M + P3 column steps, derivatives with respect to ρ or inv_dz, the implicit column steps (20), (21).  The
+ * parameters through the column: (26).  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
                                   const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
@@ -1980,6 +1980,70 @@ int32_t cmx_sb2006_column_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const c
                                   const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
                                   const double *const cotangents[CMX_SB2006_JAC_NOUT], const double *cot_precip, double *const grad[CMX_SB2006_JAC_NWRT],
                                   double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (26) The derivatives of the SB2006 COLUMN step (2b), (25) with respect to the scheme's PARAMETERS, the fall-speed parameters and the surface
+ * precipitation flux included: cmx_sb2006_column_param_jvp_* (per point, J_θ·δθ) and cmx_sb2006_column_param_vjp_* (the reduced gradient dL/dθ).  (22)
+ * stops before the fall speeds; (25) reaches the state but not θ.  This is what loss(precip_flux).backward() needs to reach `theta` (cmx.autograd).
+ * The function is that of (25), normative, with the state, ρ and inv_dz held FIXED and θ = every floating field of the four parameter structs the (2b)
+ * entry reads:
+ *     out_k = tend(ρ_k, x_k; θ) + g_k·(F_{k+1}(θ) − F_k(θ))        precip = F_0[q_rai]
+ * With Ḟ_k = ∂F_k/∂θ·δθ:
+ *     J_θ δθ:    ẏ_k = ∂tend/∂θ·δθ + g_k·(Ḟ_{k+1} − Ḟ_k)          ṗ = Ḟ_0[q_rai], one value per column
+ *     gradient:  grad[d] = Σ_columns Σ_k ( Σ_o ḡ_{o,k}·(∂tend_o/∂θ·δθ⁽ᵈ⁾)_k + Σ_s λ_k[s]·Ḟ_k[s]⁽ᵈ⁾ ),  λ_k exactly that of (25), p̄ at level 0 for q_rai
+ * A DIRECTION is four structs of the entry's own types holding δθ: d_warm_rain[ndir] (required), d_tps[ndir], d_vel[ndir], d_cloud_vel[ndir] (each may be
+ * NULL: zero).  Without `cloud_vel`, d_cloud_vel is IGNORED (not read, not checked).  The tangents of the folded constants are formed on the host in exact
+ * forward mode in double (no difference quotient), as in (22); the fields loggamma_z1 and loggamma_z2 of pdf_c are read as fields, so a direction along
+ * ν_c or μ_c moves them too (cmx.parameters.column_parameter_direction does).
+ * The Chen-2022 table (vel.chen2022: a, b, c, rho_0, a3_pow, b_rho) is HELD FIXED: any non-zero component of a direction there is CMX_ERR_UNSUPPORTED,
+ * whatever the flags (the fitted instantiation takes it through a polynomial fit of log2 Γ, which has no derivative here; the general one would need ψ on the
+ * device).  With CMX_VEL_CHEN2022 every other parameter still reaches the fluxes through λ, the limiters and π ρ_w.
+ * Arguments: the head of the (2b) entries through n_rai; then
+ *   jvp:  ndir (1 … CMX_PARAM_MAX_DIRS), the four direction tables, jvp[ndir·4] (direction-major, then cmx_sb2006_jac_out), jvp_precip[ndir] (columns of
+ *         n_col values), tendencies[4], precip_flux.  Every output table, member and column may be NULL; no output at all is CMX_ERR_BAD_ARG.
+ *   vjp:  cotangents[4] (the table or a member NULL: absent), cot_precip (n_col values or NULL), ndir, the direction tables, grad (ndir doubles, device),
+ *         workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles, device), tendencies[4], precip_flux.
+ * Statuses, in order: the parameter pointers and counts, the flags, the limit on n_col·n_lev [jvp: n_col = 0 is CMX_OK here], the columns, ndir and
+ * d_warm_rain, [vjp: grad and workspace], the outputs (none may be an input column, inv_dz or a cotangent: a lane reads its neighbours), a non-finite
+ * component of a direction (CMX_ERR_BAD_ARG), a direction on the Chen-2022 table (CMX_ERR_UNSUPPORTED), the limiters and the fall-speed parameters as in
+ * (2b).  n_col = 0 of the gradient entry passes all of these but the columns and writes zeros to grad.
+ * The rules of (22) and (25) hold: a direction on acnv.b, accr.c or self.d selects the general-exponent instantiation for the whole call; the derivative is
+ * that of the branch taken; a NaN in a state input of a point poisons that point's outputs, a NaN in an input of the fluxes reaches the cell below and the
+ * precipitation outputs, and in the gradient any such NaN — or one in a cotangent — makes every grad[d] NaN.
+ * Requested `tendencies` and `precip_flux` are those of the (2b) entry bit for bit when no direction touches an exponent.  A jvp column's bits and a grad
+ * value's bits do not depend on ndir, on which other directions are in the call, or on how the call is split into launches; the gradient is a fixed-order
+ * reduction without atomics (the decomposition of (22)), bit-identical from run to run.  No allocation, graph-capturable.
+ * Not shipped: the Float64 GRADIENT entry with a Chen-2022 table that takes the general instantiation (run-time Γ) returns CMX_ERR_UNSUPPORTED — its kernel
+ * needs 482–511 vector registers at one direction per evaluation and spills 8; the jvp entry serves that case (264–278).
+ * Not done here: the 1-moment and 2M + P3 columns, the implicit column steps, derivatives with respect to ρ or inv_dz, of the Chen-2022 table, second
+ * derivatives.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * ------------------------------------------------------------------------- */
+int32_t cmx_sb2006_column_param_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                        const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
+                                        const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai, int32_t ndir,
+                                        const cmx_warm_rain_2m_f32 *d_warm_rain, const cmx_thermo_f32 *d_tps, const cmx_rain_vel_f32 *d_vel,
+                                        const cmx_stokes_vel_f32 *d_cloud_vel, float *const *jvp, float *const *jvp_precip,
+                                        float *const tendencies[CMX_SB2006_JAC_NOUT], float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_param_vjp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                        const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
+                                        const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai, const float *n_rai,
+                                        const float *const cotangents[CMX_SB2006_JAC_NOUT], const float *cot_precip, int32_t ndir,
+                                        const cmx_warm_rain_2m_f32 *d_warm_rain, const cmx_thermo_f32 *d_tps, const cmx_rain_vel_f32 *d_vel,
+                                        const cmx_stokes_vel_f32 *d_cloud_vel, double *grad, double *workspace,
+                                        float *const tendencies[CMX_SB2006_JAC_NOUT], float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_param_jvp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                        const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho,
+                                        const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai, int32_t ndir,
+                                        const cmx_warm_rain_2m_f64 *d_warm_rain, const cmx_thermo_f64 *d_tps, const cmx_rain_vel_f64 *d_vel,
+                                        const cmx_stokes_vel_f64 *d_cloud_vel, double *const *jvp, double *const *jvp_precip,
+                                        double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
+int32_t cmx_sb2006_column_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                        const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho,
+                                        const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai, const double *n_rai,
+                                        const double *const cotangents[CMX_SB2006_JAC_NOUT], const double *cot_precip, int32_t ndir,
+                                        const cmx_warm_rain_2m_f64 *d_warm_rain, const cmx_thermo_f64 *d_tps, const cmx_rain_vel_f64 *d_vel,
+                                        const cmx_stokes_vel_f64 *d_cloud_vel, double *grad, double *workspace,
+                                        double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

@@ -1886,6 +1886,81 @@ function column_vjp_2m!(grad, tendencies, precip_flux, mp::CMP.Microphysics2MPar
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (26) the derivatives of the SB2006 column step (2b), (25) with respect to the parameters, the fall-speed parameters and the precipitation flux included
+# ----------------------------------------------------------------------------------------------------------------
+# the four direction tables of (26): `d_warm_rain`, `d_tps` as in (22); `d_vel` = nothing (zero) or one `CmxRainVel` per direction whose fields hold δθ — its
+# Chen-2022 part must hold ZEROS, the table is held fixed (CMX_ERR_UNSUPPORTED otherwise); `d_cloud_vel` = nothing or one CMP.StokesRegimeVelType per direction
+function _column_param_directions(d_warm_rain, d_tps, d_vel, d_cloud_vel)
+    dw, dt = _param_directions(d_warm_rain, d_tps)
+    d_vel === nothing || length(d_vel) == length(dw) || error("d_vel: nothing or one per direction expected")
+    d_cloud_vel === nothing || length(d_cloud_vel) == length(dw) || error("d_cloud_vel: nothing or one per direction expected")
+    dv = d_vel === nothing ? nothing : collect(d_vel)
+    dc = d_cloud_vel === nothing ? nothing : collect(d_cloud_vel)
+    return dw, dt, dv, dc
+end
+
+"""
+    column_param_jvp_2m!(jvp, jvp_precip, tendencies, precip_flux, mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+                         d_warm_rain, d_tps = nothing, d_vel = nothing, d_cloud_vel = nothing; stream = C_NULL)
+
+The derivative of `column_tendencies_sedimentation!(out, BMT.Microphysics2Moment(), …)` and of its precipitation flux with respect to the PARAMETERS along the
+directions (`d_warm_rain[d]`, `d_tps[d]`, `d_vel[d]`, `d_cloud_vel[d]`): objects of the types of the four parameter arguments whose fields hold δθ (`d_vel`:
+`CmxRainVel`s with a zero Chen-2022 part).  `jvp` = `length(d_warm_rain)·4` device columns (or `nothing`s), direction-major; `jvp_precip` = one column of
+`n_col` values per direction (or `nothing`s).  The state, ρ and `inv_dz` are held fixed.  include/cmx.h §(26) has the definition.
+"""
+function column_param_jvp_2m!(jvp, jvp_precip, tendencies, precip_flux, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, vel, cloud_vel, n_col::Integer,
+    n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, d_warm_rain, d_tps = nothing, d_vel = nothing, d_cloud_vel = nothing;
+    stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    dw, dt, dv, dc = _column_param_directions(d_warm_rain, d_tps, d_vel, d_cloud_vel)
+    jvp === nothing || length(jvp) == length(dw) * CMX_SB2006_JAC_NOUT || error("jvp: $(CMX_SB2006_JAC_NOUT) columns (or nothing) per direction expected")
+    jvp_precip === nothing || length(jvp_precip) == length(dw) || error("jvp_precip: one column (or nothing) per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = (is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vel)
+    st = GC.@preserve dw dt dv dc ccall(_fn("cmx_sb2006_column_param_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt), dv === nothing ? C_NULL : pointer(dv), dc === nothing ? C_NULL : pointer(dc),
+        _opt_ptrs(FT, jvp), _opt_ptrs(FT, jvp_precip), _opt_ptrs(FT, tendencies), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_param_jvp")
+    return jvp
+end
+
+"""
+    column_param_vjp_2m!(grad, workspace, tendencies, precip_flux, mp, tps, vel, cloud_vel, n_col, n_lev, inv_dz, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai,
+                         cotangents, cot_precip, d_warm_rain, d_tps = nothing, d_vel = nothing, d_cloud_vel = nothing; stream = C_NULL)
+
+The gradient of Σ ḡ·out + Σ p̄·precip_flux along the parameter directions of `column_param_jvp_2m!`: `grad` = a device array of `length(d_warm_rain)` Float64,
+`workspace` = `length(d_warm_rain)·CMX_PARAM_VJP_PARTIALS` Float64 owned by the caller, `cotangents` = `nothing` or 4 columns (or `nothing`s), `cot_precip` =
+`nothing` or `n_col` values.  A deterministic reduction in double: no atomics, the same bits from run to run.
+"""
+function column_param_vjp_2m!(grad, workspace, tendencies, precip_flux, mp::CMP.Microphysics2MParams{WR, Nothing}, tps, vel, cloud_vel, n_col::Integer,
+    n_lev::Integer, inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, cotangents, cot_precip, d_warm_rain, d_tps = nothing, d_vel = nothing,
+    d_cloud_vel = nothing; stream = C_NULL) where {WR, FT}
+    vel === nothing && error("the column step needs a rain fall-speed scheme (CMP.SB2006VelType or CMP.Chen2022VelTypeRain)")
+    dw, dt, dv, dc = _column_param_directions(d_warm_rain, d_tps, d_vel, d_cloud_vel)
+    cotangents === nothing || length(cotangents) == CMX_SB2006_JAC_NOUT || error("cotangents: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    length(grad) >= length(dw) || error("grad: one Float64 per direction expected")
+    length(workspace) >= length(dw) * CMX_PARAM_VJP_PARTIALS || error("workspace: $(CMX_PARAM_VJP_PARTIALS) Float64 per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_SB2006_JAC_NOUT || error("tendencies: $(CMX_SB2006_JAC_NOUT) columns (or nothing) expected")
+    wr = _warm_rain(mp)
+    flags = (is_limited(wr) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vel)
+    st = GC.@preserve dw dt dv dc ccall(_fn("cmx_sb2006_column_param_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{Ptr{FT}}, Ptr{FT}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(wr)), Ref(CmxThermo(tps)), Ref(_rain_vel(vel, FT)), _ref_or_null(cloud_vel), flags, n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _opt_ptrs(FT, cotangents), _dp(FT, cot_precip), Int32(length(dw)), pointer(dw), dt === nothing ? C_NULL : pointer(dt),
+        dv === nothing ? C_NULL : pointer(dv), dc === nothing ? C_NULL : pointer(dc), _dp(Float64, grad), _dp(Float64, workspace),
+        _opt_ptrs(FT, tendencies), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_param_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
