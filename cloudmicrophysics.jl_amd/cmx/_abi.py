@@ -161,6 +161,10 @@ CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 # … and its derivatives with respect to the parameters (include/cmx.h §26): cmx_sb2006_column_param_jvp_* / _param_vjp_* take the same head, then ndir,
 # d_warm_rain, d_tps, d_vel, d_cloud_vel, jvp[ndir·NOUT], jvp_precip[ndir], tendencies[NOUT], precip_flux resp. cotangents[NOUT], cot_precip, ndir, the four
 # direction tables, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies[NOUT], precip_flux
+# J v and Jᵀḡ of the 1-moment column step with sedimentation (include/cmx.h §27): cmx_mp1m_column_jvp_* / _vjp_* take the head of
+# cmx_mp1m_column_tendencies_sedimentation_* through `in` without q_min, dt, nsub (Instantaneous mode), then tangents[NWRT], jvp[NOUT], jvp_precip_rai,
+# jvp_precip_sno, tendencies[NOUT], precip_rai, precip_sno resp. cotangents[NOUT], cot_precip_rai, cot_precip_sno, grad[NWRT], tendencies[NOUT], precip_rai,
+# precip_sno, in the orders of MP1M_JAC_WRT / MP1M_JAC_OUT
 # the derivatives with respect to the parameters (include/cmx.h §22, §23: cmx_mp1m_param_jvp_* / _param_vjp_* take the same lists over cmx_microphysics_1m): cmx_sb2006_warm_rain_param_jvp_* takes ndir, d_warm_rain[ndir], d_tps[ndir], jvp[ndir·NOUT],
 # tendencies[NOUT]; …_param_vjp_* takes cotangents[NOUT], ndir, d_warm_rain, d_tps, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies
 CMX_PARAM_MAX_DIRS = 16

@@ -272,6 +272,17 @@ def _declare(lib):
         f = getattr(lib, f"cmx_sb2006_column_param_vjp_{s}")
         f.restype = i32
         f.argtypes = head + [C.POINTER(vp), vp] + dirs + [vp, vp, C.POINTER(vp), vp, vp]
+        # J v and Jᵀḡ of the 1-moment column step (include/cmx.h §27): the head of cmx_mp1m_column_tendencies_sedimentation_* through `in` without q_min, dt,
+        # nsub, then (tangents[6], jvp[4], jvp_precip_rai, jvp_precip_sno, tendencies[4], precip_rai, precip_sno) /
+        # (cotangents[4], cot_precip_rai, cot_precip_sno, grad[6], tendencies[4], precip_rai, precip_sno)
+        head = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), C.POINTER(fam.stokes_vel), C.POINTER(fam.chen2022_rain_vel),
+                C.POINTER(fam.chen2022_ice_vel), u32, i64, i32, vp, C.POINTER(vp)]
+        f = getattr(lib, f"cmx_mp1m_column_jvp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), C.POINTER(vp), vp, vp, C.POINTER(vp), vp, vp, vp]
+        f = getattr(lib, f"cmx_mp1m_column_vjp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

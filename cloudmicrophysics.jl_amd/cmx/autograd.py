@@ -11,7 +11,8 @@ gradient is worse than an error.  `warm_rain_tendencies_2m(…, theta=, names=)`
 values of the ClimaParams `names`; the forward pass rebuilds the parameter structs with those values (host work, no device sync) and is otherwise the same
 entry; backward calls the parameter-gradient entry (`warm_rain_param_vjp_2m` / `param_vjp_1m`) once for `theta.grad` (and the state Jᵀḡ entry if a state column needs a gradient), forward mode with a tangent on
 `theta` calls `warm_rain_param_jvp_2m` / `param_jvp_1m`.  `cmx.autograd.column_tendencies_sedimentation_2m` is the SB2006 column step with sedimentation and its precipitation flux (`cmx.column_tendencies_sedimentation`),
-differentiated through the fall speeds and the flux divergence by `column_vjp_2m` / `column_jvp_2m`; ρ and `inv_dz` are held fixed.  Not built: double backward (backward is once-differentiable), vmap, the
+differentiated through the fall speeds and the flux divergence by `column_vjp_2m` / `column_jvp_2m`; ρ and `inv_dz` are held fixed.  `cmx.autograd.column_tendencies_sedimentation_1m` is the same for the 1-moment column step
+(`cmx.column_tendencies_sedimentation_1m`, Instantaneous mode) with its two precipitation fluxes, by `column_vjp_1m` / `column_jvp_1m`.  Not built: double backward (backward is once-differentiable), vmap, the
 fall-speed outputs of the pointwise entry, LinearizedAverage and the 2M + P3 scheme.  With `theta=, names=` the column step is also differentiated with respect to the
 parameters, the fall-speed parameters included (`column_param_vjp_2m` / `column_param_jvp_2m`, include/cmx.h §26)."""
 import torch
@@ -94,6 +95,16 @@ _Column2M = _function(
     lambda step, tps, cols, cotangents, wrt: _bt.column_vjp_2m(step.mp, tps, step.inv_dz, *cols, cotangents[:4], cotangents[4], wrt=wrt, **step.options),
     lambda step, tps, cols, tangents: _bt.column_jvp_2m(step.mp, tps, step.inv_dz, *cols, tangents, **step.options),
     tangents_out=lambda r: (*(r.jvp[o] for o in range(4)), r.jvp_precip))
+
+# the 1-moment column step: `step.mp` holds (mp, stokes, chen_rain, chen_ice); six outputs — the four tendencies and the two precipitation fluxes
+_Column1M = _function(
+    "ColumnTendenciesSedimentation1M", _m1.JACOBIAN_WRT_1M,
+    lambda step, tps, cols: tuple(_m1.column_tendencies_sedimentation_1m(_m1.Instantaneous(), _m1.Microphysics1Moment(), step.mp[0], tps, *step.mp[1:],
+                                                                          step.inv_dz, *cols)),
+    lambda step, tps, cols, cotangents, wrt: _m1.column_vjp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, cotangents[:4], cotangents[4], cotangents[5],
+                                                                wrt=wrt),
+    lambda step, tps, cols, tangents: _m1.column_jvp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, tangents),
+    tangents_out=lambda r: (*(r.jvp[o] for o in range(4)), r.jvp_precip_rai, r.jvp_precip_sno))
 
 _Tendencies1M = _function(
     "Tendencies1M", _m1.JACOBIAN_WRT_1M,
@@ -256,6 +267,19 @@ def column_tendencies_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_
     if names is not None:
         raise ValueError("names without theta")
     return _Column2M.apply(_ColumnStep(mp, inv_dz, dict(vel=vel, vel_params=vel_params, cloud_vel=cloud_vel)), tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+
+
+def column_tendencies_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno):
+    """(dq_lcl_dt, dq_icl_dt, dq_rai_dt, dq_sno_dt, precip_rai, precip_sno) of `cmx.column_tendencies_sedimentation_1m(Instantaneous(),
+    Microphysics1Moment(), mp, tps, stokes, chen_rain, chen_ice, inv_dz, …)`, bit for bit — the tendencies with the sedimentation flux divergence, shape
+    (n_col, n_lev), and the surface fluxes of rain and snow, shape (n_col,) — differentiable by torch with respect to T, q_tot, q_lcl, q_icl, q_rai, q_sno:
+    backward is ONE Jᵀḡ launch (`cmx.column_vjp_1m`, the cotangents of both precipitation fluxes included: `(precip_rai.sum() + precip_sno.sum()).backward()`
+    fills `.grad` of the state), forward mode ONE J v launch (`cmx.column_jvp_1m`).  ρ and `inv_dz` are held fixed: asking for their gradient, or a
+    forward-mode tangent on them, raises NotImplementedError."""
+    _check_rho(rho)
+    if inv_dz.requires_grad or torch.autograd.forward_ad.unpack_dual(inv_dz).tangent is not None:
+        raise NotImplementedError("inv_dz is held fixed: the column step is not differentiated with respect to the layer thickness")
+    return _Column1M.apply(_ColumnStep((mp, stokes, chen_rain, chen_ice), inv_dz, {}), tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
 
 
 def tendencies_1m(mp, tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, theta=None, names=None):

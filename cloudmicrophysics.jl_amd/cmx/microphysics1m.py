@@ -18,7 +18,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
-from ._jacobian import _check_step, _check_step_normal, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _vjp
+from ._jacobian import _check_step, _check_step_normal, _check_wrt, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _table, _vjp
 from .parameters import Chen2022VelTypeRain, Microphysics1MParams
 
 
@@ -359,6 +359,101 @@ def column_tendencies_sedimentation_1m(mode, scheme, mp, tps, stokes, chen_rain,
               C.byref(chen_ice), mp.flags | (shape._column_bit if shape else 0), q_min if lin else 0.0, dt if lin else 0.0, int(nsub) if lin else 0,
               n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]), stream=stream)
     return ColumnStep1M(*out, *pr)
+
+
+ColumnJvp1M = namedtuple("ColumnJvp1M", ["jvp", "jvp_precip_rai", "jvp_precip_sno", "tendencies", "precip_rai", "precip_sno"])
+ColumnVjp1M = namedtuple("ColumnVjp1M", ["grad", "tendencies", "precip_rai", "precip_sno", "wrt"])
+
+
+def _column_products_head_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols):
+    """The checks of `column_tendencies_sedimentation_1m` for the two products with its Jacobian: (reference column of shape (n_col, n_lev), float family,
+    what the ABI arguments refer to, the ABI arguments from the parameter structs through `in`)."""
+    rho = cols[0]
+    if rho.dim() != 2:
+        raise ValueError("state tensors must have shape (n_col, n_lev)")
+    # the 2-D tensors THEMSELVES, as in column_tendencies_sedimentation_1m: the kernels read flat row-major (n_col, n_lev) storage
+    for c, nm in zip(cols, _NAMES):
+        if c.shape != rho.shape:
+            raise ValueError(f"column {nm}: shape {tuple(c.shape)} differs from rho's {tuple(rho.shape)}")
+        if not c.is_contiguous():
+            raise ValueError(f"column {nm} must be a contiguous (n_col, n_lev) tensor (levels contiguous within a column)")
+    _, fam = _prep(mp, tps, [c.view(-1) for c in cols])
+    for obj, cls, nm in ((stokes, fam.stokes_vel, "stokes"), (chen_rain, fam.chen2022_rain_vel, "chen_rain"), (chen_ice, fam.chen2022_ice_vel, "chen_ice")):
+        if not isinstance(obj, cls):
+            raise TypeError(f"{nm}: expected the {cls.__name__} struct of the state's float type, got {type(obj).__name__}")
+    n_col, n_lev = rho.shape
+    if inv_dz.numel() != n_lev or inv_dz.dtype != rho.dtype or inv_dz.device != rho.device or not inv_dz.is_contiguous():
+        raise ValueError("inv_dz: n_lev contiguous values of the state's dtype on the state's device")
+    in_p = (C.c_void_p * 7)(*[c.data_ptr() for c in cols])
+    return rho, fam, in_p, (C.byref(mp.c), C.byref(tps), C.byref(stokes), C.byref(chen_rain), C.byref(chen_ice), mp.flags, n_col, n_lev, _ptr(inv_dz), in_p)
+
+
+def _column_primal_out_1m(ref, with_tendencies):
+    if not with_tendencies:
+        return None, None, None
+    return (torch.empty((4, *ref.shape), dtype=ref.dtype, device=ref.device), torch.empty(ref.shape[0], dtype=ref.dtype, device=ref.device),
+            torch.empty(ref.shape[0], dtype=ref.dtype, device=ref.device))
+
+
+def column_jvp_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, tangents, with_tendencies=False, *,
+                  stream=None) -> ColumnJvp1M:
+    """J v of `column_tendencies_sedimentation_1m(Instantaneous(), …)` — the four tendencies WITH the upwind flux divergence of the four falling species —
+    and of its two precipitation fluxes, behind `cmx_mp1m_column_jvp_*` (include/cmx.h §27): the matvec of a Newton–Krylov solver that treats 1-moment
+    microphysics and sedimentation implicitly together.  One launch; ρ and `inv_dz` are held fixed.
+
+    Parameters, `inv_dz` and the state columns of shape (n_col, n_lev) as for `column_tendencies_sedimentation_1m`.  `tangents`: dict name -> tensor of the
+    state's shape over `JACOBIAN_WRT_1M`; a missing name is a zero tangent, a `rho` tangent a ValueError.  Returns `ColumnJvp1M(jvp, jvp_precip_rai,
+    jvp_precip_sno, tendencies, precip_rai, precip_sno)`: `jvp` of shape (4, n_col, n_lev) in the order of `JACOBIAN_OUTPUTS_1M`, `jvp_precip_*` (n_col,);
+    with `with_tendencies=True` also `tendencies` (4, n_col, n_lev) and `precip_*` (n_col,), bit-identical to the primal wrapper, else None.  Asynchronous on
+    `stream`."""
+    if not isinstance(tangents, dict):
+        raise TypeError("tangents must be a dict: name of a differentiable input -> tensor")
+    _check_wrt(tangents.keys(), JACOBIAN_WRT_1M, "tangents")
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    ref, fam, keep, head = _column_products_head_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols)
+    given = [(k, v) for k, v in tangents.items() if v is not None]
+    if given:
+        _check_cols([ref] + [v for _, v in given], ["rho"] + [f"tangent of {k}" for k, _ in given])
+    jvp = torch.empty((4, *ref.shape), dtype=ref.dtype, device=ref.device)
+    jvp_precip = torch.empty((2, ref.shape[0]), dtype=ref.dtype, device=ref.device)
+    tend, pr, ps = _column_primal_out_1m(ref, with_tendencies)
+    _lib.call("cmx_mp1m_column_jvp", fam, ref.device, *head, _table([tangents.get(name) for name in JACOBIAN_WRT_1M]), _table([jvp[o] for o in range(4)]),
+              _ptr(jvp_precip[0]), _ptr(jvp_precip[1]), _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(pr), _ptr(ps), stream=stream)
+    return ColumnJvp1M(jvp, jvp_precip[0], jvp_precip[1], tend, pr, ps)
+
+
+def column_vjp_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, cot_precip_rai=None,
+                  cot_precip_sno=None, wrt=JACOBIAN_WRT_1M, with_tendencies=False, *, stream=None) -> ColumnVjp1M:
+    """Jᵀḡ of `column_tendencies_sedimentation_1m(Instantaneous(), …)` and its precipitation fluxes behind `cmx_mp1m_column_vjp_*` (include/cmx.h §27): the
+    gradient of Σ ḡ·tendencies + Σ p̄_rai·precip_rai + Σ p̄_sno·precip_sno with respect to the inputs `wrt` — what
+    `loss(precip_rai + precip_sno).backward()` needs (cmx.autograd).  One launch.
+
+    `cotangents`: a sequence of 4 tensors of the state's shape or None in the order of `JACOBIAN_OUTPUTS_1M` (None: that output is not part of the sum), or
+    None for none at all; `cot_precip_rai`, `cot_precip_sno`: tensors of n_col values or None.  `wrt`: any subset of `JACOBIAN_WRT_1M` in any order.  Returns
+    `ColumnVjp1M(grad, tendencies, precip_rai, precip_sno, wrt)`: `grad` of shape (len(wrt), n_col, n_lev) — a cotangent at level k reaches the gradients at
+    levels k and k + 1 of its column; a gradient does not depend on which others are requested.  The other arguments as for `column_jvp_1m`."""
+    wrt = _check_wrt(wrt, JACOBIAN_WRT_1M)
+    cotangents = [None] * 4 if cotangents is None else list(cotangents)
+    if len(cotangents) != 4:
+        raise ValueError("cotangents: 4 tensors (or None) expected, one per output")
+    if not wrt and not with_tendencies:
+        raise ValueError("nothing to compute: wrt is empty and with_tendencies is False")
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    ref, fam, keep, head = _column_products_head_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols)
+    given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
+    if given:
+        _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])
+    for nm, p in (("cot_precip_rai", cot_precip_rai), ("cot_precip_sno", cot_precip_sno)):
+        if p is not None and (p.dtype != ref.dtype or p.device != ref.device or p.shape != (ref.shape[0],) or not p.is_contiguous()):
+            raise ValueError(f"{nm} must be a contiguous device vector of n_col values of the state dtype")
+    grad = torch.empty((len(wrt), *ref.shape), dtype=ref.dtype, device=ref.device)
+    grads = [None] * len(JACOBIAN_WRT_1M)
+    for k, name in enumerate(wrt):
+        grads[JACOBIAN_WRT_1M.index(name)] = grad[k]
+    tend, pr, ps = _column_primal_out_1m(ref, with_tendencies)
+    _lib.call("cmx_mp1m_column_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip_rai), _ptr(cot_precip_sno), _table(grads),
+              _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(pr), _ptr(ps), stream=stream)
+    return ColumnVjp1M(grad, tend, pr, ps, wrt)
 
 
 def _column_implicit_1m(entry, mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols, dt, nsub, nonnegative, precip, stream):

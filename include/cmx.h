@@ -1957,8 +1957,8 @@ int32_t cmx_mp2m_p3_column_implicit_sedimentation_f64(const cmx_warm_rain_2m_f64
  * propagation through λ_k.  There is no other rule.
  * Results do not depend on how the kernels divide the columns among workgroups, on alignment, or on the number of columns in the call.  Both entries are
  * pure launches on `stream`: no allocation, no synchronisation, graph-capturable.
- * Not done here: the 1-moment and the 2M + P3 column steps, derivatives with respect to ρ or inv_dz, the implicit column steps (20), (21).  The
- * parameters through the column: (26).  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * Not done here: the 2M + P3 column step, derivatives with respect to ρ or inv_dz, the implicit column steps (20), (21).  The
+ * parameters through the column: (26).  The 1-moment column step: (27).  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
                                   const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
@@ -2015,8 +2015,8 @@ int32_t cmx_sb2006_column_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const c
  * reduction without atomics (the decomposition of (22)), bit-identical from run to run.  No allocation, graph-capturable.
  * Not shipped: the Float64 GRADIENT entry with a Chen-2022 table that takes the general instantiation (run-time Γ) returns CMX_ERR_UNSUPPORTED — its kernel
  * needs 482–511 vector registers at one direction per evaluation and spills 8; the jvp entry serves that case (264–278).
- * Not done here: the 1-moment and 2M + P3 columns, the implicit column steps, derivatives with respect to ρ or inv_dz, of the Chen-2022 table, second
- * derivatives.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * Not done here: the 1-moment (its state products: (27)) and 2M + P3 columns, the implicit column steps, derivatives with respect to ρ or inv_dz, of the
+ * Chen-2022 table, second derivatives.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_param_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
                                         const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
@@ -2044,6 +2044,73 @@ int32_t cmx_sb2006_column_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, c
                                         const cmx_warm_rain_2m_f64 *d_warm_rain, const cmx_thermo_f64 *d_tps, const cmx_rain_vel_f64 *d_vel,
                                         const cmx_stokes_vel_f64 *d_cloud_vel, double *grad, double *workspace,
                                         double *const tendencies[CMX_SB2006_JAC_NOUT], double *precip_flux, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (27) The products J v and Jᵀḡ with the Jacobian of the 1-moment COLUMN step cmx_mp1m_column_tendencies_sedimentation_* in Instantaneous mode (nsub = 0) —
+ * tendencies, the four fall speeds and the upwind flux divergence in one call, plus the surface fluxes of rain and snow — with respect to the prognostic
+ * state: cmx_mp1m_column_jvp_* and cmx_mp1m_column_vjp_*.  (17) differentiates the point function, which knows nothing of the fall speeds; these differentiate
+ * what a mixed-phase host model steps.  J v is the matvec of a Newton–Krylov solver that treats 1-moment microphysics and sedimentation implicitly together;
+ * Jᵀḡ with the cotangents of the two precipitation fluxes is what loss(precip_rai + precip_sno).backward() needs (cmx.autograd).
+ * The function that is differentiated, normative — per column, level 0 the lowest, x_k = (T, q_tot, q_lcl, q_icl, q_rai, q_sno)_k:
+ *     out_k  = tend(ρ_k, x_k) + g_k·(F_{k+1} − F_k)        g_k = inv_dz[k]/ρ_k, formed exactly as the primal kernel forms it: inv_dz[k]·rcp(max(0, ρ_k))
+ *     F_{n_lev} = 0        precip_rai = F_0[q_rai]        precip_sno = F_0[q_sno]
+ * tend is the Instantaneous 1-moment tendencies (15).  F_k[s] = ρ⁺χ⁺w_s for s = q_lcl, q_icl, q_rai, q_sno — the fluxes of the primal entry: Stokes cloud
+ * liquid, Chen-2022 small ice, Chen-2022 rain, Chen-2022 large ice with the fixed aspect ratio.  ρ and inv_dz are held FIXED, as ρ is in (14) – (19).
+ * The clamps of the inputs, the ε gates, the floors and the max(0, w) of the fall speeds are part of the function; the derivative is that of the branch taken,
+ * as in (15).  Γ(b(ρ) + …) of the Chen-2022 rain curve depends on ρ only: it is evaluated on the value and carries no tangent, in the fitted and in the
+ * general (run-time Γ) instantiation alike.
+ * With Ḟ_k = (∂F_k/∂x_k)·v_k, and J_pt the Jacobian of tend at the point:
+ *     J v:    ẏ_k = J_pt(x_k)·v_k + g_k·(Ḟ_{k+1} − Ḟ_k)          ṗ_rai = Ḟ_0[q_rai], ṗ_sno = Ḟ_0[q_sno], one value per column each
+ *     Jᵀḡ:    x̄_k = J_pt(x_k)ᵀ·ḡ_k + (∂F_k/∂x_k)ᵀ·λ_k            λ_k[s] = −g_k·ḡ_k[s] + [k > 0]·g_{k−1}·ḡ_{k−1}[s] + [k = 0]·p̄_s
+ * for each falling species s; p̄_s is the cotangent of the precipitation flux of s, non-zero for rain and snow only.  F_k[s] depends on ρ_k and on its own
+ * species (q_s)_k alone: ∂F_k/∂x_k has the one entry ∂F_k[s]/∂q_s per species, the block Jacobian is upper bidiagonal in the level index and never couples
+ * two columns.
+ * Arguments: the head of cmx_mp1m_column_tendencies_sedimentation_* through `in` (a HOST array of the 7 device columns rho, T, q_tot, q_lcl, q_icl, q_rai,
+ * q_sno; n_col columns of n_lev contiguous levels) WITHOUT q_min, dt and nsub — Instantaneous mode only; then
+ *   jvp:  tangents[6] in the order of cmx_mp1m_jac_wrt (the table or a member NULL: a zero tangent), jvp[4] in the order of cmx_mp1m_jac_out, jvp_precip_rai,
+ *         jvp_precip_sno (n_col values each), tendencies[4], precip_rai, precip_sno;
+ *   vjp:  cotangents[4] (the table or a member NULL: that output is structurally absent from the sum), cot_precip_rai, cot_precip_sno (n_col values or
+ *         NULL: absent), grad[6], tendencies[4], precip_rai, precip_sno.
+ * Every output table, every member and every output column may be NULL; a call with no output at all is CMX_ERR_BAD_ARG, and so is an output that is one of
+ * the call's input columns, inv_dz, a tangent or a cotangent (a lane reads its neighbours).  n_col·n_lev is limited as in the primal entry; n_col = 0 is
+ * CMX_OK.  Statuses in the primal entry's order: the parameter pointers and counts, both snow-shape bits (CMX_ERR_BAD_ARG), the Microphysics1MOptions bits
+ * exactly as the primal entry checks them, a single snow-shape bit (CMX_ERR_UNSUPPORTED, below), the limit, n_col = 0, the columns, the outputs.
+ * Requested `tendencies` and `precip_*` are those of the primal entry on the same columns with nsub = 0, bit for bit; the instantiation is the one the primal
+ * chooses (default options or run-time flags; fitted or general Γ of the Chen-2022 rain table).  The products are plain IEEE arithmetic on the tangents: Jᵀḡ
+ * accumulates the point sums with ḡ in output order, then — in the gradient of q_s only — the one flux term λ_k[s]·∂F_k[s]/∂q_s, as one chain of fma seeded
+ * with −0 (no term at all: +0); each gradient comes from its own tangent slot, so its bits do not depend on which other gradients are requested.  T and q_tot
+ * do not enter the fluxes.  With inv_dz ≡ 0 the products equal those of (17) under == wherever the flux tangents are finite.
+ * NaN rule: the poison rule of the 1-moment entries holds per point — a NaN in any state input (Float64: also ρ ≤ 0), or in any given tangent or cotangent
+ * value of the point (p̄ counts for the level-0 point), gives NaN in every output of that point.  A NaN in ρ or in a species' q (Float64: ρ ≤ 0) reaches the
+ * cell below through F and Ḟ of that species exactly as in the primal, and the column's precipitation outputs at level 0; a NaN tangent reaches Ḟ by plain
+ * IEEE arithmetic.  In Jᵀḡ a NaN in ḡ_{k−1}[s] reaches the gradient of q_s at level k by plain IEEE propagation through λ_k[s]; a NaN in ρ_{k−1} makes
+ * g_{k−1} what the primal makes it — max(0, NaN) = 0, its reciprocal +Inf — and the flux terms of x̄_k non-finite.  There is no other rule.
+ * Results do not depend on how the kernels divide the columns among workgroups, on alignment, or on the number of columns in the call.  Both entries are
+ * pure launches on `stream`: no allocation, no synchronisation, graph-capturable.
+ * Not done here: the LinearizedAverage mode (nsub > 0); the implicit column steps (20), (21); the snow shapes — a CMX_1M_SED_SNOW_OBLATE / _PROLATE bit returns
+ * CMX_ERR_UNSUPPORTED: the oracle's column step has no shaped snow to difference against —; parameter derivatives of this column step; derivatives with
+ * respect to ρ or inv_dz; the 2M + P3 column.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * ------------------------------------------------------------------------- */
+int32_t cmx_mp1m_column_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, int64_t n_col,
+                                int32_t n_lev, const float *inv_dz, const float *const *in, const float *const tangents[CMX_MP1M_JAC_NWRT],
+                                float *const jvp[CMX_MP1M_JAC_NOUT], float *jvp_precip_rai, float *jvp_precip_sno,
+                                float *const tendencies[CMX_MP1M_JAC_NOUT], float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_jvp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, int64_t n_col,
+                                int32_t n_lev, const double *inv_dz, const double *const *in, const double *const tangents[CMX_MP1M_JAC_NWRT],
+                                double *const jvp[CMX_MP1M_JAC_NOUT], double *jvp_precip_rai, double *jvp_precip_sno,
+                                double *const tendencies[CMX_MP1M_JAC_NOUT], double *precip_rai, double *precip_sno, void *stream);
+int32_t cmx_mp1m_column_vjp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, int64_t n_col,
+                                int32_t n_lev, const float *inv_dz, const float *const *in, const float *const cotangents[CMX_MP1M_JAC_NOUT],
+                                const float *cot_precip_rai, const float *cot_precip_sno, float *const grad[CMX_MP1M_JAC_NWRT],
+                                float *const tendencies[CMX_MP1M_JAC_NOUT], float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, int64_t n_col,
+                                int32_t n_lev, const double *inv_dz, const double *const *in, const double *const cotangents[CMX_MP1M_JAC_NOUT],
+                                const double *cot_precip_rai, const double *cot_precip_sno, double *const grad[CMX_MP1M_JAC_NWRT],
+                                double *const tendencies[CMX_MP1M_JAC_NOUT], double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

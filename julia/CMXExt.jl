@@ -1961,6 +1961,56 @@ function column_param_vjp_2m!(grad, workspace, tendencies, precip_flux, mp::CMP.
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (27) products with the Jacobian of the 1-moment column step: tendencies, the four fall speeds and sedimentation, and the two precipitation fluxes
+# ----------------------------------------------------------------------------------------------------------------
+"""
+    column_jvp_1m!(jvp, jvp_precip_rai, jvp_precip_sno, tendencies, precip_rai, precip_sno, mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols, tangents; stream = C_NULL)
+
+J v of `column_tendencies_sedimentation!(out, BMT.Instantaneous(), BMT.Microphysics1Moment(), …)` — the four tendencies WITH the upwind flux divergence of the
+four falling species — and of its two precipitation fluxes, with respect to (T, q_tot, q_lcl, q_icl, q_rai, q_sno); ρ and `inv_dz` are held fixed.  The matvec
+of a Newton–Krylov solver over a mixed-phase column.  `cols` = the 7 state columns, `tangents` = `nothing` or 6 columns (or `nothing`s: a zero tangent), `jvp`,
+`tendencies` = `nothing` or 4 columns (or `nothing`s), `jvp_precip_*`, `precip_*` = `nothing` or `n_col` values.  `tendencies` and `precip_*` are those of
+`column_tendencies_sedimentation!`, bit for bit.  No output may be one of the input columns.  include/cmx.h §(27) has the definition.
+"""
+function column_jvp_1m!(jvp, jvp_precip_rai, jvp_precip_sno, tendencies, precip_rai, precip_sno, mp::CMP.Microphysics1MParams, tps,
+    stokes::CMP.StokesRegimeVelType{FT}, chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, tangents; stream = C_NULL) where {FT}
+    tangents === nothing || length(tangents) == CMX_MP1M_JAC_NWRT || error("tangents: $(CMX_MP1M_JAC_NWRT) columns (or nothing) expected")
+    jvp === nothing || length(jvp) == CMX_MP1M_JAC_NOUT || error("jvp: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_column_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT},
+            Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols),
+        _opt_ptrs(FT, tangents), _opt_ptrs(FT, jvp), _dp(FT, jvp_precip_rai), _dp(FT, jvp_precip_sno), _opt_ptrs(FT, tendencies), _dp(FT, precip_rai),
+        _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_jvp")
+    return jvp
+end
+
+"""
+    column_vjp_1m!(grad, tendencies, precip_rai, precip_sno, mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols, cotangents, cot_precip_rai, cot_precip_sno; stream = C_NULL)
+
+Jᵀḡ of the same function: `cotangents` = `nothing` or 4 columns (or `nothing`s: that output is not part of the sum), `cot_precip_rai`, `cot_precip_sno` =
+`nothing` or the `n_col` cotangents of the two precipitation fluxes, `grad` = `nothing` or 6 columns (or `nothing`s: that input is not differentiated).  The
+gradient of Σ ḡ·out + Σ p̄_rai·precip_rai + Σ p̄_sno·precip_sno, contracted on the device; a cotangent at level k reaches the gradients at levels k and k + 1
+of its column.  `tendencies`, `precip_*` and the aliasing rule as for `column_jvp_1m!`.
+"""
+function column_vjp_1m!(grad, tendencies, precip_rai, precip_sno, mp::CMP.Microphysics1MParams, tps, stokes::CMP.StokesRegimeVelType{FT},
+    chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, cotangents, cot_precip_rai, cot_precip_sno; stream = C_NULL) where {FT}
+    cotangents === nothing || length(cotangents) == CMX_MP1M_JAC_NOUT || error("cotangents: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    grad === nothing || length(grad) == CMX_MP1M_JAC_NWRT || error("grad: $(CMX_MP1M_JAC_NWRT) columns (or nothing) expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = ccall(_fn("cmx_mp1m_column_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Ptr{FT}},
+            Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols),
+        _opt_ptrs(FT, cotangents), _dp(FT, cot_precip_rai), _dp(FT, cot_precip_sno), _opt_ptrs(FT, grad), _opt_ptrs(FT, tendencies), _dp(FT, precip_rai),
+        _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
