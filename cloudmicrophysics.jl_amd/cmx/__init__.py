@@ -49,7 +49,8 @@ from .microphysics1m import (Instantaneous, LinearizedAverage, Microphysics1Mome
                              column_tendencies_sedimentation_1m, AbstractSnowShape, Oblate, Prolate, snow_terminal_velocity, Jacobian1M,
                              JACOBIAN_WRT_1M, JACOBIAN_OUTPUTS_1M, jacobian_1m, Jvp1M, Vjp1M, jvp_1m, vjp_1m, ParamJvp1M, ParamVjp1M, param_jvp_1m, param_vjp_1m, Implicit1M, implicit_tendencies_1m,
                              implicit_average_1m, column_implicit_average_sedimentation_1m, column_implicit_step_1m,
-                             ColumnJvp1M, ColumnVjp1M, column_jvp_1m, column_vjp_1m)
+                             ColumnJvp1M, ColumnVjp1M, column_jvp_1m, column_vjp_1m,
+                             ColumnParamJvp1M, ColumnParamVjp1M, column_param_jvp_1m, column_param_vjp_1m)
 
 from .microphysics0m import (Microphysics0Moment, bulk_microphysics_tendencies_0m, d_remove_precipitation_d_q_tot,  # noqa: F401
                              remove_precipitation)

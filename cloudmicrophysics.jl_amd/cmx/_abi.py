@@ -165,6 +165,10 @@ CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 # cmx_mp1m_column_tendencies_sedimentation_* through `in` without q_min, dt, nsub (Instantaneous mode), then tangents[NWRT], jvp[NOUT], jvp_precip_rai,
 # jvp_precip_sno, tendencies[NOUT], precip_rai, precip_sno resp. cotangents[NOUT], cot_precip_rai, cot_precip_sno, grad[NWRT], tendencies[NOUT], precip_rai,
 # precip_sno, in the orders of MP1M_JAC_WRT / MP1M_JAC_OUT
+# … and its derivatives with respect to the parameters (include/cmx.h §28): cmx_mp1m_column_param_jvp_* / _param_vjp_* take the same head, then ndir, d_mp,
+# d_tps, d_stokes, d_chen_rain, d_chen_ice, jvp[ndir·NOUT], jvp_precip_rai[ndir], jvp_precip_sno[ndir], tendencies[NOUT], precip_rai, precip_sno resp.
+# cotangents[NOUT], cot_precip_rai, cot_precip_sno, ndir, the five direction tables, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles),
+# tendencies[NOUT], precip_rai, precip_sno
 # the derivatives with respect to the parameters (include/cmx.h §22, §23: cmx_mp1m_param_jvp_* / _param_vjp_* take the same lists over cmx_microphysics_1m): cmx_sb2006_warm_rain_param_jvp_* takes ndir, d_warm_rain[ndir], d_tps[ndir], jvp[ndir·NOUT],
 # tendencies[NOUT]; …_param_vjp_* takes cotangents[NOUT], ndir, d_warm_rain, d_tps, grad (ndir doubles), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles), tendencies
 CMX_PARAM_MAX_DIRS = 16

@@ -283,6 +283,16 @@ def _declare(lib):
         f = getattr(lib, f"cmx_mp1m_column_vjp_{s}")
         f.restype = i32
         f.argtypes = head + [C.POINTER(vp), vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
+        # the derivatives of the same step with respect to the parameters (include/cmx.h §28): the same head, then
+        # (ndir, d_mp, d_tps, d_stokes, d_chen_rain, d_chen_ice, jvp[ndir·4], jvp_precip_rai[ndir], jvp_precip_sno[ndir], tendencies[4], precip_rai, precip_sno) /
+        # (cotangents[4], cot_precip_rai, cot_precip_sno, ndir, the five direction tables, grad, workspace, tendencies[4], precip_rai, precip_sno)
+        dirs = [i32] + head[:5]
+        f = getattr(lib, f"cmx_mp1m_column_param_jvp_{s}")
+        f.restype = i32
+        f.argtypes = head + dirs + [C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
+        f = getattr(lib, f"cmx_mp1m_column_param_vjp_{s}")
+        f.restype = i32
+        f.argtypes = head + [C.POINTER(vp), vp, vp] + dirs + [vp, vp, C.POINTER(vp), vp, vp, vp]
         f = getattr(lib, f"cmx_parcel_tendencies_{s}")
         f.restype = i32
         f.argtypes = [C.POINTER(fam.parcel_params), u32, i64, C.POINTER(vp), vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]

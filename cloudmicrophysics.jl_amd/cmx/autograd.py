@@ -14,7 +14,8 @@ entry; backward calls the parameter-gradient entry (`warm_rain_param_vjp_2m` / `
 differentiated through the fall speeds and the flux divergence by `column_vjp_2m` / `column_jvp_2m`; ρ and `inv_dz` are held fixed.  `cmx.autograd.column_tendencies_sedimentation_1m` is the same for the 1-moment column step
 (`cmx.column_tendencies_sedimentation_1m`, Instantaneous mode) with its two precipitation fluxes, by `column_vjp_1m` / `column_jvp_1m`.  Not built: double backward (backward is once-differentiable), vmap, the
 fall-speed outputs of the pointwise entry, LinearizedAverage and the 2M + P3 scheme.  With `theta=, names=` the column step is also differentiated with respect to the
-parameters, the fall-speed parameters included (`column_param_vjp_2m` / `column_param_jvp_2m`, include/cmx.h §26)."""
+parameters, the fall-speed parameters included (`column_param_vjp_2m` / `column_param_jvp_2m`, include/cmx.h §26; the 1-moment column step:
+`column_param_vjp_1m` / `column_param_jvp_1m`, §28)."""
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -189,6 +190,34 @@ _Column2MTheta = _theta_function(
     param_tangents_out=lambda r: (*(r.jvp[0][o] for o in range(4)), r.jvp_precip[0]))
 
 
+_Column1MTheta = _theta_function(
+    "ColumnTendenciesSedimentation1MTheta", _m1.JACOBIAN_WRT_1M,
+    lambda step, tps, cols: tuple(_m1.column_tendencies_sedimentation_1m(_m1.Instantaneous(), _m1.Microphysics1Moment(), step.mp[0], tps, *step.mp[1:],
+                                                                          step.inv_dz, *cols)),
+    lambda step, tps, cols, cotangents, wrt: _m1.column_vjp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, cotangents[:4], cotangents[4], cotangents[5],
+                                                                wrt=wrt),
+    lambda step, tps, cols, tangents: _m1.column_jvp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, tangents),
+    lambda step, tps, cols, cotangents, names: _m1.column_param_vjp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, cotangents[:4], cotangents[4],
+                                                                        cotangents[5], names),
+    lambda step, tps, cols, directions: _m1.column_param_jvp_1m(step.mp[0], tps, *step.mp[1:], step.inv_dz, *cols, directions),
+    tangents_out=lambda r: (*(r.jvp[o] for o in range(4)), r.jvp_precip_rai, r.jvp_precip_sno),
+    param_tangents_out=lambda r: (*(r.jvp[0][o] for o in range(4)), r.jvp_precip_rai[0], r.jvp_precip_sno[0]))
+
+
+def _overridden(base, td, names, values):
+    """The overrides `base` with names[k] = values[k]; "name[i]" sets entry i of a vector-valued name (the Chen-2022 tables of the 1-moment column step)."""
+    ov = dict(base)
+    for name, value in zip(names, values):
+        key, idx = _P.split_indexed_name(name)
+        if idx is None:
+            ov[key] = value
+        else:
+            entries = list(ov.get(key, td[key]))
+            entries[idx] = value
+            ov[key] = entries
+    return ov
+
+
 def _with_theta(mp, tps, theta, names, known=None):
     """(parameter object, thermodynamics struct, names) rebuilt from mp's own dictionary with names[k] = theta[k]; `tps` itself unless a name feeds it."""
     if not (isinstance(theta, torch.Tensor) and theta.device.type == "cpu" and theta.dtype == torch.float64 and theta.dim() == 1):
@@ -212,7 +241,7 @@ def _with_theta(mp, tps, theta, names, known=None):
         raise ValueError("theta: the fields of mp were changed after construction; put the values into the dictionary mp is built from (create_toml_dict)")
     if feeds_tps and bytes(_P.ThermodynamicsParameters(td0)) != bytes(tps):
         raise ValueError("theta: a thermodynamics name rebuilds tps from mp's dictionary, and tps is not what that dictionary builds")
-    td = _P.create_toml_dict(p.td.FT, {**base, **dict(zip(names, theta.detach().tolist()))})
+    td = _P.create_toml_dict(p.td.FT, _overridden(base, p.td, names, theta.detach().tolist()))
     return rebuild(td), (_P.ThermodynamicsParameters(td) if feeds_tps else tps), names
 
 
@@ -227,6 +256,20 @@ def _column_with_theta(mp, tps, theta, names, vel_params, cloud_vel):
     if cloud_vel is not None and bytes(_P.StokesRegimeVelType(td0)) != bytes(cloud_vel):
         raise ValueError("theta: cloud_vel is not what mp's dictionary builds; put the values into the dictionary mp is built from (create_toml_dict)")
     return wr, tps_t, names, _P.rain_vel_params(wr.td), (_P.StokesRegimeVelType(wr.td) if cloud_vel is not None else None)
+
+
+def _column_1m_with_theta(mp, tps, stokes, chen_rain, chen_ice, theta, names):
+    """_with_theta for the 1-moment column step: the Stokes struct and the two Chen-2022 tables are rebuilt from the same dictionary as `mp`, and one that
+    this dictionary does not build is refused like an edited `mp`."""
+    for n in names or ():
+        if _P.split_indexed_name(n)[0] in _P._CHEN_FIXED_NAMES:
+            raise ValueError(f"names: '{n}' is held fixed: it reaches the rain fall speed through Γ(b − b_ρ ρ + 4), which carries no tangent on the device")
+    mp_t, tps_t, names = _with_theta(mp, tps, theta, names, known=_P.COLUMN_1M_DIRECTION_NAMES)
+    td0 = _P.create_toml_dict(mp.td.FT, {k: mp.td[k] for k in mp.td.overridden})
+    for what, given, build in (("stokes", stokes, _P.StokesRegimeVelType), ("chen_rain", chen_rain, _P.Chen2022VelTypeRain), ("chen_ice", chen_ice, _P.Chen2022VelTypeIce)):
+        if bytes(build(td0)) != bytes(given):
+            raise ValueError(f"theta: {what} is not what mp's dictionary builds; put the values into the dictionary mp is built from (create_toml_dict)")
+    return mp_t, tps_t, names, _P.StokesRegimeVelType(mp_t.td), _P.Chen2022VelTypeRain(mp_t.td), _P.Chen2022VelTypeIce(mp_t.td)
 
 
 def warm_rain_tendencies_2m(mp, tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, theta=None, names=None):
@@ -269,16 +312,28 @@ def column_tendencies_sedimentation_2m(mp, tps, inv_dz, rho, T, q_tot, q_lcl, n_
     return _Column2M.apply(_ColumnStep(mp, inv_dz, dict(vel=vel, vel_params=vel_params, cloud_vel=cloud_vel)), tps, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
 
 
-def column_tendencies_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno):
+def column_tendencies_sedimentation_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, *, theta=None, names=None):
     """(dq_lcl_dt, dq_icl_dt, dq_rai_dt, dq_sno_dt, precip_rai, precip_sno) of `cmx.column_tendencies_sedimentation_1m(Instantaneous(),
     Microphysics1Moment(), mp, tps, stokes, chen_rain, chen_ice, inv_dz, …)`, bit for bit — the tendencies with the sedimentation flux divergence, shape
     (n_col, n_lev), and the surface fluxes of rain and snow, shape (n_col,) — differentiable by torch with respect to T, q_tot, q_lcl, q_icl, q_rai, q_sno:
     backward is ONE Jᵀḡ launch (`cmx.column_vjp_1m`, the cotangents of both precipitation fluxes included: `(precip_rai.sum() + precip_sno.sum()).backward()`
     fills `.grad` of the state), forward mode ONE J v launch (`cmx.column_jvp_1m`).  ρ and `inv_dz` are held fixed: asking for their gradient, or a
-    forward-mode tangent on them, raises NotImplementedError."""
+    forward-mode tangent on them, raises NotImplementedError.
+
+    With `theta` (1-D CPU float64) and `names` (`cmx.parameters.COLUMN_1M_DIRECTION_NAMES` — the Stokes fall speed, the sedimentation number concentrations,
+    the apparent densities and the entries "name[i]" of the Chen-2022 tables included) also with respect to those parameters: ALL five structs are rebuilt
+    from `mp`'s dictionary with names[k] = theta[k]; backward fills `theta.grad` in the launches of ONE `cmx.column_param_vjp_1m` call (plus the Jᵀḡ launch
+    if a state column needs a gradient), forward mode with a tangent on `theta` calls `cmx.column_param_jvp_1m`.  A `stokes`, `chen_rain` or `chen_ice`
+    that the dictionary does not build is a ValueError; b and b_ρ of the Chen-2022 rain table are held fixed (ValueError).  Without `theta` the function is
+    what it is without these two arguments."""
     _check_rho(rho)
     if inv_dz.requires_grad or torch.autograd.forward_ad.unpack_dual(inv_dz).tangent is not None:
         raise NotImplementedError("inv_dz is held fixed: the column step is not differentiated with respect to the layer thickness")
+    if theta is not None:
+        mp_t, tps_t, names, st, cr, ci = _column_1m_with_theta(mp, tps, stokes, chen_rain, chen_ice, theta, names)
+        return _Column1MTheta.apply(_ColumnStep((mp_t, st, cr, ci), inv_dz, {}), tps_t, names, theta, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    if names is not None:
+        raise ValueError("names without theta")
     return _Column1M.apply(_ColumnStep((mp, stokes, chen_rain, chen_ice), inv_dz, {}), tps, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
 
 

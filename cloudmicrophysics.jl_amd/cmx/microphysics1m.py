@@ -19,7 +19,7 @@ import torch
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _fields_call, _ptr
 from ._jacobian import _check_step, _check_step_normal, _check_wrt, _implicit, _implicit_average, _jacobian, _jvp, _param_jvp, _param_vjp, _table, _vjp
-from .parameters import Chen2022VelTypeRain, Microphysics1MParams
+from .parameters import Chen2022VelTypeRain, Microphysics1MParams, column_parameter_direction_1m
 
 
 class AbstractSnowShape:
@@ -454,6 +454,87 @@ def column_vjp_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q
     _lib.call("cmx_mp1m_column_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip_rai), _ptr(cot_precip_sno), _table(grads),
               _table([tend[o] for o in range(4)]) if tend is not None else None, _ptr(pr), _ptr(ps), stream=stream)
     return ColumnVjp1M(grad, tend, pr, ps, wrt)
+
+
+ColumnParamJvp1M = namedtuple("ColumnParamJvp1M", ["jvp", "jvp_precip_rai", "jvp_precip_sno", "tendencies", "precip_rai", "precip_sno"])
+ColumnParamVjp1M = namedtuple("ColumnParamVjp1M", ["grad", "tendencies", "precip_rai", "precip_sno", "wrt"])
+
+
+def _column_param_directions_1m(mp, fam, directions, stokes, chen_rain, chen_ice):
+    """The five direction tables of include/cmx.h §28 from a sequence whose members are {ClimaParams name: weight} mappings or the 5-tuples of
+    `parameters.column_parameter_direction_1m`."""
+    quints = [column_parameter_direction_1m(mp, d, stokes, chen_rain, chen_ice) if isinstance(d, dict) else tuple(d) for d in directions]
+    if not quints:
+        raise ValueError("directions: at least one direction expected")
+    types = (fam.microphysics_1m, fam.thermo, fam.stokes_vel, fam.chen2022_rain_vel, fam.chen2022_ice_vel)
+    for q in quints:
+        if len(q) != 5 or not all(isinstance(a, t) for a, t in zip(q, types)):
+            raise TypeError("directions: (d_microphysics_1m, d_thermo, d_stokes_vel, d_chen2022_rain_vel, d_chen2022_ice_vel) structs of the state's float "
+                            "type, or {name: weight} mappings")
+    return [(t * len(quints))(*[q[k] for q in quints]) for k, t in enumerate(types)]
+
+
+def column_param_jvp_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, directions, with_tendencies=False, *,
+                        stream=None) -> ColumnParamJvp1M:
+    """J_θ·δθ of `column_tendencies_sedimentation_1m(Instantaneous(), …)` — the four tendencies with the flux divergence of the four falling species — and of
+    its two precipitation fluxes with respect to the scheme's PARAMETERS, the fall-speed parameters included, behind `cmx_mp1m_column_param_jvp_*`
+    (include/cmx.h §28).  The state, ρ and `inv_dz` are held fixed.
+
+    Arguments as for `column_jvp_1m`; `directions`: a sequence of {ClimaParams name: weight} mappings (`parameters.COLUMN_1M_DIRECTION_NAMES` has the names)
+    or of the 5-tuples of `parameters.column_parameter_direction_1m`.  Returns `ColumnParamJvp1M(jvp, jvp_precip_rai, jvp_precip_sno, tendencies, precip_rai,
+    precip_sno)`: `jvp` of shape (len(directions), 4, n_col, n_lev), `jvp_precip_*` (len(directions), n_col); a column does not depend on which other
+    directions are in the call.  More than `CMX_PARAM_MAX_DIRS` = 16 directions are several calls.  b and b_ρ of the Chen-2022 rain table are held fixed: a
+    direction on them raises CmxStatusError (CMX_ERR_UNSUPPORTED).  Asynchronous on `stream`."""
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    ref, fam, keep, head = _column_products_head_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols)
+    tables = _column_param_directions_1m(mp, fam, directions, stokes, chen_rain, chen_ice)
+    ndir = len(tables[0])
+    jvp = torch.empty((ndir, 4, *ref.shape), dtype=ref.dtype, device=ref.device)
+    jvp_precip = torch.empty((2, ndir, ref.shape[0]), dtype=ref.dtype, device=ref.device)
+    tend, pr, ps = _column_primal_out_1m(ref, with_tendencies)
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        first = d0 == 0 and tend is not None
+        _lib.call("cmx_mp1m_column_param_jvp", fam, ref.device, *head, nd, *[C.byref(t[d0]) for t in tables],
+                  _table([jvp[d, o] for d in range(d0, d0 + nd) for o in range(4)]), _table([jvp_precip[0, d] for d in range(d0, d0 + nd)]),
+                  _table([jvp_precip[1, d] for d in range(d0, d0 + nd)]), _table([tend[o] for o in range(4)]) if first else None,
+                  _ptr(pr) if first else None, _ptr(ps) if first else None, stream=stream)
+    return ColumnParamJvp1M(jvp, jvp_precip[0], jvp_precip[1], tend, pr, ps)
+
+
+def column_param_vjp_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, cotangents, cot_precip_rai=None,
+                        cot_precip_sno=None, wrt=(), with_tendencies=False, *, stream=None) -> ColumnParamVjp1M:
+    """The gradient of Σ ḡ·tendencies + Σ p̄_rai·precip_rai + Σ p̄_sno·precip_sno of `column_tendencies_sedimentation_1m(Instantaneous(), …)` with respect to
+    the PARAMETERS behind `cmx_mp1m_column_param_vjp_*` (include/cmx.h §28): what `loss(precip_rai + precip_sno).backward()` needs to reach `theta`
+    (cmx.autograd).
+
+    `cotangents`, `cot_precip_rai`, `cot_precip_sno` as for `column_vjp_1m`; `wrt`: ClimaParams names (one-hot directions) or directions as for
+    `column_param_jvp_1m`.  Returns `ColumnParamVjp1M(grad, tendencies, precip_rai, precip_sno, wrt)`: `grad` a float64 tensor of len(wrt) values on the
+    state's device — a fixed-order reduction, bit-identical from run to run."""
+    wrt = tuple(wrt)
+    cotangents = [None] * 4 if cotangents is None else list(cotangents)
+    if len(cotangents) != 4:
+        raise ValueError("cotangents: 4 tensors (or None) expected, one per output")
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    ref, fam, keep, head = _column_products_head_1m(mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols)
+    tables = _column_param_directions_1m(mp, fam, [{w: 1.0} if isinstance(w, str) else w for w in wrt], stokes, chen_rain, chen_ice)
+    given = [(o, g) for o, g in enumerate(cotangents) if g is not None]
+    if given:
+        _check_cols([ref] + [g for _, g in given], ["rho"] + [f"cotangent {o}" for o, _ in given])
+    for nm, p in (("cot_precip_rai", cot_precip_rai), ("cot_precip_sno", cot_precip_sno)):
+        if p is not None and (p.dtype != ref.dtype or p.device != ref.device or p.shape != (ref.shape[0],) or not p.is_contiguous()):
+            raise ValueError(f"{nm} must be a contiguous device vector of n_col values of the state dtype")
+    ndir = len(tables[0])
+    grad = torch.empty(ndir, dtype=torch.float64, device=ref.device)
+    workspace = torch.empty(min(ndir, _abi.CMX_PARAM_MAX_DIRS) * _abi.CMX_PARAM_VJP_PARTIALS, dtype=torch.float64, device=ref.device)
+    tend, pr, ps = _column_primal_out_1m(ref, with_tendencies)
+    for d0 in range(0, ndir, _abi.CMX_PARAM_MAX_DIRS):
+        nd = min(_abi.CMX_PARAM_MAX_DIRS, ndir - d0)
+        first = d0 == 0 and tend is not None
+        _lib.call("cmx_mp1m_column_param_vjp", fam, ref.device, *head, _table(cotangents), _ptr(cot_precip_rai), _ptr(cot_precip_sno), nd,
+                  *[C.byref(t[d0]) for t in tables], _ptr(grad[d0:]), _ptr(workspace), _table([tend[o] for o in range(4)]) if first else None,
+                  _ptr(pr) if first else None, _ptr(ps) if first else None, stream=stream)
+    return ColumnParamVjp1M(grad, tend, pr, ps, wrt)
 
 
 def _column_implicit_1m(entry, mp, tps, stokes, chen_rain, chen_ice, inv_dz, cols, dt, nsub, nonnegative, precip, stream):

@@ -1231,3 +1231,61 @@ def column_parameter_direction(mp, weights: Mapping, vel_params=None, cloud_vel=
         for which, path, dfield in fields:
             _add_field(d[which], path, float(weight) * (dfield(wr.c) if callable(dfield) else dfield))
     return d["wr"], d["tps"], d["vel"], d["cloud_vel"]
+
+
+# The directions of the 1-moment COLUMN step with its four fall speeds (include/cmx.h §28): the names of `parameter_direction` for the 1-moment scheme —
+# _values_1m also fills the fields only the fall speeds read: cloud_liquid.N_0 / rho_w, cloud_ice.N_0 / rho_i, snow.rho_i / phi / kappa — plus the Stokes
+# struct and the Chen-2022 tables.  A vector-valued name is addressed entry by entry: "Chen2022_table_B5_Al[1]".
+_STOKES_DIRECTION_FIELDS = {"density_liquid_water": "rho_w", "gravitational_acceleration": "grav", "kinematic_viscosity_of_air": "nu_air"}
+_CHEN_RAIN_DIRECTION_FIELDS = {"Chen2022_table_B1_q_coeff": "rho_0", "Chen2022_table_B1_a3_pow_coeff": "a3_pow"}
+_CHEN_VECTOR_DIRECTION_FIELDS = {"Chen2022_table_B1_ai": ("chen_rain", "a", 3), "Chen2022_table_B1_ci": ("chen_rain", "c", 3)}
+_CHEN_VECTOR_DIRECTION_FIELDS.update({f"Chen2022_table_B3_{x}s": ("chen_ice", f"small_ice.{x}", 4 if x == "C" else 3) for x in "ABCEFG"})
+_CHEN_VECTOR_DIRECTION_FIELDS.update({f"Chen2022_table_B5_{x}l": ("chen_ice", f"large_ice.{x}", 3) for x in "ABCEFGH"})
+# held fixed: they reach the rain fall speed through Γ(b − b_ρ ρ + 4), which has no derivative on the device
+_CHEN_FIXED_NAMES = ("Chen2022_table_B1_bi", "Chen2022_table_B1_b_rho_coeff")
+COLUMN_1M_DIRECTION_NAMES = (MICROPHYSICS_1M_DIRECTION_NAMES + tuple(_CHEN_RAIN_DIRECTION_FIELDS)
+                             + tuple(f"{k}[{i}]" for k, (_, _, n) in _CHEN_VECTOR_DIRECTION_FIELDS.items() for i in range(n)))
+
+
+def split_indexed_name(name):
+    """("Chen2022_table_B5_Al", 1) of "Chen2022_table_B5_Al[1]"; (name, None) of a scalar name."""
+    if name.endswith("]") and "[" in name:
+        base, idx = name[:-1].split("[", 1)
+        return base, int(idx)
+    return name, None
+
+
+def column_parameter_direction_1m(mp, weights: Mapping, stokes=None, chen_rain=None, chen_ice=None):
+    """A direction δθ for the parameter derivatives of the 1-moment column step (`cmx.column_param_jvp_1m` / `column_param_vjp_1m`; include/cmx.h §28): the
+    five structs (d_microphysics_1m, d_thermo, d_stokes_vel, d_chen2022_rain_vel, d_chen2022_ice_vel) of the entry's own types whose fields hold
+    Σ_name ∂field/∂name · δ(name).  The names are `COLUMN_1M_DIRECTION_NAMES`: those of `parameter_direction` for `Microphysics1MParams`, the scalars and the
+    entries ("name[i]") of the Chen-2022 tables; the density of water, the gravitational acceleration and the viscosity of air also feed the Stokes struct.
+    `stokes`, `chen_rain`, `chen_ice`: accepted for symmetry with the wrappers (no row is a function of their values).  b and b_ρ of the Chen-2022 rain
+    table are held fixed and raise ValueError."""
+    if not isinstance(mp, Microphysics1MParams):
+        raise TypeError("column_parameter_direction_1m: Microphysics1MParams expected")
+    fam = mp.fam
+    d = {"stokes": fam.stokes_vel(), "chen_rain": fam.chen2022_rain_vel(), "chen_ice": fam.chen2022_ice_vel()}
+    point = {}
+    for name, weight in weights.items():
+        base, idx = split_indexed_name(name)
+        if base in _CHEN_FIXED_NAMES:
+            raise ValueError(f"column_parameter_direction_1m: '{name}' is held fixed: it reaches the rain fall speed through Γ(b − b_ρ ρ + 4), which carries "
+                             "no tangent on the device")
+        if name not in COLUMN_1M_DIRECTION_NAMES:
+            raise ValueError(f"column_parameter_direction_1m: '{name}' feeds no floating field of the column step's parameters")
+        if idx is not None:
+            which, path, _ = _CHEN_VECTOR_DIRECTION_FIELDS[base]
+            *head, leaf = path.split(".")
+            s = d[which]
+            for h in head:
+                s = getattr(s, h)
+            getattr(s, leaf)[idx] += float(weight)
+        elif name in _CHEN_RAIN_DIRECTION_FIELDS:
+            _add_field(d["chen_rain"], _CHEN_RAIN_DIRECTION_FIELDS[name], float(weight))
+        else:
+            point[name] = weight
+            if name in _STOKES_DIRECTION_FIELDS:
+                _add_field(d["stokes"], _STOKES_DIRECTION_FIELDS[name], float(weight))
+    d_mp, d_tps = _direction_1m(mp, point)
+    return d_mp, d_tps, d["stokes"], d["chen_rain"], d["chen_ice"]

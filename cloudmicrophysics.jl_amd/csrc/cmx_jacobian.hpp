@@ -723,6 +723,31 @@ template <typename FT, typename F> inline void for_each_param_launch(int ndir, F
     }
 }
 
+// (shared by the column steps' parameter derivatives, cmx_sb2006_column_param.hpp and cmx_mp1m_column_param.hpp)
+// f(std::integral_constant<int, 0>{}) … f(std::integral_constant<int, N − 1>{}): the loops over the flux slots with the slot a compile-time constant.  With KP
+// tangents inside, `#pragma unroll` alone left the slot loop of the cloud instantiations rolled, and Av[flux_out(s)] became a run-time index into a
+// stack copy of the point (77 scratch instructions at KP = 4).
+template <int N, typename F> __device__ __forceinline__ void for_each_slot(F &&f) {
+    if constexpr (N > 0) {
+        for_each_slot<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// The launches of a call: f(std::integral_constant<int, K>{}, d0) for the directions d0 … d0 + K − 1 — KW at a time while at least min(KW, 2) remain, then
+// one at a time.
+template <int KW, typename F> inline void for_each_column_param_launch(int ndir, F &&f) {
+    for (int d0 = 0; d0 < ndir;) {
+        if (KW > 1 && ndir - d0 >= 2) {
+            f(std::integral_constant<int, KW>{}, d0);
+            d0 += KW;
+        } else {
+            f(std::integral_constant<int, 1>{}, d0);
+            d0 += 1;
+        }
+    }
+}
+
 // `jvp[k][q]`: the column of Σ_p ∂out_q/∂θ_p·δθ_p of the direction in tangent slot k (NULL: not wanted, or an idle slot).  `tend`: the optional primal columns.
 template <typename FT, int KP, int NOUT, int NWRT> struct ParamJvpArgs {
     const FT *in[NWRT + 1];           // rho, then the other inputs

@@ -4,6 +4,9 @@
 // (CMNonEq.terminal_velocity, MicrophysicsNonEq.jl:250-281).  Shared by the velocity / sedimentation kernels (cmx_mp1m_kernels.hip)
 // and the fused 1-moment column step (cmx_mp1m_column.hip).
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "cmx_mp1m.hpp"
 
 namespace cmx {
@@ -189,26 +192,50 @@ __device__ __forceinline__ SedFluxW4<FT> mp1m_sed_fluxes_w(const VC &vc, FT rho,
     return F;
 }
 
-// *chen_general (optional): true when the Chen-2022 rain table needs the GENERAL instantiation (the Γ fit is not accurate for it)
-template <typename FT, typename MP, typename CH>
-static Vel1mConsts<FT> make_vel1m_consts(const MP &mp, const CH *chen, bool *chen_general = nullptr) {
+// The folds below are generic in how a parameter is read and in the scalar the result holds, as make_mp1m_consts_from (cmx_mp1m.hpp): a reader returns a
+// field as the working scalar W — double for the plain folds (make_vel1m_consts, add_sedimentation_consts: the double arithmetic they always were), a value
+// with a tangent for the parameter derivatives of the column step (cmx_mp1m_column_param.hpp, W = ParamTan; the value parts are the plain fold's in every
+// bit).  VC: Vel1mConsts<FT> or a struct with the members the Chen-2022 / Stokes fall speeds read; a member of an arithmetic type holds the value only.
+template <typename M, typename W> inline void put_const(M &m, const W &w) {
+    if constexpr (std::is_arithmetic<M>::value) m = (M)(double)w;
+    else m = (M)w;
+}
+template <typename VC, typename = void> struct has_blk1m_consts : std::false_type {};
+template <typename VC> struct has_blk1m_consts<VC, std::void_t<decltype(std::declval<VC>().vt_k_rai)>> : std::true_type {};
+
+// *chen_general (optional): true when the Chen-2022 rain table needs the GENERAL instantiation (the Γ fit is not accurate for it).  P reads `mp`, C reads
+// `*chen`; b and b_ρ of the table are read as values: they reach the fall speed through Γ, which carries no tangent (ChenGamma stays plain).
+template <typename FT, typename R, typename VC, typename MP, typename CH, typename PM, typename PC>
+static void make_vel1m_consts_from(VC &c, const MP &mp, const CH *chen, bool *chen_general, const PM &P, const PC &C) {
+    using W = decltype(P(mp.rain.n0));
     // reuse the folding of the tendencies kernel (thermo part unused): a neutral thermo struct keeps it well-defined
     cmx_thermo_f64 tp{461.5, 287.0, 1004.5, 1859.0, 4181.0, 2070.0, 2.5008e6, 2.8344e6, 273.16, 273.16, 611.657, 273.15, 4181.0};
-    const Mp1mConsts<FT> m = make_mp1m_consts<FT>(mp, tp, 0u, (double)Math<FT>::eps_1m());
-    Vel1mConsts<FT> c{};
-    c.eps_1m = m.eps_1m; c.l2_eps = m.l2_eps; c.lam_a_rai = m.lam_a_rai; c.lam_b_rai = m.lam_b_rai; c.lam_floor_rai = m.lam_floor_rai;
-    c.lam_a_sno = m.lam_a_sno; c.lam_b_sno = m.lam_b_sno; c.lam_floor_sno = m.lam_floor_sno; c.sno_l2_mu = m.sno_l2_mu; c.sno_nu = m.sno_nu;
-    c.rho_w = m.rho_w; c.vt_k_rai = m.vt_k_rai; c.vt_e_rai = m.vt_e_rai; c.vt_k_sno = m.vt_k_sno; c.vt_e_sno = m.vt_e_sno;
-    c.l2_1000 = (FT)std::log2(1000.0);
+    const Mp1mConsts<R> m = make_mp1m_consts_from<FT, R>(mp, tp, 0u, (double)Math<FT>::eps_1m(), P, [](const auto &f) { return W((double)f); });
+    put_const(c.eps_1m, m.eps_1m); put_const(c.l2_eps, m.l2_eps); put_const(c.lam_a_rai, m.lam_a_rai); put_const(c.lam_b_rai, m.lam_b_rai);
+    put_const(c.lam_floor_rai, m.lam_floor_rai); put_const(c.lam_a_sno, m.lam_a_sno); put_const(c.lam_b_sno, m.lam_b_sno);
+    put_const(c.lam_floor_sno, m.lam_floor_sno); put_const(c.sno_l2_mu, m.sno_l2_mu); put_const(c.sno_nu, m.sno_nu);
+    if constexpr (has_blk1m_consts<VC>::value) {
+        put_const(c.rho_w, m.rho_w); put_const(c.vt_k_rai, m.vt_k_rai); put_const(c.vt_e_rai, m.vt_e_rai); put_const(c.vt_k_sno, m.vt_k_sno);
+        put_const(c.vt_e_sno, m.vt_e_sno);
+    }
+    put_const(c.l2_1000, std::log2(1000.0));
     if (chen) {
-        c.ch_rho0_l2e = (FT)((double)chen->rho_0 * 1.4426950408889634074);
-        for (int k = 0; k < 3; ++k) { c.ch_a[k] = (FT)chen->a[k]; c.ch_b[k] = (FT)chen->b[k]; c.ch_c1000[k] = (FT)((double)chen->c[k] * 1000.0); }
-        c.ch_a3_pow = (FT)chen->a3_pow; c.ch_b_rho = (FT)chen->b_rho;
+        put_const(c.ch_rho0_l2e, C(chen->rho_0) * 1.4426950408889634074);
+        for (int k = 0; k < 3; ++k) {
+            put_const(c.ch_a[k], C(chen->a[k])); put_const(c.ch_b[k], (double)chen->b[k]); put_const(c.ch_c1000[k], C(chen->c[k]) * 1000.0);
+        }
+        put_const(c.ch_a3_pow, C(chen->a3_pow)); put_const(c.ch_b_rho, (double)chen->b_rho);
         const bool fit_ok = make_chen_gamma<FT>(*chen, c.chg, 3);
         if (chen_general) *chen_general = !fit_ok;
     } else if (chen_general) {
         *chen_general = false;
     }
+}
+template <typename FT, typename MP, typename CH>
+static Vel1mConsts<FT> make_vel1m_consts(const MP &mp, const CH *chen, bool *chen_general = nullptr) {
+    Vel1mConsts<FT> c{};
+    const auto rd = [](const auto &f) { return (double)f; };
+    make_vel1m_consts_from<FT, FT>(c, mp, chen, chen_general, rd, rd);
     return c;
 }
 
@@ -216,72 +243,86 @@ static Vel1mConsts<FT> make_vel1m_consts(const MP &mp, const CH *chen, bool *che
 //   CMX_SNOW_SHAPE_ASPR     ϕ^κ of the fixed aspect ratio (CM1:287-295): amp = ϕ^κ, ka = 0
 //   CMX_SNOW_SHAPE_OBLATE   ϕ_av^κ, ϕ_av = ϕ₀ (λ⁻¹)^α Γ_aspect (CM1:299-324) with CM1.aspect_ratio_coeffs (CM1:155-195):
 //   CMX_SNOW_SHAPE_PROLATE    amp = (ϕ₀ Γ_aspect)^κ 2^(−κα), ka = κα
-struct SnowAspect { double amp, ka; };
-template <typename MP> static SnowAspect snow_aspect(const MP &mp, uint32_t shape) {
+template <typename W> struct SnowAspectOf { W amp, ka; };
+using SnowAspect = SnowAspectOf<double>;
+template <typename MP, typename PM> static auto snow_aspect_from(const MP &mp, uint32_t shape, const PM &P) {
+    using std::exp2; using std::pow; using std::sqrt;
+    using W = decltype(P(mp.snow.phi));
     const double pi = 3.14159265358979323846;
     const auto &m = mp.snow.mass;
     const auto &a = mp.snow.area;
-    const double ri = (double)mp.snow.rho_i, mexp = (double)m.me + (double)m.delta_m, aexp = (double)a.ae + (double)a.delta_a;
-    const double cm = (double)m.chi_m * (double)m.m0, ca = (double)a.chi_a * (double)a.a0, d0 = 2.0 * (double)m.r0;
-    double alpha, phi0, kappa, gam;
+    const W ri = P(mp.snow.rho_i), mexp = P(m.me) + P(m.delta_m), aexp = P(a.ae) + P(a.delta_a);
+    const W cm = P(m.chi_m) * P(m.m0), ca = P(a.chi_a) * P(a.a0), d0 = 2.0 * P(m.r0);
+    W alpha, phi0, kappa, gam;
     if (shape == CMX_SNOW_SHAPE_OBLATE) {            // ϕ(r) = 3√π m(r) / (4 ρᵢ a(r)^{3/2})
         alpha = mexp - 1.5 * aexp;
-        phi0 = 3.0 * std::sqrt(pi) / 4.0 / ri * cm / std::pow(ca, 1.5) / std::pow(d0, alpha);
-        kappa = 1.0 / 3.0;
-        gam = (double)mp.snow.gamma_aspect_oblate;
+        phi0 = 3.0 * std::sqrt(pi) / 4.0 / ri * cm / pow(ca, W(1.5)) / pow(d0, alpha);
+        kappa = W(1.0 / 3.0);
+        gam = P(mp.snow.gamma_aspect_oblate);
     } else if (shape == CMX_SNOW_SHAPE_PROLATE) {    // ϕ(r) = 16 ρᵢ² a(r)³ / (9π m(r)²)
         alpha = 3.0 * aexp - 2.0 * mexp;
-        phi0 = 16.0 * ri * ri / 9.0 / pi * std::pow(ca, 3.0) / (cm * cm) / std::pow(d0, alpha);
-        kappa = -1.0 / 6.0;
-        gam = (double)mp.snow.gamma_aspect_prolate;
+        phi0 = 16.0 * ri * ri / 9.0 / pi * pow(ca, W(3.0)) / (cm * cm) / pow(d0, alpha);
+        kappa = W(-1.0 / 6.0);
+        gam = P(mp.snow.gamma_aspect_prolate);
     } else {
-        return {std::pow((double)mp.snow.phi, (double)mp.snow.kappa), 0.0};
+        return SnowAspectOf<W>{pow(P(mp.snow.phi), P(mp.snow.kappa)), W(0.0)};
     }
-    const double ka = kappa * alpha;
-    return {std::pow(phi0 * gam, kappa) * std::exp2(-ka), ka};
+    const W ka = kappa * alpha;
+    return SnowAspectOf<W>{pow(phi0 * gam, kappa) * exp2(-ka), ka};
+}
+template <typename MP> static SnowAspect snow_aspect(const MP &mp, uint32_t shape) {
+    return snow_aspect_from(mp, shape, [](const auto &f) { return (double)f; });
 }
 
 // adds the cloud-liquid (Stokes) and Chen-2022 ice constants of the four sedimentation velocities a host model precomputes
 // (ClimaAtmos set_sedimentation_precomputed_quantities; test/gpu_clima_core_test.jl:36-45, KA kernel test/gpu_tests.jl:608-630);
 // snow_shape (CMX_SNOW_SHAPE_*): the aspect-ratio factor folded into the snow constants (snow_aspect; vel_snow_chen<FT, true> then also
-// needs Vel1mShapeConsts::sn_e2 = ka − 4, see make_snow_shape_consts)
-template <typename FT, typename MP, typename ST, typename CI>
-static void add_sedimentation_consts(Vel1mConsts<FT> &c, const MP &mp, const ST *stokes, const CI *chen_ice, uint32_t snow_shape = CMX_SNOW_SHAPE_ASPR) {
+// needs Vel1mShapeConsts::sn_e2 = ka − 4, see make_snow_shape_consts).  P reads `mp`, S `*stokes`, I `*chen_ice`: the Chen-2022 ice tables are reduced at
+// the apparent densities in closed form, so every coefficient, ρᵢ and N_0 carry exact tangents (Γ(C_l + 4), Γ(F_l + 4): tgamma of the working scalar).
+template <typename FT, typename VC, typename MP, typename ST, typename CI, typename PM, typename PS, typename PI>
+static void add_sedimentation_consts_from(VC &c, const MP &mp, const ST *stokes, const CI *chen_ice, uint32_t snow_shape, const PM &P, const PS &S, const PI &I) {
+    using std::exp; using std::log; using std::pow; using std::sqrt; using std::tgamma;
+    using W = decltype(P(mp.snow.rho_i));
     const double pi = 3.14159265358979323846;
     if (stokes) {
-        c.st_pref = (FT)((double)stokes->grav / (18.0 * (double)stokes->nu_air));
-        c.st_rho_w = (FT)stokes->rho_w;
-        c.st_D3 = (FT)(6.0 / pi / ((double)mp.cloud_liquid.N_0 * (double)mp.cloud_liquid.rho_w));
+        put_const(c.st_pref, S(stokes->grav) / (18.0 * S(stokes->nu_air)));
+        put_const(c.st_rho_w, S(stokes->rho_w));
+        put_const(c.st_D3, 6.0 / pi / (P(mp.cloud_liquid.N_0) * P(mp.cloud_liquid.rho_w)));
     }
     if (chen_ice) {
         {   // small ice reduced at the cloud-ice apparent density — Common.jl:304-325
             const auto &t = chen_ice->small_ice;
-            const double ri = (double)mp.cloud_ice.rho_i, l = std::log(ri), sq = std::sqrt(ri);
-            c.ci_D3 = (FT)(6.0 / pi / ((double)mp.cloud_ice.N_0 * ri));
-            c.ci_A = (FT)((double)t.A[1] * l * l - (double)t.A[2] * l + (double)t.A[0]);
-            c.ci_B = (FT)(1.0 / ((double)t.B[0] + (double)t.B[1] * l + (double)t.B[2] / sq));
-            c.ci_C = (FT)((double)t.C[0] + (double)t.C[1] * std::exp((double)t.C[2] * ri) + (double)t.C[3] * sq);
-            c.ci_E = (FT)((double)t.E[0] - (double)t.E[1] * l * l + (double)t.E[2] * sq);
-            c.ci_F = (FT)(-std::exp((double)t.F[0] - (double)t.F[1] * l * l + (double)t.F[2] * l));
-            c.ci_c2 = (FT)(1000.0 / ((double)t.G[0] + (double)t.G[1] / l - (double)t.G[2] * l / ri));
+            const W ri = P(mp.cloud_ice.rho_i), l = log(ri), sq = sqrt(ri);
+            put_const(c.ci_D3, 6.0 / pi / (P(mp.cloud_ice.N_0) * ri));
+            put_const(c.ci_A, I(t.A[1]) * l * l - I(t.A[2]) * l + I(t.A[0]));
+            put_const(c.ci_B, 1.0 / (I(t.B[0]) + I(t.B[1]) * l + I(t.B[2]) / sq));
+            put_const(c.ci_C, I(t.C[0]) + I(t.C[1]) * exp(I(t.C[2]) * ri) + I(t.C[3]) * sq);
+            put_const(c.ci_E, I(t.E[0]) - I(t.E[1]) * l * l + I(t.E[2]) * sq);
+            put_const(c.ci_F, -exp(I(t.F[0]) - I(t.F[1]) * l * l + I(t.F[2]) * l));
+            put_const(c.ci_c2, 1000.0 / (I(t.G[0]) + I(t.G[1]) / l - I(t.G[2]) * l / ri));
         }
         {   // large ice reduced at the snow apparent density — Common.jl:327-350; ϕ^κ Γ(b+4)/3! folded in (CM1:287-295)
             const auto &t = chen_ice->large_ice;
-            const double ri = (double)mp.snow.rho_i, l = std::log(ri), sq = std::sqrt(ri);
-            const double Al = (double)t.A[0] + (double)t.A[1] * l + (double)t.A[2] / (ri * sq);
-            const double Bl = std::exp((double)t.B[0] + (double)t.B[1] * l * l + (double)t.B[2] * l);
-            const double Cl = std::exp((double)t.C[0] + (double)t.C[1] / l + (double)t.C[2] / ri);
-            const double El = (double)t.E[0] + (double)t.E[1] * l * sq + (double)t.E[2] * sq;
-            const double Fl = (double)t.F[0] + (double)t.F[1] * l - std::exp(std::log(-(double)t.F[2]) - ri);
-            const double Gl = 1.0 / ((double)t.G[0] + (double)t.G[1] * l * sq + (double)t.G[2] / sq);
-            const double Hl = (double)t.H[0] + (double)t.H[1] * ri * ri * sq + std::exp(std::log(-(double)t.H[2]) - ri);
-            const SnowAspect sa = snow_aspect(mp, snow_shape);
-            const double pk = sa.amp;
-            c.sn_A = (FT)Al; c.sn_b1 = (FT)(Cl + sa.ka); c.sn_b2 = (FT)Fl; c.sn_H = (FT)Hl; c.sn_c2 = (FT)(1000.0 * Gl);
-            c.sn_a1 = (FT)(pk * Bl * std::pow(1000.0, Cl) * std::tgamma(Cl + 4.0) / 6.0);
-            c.sn_a2 = (FT)(pk * El * std::pow(1000.0, Fl) * std::tgamma(Fl + 4.0) / 6.0);
+            const W ri = P(mp.snow.rho_i), l = log(ri), sq = sqrt(ri);
+            const W Al = I(t.A[0]) + I(t.A[1]) * l + I(t.A[2]) / (ri * sq);
+            const W Bl = exp(I(t.B[0]) + I(t.B[1]) * l * l + I(t.B[2]) * l);
+            const W Cl = exp(I(t.C[0]) + I(t.C[1]) / l + I(t.C[2]) / ri);
+            const W El = I(t.E[0]) + I(t.E[1]) * l * sq + I(t.E[2]) * sq;
+            const W Fl = I(t.F[0]) + I(t.F[1]) * l - exp(log(-I(t.F[2])) - ri);
+            const W Gl = 1.0 / (I(t.G[0]) + I(t.G[1]) * l * sq + I(t.G[2]) / sq);
+            const W Hl = I(t.H[0]) + I(t.H[1]) * ri * ri * sq + exp(log(-I(t.H[2])) - ri);
+            const auto sa = snow_aspect_from(mp, snow_shape, P);
+            const W pk = sa.amp;
+            put_const(c.sn_A, Al); put_const(c.sn_b1, Cl + sa.ka); put_const(c.sn_b2, Fl); put_const(c.sn_H, Hl); put_const(c.sn_c2, 1000.0 * Gl);
+            put_const(c.sn_a1, pk * Bl * pow(W(1000.0), Cl) * tgamma(Cl + 4.0) / 6.0);
+            put_const(c.sn_a2, pk * El * pow(W(1000.0), Fl) * tgamma(Fl + 4.0) / 6.0);
         }
     }
+}
+template <typename FT, typename MP, typename ST, typename CI>
+static void add_sedimentation_consts(Vel1mConsts<FT> &c, const MP &mp, const ST *stokes, const CI *chen_ice, uint32_t snow_shape = CMX_SNOW_SHAPE_ASPR) {
+    const auto rd = [](const auto &f) { return (double)f; };
+    add_sedimentation_consts_from<FT>(c, mp, stokes, chen_ice, snow_shape, rd, rd, rd);
 }
 
 // the constants of cmx_snow_terminal_velocity_* and of the shaped column step: chen_rain / stokes may be NULL (CR / ST name their types)

@@ -66,6 +66,16 @@ inline double digamma(double x) {
     return s + std::log(x) - 0.5 / x - series;
 }
 inline ParamTan lgamma(ParamTan x) { return {std::lgamma(x.v), digamma(x.v) * x.d}; }
+// Γ(x) with Γ·ψ(x)·ẋ (the Chen-2022 large-ice fold add_sedimentation_consts_from, cmx_mp1m_vel.hpp: Γ(C_l + 4), Γ(F_l + 4)); an argument that does not
+// move carries the literal zero, so ψ's NaN at x ≤ 0 stays out of a direction that does not touch it
+inline ParamTan tgamma(ParamTan x) {
+    const double g = std::tgamma(x.v);
+    return {g, x.d == 0.0 ? 0.0 : g * digamma(x.v) * x.d};
+}
+inline ParamTan exp2(ParamTan x) {
+    const double e = std::exp2(x.v);
+    return {e, 0.69314718055994530942 * e * x.d};
+}
 inline ParamTan fmax(ParamTan a, ParamTan b) { return (b.v > a.v || a.v != a.v) ? ParamTan{std::fmax(a.v, b.v), b.d} : ParamTan{std::fmax(a.v, b.v), a.d}; }
 
 // every floating member of a parameter struct or of a direction is finite (the structs hold nothing else)

@@ -49,30 +49,6 @@ namespace cmx {
 template <typename FT, int VEL>
 constexpr int kColParamK = sizeof(FT) == 4 ? CMX_COLPARAM_K_F32 : (VEL == VEL_CHEN_GEN ? CMX_COLPARAM_K_F64_GEN : CMX_COLPARAM_K_F64);
 
-// f(std::integral_constant<int, 0>{}) … f(std::integral_constant<int, N − 1>{}): the loops over the flux slots with the slot a compile-time constant.  With KP
-// tangents inside, `#pragma unroll` alone left the slot loop of the cloud instantiations rolled, and Av[flux_out(s)] became a run-time index into a
-// stack copy of the point (77 scratch instructions at KP = 4).
-template <int N, typename F> __device__ __forceinline__ void for_each_slot(F &&f) {
-    if constexpr (N > 0) {
-        for_each_slot<N - 1>(f);
-        f(std::integral_constant<int, N - 1>{});
-    }
-}
-
-// The launches of a call: f(std::integral_constant<int, K>{}, d0) for the directions d0 … d0 + K − 1 — KW at a time while at least min(KW, 2) remain, then
-// one at a time.
-template <int KW, typename F> inline void for_each_column_param_launch(int ndir, F &&f) {
-    for (int d0 = 0; d0 < ndir;) {
-        if (KW > 1 && ndir - d0 >= 2) {
-            f(std::integral_constant<int, KW>{}, d0);
-            d0 += KW;
-        } else {
-            f(std::integral_constant<int, 1>{}, d0);
-            d0 += 1;
-        }
-    }
-}
-
 // The constants of ONE launch: tangent slot k holds ċ of direction d0 + k (an idle slot past ndir: zeros).  Every slot's value parts are the same, and the
 // plain fold's, bit for bit.  d_tps, d_vel, d_cloud_vel: NULL is a zero direction; without cloud_vel the cloud constants are zeros and d_cloud_vel is not read.
 template <typename FT, int KP, typename WR, typename TH, typename VL, typename ST>

@@ -1856,6 +1856,7 @@ int32_t cmx_sb2006_warm_rain_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain
  * sink, snow–rain kernel, ventilation; snow: the same without the sink).  It runs — and `tendencies` is bit-identical to cmx_mp1m_tendencies_* — only if the
  * tendencies entry would select it AND no direction gives one of the nine a non-zero tangent (the size-relation exponents me, Δm, ae, Δa, ve, Δv of rain and
  * snow do).  Otherwise the run-time-flags instantiation runs for the whole call and `tendencies` agrees to the parity bound, not bit for bit.
+ * The 1-moment column step with its four fall speeds and both precipitation fluxes: (28).
  * ------------------------------------------------------------------------- */
 int32_t cmx_mp1m_param_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, uint32_t flags, int64_t n_points, const float *rho, const float *T,
                                const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai, const float *q_sno, int32_t ndir,
@@ -2015,7 +2016,7 @@ int32_t cmx_sb2006_column_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, const c
  * reduction without atomics (the decomposition of (22)), bit-identical from run to run.  No allocation, graph-capturable.
  * Not shipped: the Float64 GRADIENT entry with a Chen-2022 table that takes the general instantiation (run-time Γ) returns CMX_ERR_UNSUPPORTED — its kernel
  * needs 482–511 vector registers at one direction per evaluation and spills 8; the jvp entry serves that case (264–278).
- * Not done here: the 1-moment (its state products: (27)) and 2M + P3 columns, the implicit column steps, derivatives with respect to ρ or inv_dz, of the
+ * Not done here: the 1-moment column — (28); its state products: (27) —, the 2M + P3 column, the implicit column steps, derivatives with respect to ρ or inv_dz, of the
  * Chen-2022 table, second derivatives.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 int32_t cmx_sb2006_column_param_jvp_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
@@ -2088,7 +2089,7 @@ int32_t cmx_sb2006_column_param_vjp_f64(const cmx_warm_rain_2m_f64 *warm_rain, c
  * Results do not depend on how the kernels divide the columns among workgroups, on alignment, or on the number of columns in the call.  Both entries are
  * pure launches on `stream`: no allocation, no synchronisation, graph-capturable.
  * Not done here: the LinearizedAverage mode (nsub > 0); the implicit column steps (20), (21); the snow shapes — a CMX_1M_SED_SNOW_OBLATE / _PROLATE bit returns
- * CMX_ERR_UNSUPPORTED: the oracle's column step has no shaped snow to difference against —; parameter derivatives of this column step; derivatives with
+ * CMX_ERR_UNSUPPORTED: the oracle's column step has no shaped snow to difference against —; parameter derivatives of this column step — (28) —; derivatives with
  * respect to ρ or inv_dz; the 2M + P3 column.  cmx_version() stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 int32_t cmx_mp1m_column_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
@@ -2111,6 +2112,79 @@ int32_t cmx_mp1m_column_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_the
                                 int32_t n_lev, const double *inv_dz, const double *const *in, const double *const cotangents[CMX_MP1M_JAC_NOUT],
                                 const double *cot_precip_rai, const double *cot_precip_sno, double *const grad[CMX_MP1M_JAC_NWRT],
                                 double *const tendencies[CMX_MP1M_JAC_NOUT], double *precip_rai, double *precip_sno, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * (28) The derivatives of the 1-moment COLUMN step (27) with respect to the scheme's PARAMETERS, the fall-speed parameters and the two surface
+ * precipitation fluxes included: cmx_mp1m_column_param_jvp_* (per point, J_θ·δθ) and cmx_mp1m_column_param_vjp_* (the reduced gradient dL/dθ).  (23) stops
+ * at the point function, which knows nothing of the fall speeds; (27) reaches the state but not θ.  This is what loss(precip_rai + precip_sno).backward()
+ * needs to reach `theta` (cmx.autograd), and where the parameters that act through sedimentation only — the Stokes cloud fall speed, the sedimentation
+ * number concentrations, the apparent densities of cloud ice and snow, ϕ, κ and the Chen-2022 coefficients — get a derivative at all.
+ * The function is that of (27), normative, with the state, ρ and inv_dz held FIXED and θ = the floating fields of the five parameter structs:
+ *     out_k = tend(ρ_k, x_k; θ) + g_k·(F_{k+1}(θ) − F_k(θ))        F_{n_lev} = 0        precip_rai = F_0[q_rai]        precip_sno = F_0[q_sno]
+ * With Ḟ_k = ∂F_k/∂θ·δθ:
+ *     J_θ δθ:    ẏ_k = ∂tend/∂θ·δθ + g_k·(Ḟ_{k+1} − Ḟ_k)          ṗ_rai = Ḟ_0[q_rai], ṗ_sno = Ḟ_0[q_sno], one value per column each
+ *     gradient:  grad[d] = Σ_columns Σ_k ( Σ_o ḡ_{o,k}·(∂tend_o/∂θ·δθ⁽ᵈ⁾)_k + Σ_s λ_k[s]·Ḟ_k[s]⁽ᵈ⁾ ),  λ_k exactly that of (27), p̄_rai and p̄_sno at level 0
+ * A DIRECTION is five structs of the entry's own types holding δθ: d_mp[ndir] (required), d_tps[ndir], d_stokes[ndir], d_chen_rain[ndir],
+ * d_chen_ice[ndir] (each of the last four may be NULL: zero).  The tangents of the folded constants are formed on the host in exact forward mode in double
+ * (no difference quotient), as in (22), (23) and (26).
+ * What carries a tangent: every floating field of cmx_microphysics_1m and cmx_thermo that (23) differentiates; the fields of `mp` only the fall speeds read —
+ * cloud_liquid.N_0, cloud_liquid.rho_w, cloud_ice.N_0, cloud_ice.rho_i, snow.rho_i, snow.phi, snow.kappa — and the slope-parameter fields; cmx_stokes_vel
+ * (grav, nu_air, rho_w); every coefficient of chen_ice.small_ice (A, B, C, E, F, G) and .large_ice (A, B, C, E, F, G, H) through the closed forms that
+ * reduce the tables at the apparent densities, Γ(C_l + 4) and Γ(F_l + 4) with Γ·ψ; of chen_rain a[3], c[3], rho_0 and a3_pow.
+ * HELD FIXED: chen_rain.b[3] and chen_rain.b_rho.  They reach the fall speed through Γ(b − b_ρ ρ + 4), a polynomial fit in ρ in the fitted instantiation and
+ * a run-time Γ in the general one, neither with a derivative on the device: any non-zero component of a direction there is CMX_ERR_UNSUPPORTED, whatever
+ * the flags; Γ is evaluated on the value and carries no tangent in both instantiations, as in (27).  The `cutoff` fields of the ice tables are not read by
+ * this step: a direction there contributes nothing.
+ * Arguments: the head of the (27) entries through `in` (mp, tps, stokes, chen_rain, chen_ice, flags, n_col, n_lev, inv_dz, the HOST array of the 7 device
+ * columns); then
+ *   jvp:  ndir (1 … CMX_PARAM_MAX_DIRS), the five direction tables, jvp[ndir·4] (direction-major, then cmx_mp1m_jac_out), jvp_precip_rai[ndir],
+ *         jvp_precip_sno[ndir] (tables of columns of n_col values), tendencies[4], precip_rai, precip_sno.  Every output table, member and column may be
+ *         NULL; no output at all is CMX_ERR_BAD_ARG.
+ *   vjp:  cotangents[4] (the table or a member NULL: absent), cot_precip_rai, cot_precip_sno (n_col values or NULL: absent), ndir, the five direction
+ *         tables, grad (ndir doubles, device), workspace (ndir·CMX_PARAM_VJP_PARTIALS doubles, device), tendencies[4], precip_rai, precip_sno.
+ * Statuses, in order: those of (27) — the parameter pointers and counts, both snow-shape bits (CMX_ERR_BAD_ARG), the Microphysics1MOptions bits, a single
+ * snow-shape bit (CMX_ERR_UNSUPPORTED), the limit on n_col·n_lev [jvp: n_col = 0 is CMX_OK here], the columns —, ndir and d_mp, [vjp: grad and
+ * workspace], the outputs (none may be an input column, inv_dz or a cotangent: a lane reads its neighbours), a non-finite component of a direction
+ * (CMX_ERR_BAD_ARG), a direction on b or b_ρ (CMX_ERR_UNSUPPORTED).  n_col = 0 of the gradient entry passes all of these but the columns and writes zeros
+ * to grad.
+ * The instantiation is the one the primal entry selects (default options or run-time flags, fitted or general Γ); a direction on one of the nine
+ * slope-parameter exponents that the default-options instantiation holds at compile time selects the run-time-flags instantiation for the whole call (23).
+ * Requested `tendencies` and `precip_*` are those of the primal entry (nsub = 0) bit for bit when no direction moves such an exponent.  A jvp column's bits
+ * and a grad value's bits do not depend on ndir, on which other directions are in the call, or on how the call is split into launches; the gradient is a
+ * fixed-order reduction in double without atomics (the decomposition of (22)), bit-identical from run to run.  With inv_dz ≡ 0 and directions on mp and
+ * tps only the four jvp rows equal those of (23) under == wherever the flux tangents of the point and of the point above are finite.
+ * NaN rule: the point and flux poison rules of (27); in the gradient any such NaN, or a NaN in a cotangent, makes every grad[d] NaN (26).
+ * Pure launches on `stream`: no allocation, graph-capturable.
+ * Not done here: the LinearizedAverage mode (nsub > 0); the implicit column steps (20), (21); the snow shapes; derivatives with respect to ρ or inv_dz; b
+ * and b_ρ of the Chen-2022 rain table; the 2M + P3 column; second derivatives; tuning beyond the choice of the directions per evaluation.  cmx_version()
+ * stays at 0.5 (no struct layout changed; an older library fails on the symbol lookup).
+ * ------------------------------------------------------------------------- */
+int32_t cmx_mp1m_column_param_jvp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                        const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, int64_t n_col,
+                                        int32_t n_lev, const float *inv_dz, const float *const *in, int32_t ndir, const cmx_microphysics_1m_f32 *d_mp,
+                                        const cmx_thermo_f32 *d_tps, const cmx_stokes_vel_f32 *d_stokes, const cmx_chen2022_rain_vel_f32 *d_chen_rain,
+                                        const cmx_chen2022_ice_vel_f32 *d_chen_ice, float *const *jvp, float *const *jvp_precip_rai, float *const *jvp_precip_sno,
+                                        float *const tendencies[CMX_MP1M_JAC_NOUT], float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_param_vjp_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                        const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, int64_t n_col,
+                                        int32_t n_lev, const float *inv_dz, const float *const *in, const float *const cotangents[CMX_MP1M_JAC_NOUT],
+                                        const float *cot_precip_rai, const float *cot_precip_sno, int32_t ndir, const cmx_microphysics_1m_f32 *d_mp,
+                                        const cmx_thermo_f32 *d_tps, const cmx_stokes_vel_f32 *d_stokes, const cmx_chen2022_rain_vel_f32 *d_chen_rain,
+                                        const cmx_chen2022_ice_vel_f32 *d_chen_ice, double *grad, double *workspace, float *const tendencies[CMX_MP1M_JAC_NOUT],
+                                        float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_param_jvp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                        const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, int64_t n_col,
+                                        int32_t n_lev, const double *inv_dz, const double *const *in, int32_t ndir, const cmx_microphysics_1m_f64 *d_mp,
+                                        const cmx_thermo_f64 *d_tps, const cmx_stokes_vel_f64 *d_stokes, const cmx_chen2022_rain_vel_f64 *d_chen_rain,
+                                        const cmx_chen2022_ice_vel_f64 *d_chen_ice, double *const *jvp, double *const *jvp_precip_rai, double *const *jvp_precip_sno,
+                                        double *const tendencies[CMX_MP1M_JAC_NOUT], double *precip_rai, double *precip_sno, void *stream);
+int32_t cmx_mp1m_column_param_vjp_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                        const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, int64_t n_col,
+                                        int32_t n_lev, const double *inv_dz, const double *const *in, const double *const cotangents[CMX_MP1M_JAC_NOUT],
+                                        const double *cot_precip_rai, const double *cot_precip_sno, int32_t ndir, const cmx_microphysics_1m_f64 *d_mp,
+                                        const cmx_thermo_f64 *d_tps, const cmx_stokes_vel_f64 *d_stokes, const cmx_chen2022_rain_vel_f64 *d_chen_rain,
+                                        const cmx_chen2022_ice_vel_f64 *d_chen_ice, double *grad, double *workspace, double *const tendencies[CMX_MP1M_JAC_NOUT],
+                                        double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

@@ -2011,6 +2011,77 @@ function column_vjp_1m!(grad, tendencies, precip_rai, precip_sno, mp::CMP.Microp
 end
 
 # ----------------------------------------------------------------------------------------------------------------
+# (28) the derivatives of the 1-moment column step (27) with respect to the parameters, the fall-speed parameters and both precipitation fluxes included
+# ----------------------------------------------------------------------------------------------------------------
+# the five direction tables of (28): `d_mp`, `d_tps` as in (23); `d_stokes` = nothing (zero) or one CMP.StokesRegimeVelType per direction; `d_chen` = nothing or
+# one CMP.Chen2022VelType per direction whose fields hold δθ — its rain part gives d_chen_rain, its ice tables d_chen_ice; b and b_ρ of the rain part must hold
+# ZEROS: they are held fixed (CMX_ERR_UNSUPPORTED otherwise)
+function _column_param_directions_1m(d_mp, d_tps, d_stokes, d_chen)
+    dm, dt = _param_directions_1m(d_mp, d_tps)
+    d_stokes === nothing || length(d_stokes) == length(dm) || error("d_stokes: nothing or one per direction expected")
+    d_chen === nothing || length(d_chen) == length(dm) || error("d_chen: nothing or one per direction expected")
+    ds = d_stokes === nothing ? nothing : collect(d_stokes)
+    dr = d_chen === nothing ? nothing : [_rain(d) for d in d_chen]
+    di = d_chen === nothing ? nothing : [pack(d) for d in d_chen]
+    return dm, dt, ds, dr, di
+end
+
+"""
+    column_param_jvp_1m!(jvp, jvp_precip_rai, jvp_precip_sno, tendencies, precip_rai, precip_sno, mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols,
+                         d_mp, d_tps = nothing, d_stokes = nothing, d_chen = nothing; stream = C_NULL)
+
+The derivative of `column_tendencies_sedimentation!(out, BMT.Instantaneous(), BMT.Microphysics1Moment(), …)` and of its two precipitation fluxes with respect to
+the PARAMETERS along the directions (`d_mp[d]`, `d_tps[d]`, `d_stokes[d]`, `d_chen[d]`): objects of the types of the parameter arguments whose fields hold δθ.
+`jvp` = `length(d_mp)·4` device columns (or `nothing`s), direction-major; `jvp_precip_rai`, `jvp_precip_sno` = one column of `n_col` values per direction (or
+`nothing`s).  The state, ρ and `inv_dz` are held fixed.  include/cmx.h §(28) has the definition.
+"""
+function column_param_jvp_1m!(jvp, jvp_precip_rai, jvp_precip_sno, tendencies, precip_rai, precip_sno, mp::CMP.Microphysics1MParams, tps,
+    stokes::CMP.StokesRegimeVelType{FT}, chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, d_mp, d_tps = nothing, d_stokes = nothing,
+    d_chen = nothing; stream = C_NULL) where {FT}
+    dm, dt, ds, dr, di = _column_param_directions_1m(d_mp, d_tps, d_stokes, d_chen)
+    jvp === nothing || length(jvp) == length(dm) * CMX_MP1M_JAC_NOUT || error("jvp: $(CMX_MP1M_JAC_NOUT) columns (or nothing) per direction expected")
+    jvp_precip_rai === nothing || length(jvp_precip_rai) == length(dm) || error("jvp_precip_rai: one column (or nothing) per direction expected")
+    jvp_precip_sno === nothing || length(jvp_precip_sno) == length(dm) || error("jvp_precip_sno: one column (or nothing) per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = GC.@preserve dm dt ds dr di ccall(_fn("cmx_mp1m_column_param_jvp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+            Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols),
+        Int32(length(dm)), pointer(dm), dt === nothing ? C_NULL : pointer(dt), ds === nothing ? C_NULL : pointer(ds), dr === nothing ? C_NULL : pointer(dr),
+        di === nothing ? C_NULL : pointer(di), _opt_ptrs(FT, jvp), _opt_ptrs(FT, jvp_precip_rai), _opt_ptrs(FT, jvp_precip_sno), _opt_ptrs(FT, tendencies),
+        _dp(FT, precip_rai), _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_param_jvp")
+    return jvp
+end
+
+"""
+    column_param_vjp_1m!(grad, workspace, tendencies, precip_rai, precip_sno, mp, tps, stokes, chen, n_col, n_lev, inv_dz, cols, cotangents, cot_precip_rai,
+                         cot_precip_sno, d_mp, d_tps = nothing, d_stokes = nothing, d_chen = nothing; stream = C_NULL)
+
+The gradient of Σ ḡ·out + Σ p̄_rai·precip_rai + Σ p̄_sno·precip_sno along the parameter directions of `column_param_jvp_1m!`: `grad` = a device array of
+`length(d_mp)` Float64, `workspace` = `length(d_mp)·CMX_PARAM_VJP_PARTIALS` Float64 owned by the caller, `cotangents` = `nothing` or 4 columns (or `nothing`s),
+`cot_precip_rai`, `cot_precip_sno` = `nothing` or `n_col` values.  A deterministic reduction in double: no atomics, the same bits from run to run.
+"""
+function column_param_vjp_1m!(grad, workspace, tendencies, precip_rai, precip_sno, mp::CMP.Microphysics1MParams, tps, stokes::CMP.StokesRegimeVelType{FT},
+    chen::CMP.Chen2022VelType, n_col::Integer, n_lev::Integer, inv_dz, cols, cotangents, cot_precip_rai, cot_precip_sno, d_mp, d_tps = nothing,
+    d_stokes = nothing, d_chen = nothing; stream = C_NULL) where {FT}
+    dm, dt, ds, dr, di = _column_param_directions_1m(d_mp, d_tps, d_stokes, d_chen)
+    cotangents === nothing || length(cotangents) == CMX_MP1M_JAC_NOUT || error("cotangents: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    length(grad) >= length(dm) || error("grad: one Float64 per direction expected")
+    length(workspace) >= length(dm) * CMX_PARAM_VJP_PARTIALS || error("workspace: $(CMX_PARAM_VJP_PARTIALS) Float64 per direction expected")
+    tendencies === nothing || length(tendencies) == CMX_MP1M_JAC_NOUT || error("tendencies: $(CMX_MP1M_JAC_NOUT) columns (or nothing) expected")
+    st = GC.@preserve dm dt ds dr di ccall(_fn("cmx_mp1m_column_param_vjp", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Int32,
+            Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(pack(mp)), Ref(CmxThermo(tps)), Ref(stokes), Ref(_rain(chen)), Ref(pack(chen)), option_bits(mp), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols),
+        _opt_ptrs(FT, cotangents), _dp(FT, cot_precip_rai), _dp(FT, cot_precip_sno), Int32(length(dm)), pointer(dm), dt === nothing ? C_NULL : pointer(dt),
+        ds === nothing ? C_NULL : pointer(ds), dr === nothing ? C_NULL : pointer(dr), di === nothing ? C_NULL : pointer(di), _dp(Float64, grad),
+        _dp(Float64, workspace), _opt_ptrs(FT, tendencies), _dp(FT, precip_rai), _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_param_vjp")
+    return grad
+end
+
+# ----------------------------------------------------------------------------------------------------------------
 # (13) the adiabatic parcel model over an ensemble — parcel/ParcelModel.jl, ParcelTendencies.jl, ParcelDistributions.jl
 # ----------------------------------------------------------------------------------------------------------------
 struct CmxParcelParams{FT, AP, AA, KO, MO, MM}     # == cmx_parcel_params
