@@ -1,5 +1,5 @@
 // cmx_column_geom.hpp — (column, level) of a flat point index, for the kernels that run one point per lane over columns stored level-fastest
-// (cmx_sb2006_column_products.hip, cmx_sb2006_column_param.hip).
+// (the shells of cmx_column_products.hpp).
 #pragma once
 #include <cstdint>
 

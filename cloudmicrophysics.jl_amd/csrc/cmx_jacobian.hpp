@@ -910,7 +910,7 @@ __global__ __launch_bounds__(BS) void param_jvp_kernel(const CD c, const ParamJv
 }
 
 // The end of stage 1 of the gradient, shared by every kernel that feeds the reduction (param_vjp_kernel below; column_param_vjp_kernel,
-// cmx_sb2006_column_param.hip): the lane's accumulators, then the 64 lanes of a wave in a fixed shuffle tree, then the waves left to right →
+// cmx_column_products.hpp): the lane's accumulators, then the 64 lanes of a wave in a fixed shuffle tree, then the waves left to right →
 // ws[k·CMX_PARAM_VJP_PARTIALS + b].  Every lane of the workgroup calls it.
 template <int KP, int BS> __device__ __forceinline__ void param_vjp_reduce(const double (&acc)[KP], const int32_t nlive, double *__restrict__ ws) {
     static_assert(BS % 64 == 0 && KP <= BS, "whole waves");

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "../../include/cmx.h"
+#include "cmx_column_products.hpp"
 #include "cmx_dispatch.hpp"
 #include "cmx_jacobian.hpp"
 #include "cmx_mp1m_jacobian.hpp"
@@ -175,6 +176,24 @@ template <typename FT> struct Col1mJvpPoint {
     FT g;
 };
 
+// The statuses of the J v entry after the NULL checks of the parameter structs: the ladder (cmx_column_products.hpp) with the entry's columns
+template <typename FT>
+inline int32_t mp1m_column_jvp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *tangents, FT *const *jvp,
+                                      FT *jvp_precip_rai, FT *jvp_precip_sno, FT *const *tendencies, FT *precip_rai, FT *precip_sno) {
+    const void *given[CMX_MP1M_JAC_NWRT];
+    void *outs[2 * CMX_MP1M_JAC_NOUT + 4];
+    for (int j = 0; j < CMX_MP1M_JAC_NWRT; ++j) given[j] = tangents ? tangents[j] : nullptr;
+    for (int q = 0; q < CMX_MP1M_JAC_NOUT; ++q) {
+        outs[q] = jvp ? jvp[q] : nullptr;
+        outs[CMX_MP1M_JAC_NOUT + q] = tendencies ? tendencies[q] : nullptr;
+    }
+    outs[2 * CMX_MP1M_JAC_NOUT] = jvp_precip_rai;
+    outs[2 * CMX_MP1M_JAC_NOUT + 1] = jvp_precip_sno;
+    outs[2 * CMX_MP1M_JAC_NOUT + 2] = precip_rai;
+    outs[2 * CMX_MP1M_JAC_NOUT + 3] = precip_sno;
+    return column_entry_status(n_col, n_lev, mp1m_column_jac_flags_status(flags), inv_dz, in, nullptr, given, CMX_MP1M_JAC_NWRT, outs, 2 * CMX_MP1M_JAC_NOUT + 4, false);
+}
+
 // One evaluation of the scheme on Dual<FT, 1> seeded with the caller's tangent t (0 where the column is NULL), at the level whose 1/Δz is inv_dz.  The NaN
 // rule is applied here, where the primal applies it: a NaN in a state input or in a given tangent of the point → every tendency of the point, value and
 // tangent, BEFORE the own flux is subtracted; a NaN in ρ or q_s → the flux of species s, value and tangent (a NaN tangent reaches it by plain IEEE arithmetic).
@@ -248,6 +267,25 @@ template <typename FT, int K> struct Col1mVjpArgs {
     int32_t primal;                   // tend or precip requested
 };
 
+// The statuses of the Jᵀḡ entry after the NULL checks of the parameter structs: the ladder (cmx_column_products.hpp) with the entry's columns
+template <typename FT>
+inline int32_t mp1m_column_vjp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *cotangents,
+                                      const FT *cot_precip_rai, const FT *cot_precip_sno, FT *const *grad, FT *const *tendencies, FT *precip_rai, FT *precip_sno) {
+    const void *given[CMX_MP1M_JAC_NOUT + 2];
+    void *outs[CMX_MP1M_JAC_NOUT + CMX_MP1M_JAC_NWRT + 2];
+    for (int q = 0; q < CMX_MP1M_JAC_NOUT; ++q) {
+        given[q] = cotangents ? cotangents[q] : nullptr;
+        outs[q] = tendencies ? tendencies[q] : nullptr;
+    }
+    given[CMX_MP1M_JAC_NOUT] = cot_precip_rai;
+    given[CMX_MP1M_JAC_NOUT + 1] = cot_precip_sno;
+    for (int j = 0; j < CMX_MP1M_JAC_NWRT; ++j) outs[CMX_MP1M_JAC_NOUT + j] = grad ? grad[j] : nullptr;
+    outs[CMX_MP1M_JAC_NOUT + CMX_MP1M_JAC_NWRT] = precip_rai;
+    outs[CMX_MP1M_JAC_NOUT + CMX_MP1M_JAC_NWRT + 1] = precip_sno;
+    return column_entry_status(n_col, n_lev, mp1m_column_jac_flags_status(flags), inv_dz, in, nullptr, given, CMX_MP1M_JAC_NOUT + 2, outs,
+                               CMX_MP1M_JAC_NOUT + CMX_MP1M_JAC_NWRT + 2, false);
+}
+
 // An input is wanted if its gradient is not NULL.  False if the call has no output at all.
 template <typename FT, int K>
 inline bool make_col1m_vjp_args(Col1mVjpArgs<FT, K> &a, const FT *const (&in)[CMX_MP1M_JAC_NWRT + 1], const FT *inv_dz, int64_t n, int32_t n_lev, const FT *const *cotangents,
@@ -275,6 +313,33 @@ inline bool make_col1m_vjp_args(Col1mVjpArgs<FT, K> &a, const FT *const (&in)[CM
     return any || ns > 0;
 }
 
+// λ of point i = col·n_lev + lev, shared by Jᵀḡ and the parameter gradient (`a`: Col1mVjpArgs or Col1mParamVjpArgs): from g_k, g_{k−1}, the cotangents of
+// the levels k and k−1, read raw, and p̄ of rain and snow.  gnan: a p̄ is a NaN.
+template <typename S, typename FT, typename A>
+__device__ __forceinline__ void column1m_lambda(const A &a, const FT (&x)[S::NWRT + 1], FT gk, int64_t i, int64_t col, int32_t lev, FT (&lam)[4], int &gnan) {
+    using M = Math<FT>;
+    using products_detail::ld;
+    const bool surface = lev == 0;
+    const FT gm = surface ? FT(0) : S::g_of(ld(a.in[0], i - 1), a.inv_dz[lev - 1]);
+    for_each_slot<4>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        const FT *const cot = a.cot[s];
+        FT l = FT(0);
+        if (cot) {
+            l = -gk * ld(cot, i);
+            if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
+        }
+        if constexpr (s >= 2) {
+            if (surface && a.cot_precip[s - 2]) {
+                const FT pbar = ld(a.cot_precip[s - 2], col);
+                gnan |= (int)(pbar != pbar);
+                l = l + pbar;
+            }
+        }
+        lam[s] = l;
+    });
+}
+
 // Every pass of point i = col·n_lev + lev.  Pointwise: the only neighbour data are ρ_{i−1} and the cotangents ḡ_{i−1}, raw from memory (and, if the
 // tendencies are requested, the state of point i+1 for the flux values it sends down).  λ is formed first, then the passes of vjp_point (cmx_jacobian.hpp) run:
 // unit seeds, the cotangents read after eval, the sum of a slot as ONE chain of fma seeded with −0 (a slot with no term at all: +0) — the tendencies with ḡ in
@@ -283,28 +348,11 @@ template <typename S, typename FT, int K, typename CA>
 __device__ __forceinline__ void column1m_vjp_point(const CA &a0, const Col1mVjpArgs<FT, K> &a, const FT (&x)[S::NWRT + 1], int64_t i, int64_t col, int32_t lev) {
     using M = Math<FT>;
     using products_detail::ld;
-    const bool top = lev == a.n_lev - 1, surface = lev == 0;
+    const bool top = lev == a.n_lev - 1;
     const FT gk = S::g_of(x[0], a.inv_dz[lev]);
     FT lam[4] = {FT(0), FT(0), FT(0), FT(0)};
     int gnan = 0;
-    {
-        const FT gm = surface ? FT(0) : S::g_of(ld(a.in[0], i - 1), a.inv_dz[lev - 1]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const FT *const cot = a.cot[s];
-            FT l = FT(0);
-            if (cot) {
-                l = -gk * ld(cot, i);
-                if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
-            }
-            if (s >= 2 && surface && a.cot_precip[s - 2]) {
-                const FT pbar = ld(a.cot_precip[s - 2], col);
-                gnan |= (int)(pbar != pbar);
-                l = l + pbar;
-            }
-            lam[s] = l;
-        }
-    }
+    column1m_lambda<S, FT>(a, x, gk, i, col, lev, lam, gnan);
     const bool poison = S::poison(x);
     for (int pass = 0; pass < a.npass; ++pass) {
         Dual<FT, K> in[S::NWRT], o[S::NOUT], F[4];
@@ -325,7 +373,9 @@ __device__ __forceinline__ void column1m_vjp_point(const CA &a0, const Col1mVjpA
         }
         const bool bad = (bool)((int)poison | cnan);      // a NaN cotangent of the point poisons its tendencies and gradients too
         if (pass == 0 && a.primal) {
-            // the primal entry's operations: t through the NaN rule, A = fma(−F, g, t), the inflow from the flux-only evaluation of the raw point above
+            // the primal entry's operations: t through the NaN rule, A = fma(−F, g, t), the inflow from the flux-only evaluation of the raw point above.
+            // (Not shared with column1m_param_vjp_point, which has the same block in its own text: written once, as a function over the flux slots, the
+            // sign bit of the NaN that a point with a NaN tendency AND a NaN own flux stores came out differently from this loop's.)
             SedFlux4<FT> up{{FT(0), FT(0), FT(0), FT(0)}};
             if (!top) up = S::flux_values(a0, ld(a.in[0], i + 1), ld(a.in[3], i + 1), ld(a.in[4], i + 1), ld(a.in[5], i + 1), ld(a.in[6], i + 1));
 #pragma unroll
@@ -333,7 +383,7 @@ __device__ __forceinline__ void column1m_vjp_point(const CA &a0, const Col1mVjpA
                 const FT Fv = S::out(F[s].v, S::flux_poison(x, s));
                 const FT A = M::fma(-Fv, gk, S::out(o[s].v, bad));
                 if (a.tend[s]) a.tend[s][i] = M::fma(top ? FT(0) : up.f[s], gk, A);
-                if (s >= 2 && surface && a.precip[s - 2]) a.precip[s - 2][col] = Fv;
+                if (s >= 2 && lev == 0 && a.precip[s - 2]) a.precip[s - 2][col] = Fv;
             }
         }
 #pragma unroll

@@ -168,18 +168,55 @@ inline int32_t with_mp1m_column_param(const MP &mp, const TH &tps, const ST &sto
                        one_of<kDefaultFlags, kRuntimeFlags>(fast ? kDefaultFlags : kRuntimeFlags), flag(general));
 }
 
-// ---- one evaluation ---------------------------------------------------------------------------------------------------------------------------------
-// What a point keeps between its evaluation and its stores (Col1mJvpPoint with KP tangents): A = t − (own flux)·g, the fluxes it sends down, g.  The NaN rule
-// is the primal's: a NaN in a state input → every tendency of the point, value and tangents, BEFORE the own flux is subtracted; a NaN in ρ or q_s → the flux
-// of species s, value and tangents.
-template <typename FT, int KP> struct Col1mParamPoint {
-    FT Av[CMX_MP1M_JAC_NOUT], Ad[KP][CMX_MP1M_JAC_NOUT];
-    FT Fv[4], Fd[KP][4];
-    FT g;
-};
+// The statuses of the two entries after the NULL checks of the parameter structs and before with_mp1m_column_param: the ladder (cmx_column_products.hpp)
+// with the entry's columns.  The columns and inv_dz are looked at only when there is a point.
+template <typename FT>
+inline int32_t mp1m_column_param_jvp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, int32_t ndir, const void *d_mp,
+                                            FT *const *jvp, FT *const *jvp_precip_rai, FT *const *jvp_precip_sno, FT *const *tendencies, FT *precip_rai, FT *precip_sno) {
+    void *outs[CMX_PARAM_MAX_DIRS * (CMX_MP1M_JAC_NOUT + 2) + CMX_MP1M_JAC_NOUT + 2];
+    int nouts = 0;
+    const int nd = ndir < 0 ? 0 : (ndir > CMX_PARAM_MAX_DIRS ? CMX_PARAM_MAX_DIRS : ndir);
+    for (int q = 0; q < nd * CMX_MP1M_JAC_NOUT && jvp; ++q) outs[nouts++] = jvp[q];
+    for (int d = 0; d < nd && jvp_precip_rai; ++d) outs[nouts++] = jvp_precip_rai[d];
+    for (int d = 0; d < nd && jvp_precip_sno; ++d) outs[nouts++] = jvp_precip_sno[d];
+    for (int q = 0; q < CMX_MP1M_JAC_NOUT && tendencies; ++q) outs[nouts++] = tendencies[q];
+    outs[nouts++] = precip_rai;
+    outs[nouts++] = precip_sno;
+    const ColumnDirs dirs{ndir, d_mp};
+    const bool points = n_col > 0;
+    return column_entry_status(n_col, n_lev, mp1m_column_jac_flags_status(flags), points ? inv_dz : nullptr, points ? in : nullptr, &dirs, nullptr, 0, outs, nouts, false);
+}
+// grad and workspace are required
+template <typename FT>
+inline int32_t mp1m_column_param_vjp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *cotangents,
+                                            const FT *cot_precip_rai, const FT *cot_precip_sno, int32_t ndir, const void *d_mp, double *grad, double *workspace,
+                                            FT *const *tendencies, FT *precip_rai, FT *precip_sno) {
+    const void *given[CMX_MP1M_JAC_NOUT + 2];
+    void *outs[CMX_MP1M_JAC_NOUT + 4];
+    for (int q = 0; q < CMX_MP1M_JAC_NOUT; ++q) {
+        given[q] = cotangents ? cotangents[q] : nullptr;
+        outs[q] = tendencies ? tendencies[q] : nullptr;
+    }
+    given[CMX_MP1M_JAC_NOUT] = cot_precip_rai;
+    given[CMX_MP1M_JAC_NOUT + 1] = cot_precip_sno;
+    outs[CMX_MP1M_JAC_NOUT] = precip_rai;
+    outs[CMX_MP1M_JAC_NOUT + 1] = precip_sno;
+    outs[CMX_MP1M_JAC_NOUT + 2] = grad;
+    outs[CMX_MP1M_JAC_NOUT + 3] = workspace;
+    const ColumnDirs dirs{ndir, d_mp};
+    const bool points = n_col > 0;
+    return column_entry_status(n_col, n_lev, mp1m_column_jac_flags_status(flags), points ? inv_dz : nullptr, points ? in : nullptr, &dirs, given, CMX_MP1M_JAC_NOUT + 2,
+                               outs, CMX_MP1M_JAC_NOUT + 4, true);
+}
 
+// ---- one evaluation ---------------------------------------------------------------------------------------------------------------------------------
+// What a point keeps between its evaluation and its stores: Col1mJvpPoint with KP tangents, the struct that the halo shell shares between the schemes
+template <typename FT, int KP> using Col1mParamPoint = ColumnPoint<FT, KP>;
+
+// column1m_jvp_eval with the KP tangents of the constants.  The NaN rule is the primal's: a NaN in a state input → every tendency of the point, value and
+// tangents, BEFORE the own flux is subtracted; a NaN in ρ or q_s → the flux of species s, value and tangents.
 template <typename S, typename FT, int KP, typename CA>
-__device__ __forceinline__ void column1m_param_eval(const CA &a0, const FT (&x)[S::NWRT + 1], FT inv_dz, Col1mParamPoint<FT, KP> &p) {
+__device__ __forceinline__ void column1m_param_eval(const CA &a0, const FT (&x)[S::NWRT + 1], FT inv_dz, ColumnPoint<FT, KP> &p) {
     using M = Math<FT>;
     const bool poison = S::poison(x);
     Dual<FT, KP> o[S::NOUT], F[4];
@@ -236,7 +273,7 @@ inline bool make_col1m_param_jvp_args(Col1mParamJvpArgs<FT, KP> &a, const FT *co
 // The inflow through the upper face — the fluxes (upv, upd) the cell above sends down; nothing enters through the model top: a zero flux, multiplied out as in
 // the primal — and the stores of point i of column `col` (column1m_jvp_store with KP tangents).
 template <typename S, typename FT, int KP>
-__device__ __forceinline__ void column1m_param_jvp_store(const Col1mParamJvpArgs<FT, KP> &a, const Col1mParamPoint<FT, KP> &p, const FT (&upv)[4], const FT (&upd)[KP][4],
+__device__ __forceinline__ void column1m_param_jvp_store(const Col1mParamJvpArgs<FT, KP> &a, const ColumnPoint<FT, KP> &p, const FT (&upv)[4], const FT (&upd)[KP][4],
                                                          bool top, bool surface, int64_t i, int64_t col) {
     using M = Math<FT>;
     for_each_slot<S::NOUT>([&](auto sc) {
@@ -313,30 +350,11 @@ __device__ __forceinline__ void column1m_param_vjp_point(const CA &a0, const Col
                                                          double (&acc)[KP]) {
     using M = Math<FT>;
     using products_detail::ld;
-    const bool top = lev == a.n_lev - 1, surface = lev == 0;
+    const bool top = lev == a.n_lev - 1;
     const FT gk = S::g_of(x[0], a.inv_dz[lev]);
     FT lam[4] = {FT(0), FT(0), FT(0), FT(0)};
     int gnan = 0;
-    {
-        const FT gm = surface ? FT(0) : S::g_of(ld(a.in[0], i - 1), a.inv_dz[lev - 1]);
-        for_each_slot<4>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            const FT *const cot = a.cot[s];
-            FT l = FT(0);
-            if (cot) {
-                l = -gk * ld(cot, i);
-                if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
-            }
-            if constexpr (s >= 2) {
-                if (surface && a.cot_precip[s - 2]) {
-                    const FT pbar = ld(a.cot_precip[s - 2], col);
-                    gnan |= (int)(pbar != pbar);
-                    l = l + pbar;
-                }
-            }
-            lam[s] = l;
-        });
-    }
+    column1m_lambda<S, FT>(a, x, gk, i, col, lev, lam, gnan);
     const bool poison = S::poison(x);
     Dual<FT, KP> o[S::NOUT], F[4];
     S::template eval<FT, KP>(a0, x, o, F);
@@ -350,8 +368,8 @@ __device__ __forceinline__ void column1m_param_vjp_point(const CA &a0, const Col
     }
     const bool bad = (bool)((int)poison | cnan);      // a NaN cotangent of the point poisons its tendencies and sums too
     if (a.primal) {
-        // the primal entry's operations: t through the NaN rule, A = fma(−F, g, t), the inflow from the flux-only evaluation of the raw point above (its
-        // tangents are dead)
+        // the primal entry's operations: t through the NaN rule, A = fma(−F, g, t), the inflow from the flux values of the raw point above, from the
+        // constants that hold duals (its tangents are dead)
         FT up[4] = {FT(0), FT(0), FT(0), FT(0)};
         if (!top) {
             FT xu[S::NWRT + 1];
@@ -370,7 +388,7 @@ __device__ __forceinline__ void column1m_param_vjp_point(const CA &a0, const Col
             const FT A = M::fma(-Fv, gk, S::out(o[s].v, bad));
             if (a.tend[s]) a.tend[s][i] = M::fma(top ? FT(0) : up[s], gk, A);
             if constexpr (s >= 2) {
-                if (surface && a.precip[s - 2]) a.precip[s - 2][col] = Fv;
+                if (lev == 0 && a.precip[s - 2]) a.precip[s - 2][col] = Fv;
             }
         });
     }

@@ -16,6 +16,7 @@
 #include <type_traits>
 
 #include "../../include/cmx.h"
+#include "cmx_column_products.hpp"
 #include "cmx_dispatch.hpp"
 #include "cmx_jacobian.hpp"
 #include "cmx_sb2006.hpp"
@@ -92,6 +93,13 @@ template <bool LIMITED, int VEL, bool CLOUD, bool INTPOW> struct SbColJac {
     }
 };
 
+// The constants of the column scheme as ONE by-value kernel argument, the first (cmx_column_products.hpp): `c` comes first, where front_consts reads it.
+// T: FT, or Dual<FT, KP> for the parameter derivatives (cmx_sb2006_column_param.hpp).
+template <typename T> struct SbColConsts {
+    SbConsts<T> c;
+    CloudVelConsts<T> cv;
+};
+
 // The statuses of the primal entry's flag checks: no unknown bit, exactly one rain fall-speed scheme
 inline int32_t sb2006_column_flags_status(uint32_t flags) {
     if (flags & ~(uint32_t)(CMX_SB2006_LIMITED | CMX_VEL_SB2006 | CMX_VEL_CHEN2022)) return CMX_ERR_BAD_ARG;
@@ -157,6 +165,22 @@ template <typename FT> struct ColJvpPoint {
     FT Fv[4], Fd[4];
     FT g;
 };
+
+// The statuses of the J v entry after the NULL checks of the parameter structs: the ladder (cmx_column_products.hpp) with the entry's columns
+template <typename FT>
+inline int32_t sb2006_column_jvp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *tangents, FT *const *jvp,
+                                        FT *jvp_precip, FT *const *tendencies, FT *precip) {
+    const void *given[CMX_SB2006_JAC_NWRT];
+    void *outs[2 * CMX_SB2006_JAC_NOUT + 2];
+    for (int j = 0; j < CMX_SB2006_JAC_NWRT; ++j) given[j] = tangents ? tangents[j] : nullptr;
+    for (int q = 0; q < CMX_SB2006_JAC_NOUT; ++q) {
+        outs[q] = jvp ? jvp[q] : nullptr;
+        outs[CMX_SB2006_JAC_NOUT + q] = tendencies ? tendencies[q] : nullptr;
+    }
+    outs[2 * CMX_SB2006_JAC_NOUT] = jvp_precip;
+    outs[2 * CMX_SB2006_JAC_NOUT + 1] = precip;
+    return column_entry_status(n_col, n_lev, sb2006_column_flags_status(flags), inv_dz, in, nullptr, given, CMX_SB2006_JAC_NWRT, outs, 2 * CMX_SB2006_JAC_NOUT + 2, false);
+}
 
 // One evaluation of the scheme on Dual<FT, 1> seeded with the caller's tangent t (0 where the column is NULL), at the level whose 1/Δz is inv_dz.  The NaN
 // rule is applied here: a NaN in a state input or in a given tangent of the point → every A of the point; a NaN in an input of the fluxes → the fluxes, value
@@ -248,6 +272,23 @@ template <typename FT, int K> struct ColVjpArgs {
     int32_t primal;                   // tend or precip requested
 };
 
+// The statuses of the Jᵀḡ entry after the NULL checks of the parameter structs: the ladder (cmx_column_products.hpp) with the entry's columns
+template <typename FT>
+inline int32_t sb2006_column_vjp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *cotangents,
+                                        const FT *cot_precip, FT *const *grad, FT *const *tendencies, FT *precip) {
+    const void *given[CMX_SB2006_JAC_NOUT + 1];
+    void *outs[CMX_SB2006_JAC_NOUT + CMX_SB2006_JAC_NWRT + 1];
+    for (int q = 0; q < CMX_SB2006_JAC_NOUT; ++q) {
+        given[q] = cotangents ? cotangents[q] : nullptr;
+        outs[q] = tendencies ? tendencies[q] : nullptr;
+    }
+    given[CMX_SB2006_JAC_NOUT] = cot_precip;
+    for (int j = 0; j < CMX_SB2006_JAC_NWRT; ++j) outs[CMX_SB2006_JAC_NOUT + j] = grad ? grad[j] : nullptr;
+    outs[CMX_SB2006_JAC_NOUT + CMX_SB2006_JAC_NWRT] = precip;
+    return column_entry_status(n_col, n_lev, sb2006_column_flags_status(flags), inv_dz, in, nullptr, given, CMX_SB2006_JAC_NOUT + 1, outs,
+                               CMX_SB2006_JAC_NOUT + CMX_SB2006_JAC_NWRT + 1, false);
+}
+
 // An input is wanted if its gradient is not NULL.  False if the call has no output at all.
 template <typename FT, int K>
 inline bool make_col_vjp_args(ColVjpArgs<FT, K> &a, const FT *const (&in)[CMX_SB2006_JAC_NWRT + 1], const FT *inv_dz, int64_t n, int32_t n_lev,
@@ -280,6 +321,56 @@ template <typename S, typename FT, int K> inline void set_col_vjp_terms(ColVjpAr
     }
 }
 
+// λ of point i = col·n_lev + lev, shared by Jᵀḡ and the parameter gradient (`a`: ColVjpArgs or ColParamVjpArgs): from g_k, g_{k−1}, the cotangents of the
+// levels k and k−1, read raw, and p̄.  gnan: p̄ is a NaN.
+template <typename S, typename FT, typename A>
+__device__ __forceinline__ void column_lambda(const A &a, const FT (&x)[S::NWRT + 1], FT inv_dz, int64_t i, int64_t col, int32_t lev, FT (&lam)[4], int &gnan) {
+    using M = Math<FT>;
+    using products_detail::ld;
+    const bool surface = lev == 0;
+    const FT gk = inv_dz * S::inv_rho(x[0]);
+    const FT gm = surface ? FT(0) : a.inv_dz[lev - 1] * S::inv_rho(ld(a.in[0], i - 1));
+    FT pbar = FT(0);
+    if (surface && a.cot_precip) pbar = ld(a.cot_precip, col);
+    gnan |= (int)(pbar != pbar);
+    for_each_slot<S::NFLUX>([&](auto sc) {
+        constexpr int s = decltype(sc)::value;
+        const FT *const cot = a.cot[S::flux_out(s)];
+        FT l = FT(0);
+        if (cot) {
+            l = -gk * ld(cot, i);
+            if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
+        }
+        if (s == 0 && surface && a.cot_precip) l = l + pbar;
+        lam[s] = l;
+    });
+}
+
+// The primal entry's operations on the value parts of one evaluation, and the stores of the requested primal outputs: A = fma(−F, g, sum), the NaN rule, the
+// inflow upv — the flux values of the raw point above (zeros at the top), which the caller gets from the constants it has.
+template <typename S, typename FT, typename A, typename D>
+__device__ __forceinline__ void column_primal_store(const A &a, const FT (&x)[S::NWRT + 1], const D (&o)[S::NOUT], const D (&F)[4], FT gk, const FT (&upv)[4], bool top,
+                                                    bool bad, int64_t i, int64_t col, int32_t lev) {
+    using M = Math<FT>;
+    FT y[S::NOUT];
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q) y[q] = o[q].v;
+    for_each_slot<S::NFLUX>([&](auto sc) {
+        constexpr int s = decltype(sc)::value, q = S::flux_out(s);
+        y[q] = M::fma(-F[s].v, gk, y[q]);
+    });
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q) y[q] = S::out(y[q], bad);
+    for_each_slot<S::NFLUX>([&](auto sc) {
+        constexpr int s = decltype(sc)::value, q = S::flux_out(s);
+        y[q] = top ? y[q] : M::fma(upv[s], gk, y[q]);
+    });
+#pragma unroll
+    for (int q = 0; q < S::NOUT; ++q)
+        if (a.tend[q]) a.tend[q][i] = y[q];
+    if (lev == 0 && a.precip) a.precip[col] = S::out(F[0].v, S::flux_poison(x));
+}
+
 // Every pass of point i = col·n_lev + lev.  Pointwise: the only neighbour data are ρ_{i−1} and the falling species' ḡ_{i−1}, raw from memory (and, if the
 // tendencies are requested, the state of point i+1 for the flux values it sends down).  λ is formed first, then the passes of vjp_point (cmx_jacobian.hpp) run:
 // unit seeds, the cotangents read after eval, the sum of a slot as ONE chain of fma seeded with −0 — the point sums with ḡ in output order, then the fluxes with
@@ -289,28 +380,11 @@ __device__ __forceinline__ void column_vjp_point(const C &c, const CloudVelConst
                                                  int32_t lev) {
     using M = Math<FT>;
     using products_detail::ld;
-    const bool top = lev == a.n_lev - 1, surface = lev == 0;
+    const bool top = lev == a.n_lev - 1;
     const FT inv_dz = a.inv_dz[lev];
     FT lam[4] = {FT(0), FT(0), FT(0), FT(0)};
     int gnan = 0;
-    {
-        const FT gk = inv_dz * S::inv_rho(x[0]);
-        const FT gm = surface ? FT(0) : a.inv_dz[lev - 1] * S::inv_rho(ld(a.in[0], i - 1));
-        FT pbar = FT(0);
-        if (surface && a.cot_precip) pbar = ld(a.cot_precip, col);
-        gnan |= (int)(pbar != pbar);
-#pragma unroll
-        for (int s = 0; s < S::NFLUX; ++s) {
-            const FT *const cot = a.cot[S::flux_out(s)];
-            FT l = FT(0);
-            if (cot) {
-                l = -gk * ld(cot, i);
-                if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
-            }
-            if (s == 0 && surface && a.cot_precip) l = l + pbar;
-            lam[s] = l;
-        }
-    }
+    column_lambda<S, FT>(a, x, inv_dz, i, col, lev, lam, gnan);
     const bool poison = S::poison(x);
     for (int pass = 0; pass < a.npass; ++pass) {
         Dual<FT, K> in[S::NWRT], o[S::NOUT], F[4];
@@ -332,29 +406,11 @@ __device__ __forceinline__ void column_vjp_point(const C &c, const CloudVelConst
         }
         const bool bad = (bool)((int)poison | cnan);      // a NaN cotangent of the point poisons its tendencies and gradients too
         if (pass == 0 && a.primal) {
-            // the primal entry's operations: A = fma(−F, g, sum), the inflow from the flux-only evaluation of the raw point above
+            // the inflow: the primal's flux-only evaluation of the raw point above
             SedFlux<FT> up{FT(0), FT(0), FT(0), FT(0)};
             if (!top) up = S::flux_values(c, cv, ld(a.in[0], i + 1), ld(a.in[3], i + 1), ld(a.in[4], i + 1), ld(a.in[5], i + 1), ld(a.in[6], i + 1));
             const FT upv[4] = {up.q_rai, up.n_rai, up.q_lcl, up.n_lcl};
-            FT y[S::NOUT];
-#pragma unroll
-            for (int q = 0; q < S::NOUT; ++q) y[q] = o[q].v;
-#pragma unroll
-            for (int s = 0; s < S::NFLUX; ++s) {
-                const int q = S::flux_out(s);
-                y[q] = M::fma(-F[s].v, gk, y[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < S::NOUT; ++q) y[q] = S::out(y[q], bad);
-#pragma unroll
-            for (int s = 0; s < S::NFLUX; ++s) {
-                const int q = S::flux_out(s);
-                y[q] = top ? y[q] : M::fma(upv[s], gk, y[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < S::NOUT; ++q)
-                if (a.tend[q]) a.tend[q][i] = y[q];
-            if (surface && a.precip) a.precip[col] = S::out(F[0].v, S::flux_poison(x));
+            column_primal_store<S, FT>(a, x, o, F, gk, upv, top, bad, i, col, lev);
         }
 #pragma unroll
         for (int k = 0; k < K; ++k) {

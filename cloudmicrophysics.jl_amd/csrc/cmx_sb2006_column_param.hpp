@@ -107,17 +107,47 @@ inline int32_t with_sb2006_column_param(const WR &wr, const TH &tps, const VL &v
                        flag(limited), one_of<VEL_SB, VEL_CHEN, VEL_CHEN_GEN>(velk), flag(cloud_vel != nullptr), flag(sb_integer_exponents(wr) && !exponents));
 }
 
-// ---- one evaluation ---------------------------------------------------------------------------------------------------------------------------------
-// What a point keeps between its evaluation and its stores (ColJvpPoint with KP tangents): A = sum − (own flux)·g, the fluxes it sends down, g.  The NaN
-// rule is the primal's: a NaN in a state input → every A of the point; a NaN in an input of the fluxes → the fluxes, value and tangents.
-template <typename FT, int KP> struct ColParamPoint {
-    FT Av[CMX_SB2006_JAC_NOUT], Ad[KP][CMX_SB2006_JAC_NOUT];
-    FT Fv[4], Fd[KP][4];
-    FT g;
-};
+// The statuses of the two entries after the NULL checks of the parameter structs and before with_sb2006_column_param: the ladder (cmx_column_products.hpp)
+// with the entry's columns.  The seven columns and inv_dz are compared with the outputs even without a point.
+template <typename FT>
+inline int32_t sb2006_column_param_jvp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, int32_t ndir, const void *d_wr,
+                                              FT *const *jvp, FT *const *jvp_precip, FT *const *tendencies, FT *precip) {
+    void *outs[CMX_PARAM_MAX_DIRS * (CMX_SB2006_JAC_NOUT + 1) + CMX_SB2006_JAC_NOUT + 1];
+    int nouts = 0;
+    const int nd = ndir < 0 ? 0 : (ndir > CMX_PARAM_MAX_DIRS ? CMX_PARAM_MAX_DIRS : ndir);
+    for (int q = 0; q < nd * CMX_SB2006_JAC_NOUT && jvp; ++q) outs[nouts++] = jvp[q];
+    for (int d = 0; d < nd && jvp_precip; ++d) outs[nouts++] = jvp_precip[d];
+    for (int q = 0; q < CMX_SB2006_JAC_NOUT && tendencies; ++q) outs[nouts++] = tendencies[q];
+    outs[nouts++] = precip;
+    const ColumnDirs dirs{ndir, d_wr};
+    return column_entry_status(n_col, n_lev, sb2006_column_flags_status(flags), inv_dz, in, &dirs, nullptr, 0, outs, nouts, false);
+}
+// grad and workspace are required
+template <typename FT>
+inline int32_t sb2006_column_param_vjp_status(uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *in, const FT *const *cotangents,
+                                              const FT *cot_precip, int32_t ndir, const void *d_wr, double *grad, double *workspace, FT *const *tendencies, FT *precip) {
+    const void *given[CMX_SB2006_JAC_NOUT + 1];
+    void *outs[CMX_SB2006_JAC_NOUT + 3];
+    for (int q = 0; q < CMX_SB2006_JAC_NOUT; ++q) {
+        given[q] = cotangents ? cotangents[q] : nullptr;
+        outs[q] = tendencies ? tendencies[q] : nullptr;
+    }
+    given[CMX_SB2006_JAC_NOUT] = cot_precip;
+    outs[CMX_SB2006_JAC_NOUT] = precip;
+    outs[CMX_SB2006_JAC_NOUT + 1] = grad;
+    outs[CMX_SB2006_JAC_NOUT + 2] = workspace;
+    const ColumnDirs dirs{ndir, d_wr};
+    return column_entry_status(n_col, n_lev, sb2006_column_flags_status(flags), inv_dz, in, &dirs, given, CMX_SB2006_JAC_NOUT + 1, outs, CMX_SB2006_JAC_NOUT + 3, true);
+}
 
+// ---- one evaluation ---------------------------------------------------------------------------------------------------------------------------------
+// What a point keeps between its evaluation and its stores: ColJvpPoint with KP tangents, the struct that the halo shell shares between the schemes
+template <typename FT, int KP> using ColParamPoint = ColumnPoint<FT, KP>;
+
+// column_jvp_eval with the KP tangents of the constants.  The NaN rule is the primal's: a NaN in a state input → every A of the point; a NaN in an input of
+// the fluxes → the fluxes, value and tangents.
 template <typename S, typename FT, int KP, typename CD, typename CVD>
-__device__ __forceinline__ void column_param_eval(const CD &cd, const CVD &cvd, const FT (&x)[S::NWRT + 1], FT inv_dz, ColParamPoint<FT, KP> &p) {
+__device__ __forceinline__ void column_param_eval(const CD &cd, const CVD &cvd, const FT (&x)[S::NWRT + 1], FT inv_dz, ColumnPoint<FT, KP> &p) {
     using M = Math<FT>;
     const bool poison = S::poison(x), fpoison = S::flux_poison(x);
     Dual<FT, KP> in[S::NWRT], o[S::NOUT], F[4];
@@ -185,7 +215,7 @@ inline bool make_column_param_jvp_args(ColParamJvpArgs<FT, KP> &a, const FT *con
 // The inflow through the upper face — the fluxes (upv, upd) the cell above sends down; nothing enters through the model top — and the stores of point i of
 // column `col` (column_jvp_store with KP tangents).
 template <typename S, typename FT, int KP>
-__device__ __forceinline__ void column_param_jvp_store(const ColParamJvpArgs<FT, KP> &a, const ColParamPoint<FT, KP> &p, const FT (&upv)[4], const FT (&upd)[KP][4],
+__device__ __forceinline__ void column_param_jvp_store(const ColParamJvpArgs<FT, KP> &a, const ColumnPoint<FT, KP> &p, const FT (&upv)[4], const FT (&upd)[KP][4],
                                                        bool top, bool surface, int64_t i, int64_t col) {
     using M = Math<FT>;
     FT yv[S::NOUT];
@@ -285,28 +315,11 @@ __device__ __forceinline__ void column_param_vjp_point(const CD &cd, const CVD &
                                                        int32_t lev, double (&acc)[KP]) {
     using M = Math<FT>;
     using products_detail::ld;
-    const bool top = lev == a.n_lev - 1, surface = lev == 0;
+    const bool top = lev == a.n_lev - 1;
     const FT inv_dz = a.inv_dz[lev];
     FT lam[4] = {FT(0), FT(0), FT(0), FT(0)};
     int gnan = 0;
-    {
-        const FT gk = inv_dz * S::inv_rho(x[0]);
-        const FT gm = surface ? FT(0) : a.inv_dz[lev - 1] * S::inv_rho(ld(a.in[0], i - 1));
-        FT pbar = FT(0);
-        if (surface && a.cot_precip) pbar = ld(a.cot_precip, col);
-        gnan |= (int)(pbar != pbar);
-        for_each_slot<S::NFLUX>([&](auto sc) {
-            constexpr int s = decltype(sc)::value;
-            const FT *const cot = a.cot[S::flux_out(s)];
-            FT l = FT(0);
-            if (cot) {
-                l = -gk * ld(cot, i);
-                if (!surface) l = M::fma(gm, ld(cot, i - 1), l);
-            }
-            if (s == 0 && surface && a.cot_precip) l = l + pbar;
-            lam[s] = l;
-        });
-    }
+    column_lambda<S, FT>(a, x, inv_dz, i, col, lev, lam, gnan);
     const bool poison = S::poison(x);
     Dual<FT, KP> in[S::NWRT], o[S::NOUT], F[4];
     FT gk;
@@ -323,27 +336,11 @@ __device__ __forceinline__ void column_param_vjp_point(const CD &cd, const CVD &
     }
     const bool bad = (bool)((int)poison | cnan);
     if (a.primal) {
-        // the primal entry's operations: A = fma(−F, g, sum), the inflow from the flux-only evaluation of the raw point above
+        // the inflow: the flux values of the raw point above, from the constants that hold duals
         FT upv[4] = {FT(0), FT(0), FT(0), FT(0)};
         if (!top)
             column_param_flux_values<S, FT, KP>(cd, cvd, ld(a.in[0], i + 1), ld(a.in[3], i + 1), ld(a.in[4], i + 1), ld(a.in[5], i + 1), ld(a.in[6], i + 1), upv);
-        FT y[S::NOUT];
-#pragma unroll
-        for (int q = 0; q < S::NOUT; ++q) y[q] = o[q].v;
-        for_each_slot<S::NFLUX>([&](auto sc) {
-            constexpr int s = decltype(sc)::value, q = S::flux_out(s);
-            y[q] = M::fma(-F[s].v, gk, y[q]);
-        });
-#pragma unroll
-        for (int q = 0; q < S::NOUT; ++q) y[q] = S::out(y[q], bad);
-        for_each_slot<S::NFLUX>([&](auto sc) {
-            constexpr int s = decltype(sc)::value, q = S::flux_out(s);
-            y[q] = top ? y[q] : M::fma(upv[s], gk, y[q]);
-        });
-#pragma unroll
-        for (int q = 0; q < S::NOUT; ++q)
-            if (a.tend[q]) a.tend[q][i] = y[q];
-        if (surface && a.precip) a.precip[col] = S::out(F[0].v, S::flux_poison(x));
+        column_primal_store<S, FT>(a, x, o, F, gk, upv, top, bad, i, col, lev);
     }
 #pragma unroll
     for (int k = 0; k < KP; ++k) {

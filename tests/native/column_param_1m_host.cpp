@@ -18,23 +18,11 @@ namespace {
 using namespace cmx;
 constexpr int NW = CMX_MP1M_JAC_NWRT, NO = CMX_MP1M_JAC_NOUT;
 
-// the statuses of the device entry, in its order, for what the mirror checks; then f(S)
-template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI, typename F>
-int32_t checked(const MP *mp, const TH *tps, const ST *st, const CH *cr, const CI *ci, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
-                int32_t ndir, const MP *d_mp, const TH *d_tps, const ST *d_st, const CH *d_cr, const CI *d_ci, bool gradient, F &&f) {
-    if (!mp || !tps || !st || !cr || !ci || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (const int32_t s = mp1m_column_jac_flags_status(flags)) return s;
-    if (n_col == 0 && !gradient) return CMX_OK;
-    if (n_col > 0) {
-        if (!inv_dz || !x) return CMX_ERR_BAD_ARG;
-        for (int j = 0; j < NW + 1; ++j)
-            if (!x[j]) return CMX_ERR_BAD_ARG;
-    }
-    return with_mp1m_column_param<FT>(*mp, *tps, *st, *cr, *ci, flags, ndir, d_mp, d_tps, d_st, d_cr, d_ci, f);
-}
-
 // what ran: bit 0 the default-options instantiation, bit 1 the general Γ of the Chen-2022 rain table
 template <typename S> constexpr int32_t kind_of() { return (S::flags == kDefaultFlags ? 1 : 0) | (S::general ? 2 : 0); }
+
+// Both functions return the statuses of the device entries — the parameter structs, the entry's status function (the ladder of column_entry_status with its
+// columns), then with_mp1m_column_param — or what ran.
 
 // J_θ δθ: the levels of a column from the top down.  kp: directions per evaluation (0: the device kernel's choice); the split into launches is the device
 // entry's.
@@ -42,7 +30,9 @@ template <typename FT, typename MP, typename TH, typename ST, typename CH, typen
 int32_t jvp(const MP *mp, const TH *tps, const ST *st, const CH *cr, const CI *ci, uint32_t flags, int kp, int64_t n_col, int32_t n_lev, const FT *inv_dz,
             const FT *const *x, int32_t ndir, const MP *d_mp, const TH *d_tps, const ST *d_st, const CH *d_cr, const CI *d_ci, FT *const *jv, FT *const *jpr,
             FT *const *jps, FT *const *tend, FT *pr, FT *ps) {
-    return checked<FT>(mp, tps, st, cr, ci, flags, n_col, n_lev, inv_dz, x, ndir, d_mp, d_tps, d_st, d_cr, d_ci, false, [&](auto S) -> int32_t {
+    if (!mp || !tps || !st || !cr || !ci) return CMX_ERR_BAD_ARG;
+    if (const int32_t s = mp1m_column_param_jvp_status(flags, n_col, n_lev, inv_dz, x, ndir, d_mp, jv, jpr, jps, tend, pr, ps); s != kColumnEntryRun) return s;
+    return with_mp1m_column_param<FT>(*mp, *tps, *st, *cr, *ci, flags, ndir, d_mp, d_tps, d_st, d_cr, d_ci, [&](auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int KW = decltype(KT)::value;
@@ -80,8 +70,11 @@ template <typename FT, typename MP, typename TH, typename ST, typename CH, typen
 int32_t vjp(const MP *mp, const TH *tps, const ST *st, const CH *cr, const CI *ci, uint32_t flags, int kp, int64_t n_col, int32_t n_lev, const FT *inv_dz,
             const FT *const *x, const FT *const *cot, const FT *cpr, const FT *cps, int32_t ndir, const MP *d_mp, const TH *d_tps, const ST *d_st, const CH *d_cr,
             const CI *d_ci, double *grad, FT *const *tend, FT *pr, FT *ps) {
-    if (!grad) return CMX_ERR_BAD_ARG;
-    return checked<FT>(mp, tps, st, cr, ci, flags, n_col, n_lev, inv_dz, x, ndir, d_mp, d_tps, d_st, d_cr, d_ci, true, [&](auto S) -> int32_t {
+    if (!mp || !tps || !st || !cr || !ci) return CMX_ERR_BAD_ARG;
+    // (the mirror reduces in place and has no workspace: grad stands in for it)
+    if (const int32_t s = mp1m_column_param_vjp_status(flags, n_col, n_lev, inv_dz, x, cot, cpr, cps, ndir, d_mp, grad, grad, tend, pr, ps); s != kColumnEntryRun)
+        return s;
+    return with_mp1m_column_param<FT>(*mp, *tps, *st, *cr, *ci, flags, ndir, d_mp, d_tps, d_st, d_cr, d_ci, [&](auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int KW = decltype(KT)::value;

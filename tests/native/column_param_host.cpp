@@ -18,27 +18,17 @@ namespace {
 using namespace cmx;
 constexpr int NW = CMX_SB2006_JAC_NWRT, NO = CMX_SB2006_JAC_NOUT;
 
-// the statuses of the device entry, in its order, for what the mirror checks; then f(S)
-template <typename FT, typename WR, typename TH, typename VL, typename ST, typename F>
-int32_t checked(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
-                int32_t ndir, const WR *d_wr, const TH *d_tps, const VL *d_vel, const ST *d_cv, bool gradient, F &&f) {
-    if (!wr || !tps || !vel || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (const int32_t st = sb2006_column_flags_status(flags)) return st;
-    if (n_col == 0 && !gradient) return CMX_OK;
-    if (n_col > 0) {
-        if (!inv_dz || !x) return CMX_ERR_BAD_ARG;
-        for (int j = 0; j < NW + 1; ++j)
-            if (!x[j]) return CMX_ERR_BAD_ARG;
-    }
-    return with_sb2006_column_param<FT>(*wr, *tps, *vel, cloud_vel, flags, ndir, d_wr, d_tps, d_vel, d_cv, f);
-}
+// Both functions return the statuses of the device entries — the parameter structs, the entry's status function (the ladder of column_entry_status with its
+// columns), then with_sb2006_column_param — or what ran.
 
 // J_θ δθ: the levels of a column from the top down.  kp: directions per evaluation (0: the device kernel's choice); the split into launches is the device
 // entry's.  Returns the velocity kind that ran.
 template <typename FT, typename WR, typename TH, typename VL, typename ST>
 int32_t jvp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int kp, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
             int32_t ndir, const WR *d_wr, const TH *d_tps, const VL *d_vel, const ST *d_cv, FT *const *jv, FT *const *jv_precip, FT *const *tend, FT *precip) {
-    return checked<FT>(wr, tps, vel, cloud_vel, flags, n_col, n_lev, inv_dz, x, ndir, d_wr, d_tps, d_vel, d_cv, false, [&](auto S) -> int32_t {
+    if (!wr || !tps || !vel) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = sb2006_column_param_jvp_status(flags, n_col, n_lev, inv_dz, x, ndir, d_wr, jv, jv_precip, tend, precip); st != kColumnEntryRun) return st;
+    return with_sb2006_column_param<FT>(*wr, *tps, *vel, cloud_vel, flags, ndir, d_wr, d_tps, d_vel, d_cv, [&](auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int KW = decltype(KT)::value;
@@ -77,8 +67,11 @@ template <typename FT, typename WR, typename TH, typename VL, typename ST>
 int32_t vjp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int kp, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
             const FT *const *cot, const FT *cot_precip, int32_t ndir, const WR *d_wr, const TH *d_tps, const VL *d_vel, const ST *d_cv, double *grad, FT *const *tend,
             FT *precip) {
-    if (!grad) return CMX_ERR_BAD_ARG;
-    return checked<FT>(wr, tps, vel, cloud_vel, flags, n_col, n_lev, inv_dz, x, ndir, d_wr, d_tps, d_vel, d_cv, true, [&](auto S) -> int32_t {
+    if (!wr || !tps || !vel) return CMX_ERR_BAD_ARG;
+    // (the mirror reduces in place and has no workspace: grad stands in for it)
+    if (const int32_t st = sb2006_column_param_vjp_status(flags, n_col, n_lev, inv_dz, x, cot, cot_precip, ndir, d_wr, grad, grad, tend, precip); st != kColumnEntryRun)
+        return st;
+    return with_sb2006_column_param<FT>(*wr, *tps, *vel, cloud_vel, flags, ndir, d_wr, d_tps, d_vel, d_cv, [&](auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int KW = decltype(KT)::value;

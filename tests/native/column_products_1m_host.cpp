@@ -21,28 +21,20 @@ constexpr int NW = CMX_MP1M_JAC_NWRT, NO = CMX_MP1M_JAC_NOUT;
 // what ran: bit 0 the default-options instantiation, bit 1 the general Γ of the Chen-2022 rain table
 template <typename S> constexpr int32_t kind() { return (S::flags != kRuntimeFlags ? 1 : 0) | (S::general ? 2 : 0); }
 
-// the statuses of the device entry, in its order, for what the mirror checks; then f(a, S)
-template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI, typename F>
-int32_t checked(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz,
-                const FT *const *x, F &&f) {
-    if (!mp || !tps || !stokes || !chen_rain || !chen_ice || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (const int32_t st = mp1m_column_jac_flags_status(flags)) return st;
-    if (n_col == 0) return CMX_OK;
-    if (!inv_dz || !x) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < NW + 1; ++j)
-        if (!x[j]) return CMX_ERR_BAD_ARG;
-    return with_mp1m_column_jac<FT>(*mp, *tps, *stokes, *chen_rain, *chen_ice, flags, f);
-}
+// Every function returns the statuses of the device entries — the parameter structs, the entry's status function (the ladder of column_entry_status with its
+// columns), then with_mp1m_column_jac — or what ran.
 
 // J v: the levels of a column from the top down, so that the fluxes of the cell above are at hand
 template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
 int32_t jvp(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz,
             const FT *const *x, const FT *const *tan, FT *const *jv, FT *jv_pr, FT *jv_ps, FT *const *tend, FT *pr, FT *ps) {
-    return checked<FT>(mp, tps, stokes, chen_rain, chen_ice, flags, n_col, n_lev, inv_dz, x, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
+    if (!mp || !tps || !stokes || !chen_rain || !chen_ice) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = mp1m_column_jvp_status(flags, n_col, n_lev, inv_dz, x, tan, jv, jv_pr, jv_ps, tend, pr, ps); st != kColumnEntryRun) return st;
+    return with_mp1m_column_jac<FT>(*mp, *tps, *stokes, *chen_rain, *chen_ice, flags, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
         using SC = decltype(S);
         const FT *const in[NW + 1] = {x[0], x[1], x[2], x[3], x[4], x[5], x[6]};
         Col1mJvpArgs<FT> a;
-        if (!make_col1m_jvp_args(a, in, inv_dz, n_col * n_lev, n_lev, tan, jv, jv_pr, jv_ps, tend, pr, ps)) return CMX_ERR_BAD_ARG;
+        make_col1m_jvp_args(a, in, inv_dz, n_col * n_lev, n_lev, tan, jv, jv_pr, jv_ps, tend, pr, ps);
         for (int64_t col = 0; col < n_col; ++col) {
             FT upv[4] = {}, upd[4] = {};
             for (int32_t lev = n_lev - 1; lev >= 0; --lev) {
@@ -64,13 +56,15 @@ int32_t jvp(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, 
 template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
 int32_t vjp(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, int k, int64_t n_col, int32_t n_lev, const FT *inv_dz,
             const FT *const *x, const FT *const *cot, const FT *cot_pr, const FT *cot_ps, FT *const *grad, FT *const *tend, FT *pr, FT *ps) {
-    return checked<FT>(mp, tps, stokes, chen_rain, chen_ice, flags, n_col, n_lev, inv_dz, x, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
+    if (!mp || !tps || !stokes || !chen_rain || !chen_ice) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = mp1m_column_vjp_status(flags, n_col, n_lev, inv_dz, x, cot, cot_pr, cot_ps, grad, tend, pr, ps); st != kColumnEntryRun) return st;
+    return with_mp1m_column_jac<FT>(*mp, *tps, *stokes, *chen_rain, *chen_ice, flags, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int K = decltype(KT)::value;
             const FT *const in[NW + 1] = {x[0], x[1], x[2], x[3], x[4], x[5], x[6]};
             Col1mVjpArgs<FT, K> a;
-            if (!make_col1m_vjp_args(a, in, inv_dz, n_col * n_lev, n_lev, cot, cot_pr, cot_ps, grad, tend, pr, ps)) return CMX_ERR_BAD_ARG;
+            make_col1m_vjp_args(a, in, inv_dz, n_col * n_lev, n_lev, cot, cot_pr, cot_ps, grad, tend, pr, ps);
             for (int64_t col = 0; col < n_col; ++col)
                 for (int32_t lev = 0; lev < n_lev; ++lev) {
                     const int64_t i = col * n_lev + lev;
@@ -87,7 +81,9 @@ int32_t vjp(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, 
 template <typename FT, typename MP, typename TH, typename ST, typename CH, typename CI>
 int32_t plain(const MP *mp, const TH *tps, const ST *stokes, const CH *chen_rain, const CI *chen_ice, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz,
               const FT *const *x, FT *const *y, FT *pr, FT *ps) {
-    return checked<FT>(mp, tps, stokes, chen_rain, chen_ice, flags, n_col, n_lev, inv_dz, x, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
+    if (!mp || !tps || !stokes || !chen_rain || !chen_ice) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = mp1m_column_jvp_status<FT>(flags, n_col, n_lev, inv_dz, x, nullptr, nullptr, nullptr, nullptr, y, pr, ps); st != kColumnEntryRun) return st;
+    return with_mp1m_column_jac<FT>(*mp, *tps, *stokes, *chen_rain, *chen_ice, flags, [&](const Mp1mColJacConsts<FT> &c, auto S) -> int32_t {
         using SC = decltype(S);
         using M = Math<FT>;
         for (int64_t col = 0; col < n_col; ++col) {

@@ -17,28 +17,21 @@ namespace {
 using namespace cmx;
 constexpr int NW = CMX_SB2006_JAC_NWRT, NO = CMX_SB2006_JAC_NOUT;
 
-// the statuses of the device entry, in its order, for what the mirror checks; then f(c, cv, S)
-template <typename FT, typename WR, typename TH, typename VL, typename ST, typename F>
-int32_t checked(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x, F &&f) {
-    if (!wr || !tps || !vel || n_col < 0 || n_lev < 1) return CMX_ERR_BAD_ARG;
-    if (const int32_t st = sb2006_column_flags_status(flags)) return st;
-    if (n_col == 0) return CMX_OK;
-    if (!inv_dz || !x) return CMX_ERR_BAD_ARG;
-    for (int j = 0; j < NW + 1; ++j)
-        if (!x[j]) return CMX_ERR_BAD_ARG;
-    return with_sb2006_column_jac<FT>(*wr, *tps, *vel, cloud_vel, flags, f);
-}
+// Every function returns the statuses of the device entries — the parameter structs, the entry's status function (the ladder of column_entry_status with its
+// columns), then with_sb2006_column_jac — or what ran.
 
 // J v: the levels of a column from the top down, so that the fluxes of the cell above are at hand.  Returns the velocity kind that ran.
 template <typename FT, typename WR, typename TH, typename VL, typename ST>
 int32_t jvp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
             const FT *const *tan, FT *const *jv, FT *jv_precip, FT *const *tend, FT *precip) {
-    return checked<FT>(wr, tps, vel, cloud_vel, flags, n_col, n_lev, inv_dz, x, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
+    if (!wr || !tps || !vel) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = sb2006_column_jvp_status(flags, n_col, n_lev, inv_dz, x, tan, jv, jv_precip, tend, precip); st != kColumnEntryRun) return st;
+    return with_sb2006_column_jac<FT>(*wr, *tps, *vel, cloud_vel, flags, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
         using SC = decltype(S);
         const FT *in[NW + 1];
         for (int j = 0; j < NW + 1; ++j) in[j] = x[j];
         ColJvpArgs<FT> a;
-        if (!make_col_jvp_args(a, in, inv_dz, n_col * n_lev, n_lev, tan, jv, jv_precip, tend, precip)) return CMX_ERR_BAD_ARG;
+        make_col_jvp_args(a, in, inv_dz, n_col * n_lev, n_lev, tan, jv, jv_precip, tend, precip);
         for (int64_t col = 0; col < n_col; ++col) {
             FT upv[4] = {}, upd[4] = {};
             for (int32_t lev = n_lev - 1; lev >= 0; --lev) {
@@ -60,14 +53,16 @@ int32_t jvp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uin
 template <typename FT, typename WR, typename TH, typename VL, typename ST>
 int32_t vjp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int k, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
             const FT *const *cot, const FT *cot_precip, FT *const *grad, FT *const *tend, FT *precip) {
-    return checked<FT>(wr, tps, vel, cloud_vel, flags, n_col, n_lev, inv_dz, x, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
+    if (!wr || !tps || !vel) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = sb2006_column_vjp_status(flags, n_col, n_lev, inv_dz, x, cot, cot_precip, grad, tend, precip); st != kColumnEntryRun) return st;
+    return with_sb2006_column_jac<FT>(*wr, *tps, *vel, cloud_vel, flags, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
         using SC = decltype(S);
         return dispatch_or((int32_t)CMX_ERR_BAD_ARG, [&](auto KT) -> int32_t {
             constexpr int K = decltype(KT)::value;
             const FT *in[NW + 1];
             for (int j = 0; j < NW + 1; ++j) in[j] = x[j];
             ColVjpArgs<FT, K> a;
-            if (!make_col_vjp_args(a, in, inv_dz, n_col * n_lev, n_lev, cot, cot_precip, grad, tend, precip)) return CMX_ERR_BAD_ARG;
+            make_col_vjp_args(a, in, inv_dz, n_col * n_lev, n_lev, cot, cot_precip, grad, tend, precip);
             set_col_vjp_terms<SC>(a);
             for (int64_t col = 0; col < n_col; ++col)
                 for (int32_t lev = 0; lev < n_lev; ++lev) {
@@ -85,7 +80,9 @@ int32_t vjp(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uin
 template <typename FT, typename WR, typename TH, typename VL, typename ST>
 int32_t plain(const WR *wr, const TH *tps, const VL *vel, const ST *cloud_vel, uint32_t flags, int64_t n_col, int32_t n_lev, const FT *inv_dz, const FT *const *x,
               FT *const *y, FT *precip) {
-    return checked<FT>(wr, tps, vel, cloud_vel, flags, n_col, n_lev, inv_dz, x, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
+    if (!wr || !tps || !vel) return CMX_ERR_BAD_ARG;
+    if (const int32_t st = sb2006_column_jvp_status<FT>(flags, n_col, n_lev, inv_dz, x, nullptr, nullptr, nullptr, y, precip); st != kColumnEntryRun) return st;
+    return with_sb2006_column_jac<FT>(*wr, *tps, *vel, cloud_vel, flags, [&](const SbConsts<FT> &c, const CloudVelConsts<FT> &cv, auto S) -> int32_t {
         using SC = decltype(S);
         using M = Math<FT>;
         for (int64_t col = 0; col < n_col; ++col) {

@@ -167,6 +167,21 @@ def test_a_column_does_not_depend_on_ndir_or_on_the_split(dev, oracle, ft):
 
 
 @pytest.mark.parametrize("ft", FTS)
+def test_results_do_not_depend_on_tile_boundaries(dev, oracle, ft):
+    """The same columns at other places of the launch — a call on the columns [c0, c1) of the set moves every tile boundary of the halo kernel, which the
+    parameter entry shares with the state products: the same bits.  n7: 7 levels, so a 255-point tile boundary falls inside a column, and 120 columns span
+    several tiles."""
+    s = Setup(ft, KC.reference(MAIN_CASE, "cold", "n7"), dev)
+    full = s.jvp(with_tendencies=True)
+    for c0, c1 in ((1, 120), (5, 77), (36, 38), (0, 37)):
+        cut = lambda t: t[..., c0:c1, :].contiguous()  # noqa: E731
+        r = s.jvp(cols=[cut(c) for c in s.cols], with_tendencies=True)
+        assert _eq(r.jvp, cut(full.jvp)), (c0, c1)
+        assert _eq(r.jvp_precip_rai, full.jvp_precip_rai[..., c0:c1]) and _eq(r.jvp_precip_sno, full.jvp_precip_sno[..., c0:c1]), (c0, c1)
+        assert _eq(r.tendencies, cut(full.tendencies)) and _eq(r.precip_rai, full.precip_rai[c0:c1]) and _eq(r.precip_sno, full.precip_sno[c0:c1]), (c0, c1)
+
+
+@pytest.mark.parametrize("ft", FTS)
 def test_without_sedimentation_the_derivatives_are_the_pointwise_ones(dev, oracle, ft):
     """inv_dz ≡ 0, directions on mp and tps only: the four jvp rows equal cmx_mp1m_param_jvp_* under == wherever finite (here: everywhere — the flux tangents
     of these columns are finite, and the two fma per species add ∓0)."""
