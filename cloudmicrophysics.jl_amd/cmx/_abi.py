@@ -174,6 +174,21 @@ CMX_IMPLICIT_AVERAGE_MAX_NSUB = 64
 CMX_PARAM_MAX_DIRS = 16
 CMX_PARAM_VJP_PARTIALS = 1024
 
+# parameter ensembles (include/cmx.h §29): cmx_<scheme>_ensemble_pack_* fold arrays of parameter structs into a host table and this descriptor; the
+# <single entry>_ensemble_* entries take (desc, device table, n_members, ens_flags) in front of the single entry's array arguments
+CMX_ENSEMBLE_SHARED_STATE = 1 << 0
+CMX_ENSEMBLE_MAGIC = 0x434D5845
+CMX_ENSEMBLE_SCHEME_SB2006 = 1
+CMX_ENSEMBLE_SCHEME_MP1M = 2
+CMX_ENSEMBLE_MAX_MEMBERS = 65535
+
+
+class EnsembleDesc(C.Structure):
+    """cmx_ensemble_desc"""
+    _fields_ = [("magic", C.c_uint32), ("scheme", C.c_uint32), ("float_type", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_int32),
+                ("stride", C.c_uint32), ("integer_exponents", C.c_uint32), ("vel_kind", C.c_uint32), ("cloud_vel", C.c_uint32),
+                ("runtime_flags", C.c_uint32), ("sedimentation", C.c_uint32), ("general_gamma", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
 
 def _struct(name, fields):
     return type(name, (C.Structure,), {"_fields_": fields})

@@ -302,6 +302,32 @@ def _declare(lib):
         f = getattr(lib, f"cmx_column_sums_{s}")
         f.restype = i32
         f.argtypes = [i32, C.POINTER(vp), i64, vp, vp, vp]
+        # parameter ensembles (include/cmx.h §29): pack (arrays of parameter structs, flags, n_members, host table, table_bytes, desc), then the ensemble
+        # entries: (desc, device table, n_members, ens_flags) in front of the single entry's array arguments
+        desc = C.POINTER(_abi.EnsembleDesc)
+        for scheme in ("sb2006", "mp1m"):
+            f = getattr(lib, f"cmx_{scheme}_ensemble_table_stride_{s}")
+            f.restype = i32
+            f.argtypes = []
+        f = getattr(lib, f"cmx_sb2006_ensemble_pack_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.warm_rain_2m), C.POINTER(fam.thermo), C.POINTER(fam.rain_vel), C.POINTER(fam.stokes_vel), u32, i32, vp, i64, desc]
+        f = getattr(lib, f"cmx_mp1m_ensemble_pack_{s}")
+        f.restype = i32
+        f.argtypes = [C.POINTER(fam.microphysics_1m), C.POINTER(fam.thermo), C.POINTER(fam.stokes_vel), C.POINTER(fam.chen2022_rain_vel),
+                      C.POINTER(fam.chen2022_ice_vel), u32, i32, vp, i64, desc]
+        f = getattr(lib, f"cmx_sb2006_warm_rain_tendencies_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, i64] + [vp] * 13 + [vp]
+        f = getattr(lib, f"cmx_mp1m_tendencies_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, i64] + [vp] * 11 + [vp]
+        f = getattr(lib, f"cmx_sb2006_column_tendencies_sedimentation_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, i64, i32] + [vp] * 13 + [vp]
+        f = getattr(lib, f"cmx_mp1m_column_tendencies_sedimentation_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, fam.ft, fam.ft, i32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
 
 
 def lib():

@@ -531,6 +531,15 @@ inline int32_t check_flags_1m(uint32_t flags) {
     return CMX_OK;
 }
 
+// Lanes per workgroup of the tendencies kernel, per float type (same-box A/Bs, round 4, ms per 1e8 points: Float32 256 lanes 0.804, 128 lanes
+// 0.758 — and on another box 128 lanes 0.723, 64 lanes 0.714; Float64 256 lanes 2.375, 128 lanes 2.396 — profiles/r04_ab_sessions.txt, sessions
+// 13-15): short-lived one-wave workgroups free their slots as soon as their own wave has stored.  -DCMX_1M_BLOCK=n forces one size for both.
+#ifdef CMX_1M_BLOCK
+template <typename FT> constexpr int kBlock1m = CMX_1M_BLOCK;
+#else
+template <typename FT> constexpr int kBlock1m = sizeof(FT) == 4 ? 64 : 256;
+#endif
+
 template <typename FT> struct Mp1mIn { const FT *rho, *T, *q_tot, *q_lcl, *q_icl, *q_rai, *q_sno; };
 template <typename FT> struct Mp1mOut { FT *dq_lcl, *dq_icl, *dq_rai, *dq_sno; };
 template <typename FT> struct Mp1mSrcOut { FT *col[CMX_MP1M_NSRC]; };

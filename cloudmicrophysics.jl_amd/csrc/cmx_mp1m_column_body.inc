@@ -5,7 +5,7 @@
 // arguments by reference, the compiler schedules the kernel-argument loads differently).
 // (no include guard: included once per kernel)
     using M = Math<FT>;
-    const auto &a = front_consts<FT, true>(a0);
+    const auto &a = CMX_MP1M_COL_CONSTS;
     __shared__ __align__(16) FT halo[BS + 1][4];   // fluxes of every lane's FIRST point, + slot BS for the point that follows the tile
     // tiles overlap by one lane, as in sb2006_column_kernel (cmx_sb2006_column.hip): lane BS−1 evaluates the next tile's first vector and only
     // supplies the flux its first point sends down; the flux-only evaluation of that point runs in the last workgroup of a launch only
@@ -19,7 +19,7 @@
     FT x[7][VEC];
     if (active) {
 #pragma unroll
-        for (int j = 0; j < 7; ++j) load_col<FT, VEC, true>(io.in[j] + first, v, x[j]);
+        for (int j = 0; j < 7; ++j) load_col<FT, VEC, CMX_MP1M_COL_NT_IN>(io.in[j] + first, v, x[j]);
     }
     Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
     if (nvalid < BS && threadIdx.x == BS - 1) {   // last workgroup of the launch: the point after its last vector, from the raw columns
@@ -59,7 +59,7 @@
 #pragma unroll
             for (int p = 0; p < VEC; ++p) {
                 if constexpr (LIN)
-                    mp1m_linearized_point<FT, FLAGS>(k.c, [&](FT dep) -> decltype(auto) { return (consts_after(k, dep).a); }, a0.k.a.nsub, x[0][p], x[1][p], x[2][p],
+                    mp1m_linearized_point<FT, FLAGS>(k.c, [&](FT dep) -> decltype(auto) { return CMX_MP1M_COL_LIN_ARGS(k, dep); }, CMX_MP1M_COL_NSUB, x[0][p], x[1][p], x[2][p],
                                                      x[3][p], x[4][p], x[5][p], x[6][p], t[p][0], t[p][1], t[p][2], t[p][3]);
                 else
                     mp1m_tendencies_point<FT, FLAGS>(k.c, x[0][p], x[1][p], x[2][p], x[3][p], x[4][p], x[5][p], x[6][p], t[p][0], t[p][1], t[p][2], t[p][3]);
@@ -82,7 +82,7 @@
             for (int p = 0; p < VEC; p += L) {
                 VT tt[4];
                 if constexpr (LIN)
-                    mp1m_linearized_point<VT, FLAGS>(k.c, [&](VT dep) -> decltype(auto) { return (consts_after(k, dep).a); }, a0.k.a.nsub, val(0, p), val(1, p), val(2, p),
+                    mp1m_linearized_point<VT, FLAGS>(k.c, [&](VT dep) -> decltype(auto) { return CMX_MP1M_COL_LIN_ARGS(k, dep); }, CMX_MP1M_COL_NSUB, val(0, p), val(1, p), val(2, p),
                                                      val(3, p), val(4, p), val(5, p), val(6, p), tt[0], tt[1], tt[2], tt[3]);
                 else
                     mp1m_tendencies_point<VT, FLAGS>(k.c, val(0, p), val(1, p), val(2, p), val(3, p), val(4, p), val(5, p), val(6, p), tt[0], tt[1], tt[2], tt[3]);

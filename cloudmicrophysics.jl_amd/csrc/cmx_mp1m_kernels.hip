@@ -29,49 +29,14 @@ namespace cmx {
 
 
 // bulk_microphysics_tendencies(Instantaneous(), Microphysics1Moment(), …) over columns — BMT:505-514
-// Lanes per workgroup of the tendencies kernel, per float type (same-box A/Bs, round 4, ms per 1e8 points: Float32 256 lanes 0.804, 128 lanes
-// 0.758 — and on another box 128 lanes 0.723, 64 lanes 0.714; Float64 256 lanes 2.375, 128 lanes 2.396 — profiles/r04_ab_sessions.txt, sessions
-// 13-15): short-lived one-wave workgroups free their slots as soon as their own wave has stored.  -DCMX_1M_BLOCK=n forces one size for both.
-#ifdef CMX_1M_BLOCK
-template <typename FT> constexpr int kBlock1m = CMX_1M_BLOCK;
-#else
-template <typename FT> constexpr int kBlock1m = sizeof(FT) == 4 ? 64 : 256;
-#endif
 template <typename FT, int VEC, uint32_t FLAGS = kRuntimeFlags>
 __global__ __launch_bounds__(kBlock1m<FT>) void mp1m_tendencies_kernel(const Mp1mConsts<FT> c, const Mp1mIn<FT> in,
                                                                        const Mp1mOut<FT> out, const int64_t nvec) {
-    const int64_t i = (int64_t)blockIdx.x * kBlock1m<FT> + threadIdx.x;
-    FT rho[VEC], T[VEC], q_tot[VEC], q_lcl[VEC], q_icl[VEC], q_rai[VEC], q_sno[VEC];
-    if (i < nvec) {
-        load_col<FT, VEC>(in.rho, i, rho); load_col<FT, VEC>(in.T, i, T); load_col<FT, VEC>(in.q_tot, i, q_tot);
-        load_col<FT, VEC>(in.q_lcl, i, q_lcl); load_col<FT, VEC>(in.q_icl, i, q_icl); load_col<FT, VEC>(in.q_rai, i, q_rai);
-        load_col<FT, VEC>(in.q_sno, i, q_sno);
-    }
-    Math<FT>::prepare();   // Float64: exp2 / log2 tables → LDS while the loads fly (every lane of the workgroup reaches the barrier inside); no-op for Float32
-    if (i >= nvec) return;
-    FT dl[VEC], di[VEC], dr[VEC], ds[VEC];
-    if constexpr (sizeof(FT) == 4 && VEC == 4) {
-        // Float32, four points per lane: two PAIRS of points in packed arithmetic (cmx_math.hpp f32x2); the constants are read phase by phase through the
-        // kernel-argument pointer (a packed instruction takes no literal: the point function's literals occupy SGPRs next to the constants).
-        // Rounds 1–4 evaluated one point at a time here; round 3 parked the additive constants of every `a·x + b` in VGPRs once per lane for
-        // them (an instruction reads one SGPR: 12 of a point's 266 instructions were v_mov_b32 of b; 70 → 76 VGPRs, 0.782–0.793 → 0.778–0.779 ms
-        // per 1e8 points) — the packed form took over every instantiation that did.
-#pragma unroll
-        for (int k = 0; k < VEC; k += 2) {
-            f32x2 l, ic, r, sn;
-            mp1m_tendencies_point<f32x2, FLAGS>(front_consts<FT, true>(c), f32x2{rho[k], rho[k + 1]}, f32x2{T[k], T[k + 1]}, f32x2{q_tot[k], q_tot[k + 1]},
-                                                f32x2{q_lcl[k], q_lcl[k + 1]}, f32x2{q_icl[k], q_icl[k + 1]}, f32x2{q_rai[k], q_rai[k + 1]},
-                                                f32x2{q_sno[k], q_sno[k + 1]}, l, ic, r, sn);
-            dl[k] = l.x; dl[k + 1] = l.y; di[k] = ic.x; di[k + 1] = ic.y; dr[k] = r.x; dr[k + 1] = r.y; ds[k] = sn.x; ds[k + 1] = sn.y;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k)
-            mp1m_tendencies_point<FT, FLAGS>(front_consts<FT, FLAGS == kRuntimeFlags>(c), rho[k], T[k], q_tot[k], q_lcl[k], q_icl[k], q_rai[k], q_sno[k], dl[k],
-                                             di[k], dr[k], ds[k]);
-    }
-    store_col<FT, VEC>(out.dq_lcl, i, dl); store_col<FT, VEC>(out.dq_icl, i, di);
-    store_col<FT, VEC>(out.dq_rai, i, dr); store_col<FT, VEC>(out.dq_sno, i, ds);
+#define CMX_MP1M_TEND_CONSTS(ALSO) front_consts<FT, ALSO>(c)
+#define CMX_MP1M_TEND_NT_IN true
+#include "cmx_mp1m_tend_body.inc"
+#undef CMX_MP1M_TEND_CONSTS
+#undef CMX_MP1M_TEND_NT_IN
 }
 
 // bulk_microphysics_tendencies(LinearizedAverage(), Microphysics1Moment(), …, Δt, nsub) over columns — BMT:572-632 (cmx_mp1m.hpp

@@ -2187,6 +2187,120 @@ int32_t cmx_mp1m_column_param_vjp_f64(const cmx_microphysics_1m_f64 *mp, const c
                                         double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
+ * (29) Parameter ENSEMBLES: one launch evaluates E parameter sets ("members") of the SB2006 warm-rain tendencies (1), the 1-moment tendencies (5), the SB2006
+ * column step (7) and the unshaped 1-moment column step (8b) — what an ensemble Kalman inversion, a perturbed-parameter ensemble or E single-column models
+ * pay E launches and E host-side folds for with the single entries.  Member e's outputs equal, BIT FOR BIT, the single entry called with member e's
+ * parameters on member e's state: the kernels run the single entries' own code on the same operands; only the constants come from a table in device
+ * memory instead of the kernel arguments.
+ *
+ * The library stays stateless and every entry a pure sequence of launches, so the table is built in two steps.
+ *
+ * PACK (host only, no HIP call): cmx_sb2006_ensemble_pack_* and cmx_mp1m_ensemble_pack_* take ARRAYS of n_members parameter structs of the single
+ * entries' types and the single entries' `flags`, run the single entries' folds and argument checks member by member (the first member that fails a
+ * check gives that check's status), and write one constants block per member into the caller's HOST buffer `table` (table_bytes ≥ n_members · stride,
+ * stride = cmx_*_ensemble_table_stride_*(), a multiple of 16 bytes; CMX_ERR_BAD_ARG otherwise) and the plain struct cmx_ensemble_desc.  Block e is a
+ * function of member e alone — packing [A, B] and packing [B] give the same bytes for B — so one member is updated by re-packing it alone and copying
+ * its stride bytes.  One block serves the pointwise and the column entry of its scheme.
+ *   SB2006: warm_rain[E], tps[E]; vel[E] or NULL (NULL: no fall speed — the table serves the pointwise entry without vt_rai_* only; otherwise exactly
+ *     one of CMX_VEL_SB2006 / CMX_VEL_CHEN2022 in flags); cloud_vel[E] or NULL (NULL: the column entry runs without cloud sedimentation).
+ *   1-moment: mp[E], tps[E]; stokes[E], chen_rain[E], chen_ice[E] — all three, or all three NULL when the table is for the pointwise entry only.
+ *     A snow-shape bit (CMX_1M_SED_SNOW_*) in flags is CMX_ERR_UNSUPPORTED.
+ * ALL MEMBERS OF ONE TABLE RUN ONE KERNEL INSTANTIATION.  The single entries choose theirs from parameter VALUES: the integer SB2006 exponents
+ * (b = 3, c = 4, d = −5), the fitted or general Γ of a Chen-2022 rain table (here and in the 1-moment fall speeds), the default-options or run-time-flags
+ * form of the 1-moment scheme.  If two members differ in one of these choices pack returns CMX_ERR_UNSUPPORTED — perturb such a member in its own table;
+ * a table that falls back to the general instantiations would not be bit-identical to the single entries.
+ * The caller copies n_members · stride bytes to the device however it likes (hipMemcpyAsync on the stream of the calls orders the update) and passes
+ * the desc (host) and the device pointer.  The table is an ordinary device buffer the kernels only read: calls stay graph-capturable, and a captured
+ * graph sees a table updated in place between replays.
+ *
+ * ENSEMBLE ENTRIES: (desc, table, n_members, ens_flags), then the single entry's array arguments; sizes (n_points resp. n_col, n_lev) are PER MEMBER.
+ * Outputs are member-major: member e owns points [e·n, (e+1)·n) of every output column and columns [e·n_col, (e+1)·n_col) of the precipitation fluxes.
+ * Inputs are member-major too (every member its own state) or, with CMX_ENSEMBLE_SHARED_STATE, of length n: every member reads the same state (the
+ * loads then drop the non-temporal hint: the other members' workgroups want the lines from L2).  inv_dz (n_lev values) is always shared; q_min, dt and
+ * nsub of the 1-moment column step are shared.  Optional outputs stay NULL-able as in the single entries (vt_rai_n, vt_rai_m — a table packed without
+ * `vel` cannot give them: CMX_ERR_BAD_ARG —, the precipitation fluxes).  The column halo never crosses a member: the last column of a member takes a
+ * zero inflow at its top and the next member's first point is not read.  Any alignment is accepted (per-member scalar head, vector body, scalar tail, or
+ * one point per lane throughout when the columns' offsets differ) and does not change a bit.
+ * Statuses, in order: NULL desc or table (CMX_ERR_BAD_ARG); the counts as in the single entry (negative: CMX_ERR_BAD_ARG; above the single entry's limit
+ * PER MEMBER: CMX_ERR_UNSUPPORTED; 1-moment column: nsub < 0, and dt ≤ 0 or q_min < 0 with nsub > 0: CMX_ERR_BAD_ARG); wrong magic, scheme or float type,
+ * n_members < 1 or ≠ desc->n_members, a stride or flags the library would not have packed, unknown ens_flags bits (CMX_ERR_BAD_ARG); n_members > 65535,
+ * the y limit of a grid (CMX_ERR_UNSUPPORTED); a per-member size of 0 (CMX_OK); a NULL required array, the column entries on a table packed without their
+ * fall-speed parameters (CMX_ERR_BAD_ARG).  `table` is never dereferenced on the host.
+ * Not done here: ensemble forms of the derivative entries, the implicit average and the implicit column steps, 2M + P3, the snow-shaped 1-moment column
+ * step, the parcel model (it has per-parcel coefficients); tables of mixed instantiations; sharding members over devices.  cmx_version() stays at 0.5
+ * (no struct layout changed; an older library fails on the symbol lookup).
+ * ------------------------------------------------------------------------- */
+#define CMX_ENSEMBLE_SHARED_STATE (1u << 0)
+#define CMX_ENSEMBLE_MAGIC 0x434d5845u      /* "CMXE" */
+#define CMX_ENSEMBLE_SCHEME_SB2006 1u
+#define CMX_ENSEMBLE_SCHEME_MP1M 2u
+typedef struct cmx_ensemble_desc {
+    uint32_t magic;              /* CMX_ENSEMBLE_MAGIC */
+    uint32_t scheme;             /* CMX_ENSEMBLE_SCHEME_* */
+    uint32_t float_type;         /* 4: the _f32 family, 8: the _f64 family */
+    uint32_t flags;              /* the `flags` the table was packed with */
+    int32_t n_members;
+    uint32_t stride;             /* bytes from one member's block to the next */
+    /* the dispatch choices made from parameter values, equal for all members */
+    uint32_t integer_exponents;  /* SB2006: b = 3, c = 4, d = −5 */
+    uint32_t vel_kind;           /* SB2006: 0 no fall speed, 1 SB2006, 2 Chen-2022 (fitted Γ), 3 Chen-2022 (general Γ) */
+    uint32_t cloud_vel;          /* SB2006: packed with cloud_vel (the column entry sediments cloud droplets) */
+    uint32_t runtime_flags;      /* 1-moment: the run-time-flags instantiation (0: the default-options one) */
+    uint32_t sedimentation;      /* 1-moment: packed with stokes, chen_rain, chen_ice (the column entry is served) */
+    uint32_t general_gamma;      /* 1-moment: run-time Γ of the Chen-2022 rain fall speed */
+    uint32_t reserved[4];
+} cmx_ensemble_desc;
+int32_t cmx_sb2006_ensemble_table_stride_f32(void);
+int32_t cmx_sb2006_ensemble_table_stride_f64(void);
+int32_t cmx_mp1m_ensemble_table_stride_f32(void);
+int32_t cmx_mp1m_ensemble_table_stride_f64(void);
+int32_t cmx_sb2006_ensemble_pack_f32(const cmx_warm_rain_2m_f32 *warm_rain, const cmx_thermo_f32 *tps, const cmx_rain_vel_f32 *vel,
+                                     const cmx_stokes_vel_f32 *cloud_vel, uint32_t flags, int32_t n_members, void *table, int64_t table_bytes,
+                                     cmx_ensemble_desc *desc);
+int32_t cmx_sb2006_ensemble_pack_f64(const cmx_warm_rain_2m_f64 *warm_rain, const cmx_thermo_f64 *tps, const cmx_rain_vel_f64 *vel,
+                                     const cmx_stokes_vel_f64 *cloud_vel, uint32_t flags, int32_t n_members, void *table, int64_t table_bytes,
+                                     cmx_ensemble_desc *desc);
+int32_t cmx_mp1m_ensemble_pack_f32(const cmx_microphysics_1m_f32 *mp, const cmx_thermo_f32 *tps, const cmx_stokes_vel_f32 *stokes,
+                                   const cmx_chen2022_rain_vel_f32 *chen_rain, const cmx_chen2022_ice_vel_f32 *chen_ice, uint32_t flags, int32_t n_members,
+                                   void *table, int64_t table_bytes, cmx_ensemble_desc *desc);
+int32_t cmx_mp1m_ensemble_pack_f64(const cmx_microphysics_1m_f64 *mp, const cmx_thermo_f64 *tps, const cmx_stokes_vel_f64 *stokes,
+                                   const cmx_chen2022_rain_vel_f64 *chen_rain, const cmx_chen2022_ice_vel_f64 *chen_ice, uint32_t flags, int32_t n_members,
+                                   void *table, int64_t table_bytes, cmx_ensemble_desc *desc);
+int32_t cmx_sb2006_warm_rain_tendencies_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                     int64_t n_points, const float *rho, const float *T, const float *q_tot, const float *q_lcl,
+                                                     const float *n_lcl, const float *q_rai, const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt,
+                                                     float *dq_rai_dt, float *dn_rai_dt, float *vt_rai_n, float *vt_rai_m, void *stream);
+int32_t cmx_sb2006_warm_rain_tendencies_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                     int64_t n_points, const double *rho, const double *T, const double *q_tot, const double *q_lcl,
+                                                     const double *n_lcl, const double *q_rai, const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt,
+                                                     double *dq_rai_dt, double *dn_rai_dt, double *vt_rai_n, double *vt_rai_m, void *stream);
+int32_t cmx_mp1m_tendencies_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, int64_t n_points,
+                                         const float *rho, const float *T, const float *q_tot, const float *q_lcl, const float *q_icl, const float *q_rai,
+                                         const float *q_sno, float *dq_lcl_dt, float *dq_icl_dt, float *dq_rai_dt, float *dq_sno_dt, void *stream);
+int32_t cmx_mp1m_tendencies_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, int64_t n_points,
+                                         const double *rho, const double *T, const double *q_tot, const double *q_lcl, const double *q_icl,
+                                         const double *q_rai, const double *q_sno, double *dq_lcl_dt, double *dq_icl_dt, double *dq_rai_dt,
+                                         double *dq_sno_dt, void *stream);
+int32_t cmx_sb2006_column_tendencies_sedimentation_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                                int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho, const float *T,
+                                                                const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai,
+                                                                const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt,
+                                                                float *dn_rai_dt, float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_tendencies_sedimentation_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                                int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho, const double *T,
+                                                                const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                                                const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt, double *dq_rai_dt,
+                                                                double *dn_rai_dt, double *precip_flux, void *stream);
+int32_t cmx_mp1m_column_tendencies_sedimentation_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                              float q_min, float dt, int32_t nsub, int64_t n_col, int32_t n_lev, const float *inv_dz,
+                                                              const float *const *in, float *const *out, float *precip_rai, float *precip_sno,
+                                                              void *stream);
+int32_t cmx_mp1m_column_tendencies_sedimentation_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags,
+                                                              double q_min, double dt, int32_t nsub, int64_t n_col, int32_t n_lev, const double *inv_dz,
+                                                              const double *const *in, double *const *out, double *precip_rai, double *precip_sno,
+                                                              void *stream);
+
+/* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length
  * n, accumulated in double, into `sums[ncols]` (device, double).  ONE launch reduces all columns to CMX_COLUMN_SUMS_PARTIALS partial
  * sums each (`workspace`: ncols · CMX_COLUMN_SUMS_PARTIALS doubles of device memory owned by the caller — the library allocates nothing),

@@ -2214,4 +2214,150 @@ function column_sums!(sums, workspace, cols, ::Type{FT}, n::Integer; stream = C_
     return sums
 end
 
+# ----------------------------------------------------------------------------------------------------------------
+# (29) parameter ensembles: E parameter sets in one launch (EKI / UKI, perturbed-parameter ensembles, E single-column models)
+# ----------------------------------------------------------------------------------------------------------------
+const CMX_ENSEMBLE_SHARED_STATE = UInt32(1) << 0
+
+"""`cmx_ensemble_desc`: what a pack recorded about its table (scheme, float type, flags, members, stride and the instantiation all members share)."""
+struct EnsembleDesc
+    magic::UInt32
+    scheme::UInt32
+    float_type::UInt32
+    flags::UInt32
+    n_members::Int32
+    stride::UInt32
+    integer_exponents::UInt32
+    vel_kind::UInt32
+    cloud_vel::UInt32
+    runtime_flags::UInt32
+    sedimentation::UInt32
+    general_gamma::UInt32
+    reserved::NTuple{4, UInt32}
+end
+EnsembleDesc() = EnsembleDesc(ntuple(_ -> UInt32(0), 4)..., Int32(0), ntuple(_ -> UInt32(0), 7)..., ntuple(_ -> UInt32(0), 4))
+
+_one_per_member(x::AbstractVector, n) = (length(x) == n || error("$(length(x)) entries for $n members"); x)
+_one_per_member(x, n) = fill(x, n)
+_array_or_null(::Nothing) = C_NULL
+_array_or_null(x::Vector) = x
+_ens_flags(shared_state::Bool) = shared_state ? CMX_ENSEMBLE_SHARED_STATE : UInt32(0)
+
+"""
+    pack_ensemble_2m(FT, mps, tps; vel = nothing, cloud_vel = nothing) -> (desc, table)
+
+Folds the SB2006 members `mps` (a vector of `CMP.Microphysics2MParams`) into one constants block per member: `table` is a HOST `Vector{UInt8}` to copy
+to the device as it is (`copyto!(ROCVector{UInt8}(undef, length(table)), table)`), `desc` goes to the `…_ensemble!` calls.  `tps`, `vel` and `cloud_vel`
+are one object for all members or a vector of one per member; `vel = nothing` packs no fall speed (pointwise tendencies without `vt_rai_*` only).
+All members must select the same kernel instantiation (integer exponents, fitted or general Γ of a Chen-2022 table): CMX_ERR_UNSUPPORTED otherwise.
+"""
+function pack_ensemble_2m(::Type{FT}, mps::AbstractVector, tps; vel = nothing, cloud_vel = nothing) where {FT}
+    n = length(mps)
+    wrs = [_warm_rain(m) for m in mps]
+    vels = _one_per_member(vel, n)
+    flags = (is_limited(wrs[1]) ? CMX_SB2006_LIMITED : UInt32(0)) | _vel_flag(vels[1])
+    stride = ccall(_fn("cmx_sb2006_ensemble_table_stride", FT), Int32, ())
+    table = Vector{UInt8}(undef, n * stride)
+    desc = Ref(EnsembleDesc())
+    st = ccall(_fn("cmx_sb2006_ensemble_pack", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+        [pack(w) for w in wrs], [CmxThermo(t) for t in _one_per_member(tps, n)], _array_or_null(vel === nothing ? nothing : [_rain_vel(v, FT) for v in vels]),
+        _array_or_null(cloud_vel === nothing ? nothing : collect(_one_per_member(cloud_vel, n))), flags, n, table, length(table), desc)
+    _check(st, "cmx_sb2006_ensemble_pack")
+    return desc[], table
+end
+
+"""
+    pack_ensemble_1m(FT, mps, tps; stokes = nothing, chen = nothing) -> (desc, table)
+
+The same for the 1-moment members `mps` (a vector of `CMP.Microphysics1MParams` with equal process options).  `stokes = CMP.StokesRegimeVelType(FT)` and
+`chen = CMP.Chen2022VelType(FT)` (one for all members or one per member, both or neither) add the fall-speed constants the column step needs.
+"""
+function pack_ensemble_1m(::Type{FT}, mps::AbstractVector, tps; stokes = nothing, chen = nothing) where {FT}
+    n = length(mps)
+    (stokes === nothing) == (chen === nothing) || error("stokes and chen: both (the column step) or neither (the pointwise tendencies only)")
+    chens = chen === nothing ? nothing : _one_per_member(chen, n)
+    stride = ccall(_fn("cmx_mp1m_ensemble_table_stride", FT), Int32, ())
+    table = Vector{UInt8}(undef, n * stride)
+    desc = Ref(EnsembleDesc())
+    st = ccall(_fn("cmx_mp1m_ensemble_pack", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+        [pack(m) for m in mps], [CmxThermo(t) for t in _one_per_member(tps, n)], _array_or_null(stokes === nothing ? nothing : collect(_one_per_member(stokes, n))),
+        _array_or_null(chens === nothing ? nothing : [_rain(c) for c in chens]), _array_or_null(chens === nothing ? nothing : [pack(c) for c in chens]),
+        option_bits(mps[1]), n, table, length(table), desc)
+    _check(st, "cmx_mp1m_ensemble_pack")
+    return desc[], table
+end
+
+"""
+    bulk_microphysics_tendencies_ensemble!(out, BMT.Microphysics2Moment(), desc, table, n, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai; shared_state, stream)
+
+The SB2006 tendencies of every member of a packed ensemble in one launch: `table` is the DEVICE copy of the packed table, `n` the points per member.
+Outputs are member-major (member e owns `[e·n + 1 : (e + 1)·n]`); inputs too, or of length `n` with `shared_state = true`.  Member e's results are
+those of `bulk_microphysics_tendencies!` with member e's parameters, bit for bit.
+"""
+function bulk_microphysics_tendencies_ensemble!(out, ::BMT.Microphysics2Moment, desc::EnsembleDesc, table, n::Integer, ρ::AbstractArray{FT}, T, q_tot, q_lcl,
+    n_lcl, q_rai, n_rai; shared_state::Bool = false, stream = C_NULL) where {FT}
+    vt_n = hasproperty(out, :vt_rai_n) ? out.vt_rai_n : nothing
+    vt_m = hasproperty(out, :vt_rai_m) ? out.vt_rai_m : nothing
+    st = ccall(_fn("cmx_sb2006_warm_rain_tendencies_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Int64,
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), n,
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _dp(FT, out.dq_lcl_dt), _dp(FT, out.dn_lcl_dt), _dp(FT, out.dq_rai_dt), _dp(FT, out.dn_rai_dt), _dp(FT, vt_n), _dp(FT, vt_m), stream)
+    _check(st, "cmx_sb2006_warm_rain_tendencies_ensemble")
+    return out
+end
+
+"""The Instantaneous 1-moment tendencies of every member of a packed ensemble in one launch (see the 2-moment method for the layouts)."""
+function bulk_microphysics_tendencies_ensemble!(out, ::BMT.Instantaneous, ::BMT.Microphysics1Moment, desc::EnsembleDesc, table, n::Integer,
+    ρ::AbstractArray{FT}, T, q_tot, q_lcl, q_icl, q_rai, q_sno; shared_state::Bool = false, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_mp1m_tendencies_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Int64, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT},
+            Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), n,
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, q_icl), _dp(FT, q_rai), _dp(FT, q_sno),
+        _dp(FT, out.dq_lcl_dt), _dp(FT, out.dq_icl_dt), _dp(FT, out.dq_rai_dt), _dp(FT, out.dq_sno_dt), stream)
+    _check(st, "cmx_mp1m_tendencies_ensemble")
+    return out
+end
+
+"""
+    column_tendencies_sedimentation_ensemble!(out, BMT.Microphysics2Moment(), desc, table, n_col, n_lev, inv_dz, ρ, …; precip_flux, shared_state, stream)
+
+The fused SB2006 column step of every member of a packed ensemble (packed with `vel`) in one launch; `n_col`, `n_lev` per member, `inv_dz` shared,
+`precip_flux` = `n_members · n_col` values or `nothing`.  No halo crosses a member.
+"""
+function column_tendencies_sedimentation_ensemble!(out, ::BMT.Microphysics2Moment, desc::EnsembleDesc, table, n_col::Integer, n_lev::Integer,
+    inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai; precip_flux = nothing, shared_state::Bool = false, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_sb2006_column_tendencies_sedimentation_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Int64, Int32, Ptr{FT},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _dp(FT, out.dq_lcl_dt), _dp(FT, out.dn_lcl_dt), _dp(FT, out.dq_rai_dt), _dp(FT, out.dn_rai_dt), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_tendencies_sedimentation_ensemble")
+    return out
+end
+
+"""
+    column_tendencies_sedimentation_ensemble!(out, mode, BMT.Microphysics1Moment(), desc, table, n_col, n_lev, inv_dz, cols, q_min, Δt, nsub; …)
+
+The unshaped 1-moment column step of every member of a packed ensemble (packed with `stokes` and `chen`) in one launch.  `cols` = the 7 state columns,
+`out` = the 4 tendency columns; `q_min`, `Δt`, `nsub` are shared by all members (`mode = BMT.Instantaneous()`: ignored).
+"""
+function column_tendencies_sedimentation_ensemble!(out, mode, ::BMT.Microphysics1Moment, desc::EnsembleDesc, table, n_col::Integer, n_lev::Integer,
+    inv_dz::AbstractArray{FT}, cols, q_min = zero(FT), Δt = zero(FT), nsub::Integer = 0; precip_rai = nothing, precip_sno = nothing,
+    shared_state::Bool = false, stream = C_NULL) where {FT}
+    ns = mode isa BMT.LinearizedAverage ? Int32(nsub) : Int32(0)
+    st = ccall(_fn("cmx_mp1m_column_tendencies_sedimentation_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, FT, FT, Int32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), FT(q_min), FT(Δt), ns, n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols),
+        _ptrs(FT, out), _dp(FT, precip_rai), _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_tendencies_sedimentation_ensemble")
+    return out
+end
+
 end # module CMXExt
