@@ -328,6 +328,13 @@ def _declare(lib):
         f = getattr(lib, f"cmx_mp1m_column_tendencies_sedimentation_ensemble_{s}")
         f.restype = i32
         f.argtypes = [desc, vp, i32, u32, fam.ft, fam.ft, i32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
+        # … of the implicit column steps (§21): (desc, device table, n_members, ens_flags, dt, nsub, step_flags, n_col, n_lev, inv_dz, …)
+        f = getattr(lib, f"cmx_sb2006_column_implicit_step_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, C.c_double, i32, u32, i64, i32] + [vp] * 13 + [vp]
+        f = getattr(lib, f"cmx_mp1m_column_implicit_step_ensemble_{s}")
+        f.restype = i32
+        f.argtypes = [desc, vp, i32, u32, C.c_double, i32, u32, i64, i32, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp]
 
 
 def lib():

@@ -20,6 +20,7 @@ import torch
 
 from . import _abi, _lib
 from ._cols import _check_cols, _fam_of, _ptr
+from ._jacobian import _check_step, _check_step_normal
 from .bulk_tendencies import ColumnTendencies2M, SB2006VelType, WarmRainTendencies2M, _vel_flag, _warm_rain
 from .microphysics1m import ColumnStep1M, Tendencies1M
 from .parameters import Microphysics1MParams, rain_vel_params
@@ -239,4 +240,63 @@ def column_tendencies_sedimentation_1m(table, inv_dz, rho, T, q_tot, q_lcl, q_ic
     out_p = (C.c_void_p * 4)(*[o.data_ptr() for o in out])
     _lib.call("cmx_mp1m_column_tendencies_sedimentation_ensemble", fam, ref.device, *_ens_args(table, shared_state), q_min if lin else 0.0,
               dt if lin else 0.0, int(nsub) if lin else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]), stream=stream)
+    return ColumnStep1M(*out, *pr)
+
+
+def _not_state(outs, cols):
+    state = {c.data_ptr() for c in cols}
+    if any(o is not None and o.data_ptr() in state for o in outs):
+        raise ValueError("an output column must not be a state column: this step is not in place")
+
+
+def column_implicit_step_2m(table, inv_dz, rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt, nsub=1, nonnegative=True, *, shared_state=False,
+                            want_precip_flux: bool = False, out: Optional[ColumnTendencies2M] = None, stream=None) -> ColumnTendencies2M:
+    """`column_implicit_step_2m` — the sub-stepped implicit average with backward-Euler sedimentation, stable and positive at any Courant number — for
+    every member of `table` in one launch: state tensors of shape (E, n_col, n_lev) (or (n_col, n_lev) with `shared_state`), tendencies
+    (E, n_col, n_lev), precip_flux (E, n_col).  `inv_dz`, `dt`, `nsub` and `nonnegative` are shared by all members; the latent heating of the substeps
+    uses each member's own thermodynamics parameters.  The table must have been packed with a fall-speed scheme; cloud-droplet sedimentation runs when
+    it was packed with `cloud_vel`.  An output must not be a state tensor."""
+    cols = (rho, T, q_tot, q_lcl, n_lcl, q_rai, n_rai)
+    dt, nsub = _check_step(dt, nsub)
+    ref, fam, (n_col, n_lev) = _state(table, _abi.CMX_ENSEMBLE_SCHEME_SB2006, cols, _NAMES_2M, shared_state, 2)
+    if table.desc.vel_kind == 0:
+        raise ValueError("the column step needs a table packed with a rain fall-speed scheme (pack_2m(vel=SB2006VelType | Chen2022VelTypeRain))")
+    _check_step_normal(dt, nsub, ref.dtype)
+    _inv_dz(inv_dz, ref, n_lev)
+    E = len(table)
+    if out is None:
+        out = ColumnTendencies2M(*[torch.empty((E, n_col, n_lev), dtype=ref.dtype, device=ref.device) for _ in range(4)],
+                                 torch.empty((E, n_col), dtype=ref.dtype, device=ref.device) if want_precip_flux else None)
+    else:
+        if any(o is None for o in out[:4]):
+            raise ValueError("out: the four tendency columns are required")
+        _check_out(out[:4], (E, n_col, n_lev), ref, ColumnTendencies2M._fields)
+        _check_out(out[4:], (E, n_col), ref, ("precip_flux",))
+        _not_state(out, cols)
+    _lib.call("cmx_sb2006_column_implicit_step_ensemble", fam, ref.device, *_ens_args(table, shared_state), dt, nsub,
+              _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev, _ptr(inv_dz), *[_ptr(t) for t in cols], *[_ptr(t) for t in out[:4]],
+              _ptr(out.precip_flux), stream=stream)
+    return out
+
+
+def column_implicit_step_1m(table, inv_dz, rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno, dt, nsub=1, nonnegative=True, *, shared_state=False,
+                            precip: bool = True, stream=None) -> ColumnStep1M:
+    """`column_implicit_step_1m` for every member of `table` in one launch: state tensors of shape (E, n_col, n_lev) (or (n_col, n_lev) with
+    `shared_state`), tendencies (E, n_col, n_lev), precip_rai / precip_sno (E, n_col).  `inv_dz`, `dt`, `nsub` and `nonnegative` are shared by all
+    members; the latent heating of the substeps uses each member's own thermodynamics parameters.  The table must have been packed with the
+    fall-speed parameters."""
+    cols = (rho, T, q_tot, q_lcl, q_icl, q_rai, q_sno)
+    dt, nsub = _check_step(dt, nsub)
+    ref, fam, (n_col, n_lev) = _state(table, _abi.CMX_ENSEMBLE_SCHEME_MP1M, cols, _NAMES_1M, shared_state, 2)
+    if not table.desc.sedimentation:
+        raise ValueError("the column step needs a table packed with stokes, chen_rain and chen_ice")
+    _check_step_normal(dt, nsub, ref.dtype)
+    _inv_dz(inv_dz, ref, n_lev)
+    E = len(table)
+    out = [torch.empty((E, n_col, n_lev), dtype=ref.dtype, device=ref.device) for _ in range(4)]
+    pr = [torch.empty((E, n_col), dtype=ref.dtype, device=ref.device) if precip else None for _ in range(2)]
+    in_p = (C.c_void_p * 7)(*[c.data_ptr() for c in cols])
+    out_p = (C.c_void_p * 4)(*[o.data_ptr() for o in out])
+    _lib.call("cmx_mp1m_column_implicit_step_ensemble", fam, ref.device, *_ens_args(table, shared_state), dt, nsub,
+              _abi.CMX_STEP_NONNEGATIVE if nonnegative else 0, n_col, n_lev, _ptr(inv_dz), in_p, out_p, _ptr(pr[0]), _ptr(pr[1]), stream=stream)
     return ColumnStep1M(*out, *pr)

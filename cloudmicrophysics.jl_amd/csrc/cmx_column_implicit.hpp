@@ -20,7 +20,18 @@ namespace cmx {
 // outputs.  The flux options — rain velocity scheme, cloud sedimentation, run-time Γ — are wave-uniform run-time branches (with_options) around the existing
 // flux functions' instantiations: the same inline code on the same operands, the same bits.  §(20) calls the F-only functions and §(21) the (F, w) ones (the
 // operations of the F-only functions on the same operands); neither is formed from the other.
-// `dep`: the value the constants wait for (consts_after) -------------------------------------------------------------------------------------------------------
+// `dep`: the value the constants wait for (consts_after).  `ka` is the kernel's by-value argument (KA) or, in the ensemble form of §(21) (include/cmx.h §(29)),
+// the constant-address-space reference to a member's block of the table, which has the members a flux function reads under the same names ----------------------
+// The cloud fall-speed constants as the plain reference sed_fluxes_of_point takes: the by-value kernel argument's member itself, or a copy of the table
+// block's member, loaded with scalar loads where it is used (`after`: the member behind consts_after).
+template <typename FT, typename TA> __device__ __forceinline__ const CloudVelConsts<FT> &plain_consts(const CloudVelConsts<FT> &direct, const TA &) { return direct; }
+#if !defined(CMX_HOST_BUILD)
+template <typename FT> __device__ __forceinline__ CloudVelConsts<FT> plain_consts(KernArg<CloudVelConsts<FT>> &, KernArg<CloudVelConsts<FT>> &after) {
+    CloudVelConsts<FT> v;
+    __builtin_memcpy(&v, &after, sizeof v);
+    return v;
+}
+#endif
 template <typename FT, bool LIMITED> struct SbFlux {
     struct KA { SbConsts<FT> c; CloudVelConsts<FT> cv; };
     static constexpr int precip(int p) { return p == 0 ? CMX_SB2006_JAC_DQ_RAI_DT : -1; }      // the species of io.precip[p], −1: none
@@ -48,16 +59,21 @@ template <typename FT, bool LIMITED> struct SbFlux {
         F[CMX_SB2006_JAC_DN_RAI_DT] = f.n_rai;
     }
     // s: q_lcl, n_lcl, q_rai, n_rai
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
-        const auto &c = consts_after(front_consts<FT, true>(ka), dep).c;
+    template <typename KAT> static __device__ __forceinline__ void fluxes(const KAT &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
+        const auto &kd = consts_after(front_consts<FT, true>(ka), dep);
+        const auto &c = kd.c;
+        decltype(auto) cv = plain_consts(ka.cv, kd.cv);
         with_options(opt, [&](auto vel, auto cloud) __attribute__((always_inline)) {
-            put(sed_fluxes_of_point<FT, LIMITED, decltype(vel)::value, decltype(cloud)::value>(c, ka.cv, rho, s[0], s[1], s[2], s[3]), F);
+            put(sed_fluxes_of_point<FT, LIMITED, decltype(vel)::value, decltype(cloud)::value>(c, cv, rho, s[0], s[1], s[2], s[3]), F);
         });
     }
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
-        const auto &c = consts_after(front_consts<FT, true>(ka), dep).c;
+    template <typename KAT>
+    static __device__ __forceinline__ void fluxes(const KAT &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
+        const auto &kd = consts_after(front_consts<FT, true>(ka), dep);
+        const auto &c = kd.c;
+        decltype(auto) cv = plain_consts(ka.cv, kd.cv);
         with_options(opt, [&](auto vel, auto cloud) __attribute__((always_inline)) {
-            const SedFluxW<FT> f = sed_fluxes_w_of_point<FT, LIMITED, decltype(vel)::value, decltype(cloud)::value>(c, ka.cv, rho, s[0], s[1], s[2], s[3]);
+            const SedFluxW<FT> f = sed_fluxes_w_of_point<FT, LIMITED, decltype(vel)::value, decltype(cloud)::value>(c, cv, rho, s[0], s[1], s[2], s[3]);
             put(f.F, F);
             put(f.w, w);
         });
@@ -75,14 +91,15 @@ template <typename FT> struct Mp1mFlux {
         else g(std::false_type{});
     }
     // s: q_lcl, q_icl, q_rai, q_sno
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
+    template <typename KAT> static __device__ __forceinline__ void fluxes(const KAT &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4]) {
         const auto &vc = consts_after(front_consts<FT, true>(ka), dep).vc;
         SedFlux4<FT> f;
         with_options(opt, [&](auto general) __attribute__((always_inline)) { f = mp1m_sed_fluxes<FT, decltype(general)::value>(vc, rho, s[0], s[1], s[2], s[3]); });
 #pragma unroll
         for (int q = 0; q < 4; ++q) F[q] = f.f[q];
     }
-    static __device__ __forceinline__ void fluxes(const KA &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
+    template <typename KAT>
+    static __device__ __forceinline__ void fluxes(const KAT &ka, FT dep, const int32_t (&opt)[2], FT rho, const FT (&s)[4], FT (&F)[4], FT (&w)[4]) {
         const auto &vc = consts_after(front_consts<FT, true>(ka), dep).vc;
         SedFluxW4<FT> f;
         with_options(opt, [&](auto general) __attribute__((always_inline)) { f = mp1m_sed_fluxes_w<FT, decltype(general)::value>(vc, rho, s[0], s[1], s[2], s[3]); });

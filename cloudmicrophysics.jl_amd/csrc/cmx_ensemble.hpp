@@ -69,6 +69,17 @@ template <typename FT, bool ALSO, typename T> __device__ __forceinline__ decltyp
     else return (local);
 }
 
+// The constants of a scheme's eval (cmx_jacobian.hpp: S::eval reads them through scheme_consts → front_consts) in an ensemble kernel: a tag in place of the
+// constants, and the overload of front_consts that forms the reference to member blockIdx.y's block — OFFSET bytes into it — WHERE THE EVAL READS IT, from
+// the EnsArgs at the front of the kernel-argument segment.  That is the single kernels' form (a fresh kernel-argument pointer per eval).  One reference
+// formed at the top of the kernel and handed down to every eval compiles to the same loads but moved 14–22 Float64 values into spill registers in the
+// implicit column step (428 → 456, 408 → 452, 498 → 512 VGPRs + 20 spilled, HISTORY.md): the Float64 instantiations there have no register to spare.
+template <typename CT, uint32_t OFFSET> struct EnsFrontConsts {};
+template <typename FT, bool ALSO = false, typename CT, uint32_t OFFSET> __device__ __forceinline__ KernArg<CT> &front_consts(const EnsFrontConsts<CT, OFFSET> &) {
+    KernArg<EnsArgs> &ea = *(KernArg<EnsArgs> *)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(KernArg<CT> *)(ea.table + ((uint64_t)blockIdx.y * ea.stride + OFFSET));
+}
+
 template <typename BLOCK> constexpr int32_t ens_stride() { return (int32_t)((sizeof(BLOCK) + 15) / 16 * 16); }
 
 // The ensemble arguments of an entry, checked after its counts (include/cmx.h §(29) for the order): 0, or the status to return.

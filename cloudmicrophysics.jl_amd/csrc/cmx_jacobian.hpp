@@ -651,8 +651,10 @@ inline bool make_implicit_average_args(ImplicitAverageArgs<FT, K, NOUT, NWRT> &a
 // The substeps of one point, the averages returned in registers: the loop of implicit_average_kernel, of implicit_sedimentation_step_kernel
 // (cmx_column_implicit_step.hip) and of the host loop.  (implicit_average_column_kernel, cmx_column_implicit_average.hip, keeps a copy: the call was measured
 // slower there.  A change here is a change there.)  x: the point as the kernel read it; the species and T (x[1 + S::TEMP], if the scheme has one) advance in it.
-template <typename S, typename FT, int K, typename C>
-__device__ __forceinline__ void implicit_average_substeps(const C &c, const ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT> &a, FT (&x)[S::NWRT + 1], FT (&avg)[S::NOUT]) {
+// A: ImplicitAverageArgs<FT, K, S::NOUT, S::NWRT>, or a view with its members wrt, nsub, step_flags, h, inv_h, inv_dt, Lv, Ls (the ensemble form of the column
+// step, cmx_column_implicit_step_ensemble.hip, whose Lv and Ls are a member's).
+template <typename S, typename FT, int K, typename C, typename A>
+__device__ __forceinline__ void implicit_average_substeps(const C &c, const A &a, FT (&x)[S::NWRT + 1], FT (&avg)[S::NOUT]) {
     constexpr int N = S::NOUT, S0 = 1 + S::SPECIES0;
     const bool limit = a.step_flags & CMX_STEP_NONNEGATIVE;
     FT s0[N];

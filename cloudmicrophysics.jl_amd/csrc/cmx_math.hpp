@@ -444,8 +444,10 @@ template <typename T> struct is_kernarg<const __attribute__((address_space(4))) 
 template <typename FT, bool ALSO = false, typename CT> inline const CT &front_consts(const CT &c) { return c; }
 template <typename C, typename FT> inline const C &consts_after(const C &c, FT) { return c; }
 #else
+// (constants that already ARE a constant-address-space reference — a member's block of an ensemble table, cmx_ensemble.hpp — pass through)
 template <typename FT, bool ALSO = false, typename CT> __device__ __forceinline__ decltype(auto) front_consts(const CT &c) {
-    if constexpr (sizeof(FT) == 8 || ALSO) return (*(KernArg<CT> *)__builtin_amdgcn_kernarg_segment_ptr());
+    if constexpr (is_kernarg<const CT>::value) return (c);
+    else if constexpr (sizeof(FT) == 8 || ALSO) return (*(KernArg<CT> *)__builtin_amdgcn_kernarg_segment_ptr());
     else return (c);
 }
 // (a plain reference passes through: laundering the address of a by-value kernel argument would force a private copy of the struct)

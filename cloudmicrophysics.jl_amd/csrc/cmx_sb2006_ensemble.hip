@@ -64,6 +64,8 @@ static int32_t sb_pack_entry(const WR *wr, const TH *tps, const VL *vel, const S
         std::memset(&b, 0, sizeof b);
         b.c = make_sb_consts<FT>(wr[e], tps[e], vel ? vel + e : (const VL *)nullptr, (double)Math<FT>::eps_1m());
         if (cloud_vel) b.cv = make_cloud_vel_consts<FT>(wr[e].seifert_beheng.pdf_c, cloud_vel[e]);
+        b.Lv = (FT)tps[e].LH_v0 / (FT)tps[e].cp_d;      // the expressions of make_implicit_average_args (cmx_jacobian.hpp)
+        b.Ls = (FT)tps[e].LH_s0 / (FT)tps[e].cp_d;
         unsigned char *dst = static_cast<unsigned char *>(table) + (size_t)e * stride;
         std::memset(dst, 0, stride);
         std::memcpy(dst, &b, sizeof b);

@@ -2226,9 +2226,24 @@ int32_t cmx_mp1m_column_param_vjp_f64(const cmx_microphysics_1m_f64 *mp, const c
  * n_members < 1 or ≠ desc->n_members, a stride or flags the library would not have packed, unknown ens_flags bits (CMX_ERR_BAD_ARG); n_members > 65535,
  * the y limit of a grid (CMX_ERR_UNSUPPORTED); a per-member size of 0 (CMX_OK); a NULL required array, the column entries on a table packed without their
  * fall-speed parameters (CMX_ERR_BAD_ARG).  `table` is never dereferenced on the host.
- * Not done here: ensemble forms of the derivative entries, the implicit average and the implicit column steps, 2M + P3, the snow-shaped 1-moment column
- * step, the parcel model (it has per-parcel coefficients); tables of mixed instantiations; sharding members over devices.  cmx_version() stays at 0.5
- * (no struct layout changed; an older library fails on the symbol lookup).
+ *
+ * THE IMPLICIT COLUMN STEPS (21) — what a single-column model at Δt of minutes calls — have ensemble forms too:
+ * cmx_sb2006_column_implicit_step_ensemble_* and cmx_mp1m_column_implicit_step_ensemble_* take (desc, table, n_members, ens_flags), then
+ * (dt, nsub, step_flags, n_col, n_lev, inv_dz) and the arrays of the (21) entry.  The contract is the one above: member e of every output has the bits of the
+ * (21) entry called with member e's parameters on member e's state; sizes per member, outputs and fluxes member-major, inputs member-major or shared;
+ * inv_dz, dt, nsub and step_flags are shared by all members; the precipitation fluxes stay NULL-able; the outputs must not alias the state; the recurrence
+ * never crosses a member (a workgroup owns whole columns of one member).  The latent heating of the substeps uses Lv = LH_v0/cp_d and Ls = LH_s0/cp_d of
+ * member e's `tps`: the 1-moment block holds them already, the SB2006 block holds them after the cloud fall-speed constants (the SB2006 stride grew by
+ * two values; callers read it from cmx_sb2006_ensemble_table_stride_*).  The options come from the desc: limited, integer exponents, velocity kind and
+ * cloud sedimentation (SB2006); default-options or run-time-flags form and fitted or general Γ (1-moment).  The kernel runs one point per lane, so there is no
+ * alignment split and any alignment is accepted.
+ * Statuses, in order: NULL desc or table (CMX_ERR_BAD_ARG); n_col < 0 or n_lev < 1 (CMX_ERR_BAD_ARG), n_col > the single entry's limit per member
+ * (CMX_ERR_UNSUPPORTED); the descriptor checks above; n_col = 0 (CMX_OK); a NULL required array or a table packed without the fall-speed parameters
+ * (CMX_ERR_BAD_ARG); Δt, nsub and the step flags as the (21) entries check them (CMX_ERR_BAD_ARG).
+ *
+ * Not done here: ensemble forms of the derivative entries, of the pointwise implicit average (19) and of the column step with explicit fluxes (20), 2M + P3,
+ * the snow-shaped 1-moment column step, the parcel model (it has per-parcel coefficients); per-member Δt or nsub; tables of mixed instantiations; sharding
+ * members over devices.  cmx_version() stays at 0.5 (no struct of the interface changed layout; an older library fails on the symbol lookup).
  * ------------------------------------------------------------------------- */
 #define CMX_ENSEMBLE_SHARED_STATE (1u << 0)
 #define CMX_ENSEMBLE_MAGIC 0x434d5845u      /* "CMXE" */
@@ -2299,6 +2314,22 @@ int32_t cmx_mp1m_column_tendencies_sedimentation_ensemble_f64(const cmx_ensemble
                                                               double q_min, double dt, int32_t nsub, int64_t n_col, int32_t n_lev, const double *inv_dz,
                                                               const double *const *in, double *const *out, double *precip_rai, double *precip_sno,
                                                               void *stream);
+int32_t cmx_sb2006_column_implicit_step_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, double dt,
+                                                     int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *rho,
+                                                     const float *T, const float *q_tot, const float *q_lcl, const float *n_lcl, const float *q_rai,
+                                                     const float *n_rai, float *dq_lcl_dt, float *dn_lcl_dt, float *dq_rai_dt, float *dn_rai_dt,
+                                                     float *precip_flux, void *stream);
+int32_t cmx_sb2006_column_implicit_step_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, double dt,
+                                                     int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *rho,
+                                                     const double *T, const double *q_tot, const double *q_lcl, const double *n_lcl, const double *q_rai,
+                                                     const double *n_rai, double *dq_lcl_dt, double *dn_lcl_dt, double *dq_rai_dt, double *dn_rai_dt,
+                                                     double *precip_flux, void *stream);
+int32_t cmx_mp1m_column_implicit_step_ensemble_f32(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, double dt,
+                                                   int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const float *inv_dz, const float *const *in,
+                                                   float *const *out, float *precip_rai, float *precip_sno, void *stream);
+int32_t cmx_mp1m_column_implicit_step_ensemble_f64(const cmx_ensemble_desc *desc, const void *table, int32_t n_members, uint32_t ens_flags, double dt,
+                                                   int32_t nsub, uint32_t step_flags, int64_t n_col, int32_t n_lev, const double *inv_dz, const double *const *in,
+                                                   double *const *out, double *precip_rai, double *precip_sno, void *stream);
 
 /* ---------------------------------------------------------------------------
  * (3) Optional diagnostic sums over one rank's shard: Σx of `ncols` (≤ CMX_COLUMN_SUMS_MAX_COLS) device columns of length

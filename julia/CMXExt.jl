@@ -2360,4 +2360,43 @@ function column_tendencies_sedimentation_ensemble!(out, mode, ::BMT.Microphysics
     return out
 end
 
+"""
+    column_implicit_step_ensemble!(out, BMT.Microphysics2Moment(), desc, table, n_col, n_lev, inv_dz, ρ, …, dt; nsub, nonnegative, precip_flux, shared_state, stream)
+
+`column_implicit_step!` — the sub-stepped implicit average with backward-Euler sedimentation — of every member of a packed ensemble (packed with `vel`) in
+one launch; `n_col`, `n_lev` per member; `inv_dz`, `dt`, `nsub` and `nonnegative` shared; the latent heating of the substeps uses each member's own `tps`.
+`precip_flux` = `n_members · n_col` values or `nothing`.  `out` must not alias the state; the recurrence never crosses a member.
+"""
+function column_implicit_step_ensemble!(out, ::BMT.Microphysics2Moment, desc::EnsembleDesc, table, n_col::Integer, n_lev::Integer,
+    inv_dz::AbstractArray{FT}, ρ, T, q_tot, q_lcl, n_lcl, q_rai, n_rai, dt::Real; nsub::Integer = 1, nonnegative::Bool = true, precip_flux = nothing,
+    shared_state::Bool = false, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_sb2006_column_implicit_step_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Float64, Int32, UInt32, Int64, Int32, Ptr{FT},
+            Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), Float64(dt), Int32(nsub),
+        nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), n_col, n_lev, _dp(FT, inv_dz),
+        _dp(FT, ρ), _dp(FT, T), _dp(FT, q_tot), _dp(FT, q_lcl), _dp(FT, n_lcl), _dp(FT, q_rai), _dp(FT, n_rai),
+        _dp(FT, out.dq_lcl_dt), _dp(FT, out.dn_lcl_dt), _dp(FT, out.dq_rai_dt), _dp(FT, out.dn_rai_dt), _dp(FT, precip_flux), stream)
+    _check(st, "cmx_sb2006_column_implicit_step_ensemble")
+    return out
+end
+
+"""
+    column_implicit_step_ensemble!(out, BMT.Microphysics1Moment(), desc, table, n_col, n_lev, inv_dz, cols, dt; nsub, nonnegative, precip_rai, precip_sno, …)
+
+The 1-moment `column_implicit_step!` of every member of a packed ensemble (packed with `stokes` and `chen`) in one launch.  `cols` = the 7 state columns,
+`out` = the 4 tendency columns; `dt`, `nsub` and `nonnegative` are shared by all members.
+"""
+function column_implicit_step_ensemble!(out, ::BMT.Microphysics1Moment, desc::EnsembleDesc, table, n_col::Integer, n_lev::Integer,
+    inv_dz::AbstractArray{FT}, cols, dt::Real; nsub::Integer = 1, nonnegative::Bool = true, precip_rai = nothing, precip_sno = nothing,
+    shared_state::Bool = false, stream = C_NULL) where {FT}
+    st = ccall(_fn("cmx_mp1m_column_implicit_step_ensemble", FT), Int32,
+        (Ptr{Cvoid}, Ptr{Cvoid}, Int32, UInt32, Float64, Int32, UInt32, Int64, Int32, Ptr{FT}, Ptr{Ptr{FT}}, Ptr{Ptr{FT}}, Ptr{FT}, Ptr{FT}, Ptr{Cvoid}),
+        Ref(desc), _dp(UInt8, table), desc.n_members, _ens_flags(shared_state), Float64(dt), Int32(nsub),
+        nonnegative ? CMX_STEP_NONNEGATIVE : UInt32(0), n_col, n_lev, _dp(FT, inv_dz), _ptrs(FT, cols), _ptrs(FT, out), _dp(FT, precip_rai),
+        _dp(FT, precip_sno), stream)
+    _check(st, "cmx_mp1m_column_implicit_step_ensemble")
+    return out
+end
+
 end # module CMXExt

@@ -8,7 +8,8 @@ calls); the session is repeated `--runs` times.
     (c) the same with CMX_ENSEMBLE_SHARED_STATE
 With `--single-only` only the four single entries are timed, at `--points` (default 1e7), through a plain handle of the library CMX_LIB names: run so with
 the library of another build, in alternating processes, to see that the single entries did not move.
-    python tools/time_ensemble.py [--runs 3] [--single-only] [--points 1e7]"""
+With `--implicit` the two implicit column steps of §(21) are timed instead (Δt = 300 s, nsub = 2, nonnegative), in the same three cases or `--single-only`.
+    python tools/time_ensemble.py [--runs 3] [--single-only] [--points 1e7] [--implicit]"""
 import argparse
 import ctypes as C
 import statistics
@@ -26,7 +27,10 @@ from cmx import parameters as P  # noqa: E402
 
 DT = TJ.DT
 LEVELS = 64
-FAMILIES = ("SB2006 tendencies", "1-moment tendencies", "SB2006 column step", "1-moment column step")
+FAMILIES = ("SB2006 tendencies", "1-moment tendencies", "SB2006 column step", "1-moment column step", "SB2006 implicit column step",
+            "1-moment implicit column step")
+EXPLICIT, IMPLICIT = FAMILIES[:4], FAMILIES[4:]
+STEP = (300.0, 2, _abi.CMX_STEP_NONNEGATIVE)      # Δt, nsub, step flags of the implicit column steps
 
 
 def _members(ft, fam, E):
@@ -53,6 +57,8 @@ def _single_fn(lib, fam, ft):
         FAMILIES[1]: ("cmx_mp1m_tendencies", [vp, vp, u32, i64] + [vp] * 12),
         FAMILIES[2]: ("cmx_sb2006_column_tendencies_sedimentation", [vp, vp, vp, vp, u32, i64, i32] + [vp] * 14),
         FAMILIES[3]: ("cmx_mp1m_column_tendencies_sedimentation", [vp] * 5 + [u32, real, real, i32, i64, i32] + [vp] * 6),
+        FAMILIES[4]: ("cmx_sb2006_column_implicit_step", [vp, vp, vp, vp, u32, C.c_double, i32, u32, i64, i32] + [vp] * 14),
+        FAMILIES[5]: ("cmx_mp1m_column_implicit_step", [vp] * 5 + [u32, C.c_double, i32, u32, i64, i32] + [vp] * 6),
     }[fam]
     fn = getattr(lib, f"{name}_{ft}")
     fn.restype, fn.argtypes = i32, argtypes
@@ -76,7 +82,7 @@ def cases_of(ft, fam, E, n_col, shared, dev, lib, single_only=False):
     keep = [cols, out, precip, inv_dz, mps, tps, vel, stokes, cr, ci]
     flags2 = _abi.CMX_SB2006_LIMITED | _abi.CMX_VEL_SB2006
     tabs = []
-    if fam == FAMILIES[3]:
+    if fam in (FAMILIES[3], FAMILIES[5]):
         tabs = [((C.c_void_p * 7)(*[ptr(c[0 if shared else e]) for c in cols]), (C.c_void_p * 4)(*[ptr(o[e]) for o in out])) for e in range(E)]
         keep.append(tabs)
 
@@ -89,6 +95,11 @@ def cases_of(ft, fam, E, n_col, shared, dev, lib, single_only=False):
             return fn(adr(mps[e].c), adr(tps), mps[e].flags, n, *x, *y, s)
         if fam == FAMILIES[2]:
             return fn(adr(mps[e].c), adr(tps), adr(vel), None, flags2, n_col, LEVELS, ptr(inv_dz), *x, *y, ptr(precip[0][e]), s)
+        if fam == FAMILIES[4]:
+            return fn(adr(mps[e].c), adr(tps), adr(vel), None, flags2, *STEP, n_col, LEVELS, ptr(inv_dz), *x, *y, ptr(precip[0][e]), s)
+        if fam == FAMILIES[5]:
+            return fn(adr(mps[e].c), adr(tps), adr(stokes), adr(cr), adr(ci), mps[e].flags, *STEP, n_col, LEVELS, ptr(inv_dz), adr(tabs[e][0]),
+                      adr(tabs[e][1]), ptr(precip[0][e]), ptr(precip[1][e]), s)
         return fn(adr(mps[e].c), adr(tps), adr(stokes), adr(cr), adr(ci), mps[e].flags, 0.0, 0.0, 0, n_col, LEVELS, ptr(inv_dz), adr(tabs[e][0]),
                   adr(tabs[e][1]), ptr(precip[0][e]), ptr(precip[1][e]), s)
 
@@ -122,6 +133,12 @@ def cases_of(ft, fam, E, n_col, shared, dev, lib, single_only=False):
         elif fam == FAMILIES[2]:
             _lib.call("cmx_sb2006_column_tendencies_sedimentation_ensemble", fam_abi, dev, *head, n_col, LEVELS, C.c_void_p(ptr(inv_dz)), *x, *y,
                       C.c_void_p(ptr(precip[0])))
+        elif fam == FAMILIES[4]:
+            _lib.call("cmx_sb2006_column_implicit_step_ensemble", fam_abi, dev, *head, *STEP, n_col, LEVELS, C.c_void_p(ptr(inv_dz)), *x, *y,
+                      C.c_void_p(ptr(precip[0])))
+        elif fam == FAMILIES[5]:
+            _lib.call("cmx_mp1m_column_implicit_step_ensemble", fam_abi, dev, *head, *STEP, n_col, LEVELS, C.c_void_p(ptr(inv_dz)), in_p, out_p,
+                      C.c_void_p(ptr(precip[0])), C.c_void_p(ptr(precip[1])))
         else:
             _lib.call("cmx_mp1m_column_tendencies_sedimentation_ensemble", fam_abi, dev, *head, 0.0, 0.0, 0, n_col, LEVELS, C.c_void_p(ptr(inv_dz)), in_p,
                       out_p, C.c_void_p(ptr(precip[0])), C.c_void_p(ptr(precip[1])))
@@ -150,20 +167,22 @@ def main():
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--single-only", action="store_true")
     ap.add_argument("--points", type=lambda a: int(float(a)), default=10_000_000)
+    ap.add_argument("--implicit", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     print(f"library: {_lib.LIB_PATH}")
     lib = C.CDLL(str(_lib.LIB_PATH))
     cases, keep = {}, []
+    families = IMPLICIT if args.implicit else EXPLICIT
     if args.single_only:
         for ft in ("f32", "f64"):
-            for fam in FAMILIES:
+            for fam in families:
                 c, k = cases_of(ft, fam, 1, args.points // LEVELS if "column" in fam else args.points, False, dev, lib, single_only=True)
                 cases.update(c)
                 keep.append(k)
     else:
         for ft in ("f32", "f64"):
-            for fam in FAMILIES:
+            for fam in families:
                 col = "column" in fam
                 for E, n_col, shared in ((128, 1 if col else LEVELS, False), (32, 100_000 // LEVELS if col else 100_000, False),
                                          (32, 100_000 // LEVELS if col else 100_000, True)):
